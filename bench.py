@@ -14,8 +14,13 @@ SURVEY 8(d) counts into it: the H2D copy of the padded feature batch from pinned
 double-buffered, so batch k+1 travels while batch k computes) and the upload of the labels.
 Weak scaling: every rank processes its own 32 utterances; value = N*32 / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus `roofline` (dominant kernel, HIP
-event timing) and `cpu_baseline` (the numpy oracle timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 with the driver's contract plus a summary of `roofline` (dominant kernel, HIP
+event timing) and `cpu_baseline` (the numpy oracle timed on the host cores, N=1 only).  The line stays short (RESULT_LINE
+says what it keeps) so that a reader holding only the tail of the output still gets it whole; the full record (every side
+measurement, the roofline's per-kernel rows) goes to stderr as one line starting with `bench.py: full record `.
+
+--dump-outputs DIR writes what the timed path computed in its last step (losses, logits, a seeded sample of the updated
+weights and of the gradients) to DIR/<name>.npy, so that two builds can be compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -72,6 +77,53 @@ def train_step(eng, feed, reducer, lr, global_batch):
   if reducer:
     reducer.finish()
   eng.apply_update(lr)
+
+
+def seeded_sample(a, limit, seed=0):
+  """`a` itself, or -- above `limit` elements -- a fixed seeded sample of up to `limit` of its elements (sorted flat indices)."""
+  a = np.asarray(a)
+  if a.size <= limit:
+    return a
+  return a.reshape(-1)[np.unique(np.random.default_rng(seed).integers(0, a.size, limit))]
+
+
+def dump_outputs(eng, directory, limit=1 << 21):
+  """What a caller of the training step receives after the last timed step, as float32 / float64 .npy files:
+  per-utterance CTC losses (fp32 and the kernel's hi + lo pair in float64), the time-major logits of that step's forward pass,
+  and the updated weights and the gradients in the reference's layout ([W, Cin, Cout] filters then bias, layer by layer).
+  Arrays above `limit` elements (2 * `limit` for the logits) are a fixed seeded sample: 32 MB in all at most, besides the losses."""
+  os.makedirs(directory, exist_ok=True)
+  torch.cuda.synchronize()
+  flat = lambda pairs: np.concatenate([np.concatenate([F.reshape(-1), b.reshape(-1)]) for F, b in pairs])
+  arrays = {'loss': eng.loss.cpu().numpy().astype(np.float32),
+            'loss_f64': eng.losses_precise(),
+            'logits': seeded_sample(eng.logits_time_major().float().cpu().numpy(), 2 * limit),
+            'weights': seeded_sample(flat(eng.get_weights()), limit),
+            'grads': seeded_sample(flat(eng.get_grads()), limit)}
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a))
+
+
+# What the result line keeps of the full record: a key, or (key, the part of its block to keep)
+PARITY_KEYS = ['passed', 'max_logit_err_rel', 'ctc_loss_delta_rel']
+RESULT_LINE = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'ms_per_step_median', 'higher_is_better',
+               'scaling', 'vs_baseline', 'dtype', 'data', 'step_includes', ('config', ['global_batch', 'frames', 'parallelism', 'allreduce']),
+               'final_avg_loss', 'ctc_loss_delta', 'max_logit_err', 'ctc_loss_delta_rel', ('parity', PARITY_KEYS),
+               ('parity_nonzero_bias', PARITY_KEYS), 'replicas_identical', 'rccl_ranks', 'per_rank_ms_per_step',
+               ('comm', ['compute_only_ms_per_step', 'allreduce_alone_ms', 'exposed_comm_ms']), 'step_tflops_algorithmic',
+               ('roofline', ['kernel', 'bound', 'achieved', 'frac', 'ms_per_step']), 'step_hw_frac',
+               ('alt_bf16x6', ['ms_per_step']), ('alt_bf16', ['ms_per_step']),
+               ('configs2_inference', ['utterances_per_s', ('oracle_check', ['passed'])]),
+               ('configs4_decode', ['utterances_per_s', ('oracle_check', ['passed'])]), ('cpu_baseline', ['value'])]
+
+
+def pick(record, spec):
+  out = {}
+  for item in spec:
+    key, sub = item if isinstance(item, tuple) else (item, None)
+    if key in record:
+      out[key] = pick(record[key], sub) if (sub is not None and isinstance(record[key], dict)) else record[key]
+  return out
 
 
 def _lib_handle():
@@ -847,7 +899,11 @@ def main():
                   help='gradient exchange transport: the library\'s own RCCL communicator behind the C ABI (st_allreduce_buckets_f32; '
                        'default for --gpus > 1, falls back to torch.distributed if it cannot be set up) or torch.distributed')
   ap.add_argument('--tune', action='append', default=[], help='name=value override of a library policy (st_set_tuning; experiments only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed (losses, logits, sampled weights and gradients) to DIR/<name>.npy')
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
   for kv in args.tune:
     from speecht_amd._lib import set_tuning
     set_tuning(kv.split('=')[0], int(kv.split('=')[1]))
@@ -957,6 +1013,8 @@ def main():
   rank_ms = [elapsed / args.steps * 1e3]
   eng.check_ctc_status()
   loss = float(eng.loss.mean())
+  if rank == 0 and args.dump_outputs:
+    dump_outputs(eng, args.dump_outputs)       # before anything below runs more steps on this engine
   replicas_identical, comm = None, None
   if world > 1:
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -1135,7 +1193,9 @@ def main():
       # two CPU restatements of the reference path on this box's host cores; the faster one is `cpu_baseline`
       out['cpu_baseline'] = cpu_baseline_torch(args.mels, frames, args.batch)
       out['cpu_baseline_numpy_oracle'] = cpu_baseline(args.mels, frames)
-    print(json.dumps(out))
+    print('bench.py: full record ' + json.dumps(out), file=sys.stderr)
+    sys.stderr.flush()
+    print(json.dumps(pick(out, RESULT_LINE)))
   if dist.is_initialized():
     if world > 1:
       # rank 0 measured on its own for a while (roofline passes, side measurements): the others wait for it here instead of

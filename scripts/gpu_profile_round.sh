@@ -120,7 +120,7 @@ cp $(find gpurun_out/round${TAG}_prof -name '*kernel_stats.csv' | head -1) $OUT/
 grep '^{' gpurun_out/round${TAG}_prof/stdout.log > $OUT/bench_under_rocprof.json
 python - <<PY
 import json
-b = json.loads([l for l in open('$OUT/bench.json') if l.startswith('{')][-1])
+b = json.loads([l for l in open('$OUT/bench.err') if l.startswith('bench.py: full record ')][-1][len('bench.py: full record '):])
 r = b['roofline']
 print('bench: %.3f ms/step (median %.3f), %s in-step frac %.4f (isolated %s), step_hw_frac %s, traffic %s' % (
     b['ms_per_step'], b['ms_per_step_median'], r['kernel'], r['frac'], (r.get('isolated') or {}).get('frac'), b.get('step_hw_frac'),

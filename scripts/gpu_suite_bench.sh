@@ -4,9 +4,9 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/suite; mkdir -p $O
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | grep -v "^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -12 | tee $O/pytest_gpu.log
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | grep '^{' > $O/bench.json
-python - <<'PY'
-import json
-d=json.load(open('gpurun_out/suite/bench.json'))
+python - "$O/bench.err" <<'PY'
+import json, sys
+d=json.loads([l for l in open(sys.argv[1]) if l.startswith('bench.py: full record ')][-1][len('bench.py: full record '):])
 r=d['roofline']
 print('ms', d['ms_per_step'], 'value', d['value'], 'hw_frac', d.get('step_hw_frac'), 'gflop', d.get('step_executed_gflop'))
 print('dom', r['kernel'], r['frac'], r['ms_per_step'])

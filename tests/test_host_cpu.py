@@ -113,6 +113,29 @@ def test_bench_trace_line_parsing():
   assert bench.trace_field(bt, 'ms') is None and bench.trace_field(bt, 'bins') == 36.0
 
 
+def test_bench_result_line_stays_short():
+  """bench.py's stdout line is read from the tail of the output: built from a recorded full record (profiles/r6_bench.json, with
+  the data-parallel blocks of an 8-rank run added) it stays under 2 000 characters and keeps the headline, parity and roofline."""
+  import importlib.util
+  spec = importlib.util.spec_from_file_location('bench_module', os.path.join(ROOT, 'bench.py'))
+  bench = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(bench)
+  full = json.load(open(os.path.join(ROOT, 'profiles', 'r6_bench.json')))
+  full.update(rccl_ranks=dict(torch_distributed=8, backend='nccl', library_comm=8, transport='rccl', library_comm_spans_job=True,
+                              fallback=None), per_rank_ms_per_step=[6.589] * 8, replicas_identical=True,
+              comm=dict(compute_only_ms_per_step=6.512, allreduce_alone_ms=3.123, exposed_comm_ms=0.345, per_bucket=[{}] * 5))
+  line = json.dumps(bench.pick(full, bench.RESULT_LINE))
+  assert len(line) < 2000, len(line)
+  out = json.loads(line)
+  assert out['ms_per_step'] == full['ms_per_step'] and out['value'] == full['value'] and out['steps'] == full['steps']
+  assert out['parity']['passed'] is True and out['roofline']['frac'] == full['roofline']['frac']
+  assert out['cpu_baseline']['value'] == full['cpu_baseline']['value'] and 'by_kernel' not in out['roofline']
+  # --dump-outputs: a large array becomes the same seeded sample every time, a small one is kept whole
+  big = np.arange(10 ** 6, dtype=np.float32)
+  assert np.array_equal(bench.seeded_sample(big, 1000), bench.seeded_sample(big, 1000)) and bench.seeded_sample(big, 1000).size <= 1000
+  assert bench.seeded_sample(big.reshape(1000, 1000), 10 ** 6).shape == (1000, 1000)
+
+
 def test_speecht_import_names_resolve_to_the_native_modules():
   """The reference's callers import ``speecht.<module>`` (execution.py:20-23, evaluation.py:20-23): the alias package hands them
   the speecht_amd modules themselves (same objects, not copies); what is out of scope raises ImportError."""
