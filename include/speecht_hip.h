@@ -59,9 +59,17 @@ const char* st_last_error(void);
  * event (the dispatch's own begin / end time stamps, as a profiler's kernel trace shows them; no marker between
  * launches); st_trace_end then waits for them and appends " ms=<duration>" to each line -- per-launch times INSIDE the
  * real launch sequence of a step, side streams and all (bench.py's in-step roofline).
- * Tuning overrides for performance experiments ("gemm_tile", "gemm_splits", "fwd_splits", "xcd_gm",
- * "no_fast", "bf16_tile", "bf16_wgrad_splits", "bf16_sched", "streamk", "transform_wgs", "bf16_wgrad_target", "streamk_slots"); value 0 restores the library's own policy.
- * The launch path never reads the environment. */
+ * st_set_tuning forces a form the library's policy picks on other shapes (tests, A/B runs); value 0 restores the policy:
+ *   "streamk"             1: the per-bin products as the persistent stream-K launch wherever the shape allows, 2: never
+ *   "streamk_slots"       64 / 96: workgroups per XCD of that launch
+ *   "streamk_test_drop"   1: its producers publish a wrong epoch, so every hand-off is lost (the timeout path)
+ *   "no_fused_transforms" 1: the frequency-domain layers' transforms as separate kernels, never fused with a neighbour's
+ *   "bf16_lag_copies"     1: the bf16 lag products from transposed copies of the spectra instead of transposing reads
+ *   "filters_idft_valu"   1: the filter gradient's inverse transform on the vector ALU instead of the matrix pipe
+ *   "bf16_taps_panel"     1: the bf16 W-tap layers on the general kernel instead of conv_taps_bf16
+ *   "no_g3"               1: the wide layer's per-bin products in four real products instead of three
+ *   "g3_tile"             1: 64-row tiles, 2: 128-row tiles, 4: 64-row tiles and the reduction split in two (three-product kernels)
+ * Any other name fails with ST_EINVAL.  The launch path never reads the environment. */
 int st_trace_begin(void);
 int st_trace_begin_timed(void);
 /* Timed mode only times the launches whose trace line contains `text` (NULL or "": all).  A timed launch costs the stream

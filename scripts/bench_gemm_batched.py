@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times st_gemm_nn_batched_f32 on the three per-bin product shapes of the frequency-domain L8 (config 2: 48 bins,
-256 rows, 2*256 x 2*2048 channels) for tile / split experiments (--tune name=value)."""
+256 rows, 2*256 x 2*2048 channels); --tune name=value sets an st_set_tuning knob first (e.g. streamk=2: the plain
+launch instead of the persistent stream-K form)."""
 import argparse, ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

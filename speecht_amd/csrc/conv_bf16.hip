@@ -250,16 +250,7 @@ struct X6Params {
 // matrix pipe idles for the whole burst.
 // FAST = every reduction stage is whole (channel pitch / reduction length a multiple of BK): DMA sources are a
 // per-lane pointer plus the uniform k0 (no clamps) and every stage runs all its MFMA k-steps (no tail test).
-// SCH = 1 (round 3; 256 x 256 tile, FOUR waves = one per SIMD, 128 x 128 per wave, NP = 1, BK = 32, FAST): the wave
-// interleaves its own fragment reads and DMA pieces between its MFMAs instead of sharing the SIMD with a partner wave.
-// Why: in ping-pong every LDS / DMA instruction of the reading wave is issued beside the partner's streaming MFMAs and
-// costs ~100+ cycles there (PMC, DESIGN 4.3: matrix pipe 44 % busy, the read phase twice the MFMA phase); one wave per
-// SIMD hides up to ~5 single-issue instructions in each 32-cycle MFMA shadow (MI355X_MICROARCH.md), and the 128 x 128
-// wave tile needs 0.5 fragment reads + 0.25 DMA pieces per MFMA instead of 0.75 + 0.25.  The stage is software
-// pipelined across the per-stage barrier: the fragments of k-step 0 of stage kt + 1 are read during the second half of
-// the MFMAs of stage kt (the barrier sits in the middle of a stage's second k-step), so no stage opens with an exposed
-// LDS round trip.
-template <int BT, int WM, int WN, int BK, int NP, int ST = 2, bool PP = false, bool FAST = false, int SCH = 0>
+template <int BT, int WM, int WN, int BK, int NP, int ST = 2, bool PP = false, bool FAST = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_nn_bf16_kernel(X6Params p) {
   constexpr int NW = WM * WN;
   constexpr int BM = BT, BN = BT;
@@ -485,109 +476,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nn_bf16_kernel(X6Params p) 
       stage_sync(more);
     }
   };
-  if constexpr (SCH == 1) {
-    static_assert(!PP && NP == 1 && (KS == 2 || KS == 4) && MT % 2 == 0, "schedule 1: one plane, two or four k-steps per stage");
-    bf16x8 fa[2][MT], fb[2][NT];                       // fragments of even / odd k-steps (double buffer, also across stages)
-    auto reads = [&](auto slot_c, auto ks_c) {
-      constexpr int SL = decltype(slot_c)::value, KI = decltype(ks_c)::value, BUF = KI & 1;
-      const unsigned short* as = As + SL * PL;
-      const unsigned short* bs = Bs + SL * PL;
-      // in the order the MFMAs want them (LDS returns in order, so the first MFMA waits for two reads, not for all)
-      fb[BUF][0] = *reinterpret_cast<const bf16x8*>(bs + b_frag[KI]);
-      fa[BUF][0] = *reinterpret_cast<const bf16x8*>(as + a_frag[KI]);
-#pragma unroll
-      for (int n = 1; n < NT; ++n) fb[BUF][n] = *reinterpret_cast<const bf16x8*>(bs + b_frag[KI] + n * 32 * BK);
-#pragma unroll
-      for (int i = 1; i < MT; ++i) fa[BUF][i] = *reinterpret_cast<const bf16x8*>(as + a_frag[KI] + i * 32 * BK);
-    };
-    auto mfmas = [&](auto ks_c, int i0, int i1) {
-      constexpr int BUF = decltype(ks_c)::value & 1;
-#pragma unroll
-      for (int i = i0; i < i1; ++i)
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-          acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[BUF][n], fa[BUF][i], acc[i][n], 0, 0, 0);
-    };
-    // !FAST here means: every stage is whole EXCEPT possibly the last one (one-tap layers whose reduction length is a
-    // multiple of 16 but not of BK, e.g. 2016 channels with 64-deep stages).  That stage runs `nks_last` k-steps and its DMA
-    // sources are clamped into the row (what lies behind the valid range is never multiplied).
-    const int nks_last = (FAST || unit0 + nk != chunks) ? KS : (len - (chunks - 1) * BK + 15) / 16;   // (!FAST: one tap)
-    const int kp8 = p.Kp - 8;
-    auto dma_piece1 = [&](int pc, int k0, int buf, bool clamp) {
-      const int op = pc / PPW, i = pc % PPW;
-      if (op == 0) {
-        const __bf16* g = aptr[0][i] + (clamp ? min(k0, ktail - slot8[i]) : k0);
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(As + buf * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
-      } else {
-        const __bf16* g = bptr[0][i] + (clamp ? min(k0, kp8 - slot8[i]) : k0);
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(Bs + buf * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
-      }
-    };
-    constexpr int DPK = (N_DMA + KS - 2) / (KS - 1);   // DMA pieces per k-step, spread over the first KS - 1 k-steps
-    auto stage1 = [&](auto cur_c, auto more_c, int kt) {
-      constexpr int CUR = decltype(cur_c)::value, FILL = (CUR + ST - 1) % ST, NEXT = (CUR + 1) % ST;
-      constexpr bool MORE_CT = decltype(more_c)::value;
-      const bool more = MORE_CT || kt + ST - 1 < nk;   // a stage ST - 1 ahead exists: stage it into the slot freed last
-      const bool next = MORE_CT || kt + 1 < nk;        // a stage kt + 1 exists: its first fragments are read in this one
-      const int nks = (MORE_CT || FAST || kt + 1 < nk) ? KS : nks_last;
-      const bool clamp = !FAST && !MORE_CT && kt + ST == nk;    // the stage being staged is the (short) last one
-      const int nk0 = ic.k0;
-      if (more) advance(ic);
-      // ---- k-steps 0 .. KS - 2: the fragments of the k-step are in registers; between its 16 MFMAs go the 8 fragment
-      // reads of the next k-step and a share of the DMA pieces of the stage ST - 1 ahead
-      static_for<KS - 1>([&](auto ks_c) {
-        constexpr int KI = decltype(ks_c)::value;
-        reads(std::integral_constant<int, CUR>{}, std::integral_constant<int, KI + 1>{});
-        constexpr int P0 = KI * DPK, P1 = (KI + 1) * DPK < N_DMA ? (KI + 1) * DPK : N_DMA;
-        if (more) {
-#pragma unroll
-          for (int pc = P0; pc < P1; ++pc) dma_piece1(pc, nk0, FILL, clamp);
-        }
-        if (KI < nks) mfmas(ks_c, 0, MT);
-#pragma unroll
-        for (int k = 0; k < MT + NT; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA ...
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // ... one fragment read in its shadow
-        }
-#pragma unroll
-        for (int k = 0; k < P1 - P0; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);   // address arithmetic / M0 of the piece
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // one DMA piece
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-      // ---- last k-step, first half
-      using KL = std::integral_constant<int, KS - 1>;
-      if (KS - 1 < nks) mfmas(KL{}, 0, MT / 2);
-      __builtin_amdgcn_sched_barrier(0);
-      if (next) {
-        // stage kt + 1 complete in LDS: my own pieces by the counted wait, everybody else's by the barrier -- which also
-        // says that no wave still reads the slot the next stage's DMA (issued after this point) will overwrite
-        if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((ST - 2) * N_DMA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- last k-step, second half, with the first fragments of the next stage read underneath: two reads behind each of
-      // the first four MFMAs, so that the last read is four MFMAs (~130 cycles) old when the next stage opens
-      if (next) reads(std::integral_constant<int, NEXT>{}, std::integral_constant<int, 0>{});
-      if (KS - 1 < nks) mfmas(KL{}, MT / 2, MT);
-#pragma unroll
-      for (int k = 0; k < (MT + NT) / 2; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    if (nk > 0) reads(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-    int kt = 0;
-    for (; kt + 2 * ST - 2 < nk; kt += ST)
-      static_for<ST>([&](auto s_c) { stage1(s_c, std::true_type{}, kt + decltype(s_c)::value); });
-    static_for<2 * ST - 2>([&](auto r_c) {
-      constexpr int R = decltype(r_c)::value;
-      if (kt + R < nk) stage1(std::integral_constant<int, R % ST>{}, std::false_type{}, kt + R);
-    });
-  }
   auto run = [&](auto grp_c) {
     constexpr int GRP = decltype(grp_c)::value;
     if (PP && GRP == 1) phase_barrier();             // group 1 runs one phase behind
@@ -601,9 +489,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nn_bf16_kernel(X6Params p) 
     });
     if (PP && GRP == 0) phase_barrier();             // every wave executes the same number of barriers
   };
-  if constexpr (SCH == 1) {
-    (void)run;
-  } else if constexpr (PP) {
+  if constexpr (PP) {
     if (wave / (NW / 2) == 0) run(std::integral_constant<int, 0>{});   // waves i and i + NW/2 share a SIMD
     else run(std::integral_constant<int, 1>{});
   } else {
@@ -762,18 +648,16 @@ __global__ __launch_bounds__(256) void row_sum_bf16_kernel(const __bf16* __restr
 //   wide problems  -> 256 x 256 tile, 8 waves, LDS ring + ping-pong wave groups
 //                     (NP = 3: 16-deep stages, ring of 3; NP = 1: 32-deep stages, ring of 4)
 //   everything else -> 128 x 128 tile, 4 waves (NP = 3: 32-deep stages, 2 slots; NP = 1: 64-deep, ring of 4)
-// st_set_tuning("bf16_tile", 128) forces the small tile (perf experiments).
 template <int NP>
 int launch_gemm(X6Params& p, hipStream_t s) {
-  const int forced_tile = st::tuning(st::TUNE_BF16_TILE);
   if (p.splits < 1) p.splits = 1;
   const bool fits256 = NP == 1 ? p.Np >= 256 : p.Np % 256 == 0;
   const bool wide = (long)st::ceil_div(p.M, 256) * st::ceil_div(p.Np, 256) * p.splits >= 192;
   // The 250-channel layers (252 tiles of 128 x 128, ONE 128 KB workgroup per CU, 23-26 us for 14.4 GFLOP) were tried in round 3
-  // as 64 x 64 tiles of two waves with 2-5 workgroups per CU (33-35 us) and in the one-wave-per-SIMD schedule (SCH = 1: 23 us
-  // alone, no change of the step): the 128 x 128 tile of four waves stays.
+  // as 64 x 64 tiles of two waves with 2-5 workgroups per CU (33-35 us) and in a one-wave-per-SIMD schedule (23 us alone, no
+  // change of the step): the 128 x 128 tile of four waves stays.
   // (stacked per-bin products: a tile must lie inside one bin)
-  const int BT = (forced_tile != 128 && fits256 && wide && (p.rows_per_bin <= 0 || p.rows_per_bin % 256 == 0)) ? 256 : 128;
+  const int BT = (fits256 && wide && (p.rows_per_bin <= 0 || p.rows_per_bin % 256 == 0)) ? 256 : 128;
   p.tiles_m = st::ceil_div(p.M, BT);
   p.tiles_n = st::ceil_div(p.Np, BT);
   {
@@ -783,7 +667,6 @@ int launch_gemm(X6Params& p, hipStream_t s) {
     // (PMC round 3: 345 MB per launch at 2.1 TB/s, L2 hit rate 0.89); row bands read them once and the 8 MB of filters
     // eight times.
     const double a_bytes = (double)p.M * (p.taps > 1 ? p.cp : p.Kvalid) * 2.0 * NP, b_bytes = (double)p.Kp * p.Np * 2.0 * NP;
-    const int forced_gm = st::tuning(st::TUNE_XCD_GM);
     double best = 0.0;
     p.gm = 1;
     for (int gm = 1; gm <= 8; gm *= 2) {
@@ -791,8 +674,7 @@ int launch_gemm(X6Params& p, hipStream_t s) {
       if (gm > p.tiles_m || gn > p.tiles_n) continue;
       const int slots = st::ceil_div(p.tiles_m, gm) * st::ceil_div(p.tiles_n, gn) * 8;
       const double cost = (a_bytes * gn + b_bytes * gm) * ((double)slots / (p.tiles_m * p.tiles_n));   // idle slots cost time
-      if (best == 0.0 || cost < best || gm == forced_gm) { best = gm == forced_gm ? -1.0 : cost; p.gm = gm; }
-      if (gm == forced_gm) break;
+      if (best == 0.0 || cost < best) { best = cost; p.gm = gm; }
     }
     if (8 / p.gm > p.tiles_n) p.gm = 8;                       // fewer than 8/gm column panels: stack the XCDs along M
     if (p.gm > p.tiles_m && 8 / p.gm <= p.tiles_n) p.gm = 1;
@@ -806,8 +688,8 @@ int launch_gemm(X6Params& p, hipStream_t s) {
     st::trace("gemm_nn_bf16<%d,NP=%d> batched bins=%d M=%d Np=%d Kp=%d xcd=%dx%d gflop=%.3f", BT, NP, p.M / p.rows_per_bin, p.rows_per_bin,
               p.Np, p.Kvalid, p.gm, 8 / p.gm, 2e-9 * p.tiles_m * BT * (double)(p.tiles_n * BT) * p.Kvalid * (NP == 3 ? 6 : 1));
   else
-    st::trace("gemm_nn_bf16<%d,NP=%d> splits=%d M=%d Np=%d Kp=%d taps=%d sched=%d xcd=%dx%d gflop=%.3f", BT, NP, p.splits, p.M, p.Np,
-              p.Kp, p.taps, st::tuning(st::TUNE_BF16_SCHED), p.gm, 8 / p.gm,
+    st::trace("gemm_nn_bf16<%d,NP=%d> splits=%d M=%d Np=%d Kp=%d taps=%d xcd=%dx%d gflop=%.3f", BT, NP, p.splits, p.M, p.Np,
+              p.Kp, p.taps, p.gm, 8 / p.gm,
               2e-9 * p.tiles_m * BT * (double)(p.tiles_n * BT) * p.Kp * (NP == 3 ? 6 : 1));
   st::LaunchTimer timer(s);
   const auto whole = [&](int bk) { return (p.taps > 1 ? p.cp % bk : p.Kvalid % bk) == 0; };   // FAST eligibility
@@ -816,29 +698,19 @@ int launch_gemm(X6Params& p, hipStream_t s) {
     if (whole(K)) st::launch_timed(timer, gemm_nn_bf16_kernel<T, W1, W2, K, N, R, P, true>, grid, dim3(64 * W1 * W2), s, p);   \
     else st::launch_timed(timer, gemm_nn_bf16_kernel<T, W1, W2, K, N, R, P, false>, grid, dim3(64 * W1 * W2), s, p);          \
   } while (0)
-  // Schedule of the 256 x 256 bf16-activation kernel (st_set_tuning("bf16_sched", v) selects one; 0 = the policy = 1):
-  //   1  eight waves in ping-pong groups, 32-deep stages, ring of 4 (rounds 1-2) -- still the fastest (round 3, L8 forward /
-  //      back-prop / filter gradient: 0.462 / 0.419 / 0.537 ms)
-  //   2 / 3  one wave per SIMD, software pipelined (SCH = 1), 32-deep stages, ring of 4 / 3: 0.489 / 0.419 / 0.605 ms
-  //   4  SCH = 1 with 64-deep stages in a ring of 2 (a DMA row is a full 128-byte line: a third fewer L2 requests,
-  //      PMC 78 M -> 55 M per launch): 0.464 / 0.417 / 0.572 ms; L9 (short last stage) 0.175 vs 0.138
-  // None of the three moves the launch time: the limit is not instruction issue (scripts/ubench/gemm_issue.hip: the SCH = 1
-  // stage with every operand byte coming from L2 runs at 1.93 PFLOP/s on constant data, 1.49 on random data -- the board's
-  // power limit -- and 0.86 when every byte comes from HBM); see DESIGN 4.3.
-  const int sched = st::tuning(st::TUNE_BF16_SCHED);
-  const bool one_tap_tail = p.taps == 1 && p.Kvalid % 16 == 0;           // only the last stage may be short
+  // Schedule of the 256 x 256 bf16-activation kernel: eight waves in ping-pong groups, 32-deep stages, ring of 4 (rounds 1-2)
+  // -- still the fastest (round 3, L8 forward / back-prop / filter gradient: 0.462 / 0.419 / 0.537 ms).  Measured against it and
+  // removed: one wave per SIMD, software pipelined, 32-deep stages in a ring of 4 / 3 (0.489 / 0.419 / 0.605 ms), and 64-deep
+  // stages in a ring of 2 (a DMA row is a full 128-byte line: a third fewer L2 requests, PMC 78 M -> 55 M per launch; 0.464 /
+  // 0.417 / 0.572 ms; L9 with its short last stage 0.175 vs 0.138).  None of them moves the launch time: the limit is not
+  // instruction issue (scripts/ubench/gemm_issue.hip: the one-wave-per-SIMD stage with every operand byte coming from L2 runs at
+  // 1.93 PFLOP/s on constant data, 1.49 on random data -- the board's power limit -- and 0.86 when every byte comes from HBM);
+  // see DESIGN 4.3.
   if constexpr (NP == 3) {
     if (BT == 256) ST_LAUNCH(256, 2, 4, 16, 3, 3, true);
     else ST_LAUNCH(128, 2, 2, 32, 3, 2, false);
   } else {
-    if (BT == 256 && sched == 4 && (whole(64) || one_tap_tail)) {
-      if (whole(64)) st::launch_timed(timer, gemm_nn_bf16_kernel<256, 2, 2, 64, 1, 2, false, true, 1>, grid, dim3(256), s, p);
-      else st::launch_timed(timer, gemm_nn_bf16_kernel<256, 2, 2, 64, 1, 2, false, false, 1>, grid, dim3(256), s, p);
-    } else if (BT == 256 && (sched == 2 || sched == 3) && whole(32)) {
-      if (sched == 3) st::launch_timed(timer, gemm_nn_bf16_kernel<256, 2, 2, 32, 1, 3, false, true, 1>, grid, dim3(256), s, p);
-      else st::launch_timed(timer, gemm_nn_bf16_kernel<256, 2, 2, 32, 1, 4, false, true, 1>, grid, dim3(256), s, p);
-    }
-    else if (BT == 256) ST_LAUNCH(256, 2, 4, 32, 1, 4, true);
+    if (BT == 256) ST_LAUNCH(256, 2, 4, 32, 1, 4, true);
     else ST_LAUNCH(128, 2, 2, 64, 1, 4, false);
   }
 #undef ST_LAUNCH
@@ -1027,13 +899,11 @@ WgradPlan wgrad_plan(const st_tensor3& x, const st_tensor3& dz, int width, int s
   const long M = (long)width * x.c_pitch;
   const long tiles = st::ceil_div((int)M, 128) * (long)st::ceil_div(w.n_pad, 128);
   const int stages = (int)((w.red + 63) / 64);
-  const int forced = st::tuning(st::TUNE_BF16_WGRAD_SPLITS);
   // one 128 KB workgroup per CU: more than ~7/8 of the 256 CUs' worth of (tile, split) pairs starts a second round on some
   // XCD (a split's tiles are dealt to the XCDs in rectangles, 28 tiles -> 32 slots), and every split adds a slab to sum.
   // Round 3, filter gradient of a 250-channel layer incl. transposes and slab sum: 19 splits (the old "fill 512") 67 us,
   // 12 -> 60, 7 -> 51, 4 -> 65; first layer 8 -> 95, 4 -> 73; last layer 32 -> 55, 12 -> 46.
-  const int target = st::tuning(st::TUNE_BF16_WGRAD_TARGET) > 0 ? st::tuning(st::TUNE_BF16_WGRAD_TARGET) : 224;
-  w.splits = forced ? forced : tiles >= 192 ? 1 : (int)std::max(1L, std::min<long>(target / tiles, stages / 8));
+  w.splits = tiles >= 192 ? 1 : (int)std::max(1L, std::min<long>(224 / tiles, stages / 8));
   w.slab_bytes = w.splits > 1 ? (size_t)w.splits * M * w.n_pad * 4 : 0;
   return w;
 }

@@ -973,7 +973,6 @@ RowsIn rows_in(const st_tensor3& t) {
 }
 
 constexpr int TRANSFORM_WGS_DEFAULT = 512;       // persistent: two workgroups per CU, every wave walks its share of the items
-inline int transform_wgs() { const int t = st::tuning(st::TUNE_TRANSFORM_WGS); return t > 0 ? t : TRANSFORM_WGS_DEFAULT; }
 
 // tb: the tensor's bf16 form (null: read the fp32 tensor); planes: 0 -> fp32 spectra `out`, 1 / 3 -> bf16 plane(s) `outb`
 // form: 0, or 4 / 5 -- the fp32 spectra in the three-product layouts (rows of 4 / 3 parts, dft_rows_kernel OUTP)
@@ -982,7 +981,7 @@ void launch_dft(const st_tensor3& t, const void* tb, const Plan& pl, const float
                 int form = 0) {
   if (bin_stride == 0) bin_stride = (long)pl.rows_pad * (form == 4 ? 4 : form == 5 ? 3 : 2) * half;
   const int nchunks = st::ceil_div(half, 32);
-  const int wgs = std::min(transform_wgs(), st::ceil_div(pl.rows_pad * nchunks, 4));
+  const int wgs = std::min(TRANSFORM_WGS_DEFAULT, st::ceil_div(pl.rows_pad * nchunks, 4));
   const int nst = frames_used <= 6 * CH ? 3 : 4;                           // the matrix has no columns past frames_used
   // mb = the bytes the transform has to move: every frame of the tensor once, every spectrum value (and its rotated copy) once
   const double esz_in = tb ? 2.0 : 4.0, esz_out = planes == 0 ? 4.0 : 2.0 * planes;
@@ -1012,7 +1011,7 @@ void launch_dft(const st_tensor3& t, const void* tb, const Plan& pl, const float
 template <int TERMS>
 void launch_idft(const float* in, const float* winv, const Plan& p, int half_in, int nchunks, const RowsOut& out, const float* bias,
                  int relu, const void* mask, long mask_batch_stride, int mask_c_pitch, hipStream_t s) {
-  const dim3 grid(std::min(transform_wgs(), st::ceil_div(p.rows * nchunks, 4)));
+  const dim3 grid(std::min(TRANSFORM_WGS_DEFAULT, st::ceil_div(p.rows * nchunks, 4)));
   const int hp = p.bins <= 36 ? 18 : 24;
   const bool bf = out.base_b != nullptr;                       // bf16 activations: bf16 output and bf16 mask source
   st::trace("idft_rows<%d,%d%s> rows=%d chunks=%d bins=%d gflop=%.3f mb=%.2f", TERMS, hp, bf ? ",bf16" : "", p.rows, nchunks, p.bins,

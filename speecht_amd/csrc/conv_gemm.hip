@@ -1559,13 +1559,11 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(NNParams p, int ep
 // of today, 3.99 -> 3.75 ms (128.7 -> 136.8 TFLOP/s) including the slab epilogue; 3 splits leave a ragged round
 // (4.74 ms), 4 splits 3.87 ms.  (The first version of this kernel measured no gain: 4.31 vs 4.32 ms.)
 int nn_splits(int M, int Np, int Kp) {
-  const int forced = st::tuning(st::TUNE_GEMM_SPLITS);
   if (Np % 128) return 1;
   const long tiles128 = (long)st::ceil_div(M, 128) * (Np / 128);
   const int nk = Kp / BK;
-  int splits = forced ? forced
-                      : (tiles128 < 64 && nk >= 256 ? (int)std::min<long>(8, 256 / tiles128)
-                                                     : (tiles128 > 128 && tiles128 <= 320 && nk >= 512 ? 2 : 1));
+  int splits = tiles128 < 64 && nk >= 256 ? (int)std::min<long>(8, 256 / tiles128)
+                                          : (tiles128 > 128 && tiles128 <= 320 && nk >= 512 ? 2 : 1);
   while (splits > 1 && nk / splits < 64) --splits;
   return splits;
 }
@@ -1577,20 +1575,18 @@ int nn_splits(int M, int Np, int Kp) {
 // 2 s utterance: 1.18 ms unsplit, 0.355 ms with this policy (>= 8 tiles per slice 0.396, >= 2: 0.398, twice
 // the workgroups 0.363).
 int fwd_splits(int M, int Np, int nk) {
-  const int forced = st::tuning(st::TUNE_FWD_SPLITS);
   // The 29-class output layer at full batch (L10: 16032 x 2016 x 32) is an HBM stream of the activations with
   // one 128-row tile per workgroup: 126 workgroups leave half the CUs without any and every workgroup walks 1 MB
   // alone (72 us for 130 MB).  Four slices of the reduction put ~2 workgroups on every CU.
   // (round 6: shorter batches too -- 32 x 2 s is 3 232 rows = 26 workgroups, 58 us unsplit; about two workgroups per CU, at most
   // eight slices of at least four k-tiles)
-  if (Np == 32 && !forced) {
+  if (Np == 32) {
     if (M < 1024 || nk < 32) return 1;
     const int tiles_m = st::ceil_div(M, 128);
     return std::max(1, std::min(std::min(8, nk / 4), (512 + tiles_m / 2) / tiles_m));
   }
   if (Np % 128) return 1;
   const long tiles128 = (long)st::ceil_div(M, 128) * (Np / 128);
-  if (forced) return std::max(1, std::min(forced, nk));
   if (tiles128 >= 128) return 1;
   return (int)std::max<long>(1, std::min<long>(256 / tiles128, nk / 4));
 }
@@ -1603,7 +1599,6 @@ void launch_nn(NNParams& p, int epi, hipStream_t s) {
     // operand bytes an XCD's L2 has to pull in: the activation rows of its M range (once per N column group)
     // and the filter panel of its N range (once per M row group)
     const double a_bytes = (double)p.M * p.cp * 4.0, b_bytes = (double)p.Kp * p.Np * 4.0;
-    const int forced_gm = st::tuning(st::TUNE_XCD_GM);
     double best = 0.0;
     p.gm = 1;
     for (int gm = 1; gm <= 8; gm *= 2) {
@@ -1611,8 +1606,7 @@ void launch_nn(NNParams& p, int epi, hipStream_t s) {
       if (gm > p.tiles_m || gn > p.tiles_n) continue;
       const int slots = st::ceil_div(p.tiles_m, gm) * st::ceil_div(p.tiles_n, gn) * 8;
       const double cost = (a_bytes * gn + b_bytes * gm) * ((double)slots / (p.tiles_m * p.tiles_n));   // idle slots cost time
-      if (best == 0.0 || cost < best || gm == forced_gm) { best = gm == forced_gm ? -1.0 : cost; p.gm = gm; }
-      if (gm == forced_gm) break;
+      if (best == 0.0 || cost < best) { best = cost; p.gm = gm; }
     }
     if (8 / p.gm > p.tiles_n) p.gm = 8;                       // fewer than 8/gm filter panels: stack the XCDs along M
     p.tm_per = st::ceil_div(p.tiles_m, p.gm);
@@ -1642,7 +1636,6 @@ void launch_nn(NNParams& p, int epi, hipStream_t s) {
 }
 
 int run_nn(NNParams& p, int epi, hipStream_t s) {
-  const int force = st::tuning(st::TUNE_GEMM_TILE);   // perf experiments (st_set_tuning)
   if (p.bt_ld > 0) {
     // the filter operand transposed (k contiguous): whole k-tiles, one tap, 128-column tiles only
     if (!(p.Np % 128 == 0 && p.taps == 1 && p.cp % 32 == 0 && p.Kvalid % 32 == 0 && p.Kvalid == p.Kp && p.bt_ld % 4 == 0 && p.bt_rows > 0)) {
@@ -1656,14 +1649,11 @@ int run_nn(NNParams& p, int epi, hipStream_t s) {
   }
   if (p.Np % 128 == 0) {
     long tiles128 = (long)st::ceil_div(p.M, 128) * (p.Np / 128) * std::max(1, p.batches);
-    if (force == 1) launch_nn<64, 128, 2, 2>(p, epi, s);
-    else if (force == 2) launch_nn<128, 128, 2, 2>(p, epi, s);
-    else if (force == 3) launch_nn<128, 64, 2, 2>(p, epi, s);
-    else if (p.batches > 0 && (tiles128 < 512 || p.M <= 64)) {                         // per-bin products with few column tiles (or one half tile of rows)
+    if (p.batches > 0 && (tiles128 < 512 || p.M <= 64)) {                         // per-bin products with few column tiles (or one half tile of rows)
       if (p.cp % 32 == 0 && p.Kvalid % 32 == 0) launch_nn<64, 128, 2, 2, true>(p, epi, s);    // (back-prop: 8 per bin): twice the
       else launch_nn<64, 128, 2, 2>(p, epi, s);                                               // workgroups, +10 %
     }
-    else if ((tiles128 >= 192 || p.splits > 1) && p.cp % 32 == 0 && p.Kvalid % 32 == 0 && !st::tuning(st::TUNE_NO_FAST))
+    else if ((tiles128 >= 192 || p.splits > 1) && p.cp % 32 == 0 && p.Kvalid % 32 == 0)
       launch_nn<128, 128, 2, 2, true>(p, epi, s);                                      // whole k-tiles only: unclamped DMA addresses
     else if (tiles128 >= 192 || p.splits > 1) launch_nn<128, 128, 2, 2>(p, epi, s);   // >= 3/4 of the CUs busy
     else launch_nn<64, 128, 2, 2>(p, epi, s);
@@ -1740,10 +1730,9 @@ int st::gemm_nn_batched(const float* A, long lda, long a_batch, const float* B, 
   // kernel as a launch of their own (same streams of operands, plain row-major matrices: only the row offset differs).
   // Measured on the 32-tap layer at 32 x 11 s (rows 320): forward 625 us / back-prop 762 us in one launch of three row tiles.
   // Only the wide layer's products (K x N of 512 x 4096 or 4096 x 512 per bin: 100+ us of matrix work in the 64 rows saved); the
-  // narrow layers' launches are short and would pay a second launch each.  Same box, no_row_split 1 -> 0: the step at 32 x 6 s
+  // narrow layers' launches are short and would pay a second launch each.  Same box, unsplit -> split: the step at 32 x 6 s
   // 5.26 -> 5.18 ms, 11 s 8.72 -> 8.52, 12 s 9.13 -> 8.92; bucketed training +0.7 % (profiles/r6_row_split_ab.txt).
-  if (M % 128 == 64 && M > 128 && (long)K * N >= (1L << 21) && (long)st::ceil_div(M, 128) * (N / 128) * batches >= 512 &&
-      st::tuning(st::TUNE_GEMM_TILE) == 0 && st::tuning(st::TUNE_NO_ROW_SPLIT) == 0) {
+  if (M % 128 == 64 && M > 128 && (long)K * N >= (1L << 21) && (long)st::ceil_div(M, 128) * (N / 128) * batches >= 512) {
     if (int e = st::gemm_nn_batched(A, lda, a_batch, B, b_batch, C, ldc, c_batch, M - 64, K, N, batches, s, nullptr, b_transposed)) return e;
     return st::gemm_nn_batched(A + (long)(M - 64) * lda, lda, a_batch, B, b_batch, C + (long)(M - 64) * ldc, ldc, c_batch, 64, K, N, batches, s,
                                nullptr, b_transposed);
@@ -1814,8 +1803,8 @@ int st::gemm_nn_g3_batched(const float* A, long lda, long a_batch, const long a_
     st::set_error("gemm_nn_g3_batched: bad shape M=%d K=%d N=%d", M, K, N);
     return ST_EINVAL;
   }
-  if (M % 128 == 64 && M > 128 && (long)batches * st::ceil_div(M, 128) * (N / 128) >= 512 && st::tuning(st::TUNE_G3_TILE) == 0 &&
-      st::tuning(st::TUNE_NO_ROW_SPLIT) == 0) {                    // (a launch that takes 64-row tiles anyway stays whole)
+  if (M % 128 == 64 && M > 128 && (long)batches * st::ceil_div(M, 128) * (N / 128) >= 512 &&
+      st::tuning(st::TUNE_G3_TILE) == 0) {                         // (a launch that takes 64-row tiles anyway stays whole)
     if (int e = st::gemm_nn_g3_batched(A, lda, a_batch, a_off, B, ldb, b_batch, b_off, C, ldc, c_batch, c_off2, M - 64, K, N, batches, s, b_transposed)) return e;
     return st::gemm_nn_g3_batched(A + (long)(M - 64) * lda, lda, a_batch, a_off, B, ldb, b_batch, b_off, C + (long)(M - 64) * ldc, ldc, c_batch, c_off2,
                                   64, K, N, batches, s, b_transposed);

@@ -404,13 +404,10 @@ TrPlan tr_plan(const st_tensor3& x, const st_tensor3& dz, int width, int pad_lef
   // 2.62 -- but a workgroup alone on its CU is latency-bound (the 2000 x 2000 layer's 256 tiles unsplit: 0.32 us per stage for 0.11
   // us of MFMAs, 163 us; in two halves, two workgroups per CU, 146 us): about 256 pairs, and two halves when the tile grid
   // alone gives about one workgroup per CU and the reduction is long; at least 8 stages per split.
-  const int forced = st::tuning(st::TUNE_BF16_WGRAD_SPLITS);
-  const int target = st::tuning(st::TUNE_BF16_WGRAD_TARGET) > 0 ? st::tuning(st::TUNE_BF16_WGRAD_TARGET) : 256;
-  int splits = forced ? forced : (int)std::max(1L, std::min<long>(target / std::max(1L, tiles), t.stages / 8));
-  if (!forced && splits == 1 && tiles >= 128 && tiles <= 320 && t.stages >= 64) splits = 2;
+  int splits = (int)std::max(1L, std::min<long>(256 / std::max(1L, tiles), t.stages / 8));
+  if (splits == 1 && tiles >= 128 && tiles <= 320 && t.stages >= 64) splits = 2;
   // (a power of two, so that splits and XCDs divide each other: whole splits per XCD or whole XCDs per split, see the kernel)
-  if (!forced && !st::tuning(st::TUNE_BF16_WGRAD_PLAIN_ORDER))
-    while (splits & (splits - 1)) splits &= splits - 1;
+  while (splits & (splits - 1)) splits &= splits - 1;
   splits = std::max(1, std::min(splits, t.stages));
   t.stages_per_split = st::ceil_div(t.stages, splits);
   t.splits = st::ceil_div(t.stages, t.stages_per_split);
@@ -464,13 +461,9 @@ int st::lag_products_tr_bf16(const void* s_plane, const void* z_plane, int bins,
             2e-9 * 2.0 * bins * half * (double)npo * 2.0 * rows);
   {
     st::LaunchTimer timer(s);
-    if (st::tuning(st::TUNE_BF16_WGRAD_PLAIN_ORDER)) {
-      st::launch_timed(timer, wgrad_tr_bf16_kernel<true, 4>, dim3((unsigned)(bins * p.tiles_m * p.tiles_n), 2), dim3(256), s, p);
-    } else {
-      p.map = 3;
-      const unsigned groups = (unsigned)(bins * p.tiles_n), members = 2u * p.tiles_m;
-      st::launch_timed(timer, wgrad_tr_bf16_kernel<true, 4>, dim3(8u * st::ceil_div(groups, 8u) * members), dim3(256), s, p);
-    }
+    p.map = 3;
+    const unsigned groups = (unsigned)(bins * p.tiles_n), members = 2u * p.tiles_m;
+    st::launch_timed(timer, wgrad_tr_bf16_kernel<true, 4>, dim3(8u * st::ceil_div(groups, 8u) * members), dim3(256), s, p);
   }
   return st::check_launch("lag_products_tr_bf16");
 }
@@ -510,7 +503,7 @@ int st_conv1d_nwc_bwd_filter_tr_bf16(const st_tensor3* x, const void* x_bf16, co
   p.stages = t.stages; p.stages_per_split = t.stages_per_split; p.splits = t.splits;
   p.mtiles_per_tap = t.mtiles_per_tap; p.tiles_m = t.tiles_m; p.tiles_n = t.tiles_n;
   // the bias gradient from the same MFMAs (see the kernel) when the input's channel pitch has a padding channel to carry it
-  const bool in_tile = x->c_pitch > x->channels && x->c_pitch % TM == 0 && st::tuning(st::TUNE_BF16_WGRAD_BIAS_PASS) == 0;
+  const bool in_tile = x->c_pitch > x->channels && x->c_pitch % TM == 0;
   p.bias_in_tile = in_tile ? 1 : 0;
   p.bias_direct = in_tile && t.splits == 1 ? dbias : nullptr;
   st::trace("wgrad_tr_bf16<128,128,32> M=%d Np=%d rows=%ld stages=%d splits=%d gflop=%.3f", width * x->c_pitch, t.n_pad, t.rows, t.stages,
@@ -521,14 +514,12 @@ int st_conv1d_nwc_bwd_filter_tr_bf16(const st_tensor3* x, const void* x_bf16, co
     // stages (seven in flight) instead of four, the whole LDS for the one workgroup a CU gets anyway
     const int tiles = t.tiles_m * t.tiles_n;
     unsigned grid = (unsigned)(t.splits * tiles);
-    const int ring = st::tuning(st::TUNE_BF16_WGRAD_RING) ? st::tuning(st::TUNE_BF16_WGRAD_RING) : (grid <= 320 ? 8 : 4);
-    if (!st::tuning(st::TUNE_BF16_WGRAD_PLAIN_ORDER)) {
-      if (t.splits % 8 == 0) {
-        p.map = 1; p.map_a = t.splits / 8;
-      } else if (8 % t.splits == 0) {
-        p.map = 2; p.map_a = 8 / t.splits; p.map_b = st::ceil_div(tiles, p.map_a);
-        grid = 8u * p.map_b;
-      }
+    const int ring = grid <= 320 ? 8 : 4;
+    if (t.splits % 8 == 0) {
+      p.map = 1; p.map_a = t.splits / 8;
+    } else if (8 % t.splits == 0) {
+      p.map = 2; p.map_a = 8 / t.splits; p.map_b = st::ceil_div(tiles, p.map_a);
+      grid = 8u * p.map_b;
     }
     if (ring == 8) st::launch_timed(timer, wgrad_tr_bf16_kernel<false, 8>, dim3(grid), dim3(256), s, p);
     else st::launch_timed(timer, wgrad_tr_bf16_kernel<false, 4>, dim3(grid), dim3(256), s, p);
