@@ -334,6 +334,36 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
                                  int32_t* ids, int max_out, int32_t* out_lens, float* log_prob,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- word n-gram language model + LM-scored CTC prefix beam search (the reference's KenLM decoder path,
+ * speech_model.py:84-111; semantics restated in tests/lm_oracle.py) ---------------------------------------------------
+ * st_lm_create_arpa parses an ARPA model (orders 1..5) from a memory buffer into host tables: word ids (<unk> 0, <s> 1,
+ * </s> 2, then the unigrams in file order, lowercased), one open-addressing hash per order holding float32 log10 p and
+ * backoff, and a character trie over the words spelled in [a-z'] (other words keep their n-grams, unreachable from the
+ * trie: `skipped_words`).  A format error returns ST_EINVAL with "ARPA line N: ..." in err (and st_last_error).
+ * st_lm_upload copies the tables to the device of `stream` (null: the current device), once per device and handle; the
+ * decoder uses the copy on its own stream's device and refuses a handle without one.  st_lm_query_host / st_lm_trie_lookup /
+ * st_lm_word_id read the host tables (the same lookup code the kernel runs). */
+int st_lm_create_arpa(const char* text, size_t bytes, void** handle, char* err, size_t errlen);
+/* counts: order + 1 entries: counts[0] = word ids (with <unk> <s> </s>), counts[n] = n-grams of order n */
+int st_lm_info(void* handle, int* order, int64_t* counts, int64_t* skipped_words, int64_t* trie_nodes, size_t* device_bytes);
+int st_lm_upload(void* handle, void* stream);
+int st_lm_word_id(void* handle, const char* word, int32_t* id);            /* <unk> (0) for a word not in the model */
+/* log10 p(word | ctx[0..n-1]) with ARPA backoff (the last order - 1 context words are used) */
+int st_lm_query_host(void* handle, const int32_t* ctx, int n, int32_t word, float* logp);
+int st_lm_trie_lookup(void* handle, const char* prefix, int32_t* node, float* min_logp, int32_t* word);
+int st_lm_destroy(void* handle);
+/* The prefix beam search of st_ctc_beam_search_decode_ex with TF's scorer hooks: a word n-gram score enters every transition
+ * into a prefix as lm_weight * (its LM score - its parent's); a word is scored when a space follows it (+ word_count_weight, +
+ * valid_word_count_weight if in the vocabulary), an incomplete word by the lowest unigram of its completions (oov_score once
+ * it has left the vocabulary); at the end of the utterance every entry scores its incomplete word and </s>, and the top path
+ * is the best total after that.  Classes: a-z ' space blank (C = 29); beam <= 128; workspace: st_ctc_beam_ws; `lm` uploaded to
+ * the device of `stream`.
+ * log_prob includes the LM terms. */
+int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
+                                 float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                 int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* ---- K12-K13: clip_by_global_norm + AdamOptimizer(epsilon outside) (speech_model.py:77-82)
  * Flat fp32 buffers of n floats.  stats (device, 2 floats) receives {global_norm, scale}.
  * lr_t = lr * sqrt(1-beta2^t)/(1-beta1^t) is computed by the caller (host, double).

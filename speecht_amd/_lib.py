@@ -111,6 +111,15 @@ _SIGNATURES = {
                                           c_size_t, c_void_p]),
     'st_ctc_beam_search_decode_ex': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_size_t, c_void_p]),
+    'st_lm_create_arpa': (c_int, [c_char_p, c_size_t, POINTER(c_void_p), c_char_p, c_size_t]),
+    'st_lm_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_size_t)]),
+    'st_lm_upload': (c_int, [c_void_p, c_void_p]),
+    'st_lm_word_id': (c_int, [c_void_p, c_char_p, POINTER(c_int32)]),
+    'st_lm_query_host': (c_int, [c_void_p, POINTER(c_int32), c_int, c_int32, POINTER(c_float)]),
+    'st_lm_trie_lookup': (c_int, [c_void_p, c_char_p, POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
+    'st_lm_destroy': (c_int, [c_void_p]),
+    'st_ctc_beam_search_decode_lm': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'st_global_norm_ws': (c_size_t, [c_size_t]),
     'st_global_norm_clip_adam_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float,
                                              c_float, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -1,8 +1,9 @@
-// LM-free CTC prefix beam search (top path) on gfx950 -- SURVEY 8(f) item 3, BASELINE config 5.
+// CTC prefix beam search (top path) on gfx950 -- SURVEY 8(f) item 3, BASELINE config 5 -- without a scorer, and with the word
+// n-gram scorer of the reference's decoder (ctc_beam_kernel<.., LM = true>, st_ctc_beam_search_decode_lm).
 //
 // The reference reaches a beam search only through its KenLM TensorFlow fork (speech_model.py:101-111);
-// this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion without a scorer, with the
-// candidate order of oracle/w2l_oracle.py::ctc_beam_search_decode (total desc, slot*C + c asc).
+// this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion, with the candidate order of
+// oracle/w2l_oracle.py::ctc_beam_search_decode (total desc, slot*C + c asc); the scorer's hooks follow tests/lm_oracle.py.
 //
 // Mapping: ONE wavefront per utterance (the recursion is sequential in time, utterances are the
 // parallel axis), so a frame is a chain of dependent steps on one wave and its length IS the decode time
@@ -21,6 +22,7 @@
 // pure function of (frame, rank), so there are no atomics and the result is deterministic.
 #include <math.h>
 
+#include "lm_tables.h"
 #include "st_common.h"
 
 namespace {
@@ -47,6 +49,106 @@ struct BeamSet {   // structure of arrays: lane r reads/writes entry r without b
   float pl[MAXB];
   float total[MAXB];
 };
+
+// ---- word n-gram scorer of the LM-scored search (TF ctc_beam_search.h scorer hooks; the semantics: tests/lm_oracle.py) --------
+// An entry's LM state is a pure function of its prefix, and so are its 28 expansion deltas (score of the child - score of the
+// entry, labels a-z ' and space): they are computed ONCE, when the entry enters the beam -- one trie-row read and one n-gram
+// query -- and kept in LDS beside it; the scoring pass reads delta[slot][c] the way it reads lp_s[c].  "score" = lm_score (the
+// words so far) + the lowest unigram of the incomplete word's completions (`wpart`; oov_score once the prefix has left the
+// vocabulary, 0 at a word start), so the deltas are differences of small numbers, never of the running sums.
+constexpr int kSpace = 27;                 // vocabulary.SPACE_ID; the classes of an LM search are a-z ' space blank (C = 29)
+constexpr int kCtx = stlm::kMaxOrder - 1;  // context words kept per entry
+constexpr int kDeltaPitch = 32;
+
+struct LmParams {
+  stlm::View v;       // device tables
+  float lm_weight, word_count_weight, valid_word_count_weight, oov_score;
+};
+
+template <int MAXB>
+struct LmSet {        // structure of arrays, like BeamSet
+  int ctx[kCtx][MAXB];      // the last n_ctx word ids, oldest first
+  int n_ctx[MAXB];
+  int node[MAXB];           // trie node of the incomplete word, -1 once it has left the vocabulary
+  unsigned mask[MAXB];      // that node's child mask / first child / terminal word id (0 / 0 / -1 for -1)
+  int first[MAXB];
+  int word[MAXB];
+  float wpart[MAXB];        // score - lm_score
+  float dself[MAXB];        // score - the parent's score (the stay candidate's parent inflow)
+};
+
+// the node record of `node` (a global read; -1: no node)
+__device__ __forceinline__ stlm::TrieNode lm_node(const LmParams& P, int node) {
+  if (node < 0) return stlm::TrieNode{0u, 0, P.oov_score, -1};
+  return P.v.trie[node];
+}
+
+// the expansion deltas of an entry in state (node record nd, context, wpart) into an LDS row of kDeltaPitch floats: the children's
+// lowest unigrams (one read each, all independent) and, for space, the incomplete word against the context
+__device__ __forceinline__ void lm_deltas(const LmParams& P, const stlm::TrieNode& nd, const int* ctx, int n_ctx, float wpart,
+                                          float* row) {
+  float m[stlm::kLetters];
+#pragma unroll
+  for (int c = 0; c < stlm::kLetters; ++c) {
+    const bool has = (nd.mask >> c) & 1u;
+    const int child = nd.first + __builtin_popcount(nd.mask & ((1u << c) - 1u));
+    m[c] = has ? P.v.trie[child].min_logp : P.oov_score;
+  }
+  const int w = nd.word >= 0 ? nd.word : stlm::kUnk;
+  const float ws = stlm::score(P.v, ctx, n_ctx, w) + P.word_count_weight + (nd.word >= 0 ? P.valid_word_count_weight : 0.f);
+  float4* r4 = reinterpret_cast<float4*>(row);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) r4[q] = make_float4(m[4 * q] - wpart, m[4 * q + 1] - wpart, m[4 * q + 2] - wpart, m[4 * q + 3] - wpart);
+  r4[6] = make_float4(m[24] - wpart, m[25] - wpart, m[26] - wpart, ws - wpart);
+  r4[7] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// appends word w to a context of n_ctx words holding at most cap (oldest dropped); compile-time indices only (no scratch)
+__device__ __forceinline__ void push_ctx(int (&ctx)[kCtx], int& n_ctx, int cap, int w) {
+  if (cap <= 0) return;
+  const bool full = n_ctx == cap;
+#pragma unroll
+  for (int i = 0; i < kCtx; ++i) {
+    const int shifted = i + 1 < kCtx ? ctx[i + 1] : w;
+    ctx[i] = full ? (i == cap - 1 ? w : (i < cap - 1 ? shifted : ctx[i])) : (i == n_ctx ? w : ctx[i]);
+  }
+  n_ctx = full ? n_ctx : n_ctx + 1;
+}
+
+// entry e of the new set, made from parent entry `slot` of the old set by label c (stay: c is blank): its LM state, and -- for
+// a child -- its expansion deltas (the trie node record, then the children's row and the n-gram query of the word it spells)
+template <int MAXB>
+__device__ __forceinline__ void lm_enter(const LmParams& P, const LmSet<MAXB>& SL, LmSet<MAXB>& NL, const float* prow, float* row,
+                                         int slot, int e, int c, bool stay) {
+  int ctx[kCtx];
+#pragma unroll
+  for (int i = 0; i < kCtx; ++i) ctx[i] = SL.ctx[i][slot];
+  int nc = SL.n_ctx[slot];
+  if (stay) {
+#pragma unroll
+    for (int q = 0; q < kDeltaPitch / 4; ++q) reinterpret_cast<float4*>(row)[q] = reinterpret_cast<const float4*>(prow)[q];
+    NL.node[e] = SL.node[slot]; NL.mask[e] = SL.mask[slot]; NL.first[e] = SL.first[slot]; NL.word[e] = SL.word[slot];
+    NL.wpart[e] = SL.wpart[slot]; NL.dself[e] = SL.dself[slot];
+  } else {
+    int node;
+    if (c == kSpace) {
+      // the incomplete word (or <unk>) shifts into the context; the trie resets to the root
+      push_ctx(ctx, nc, P.v.order - 1, SL.word[slot] >= 0 ? SL.word[slot] : stlm::kUnk);
+      node = 0;
+    } else {
+      const unsigned pm = SL.mask[slot];
+      node = (SL.node[slot] >= 0 && ((pm >> c) & 1u)) ? SL.first[slot] + __builtin_popcount(pm & ((1u << c) - 1u)) : -1;
+    }
+    const stlm::TrieNode nd = lm_node(P, node);
+    const float wpart = c == kSpace ? 0.f : nd.min_logp;
+    NL.node[e] = node; NL.mask[e] = nd.mask; NL.first[e] = nd.first; NL.word[e] = nd.word;
+    NL.wpart[e] = wpart; NL.dself[e] = prow[c];
+    lm_deltas(P, nd, ctx, nc, wpart, row);
+  }
+#pragma unroll
+  for (int i = 0; i < kCtx; ++i) NL.ctx[i][e] = ctx[i];
+  NL.n_ctx[e] = nc;
+}
 
 __device__ __forceinline__ unsigned long long child_hash(unsigned long long h, int c) {
   unsigned long long x = h + 0x9E3779B97F4A7C15ull * (unsigned long long)(c + 1);
@@ -157,12 +259,13 @@ __global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __res
 // candidates -- so a lane's class is lane & 31 for all its candidates and its slots are (lane >> 5) + 2 j: no division, no index
 // arrays; two beam entries per lane in the per-entry phases; the selection bound is the exact W-th largest score (a bitwise binary
 // search over the sortable scores: 32 wave-parallel counts) instead of the lane / pair / quad maxima, which bound only 64.
-template <int CPL, int MAXB>
+// LM: the word n-gram scorer (LmParams) enters through the expansion deltas; LM = false compiles to the LM-free search.
+template <int CPL, int MAXB, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ lp_all, int T, int C,
                                                       const int* __restrict__ seq_lens, int W,
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
-                                                      int* __restrict__ out_lens, float* __restrict__ out_logp) {
+                                                      int* __restrict__ out_lens, float* __restrict__ out_logp, LmParams lmp) {
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -176,6 +279,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   __shared__ int sel_k[MAXB];
   __shared__ __attribute__((aligned(16))) unsigned long long surv[SURV + 16];   // compacted survivor keys of the fast selection (+ zero pad)
   __shared__ float sel_v[MAXB];
+  // LM state and expansion deltas of the entries (double buffered with the sets; a single element when LM is off)
+  constexpr int LMB = LM ? MAXB : 1;
+  __shared__ LmSet<LMB> lms[2];
+  __shared__ __attribute__((aligned(16))) float delta_s[2][LMB][kDeltaPitch];
+  const float lw = lmp.lm_weight;
 
   const int b = blockIdx.x, lane = threadIdx.x;
   const int Tb = min(seq_lens[b], T);
@@ -199,6 +307,18 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     BeamSet<MAXB>& s = sets[0];
     s.hash[0] = kRootHash; s.parent_hash[0] = 0; s.len[0] = 0; s.last[0] = -1; s.node[0] = 0;
     s.pb[0] = 0.f; s.pl[0] = -INFINITY; s.total[0] = 0.f;
+    if constexpr (LM) {
+      // root: context <s>, the trie root, lm_score = score = 0
+      LmSet<LMB>& L = lms[0];
+      const int nc = min(1, lmp.v.order - 1);
+      L.ctx[0][0] = stlm::kBos;
+      L.n_ctx[0] = nc;
+      const stlm::TrieNode nd = lm_node(lmp, 0);
+      L.node[0] = 0; L.mask[0] = nd.mask; L.first[0] = nd.first; L.word[0] = nd.word;
+      L.wpart[0] = 0.f; L.dself[0] = 0.f;
+      const int bos = stlm::kBos;
+      lm_deltas(lmp, nd, &bos, nc, 0.f, delta_s[0][0]);
+    }
   }
   __syncthreads();
 
@@ -299,7 +419,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       float npl = -INFINITY;
       if (len0 > 0) {
         float mass = pl0;
-        if (p >= 0) mass = lse(mass, (plen > 0 && plast == last0) ? ppb : ptot);
+        if constexpr (LM) {
+          if (p >= 0) mass = lse(mass, ((plen > 0 && plast == last0) ? ppb : ptot) + lw * lms[cur].dself[e]);
+        } else {
+          if (p >= 0) mass = lse(mass, (plen > 0 && plast == last0) ? ppb : ptot);
+        }
         npl = mass + lp_last;
       }
       stay_pb[e] = npb;
@@ -316,17 +440,23 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       float4 info[CPL];
       unsigned dd[CPL];
       float lpc[CPL];
+      float dl[LM ? CPL : 1];
 #pragma unroll
       for (int j = 0; j < CPL; ++j) {
         const int sl = cslot[j] < nb ? cslot[j] : 0;
         info[j] = slot_s[sl];
         dd[j] = dead[sl];
         lpc[j] = lp_s[ccls[j]];
+        if constexpr (LM) dl[j] = delta_s[cur][sl][ccls[j]];
       }
 #pragma unroll
       for (int j = CPL - 1; j >= 0; --j) {                // descending j + ">=": the lowest j wins a tie
         const int c = ccls[j];
-        const float child = ((dd[j] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[j].w) == c) ? info[j].y : info[j].x) + lpc[j];
+        float child;
+        if constexpr (LM)                                    // TF GetStateExpansionScore(child state, previous)
+          child = ((dd[j] >> c) & 1u) ? -INFINITY : (((__float_as_int(info[j].w) == c) ? info[j].y : info[j].x) + lw * dl[j]) + lpc[j];
+        else
+          child = ((dd[j] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[j].w) == c) ? info[j].y : info[j].x) + lpc[j];
         const float v = c == blank ? info[j].z : child;
         const unsigned oj = cslot[j] < nb ? order_bits(v) : 0u;
         ord[j] = oj;
@@ -341,16 +471,22 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       for (int j0 = 0; j0 < CPL; j0 += 8) {
         float4 info[8];
         unsigned dd[8];
+        float dl[LM ? 8 : 1];
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           const int sl = wslot0 + 2 * (j0 + jj);
           info[jj] = slot_s[sl < nb ? sl : 0];
           dd[jj] = dead[sl < nb ? sl : 0];
+          if constexpr (LM) dl[jj] = delta_s[cur][sl < nb ? sl : 0][c];
         }
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           const int sl = wslot0 + 2 * (j0 + jj);
-          const float child = ((dd[jj] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x) + lpc;
+          float child;
+          if constexpr (LM)
+            child = ((dd[jj] >> c) & 1u) ? -INFINITY : (((__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x) + lw * dl[jj]) + lpc;
+          else
+            child = ((dd[jj] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x) + lpc;
           const float v = c == blank ? info[jj].z : child;
           ord[j0 + jj] = (sl < nb && cls_live) ? order_bits(v) : 0u;
         }
@@ -525,12 +661,58 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       N.pl[e] = stay ? spl - top : v - top;
       N.total[e] = v - top;
     }
+    if constexpr (LM) {
+      // the new entries' LM state from their parents' (all in LDS), then -- for a child -- its expansion deltas: one entry at a
+      // time per lane (two unrolled would hold two sets of trie and n-gram loads in registers at once)
+#pragma unroll 1
+      for (int e = lane; e < n_new; e += 64) {
+        const int k = sel_k[e];
+        const int slot = WIDE ? k >> 5 : k / C, c = WIDE ? k & 31 : k - slot * C;
+        lm_enter(lmp, lms[cur], lms[cur ^ 1], delta_s[cur][slot], delta_s[cur ^ 1][e], slot, e, c, c == blank);
+      }
+    }
     nb = n_new;
     cur ^= 1;
     ST_WAVE_SYNC();
   }
 
   __syncthreads();
+  if constexpr (LM) {
+    // end of utterance: every entry scores its incomplete word (if non-empty) and then </s>; the top path is the best total
+    // after that (ties: the lower rank)
+    const LmSet<LMB>& L = lms[cur];
+    for (int e = lane; e < nb; e += 64) {
+      const float* row = delta_s[cur][e];
+      int ctx[kCtx];
+#pragma unroll
+      for (int i = 0; i < kCtx; ++i) ctx[i] = L.ctx[i][e];
+      int nc = L.n_ctx[e];
+      float d = -L.wpart[e];
+      if (L.node[e] != 0) {
+        d = row[kSpace];
+        push_ctx(ctx, nc, lmp.v.order - 1, L.word[e] >= 0 ? L.word[e] : stlm::kUnk);
+      }
+      d += stlm::score(lmp.v, ctx, nc, stlm::kEos);
+      sel_v[e] = sets[cur].total[e] + lw * d;
+    }
+    __syncthreads();
+    if (lane == 0) {
+      int e0 = 0;
+      for (int e = 1; e < nb; ++e)
+        if (sel_v[e] > sel_v[e0]) e0 = e;
+      const BeamSet<MAXB>& S = sets[cur];
+      int n = min(S.len[e0], max_out);
+      out_lens[b] = S.len[e0];
+      out_logp[b] = (float)((double)sel_v[e0] + offset);
+      int id = S.node[e0];
+      for (int i = S.len[e0] - 1; i >= 0; --i) {
+        int2 nd = nodes[id];
+        if (i < n) ids[(long)b * max_out + i] = nd.y;
+        id = nd.x;
+      }
+    }
+    return;
+  }
   // top path: entry 0 of the final set; walk the node chain backwards
   if (lane == 0) {
     const BeamSet<MAXB>& S = sets[cur];
@@ -590,10 +772,10 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
   st::trace("ctc_beam<%s> beam=%d transform=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform);
 #define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
-  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows,  \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, false>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
                      logits->frames, logits->channels, seq_lens, beam_width,                                         \
                      reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
-                     out_lens, log_prob)
+                     out_lens, log_prob, LmParams{})
   if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
   else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
   else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
@@ -601,6 +783,56 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
   else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
   return st::check_launch("ctc_beam_search");
+}
+
+int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
+                                 float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                 int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob && lm, "LM beam search: null argument");
+  ST_REQUIRE(input_transform == 0 || input_transform == 1, "LM beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
+             input_transform);
+  ST_REQUIRE(logits->channels == kSpace + 2, "LM beam search: the classes must be a-z ' space blank (%d), got %d", kSpace + 2,
+             logits->channels);
+  ST_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, "LM beam search: beam width 1..%d supported, got %d", kMaxBeam, beam_width);
+  ST_REQUIRE(max_out >= 1, "LM beam search: max_out must be positive");
+  ST_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_count_weight) && std::isfinite(valid_word_count_weight) &&
+             std::isfinite(oov_score), "LM beam search: weights and oov_score must be finite");
+  // the tables' copy on the device the search runs on (a pointer into another device's memory would fault there)
+  const stlm::Model* m = static_cast<const stlm::Model*>(lm);
+  int device = -1;
+  if (hipStreamGetDevice(st::as_stream(stream), &device) != hipSuccess) {
+    st::set_error("LM beam search: hipStreamGetDevice failed");
+    return ST_ELAUNCH;
+  }
+  const stlm::DeviceCopy* copy = m->on(device);
+  ST_REQUIRE(copy, "LM beam search: the language model is not on device %d (st_lm_upload with a stream of that device)", device);
+  size_t need = st_ctc_beam_ws(logits->batch, logits->frames, beam_width);
+  if (!workspace || workspace_bytes < need) {
+    st::set_error("LM beam search: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    return ST_EWORKSPACE;
+  }
+  if (logits->batch == 0) return ST_OK;
+  RowMap map{(long)logits->t_pitch * logits->c_pitch, (long)logits->halo * logits->c_pitch, logits->c_pitch};
+  float* lp_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + beam_pool_bytes(logits->batch, logits->frames, beam_width));
+  hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), logits->batch), dim3(256), 0, st::as_stream(stream),
+                     logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
+  const LmParams lmp{copy->view, lm_weight, word_count_weight, valid_word_count_weight, oov_score};
+  const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
+  st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform,
+            copy->view.order);
+#define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
+                     logits->frames, logits->channels, seq_lens, beam_width,                                         \
+                     reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
+                     out_lens, log_prob, lmp)
+  if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
+  else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
+  else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
+  else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
+  else ST_LAUNCH_BEAM(32, 64);
+#undef ST_LAUNCH_BEAM
+  return st::check_launch("ctc_beam_search_lm");
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Decoders of the engine (speech_model.py:101-115): greedy CTC decoding and the LM-free prefix beam search, synchronous and
+"""Decoders of the engine (speech_model.py:101-115): greedy CTC decoding, the LM-free prefix beam search and the prefix beam
+search with a word n-gram scorer, synchronous and
 with their outputs on the way to pinned host memory (`inference.transcribe` overlaps them with the next batches)."""
 import ctypes
 
@@ -118,6 +119,38 @@ class DecodeMixin:
       out = [merge_repeated_labels(seq) for seq in out]
     return out, self.dec_score.cpu().numpy().reshape(-1, 1)
 
+  def lm_beam_search_decode(self, lm, beam_width=100, input_transform='log10_softmax', lm_weight=0.8, word_count_weight=0.0,
+                            valid_word_count_weight=2.3, oov_score=-1000.0):
+    """The prefix beam search with a word n-gram scorer -- the reference's decoder (speech_model.py:84-111: beam 100,
+    merge_repeated=False, on log10(softmax + 1e-8), lm_weight 0.8, word_count_weight 0.0, valid_word_count_weight 2.3) with an
+    ARPA model (`language_model.LanguageModel`) in place of its KenLM scorer; semantics: tests/lm_oracle.py.
+    -> (list of id lists, log_prob [B,1]); log_prob includes the LM terms."""
+    lib = _lib.load()
+    B = self.dec_lens.numel()
+    need = lib.st_ctc_beam_ws(B, self.t_out, int(beam_width))
+    ws = self._storage.view('beam_ws', need // 4 + 16, torch.int32)[0]
+    handle = lm.device_handle(self.device)
+    self._wait_uploads()
+    call('st_ctc_beam_search_decode_lm', self.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), beam_input_transform(input_transform),
+         handle, float(lm_weight), float(word_count_weight), float(valid_word_count_weight), float(oov_score),
+         self._ptr(self.dec_ids), self.t_out, self._ptr(self.dec_lens), self._ptr(self.dec_score),
+         self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    lens = self.dec_lens.cpu().numpy()
+    ids = self.dec_ids.view(-1, self.t_out).cpu().numpy()
+    return [ids[b, :lens[b]].tolist() for b in range(len(lens))], self.dec_score.cpu().numpy().reshape(-1, 1)
+
+  def lm_beam_search_decode_async(self, lm, beam_width=100, decode_stream=None, input_transform='log10_softmax', lm_weight=0.8,
+                                  word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0):
+    """``lm_beam_search_decode`` on the decoder streams, like ``beam_search_decode_async``: returns a handle whose ``result()``
+    waits for this batch only."""
+    handle = lm.device_handle(self.device)
+    code = beam_input_transform(input_transform)
+
+    def launch(desc, lens, ids, T, out_lens, score, ws, ws_bytes, stream):
+      call('st_ctc_beam_search_decode_lm', desc, lens, int(beam_width), code, handle, float(lm_weight), float(word_count_weight),
+           float(valid_word_count_weight), float(oov_score), ids, T, out_lens, score, ws, ws_bytes, stream)
+    return self._beam_decode_async(beam_width, decode_stream, launch)
+
   def beam_search_decode_async(self, beam_width=16, decode_stream=None, input_transform=None):
     """``beam_search_decode`` without the host synchronisation and OFF the compute stream: the logits and lengths of this
     batch are copied into a decoder slot, the search runs on ``decode_stream`` (default: a stream of the engine's own;
@@ -125,6 +158,14 @@ class DecodeMixin:
     side) and its outputs go to pinned host memory; returns a handle whose
     ``result()`` waits for this batch only.  The caller enqueues the next batch's forward pass meanwhile -- the search is ONE
     wavefront per utterance (3.9 ms for 16 x 30 s, beam 16: as long as the forward pass) and leaves the chip to it."""
+    code = beam_input_transform(input_transform)
+
+    def launch(desc, lens, ids, T, out_lens, score, ws, ws_bytes, stream):
+      call('st_ctc_beam_search_decode_ex', desc, lens, int(beam_width), code, ids, T, out_lens, score, ws, ws_bytes, stream)
+    return self._beam_decode_async(beam_width, decode_stream, launch)
+
+  def _beam_decode_async(self, beam_width, decode_stream, launch):
+    """The slot ring of the asynchronous beam searches; `launch` issues the search itself on the decoder stream."""
     lib = _lib.load()
     B, T = self.dec_lens.numel(), self.t_out
     xl = self.X[-1]
@@ -167,10 +208,8 @@ class DecodeMixin:
       ready.record(main)
     desc = Tensor3(slot['logits'].data_ptr(), xl.batch, xl.frames, xl.channels, xl.halo, xl.t_pitch, xl.c_pitch)
     decode_stream.wait_event(ready)
-    call('st_ctc_beam_search_decode_ex', ctypes.byref(desc), self._ptr(slot['lens']), int(beam_width), beam_input_transform(input_transform),
-         self._ptr(slot['ids']), T,
-         self._ptr(slot['out_lens']), self._ptr(slot['score']), self._ptr(slot['ws']), slot['ws'].numel() * 4,
-         ctypes.c_void_p(decode_stream.cuda_stream))
+    launch(ctypes.byref(desc), self._ptr(slot['lens']), self._ptr(slot['ids']), T, self._ptr(slot['out_lens']), self._ptr(slot['score']),
+           self._ptr(slot['ws']), slot['ws'].numel() * 4, ctypes.c_void_p(decode_stream.cuda_stream))
     with torch.cuda.stream(decode_stream):
       slot['ids_h'][:B * T].copy_(slot['ids'][:B * T], non_blocking=True)
       slot['lens_h'][:B].copy_(slot['out_lens'][:B], non_blocking=True)

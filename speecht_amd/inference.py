@@ -44,7 +44,7 @@ DEFAULT_PIPELINE = True
 BEAM_DECODERS = 2
 
 
-def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None):
+def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -55,11 +55,32 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   launches on the same data as the serial loop, hence identical ids.  With ``beam_width`` the search of batch k runs on a
   decoder stream -- on compute units of its own, `engine.decoder_streams` -- under the forward passes of batches k+1 and
   k+2: one wavefront per utterance searches a little longer than the rest of the chip convolves (configs[4]: 3.9 against
-  3.6 ms), so two searches are in flight."""
+  3.6 ms), so two searches are in flight.
+
+  ``language_model`` (a `language_model.LanguageModel` or a path to an ARPA model): the LM-scored beam search instead, the
+  reference's decoder (beam 100 unless ``beam_width`` says otherwise; ``lm_options``: keyword arguments of
+  ``engine.lm_beam_search_decode`` -- input_transform, lm_weight, word_count_weight, valid_word_count_weight, oov_score)."""
   if not features:
     return [], []
   if pipeline is None:
     pipeline = DEFAULT_PIPELINE
+  lm_opts = dict(lm_options or {})
+  if language_model is not None:
+    from .language_model import LanguageModel
+    if not isinstance(language_model, LanguageModel):
+      language_model = LanguageModel.load(language_model)
+    beam_width = beam_width or 100
+
+  def decode_sync():
+    if language_model is not None:
+      return engine.lm_beam_search_decode(language_model, beam_width, **lm_opts)[0]
+    return engine.beam_search_decode(beam_width)[0] if beam_width else engine.greedy_decode()[0]
+
+  def decode_async(decode_stream):
+    if language_model is not None:
+      return engine.lm_beam_search_decode_async(language_model, beam_width, decode_stream, **lm_opts)
+    return engine.beam_search_decode_async(beam_width, decode_stream) if beam_width else engine.greedy_decode_async()
+
   lengths, buckets = _plan(features, batch_size, bucket)
   ids_out = [None] * len(features)
   if not pipeline:
@@ -70,7 +91,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         x[row, :lengths[i]] = features[i]
       engine.load_batch(x, [lengths[i] for i in idx])
       engine.forward()
-      ids, _ = engine.beam_search_decode(beam_width) if beam_width else engine.greedy_decode()
+      ids = decode_sync()
       for row, i in enumerate(idx):
         ids_out[i] = ids[row]
     return ids_out, [vocabulary.ids_to_sentence(s) for s in ids_out]
@@ -101,7 +122,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         with on_compute():
           engine.load_batch(staged, [lengths[i] for i in idx])
           engine.forward()
-          handle = engine.beam_search_decode_async(beam_width, decode_stream) if beam_width else engine.greedy_decode_async()
+          handle = decode_async(decode_stream if beam_width else None)
         pending.append((handle, idx))
         if len(pending) > depth:
           collect(*pending.pop(0))

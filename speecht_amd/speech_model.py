@@ -283,13 +283,18 @@ class SpeechModel:
 
   def add_decoding_ops(self, language_model=None, lm_weight=0.8, word_count_weight=0.0, valid_word_count_weight=2.3,
                        beam_width=0, beam_input=None):
-    """Greedy CTC decoding (speech_model.py:112-115).  The LM beam search needs the reference's
-    custom tensorflow-with-kenlm fork (speech_model.py:101-111) and is not part of this path.
-    ``beam_width`` > 0 (not a reference argument) selects the LM-free prefix beam search instead (up to 128; the reference's
-    operating point is 100 with merge_repeated=False on ``beam_input='log10_softmax'``, i.e. log10(softmax + 1e-8),
-    speech_model.py:102-110 -- without its KenLM scorer)."""
+    """Greedy CTC decoding (speech_model.py:112-115), or with ``language_model`` the reference's LM-scored beam search
+    (speech_model.py:84-111): beam 100 (``beam_width`` if given), merge_repeated=False, on log10(softmax + 1e-8) unless
+    ``beam_input`` says otherwise, scored by the word n-gram model of an ARPA file (or a directory holding one) in place of the
+    KenLM fork's scorer.  A path holding no ARPA model (a KenLM binary directory, say) raises UnsupportedLanguageModel, a
+    NotImplementedError.  ``beam_width`` > 0 without a language model (not a reference argument) selects the LM-free prefix beam
+    search (up to 128; the reference's operating point is 100 with merge_repeated=False on ``beam_input='log10_softmax'``)."""
+    self.language_model = None
     if language_model:
-      raise NotImplementedError('KenLM beam-search decoding depends on a TensorFlow fork that is not vendored')
+      from .language_model import LanguageModel
+      self.language_model = LanguageModel.load(language_model)
+      beam_width = beam_width or 100
+      beam_input = beam_input or 'log10_softmax'
     self.beam_width = int(beam_width or 0)
     self.beam_input = beam_input
     self.lm_weight, self.word_count_weight = lm_weight, word_count_weight
@@ -406,7 +411,12 @@ class SpeechModel:
     if decode:
       if not self._decoding:
         raise RuntimeError('add_decoding_ops() was not called')
-      ids, _ = eng.beam_search_decode(self.beam_width, getattr(self, 'beam_input', None)) if self.beam_width else eng.greedy_decode()
+      if getattr(self, 'language_model', None) is not None:
+        ids, _ = eng.lm_beam_search_decode(self.language_model, self.beam_width, self.beam_input, lm_weight=self.lm_weight,
+                                           word_count_weight=self.word_count_weight,
+                                           valid_word_count_weight=self.valid_word_count_weight)
+      else:
+        ids, _ = eng.beam_search_decode(self.beam_width, getattr(self, 'beam_input', None)) if self.beam_width else eng.greedy_decode()
       idx = [[b, p] for b, seq in enumerate(ids) for p in range(len(seq))]
       out.append([SparseTensorValue(np.array(idx, dtype=np.int64).reshape(-1, 2),
                                     np.array([v for seq in ids for v in seq], dtype=np.int64),
