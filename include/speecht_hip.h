@@ -363,6 +363,29 @@ int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_le
                                  float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
                                  int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* The same search for several weight triples at once (the LM weight search scores a generation of candidates on one batch): the
+ * log-softmax rows are computed once, and one launch of (batch x candidates) blocks decodes every (candidate, utterance) pair
+ * with its own node pool.  weights: HOST [candidates][3] = {lm_weight, word_count_weight, valid_word_count_weight}, all finite;
+ * candidates >= 1.  A launch takes at most 64 triples (kernel-argument space); more are split into launches of 64 that reuse the
+ * same node pools in stream order, so the workspace (st_ctc_beam_lm_candidates_ws) grows with min(candidates, 64).  Outputs per
+ * candidate p: ids [p][batch][max_out], out_lens [p][batch], log_prob [p][batch], each bit-identical to
+ * st_ctc_beam_search_decode_lm with p's weights (which is this entry point with one triple). */
+size_t st_ctc_beam_lm_candidates_ws(int batch, int frames, int beam_width, int candidates);
+int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                            void* lm, const float* weights, int candidates, float oov_score, int32_t* ids,
+                                            int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+
+/* ---- exact Levenshtein distances of id sequences (the evaluation's letter and word edit distances, evaluation.py:40-49) ------
+ * expected [expected_rows][expected_pitch] with lengths expected_lens, decoded [decoded_rows][decoded_pitch] with decoded_lens, all
+ * device int32; pairs: DEVICE [n_pairs][2] = (expected row, decoded row).  distances: DEVICE [n_pairs][2] = {letter distance, word
+ * distance}, where letters are the ids and words are the maximal runs of ids other than space (27): editdistance.eval of
+ * ids_to_sentence and of its str.split() for ids 0..27.  A pair with an id outside 0..27, a length outside 0..min(pitch,
+ * st_edit_distance_max_len()) or a row index out of range gets {-1, -1}: score it on the host.  No workspace. */
+int st_edit_distance_max_len(void);
+int st_edit_distance_pairs(const int32_t* expected, int expected_rows, int expected_pitch, const int32_t* expected_lens,
+                           const int32_t* decoded, int decoded_rows, int decoded_pitch, const int32_t* decoded_lens,
+                           const int32_t* pairs, int n_pairs, int32_t* distances, void* stream);
 
 /* ---- K12-K13: clip_by_global_norm + AdamOptimizer(epsilon outside) (speech_model.py:77-82)
  * Flat fp32 buffers of n floats.  stats (device, 2 floats) receives {global_norm, scale}.

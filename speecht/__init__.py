@@ -2,13 +2,14 @@
 
 The reference's callers import ``speecht.<module>`` (execution.py:20-23, evaluation.py:20-23, speecht-cli:163-205); with
 this package on the path in place of the reference's, they run unmodified on the HIP path.  Modules the reference has and
-this path leaves out of scope (corpus download, microphone recording, KenLM parameter search) are not
-aliased: importing them raises ImportError, never a silent stand-in."""
+this path leaves out of scope (corpus download, microphone recording) are not aliased: importing them
+raises ImportError, never a silent stand-in."""
 import importlib
 import sys
 
-_MODULES = ('vocabulary', 'preprocessing', 'speech_input', 'speech_model', 'evaluation', 'training', 'execution', 'exporting')
-_OUT_OF_SCOPE = ('corpus', 'recording', 'record_utils', 'parameter_search')
+_MODULES = ('vocabulary', 'preprocessing', 'speech_input', 'speech_model', 'evaluation', 'training', 'execution', 'exporting',
+            'parameter_search')
+_OUT_OF_SCOPE = ('corpus', 'recording', 'record_utils')
 
 
 def __getattr__(name):

@@ -120,6 +120,12 @@ _SIGNATURES = {
     'st_lm_destroy': (c_int, [c_void_p]),
     'st_ctc_beam_search_decode_lm': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p,
                                              c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_lm_candidates_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'st_ctc_beam_search_decode_lm_candidates': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, POINTER(c_float), c_int, c_float,
+                                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_edit_distance_max_len': (c_int, []),
+    'st_edit_distance_pairs': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p]),
     'st_global_norm_ws': (c_size_t, [c_size_t]),
     'st_global_norm_clip_adam_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float,
                                              c_float, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),

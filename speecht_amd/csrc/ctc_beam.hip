@@ -1,5 +1,6 @@
 // CTC prefix beam search (top path) on gfx950 -- SURVEY 8(f) item 3, BASELINE config 5 -- without a scorer, and with the word
-// n-gram scorer of the reference's decoder (ctc_beam_kernel<.., LM = true>, st_ctc_beam_search_decode_lm).
+// n-gram scorer of the reference's decoder (ctc_beam_kernel<.., LM = true>, st_ctc_beam_search_decode_lm), also for several
+// weight triples in one launch (a grid of utterances x candidates, st_ctc_beam_search_decode_lm_candidates: the LM weight search).
 //
 // The reference reaches a beam search only through its KenLM TensorFlow fork (speech_model.py:101-111);
 // this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion, with the candidate order of
@@ -61,8 +62,19 @@ constexpr int kCtx = stlm::kMaxOrder - 1;  // context words kept per entry
 constexpr int kDeltaPitch = 32;
 
 struct LmParams {
-  stlm::View v;       // device tables
+  const stlm::View& v;  // device tables (the kernel argument's: a copy indexed by order would live in scratch)
   float lm_weight, word_count_weight, valid_word_count_weight, oov_score;
+};
+
+// The scorer's kernel argument: the tables and up to kLaunchCandidates weight triples {lm, word count, valid word count}; the
+// block (utterance b, candidate blockIdx.y) decodes with triple blockIdx.y.  The triples travel in the kernel arguments (with the
+// tables 1 208 of the 4 096 argument bytes), so a launch takes at most kLaunchCandidates of them and the host splits larger
+// requests.
+constexpr int kLaunchCandidates = 64;
+struct LmArgs {
+  stlm::View v;
+  float oov_score;
+  float w[kLaunchCandidates][3];
 };
 
 template <int MAXB>
@@ -265,7 +277,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
                                                       const int* __restrict__ seq_lens, int W,
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
-                                                      int* __restrict__ out_lens, float* __restrict__ out_logp, LmParams lmp) {
+                                                      int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma) {
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -283,12 +295,16 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   constexpr int LMB = LM ? MAXB : 1;
   __shared__ LmSet<LMB> lms[2];
   __shared__ __attribute__((aligned(16))) float delta_s[2][LMB][kDeltaPitch];
-  const float lw = lmp.lm_weight;
 
   const int b = blockIdx.x, lane = threadIdx.x;
+  // LM: the candidate axis -- blockIdx.y picks the weight triple, its own node pool and its own output rows
+  const int p = LM ? (int)blockIdx.y : 0;
+  const LmParams lmp{lma.v, lma.w[p][0], lma.w[p][1], lma.w[p][2], lma.oov_score};
+  const long ob = LM ? (long)p * gridDim.x + b : b;
+  const float lw = lmp.lm_weight;
   const int Tb = min(seq_lens[b], T);
   const int blank = C - 1;
-  int2* nodes = node_pool + (long)b * pool_stride;
+  int2* nodes = node_pool + ob * pool_stride;
 
   // (slot, class) of this lane's candidates k = lane + 64 j: fixed for the whole utterance
   constexpr int NIDX = WIDE ? 1 : CPL;               // (wide beams compute them on the fly: slot (lane >> 5) + 2 j, class lane & 31)
@@ -702,12 +718,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         if (sel_v[e] > sel_v[e0]) e0 = e;
       const BeamSet<MAXB>& S = sets[cur];
       int n = min(S.len[e0], max_out);
-      out_lens[b] = S.len[e0];
-      out_logp[b] = (float)((double)sel_v[e0] + offset);
+      out_lens[ob] = S.len[e0];
+      out_logp[ob] = (float)((double)sel_v[e0] + offset);
       int id = S.node[e0];
       for (int i = S.len[e0] - 1; i >= 0; --i) {
         int2 nd = nodes[id];
-        if (i < n) ids[(long)b * max_out + i] = nd.y;
+        if (i < n) ids[ob * max_out + i] = nd.y;
         id = nd.x;
       }
     }
@@ -775,7 +791,7 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
   hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, false>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
                      logits->frames, logits->channels, seq_lens, beam_width,                                         \
                      reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
-                     out_lens, log_prob, LmParams{})
+                     out_lens, log_prob, LmArgs{})
   if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
   else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
   else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
@@ -785,19 +801,37 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
   return st::check_launch("ctc_beam_search");
 }
 
-int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
-                                 float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
-                                 int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob && lm, "LM beam search: null argument");
+// [node pools of min(candidates, kLaunchCandidates) x batch searches | log-softmax rows [batch][frames][32]]: a launch of more
+// candidates than kLaunchCandidates is split, and the launches of one call run in stream order on the same pools
+size_t st_ctc_beam_lm_candidates_ws(int batch, int frames, int beam_width, int candidates) {
+  if (batch <= 0 || frames < 0 || beam_width <= 0 || candidates <= 0) return 0;
+  const int per_launch = candidates < kLaunchCandidates ? candidates : kLaunchCandidates;
+  return beam_pool_bytes(batch * per_launch, frames, beam_width) + (size_t)batch * frames * kMaxClasses * sizeof(float);
+}
+
+int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                            void* lm, const float* weights, int candidates, float oov_score, int32_t* ids,
+                                            int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob && lm && weights, "LM beam search: null argument");
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "LM beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
              input_transform);
   ST_REQUIRE(logits->channels == kSpace + 2, "LM beam search: the classes must be a-z ' space blank (%d), got %d", kSpace + 2,
              logits->channels);
+  ST_REQUIRE(logits->batch >= 0 && logits->frames >= 0, "LM beam search: negative batch or frames (%d, %d)", logits->batch,
+             logits->frames);
   ST_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, "LM beam search: beam width 1..%d supported, got %d", kMaxBeam, beam_width);
   ST_REQUIRE(max_out >= 1, "LM beam search: max_out must be positive");
-  ST_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_count_weight) && std::isfinite(valid_word_count_weight) &&
-             std::isfinite(oov_score), "LM beam search: weights and oov_score must be finite");
+  ST_REQUIRE(candidates >= 1, "LM beam search: candidates must be >= 1, got %d", candidates);
+  ST_REQUIRE(std::isfinite(oov_score), "LM beam search: weights and oov_score must be finite");
+  for (int p = 0; p < candidates; ++p)
+    ST_REQUIRE(std::isfinite(weights[3 * p]) && std::isfinite(weights[3 * p + 1]) && std::isfinite(weights[3 * p + 2]),
+               "LM beam search: weights and oov_score must be finite (candidate %d)", p);
+  size_t need = st_ctc_beam_lm_candidates_ws(logits->batch, logits->frames, beam_width, candidates);
+  if (!workspace || workspace_bytes < need) {
+    st::set_error("LM beam search: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    return ST_EWORKSPACE;
+  }
   // the tables' copy on the device the search runs on (a pointer into another device's memory would fault there)
   const stlm::Model* m = static_cast<const stlm::Model*>(lm);
   int device = -1;
@@ -807,32 +841,50 @@ int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_le
   }
   const stlm::DeviceCopy* copy = m->on(device);
   ST_REQUIRE(copy, "LM beam search: the language model is not on device %d (st_lm_upload with a stream of that device)", device);
-  size_t need = st_ctc_beam_ws(logits->batch, logits->frames, beam_width);
-  if (!workspace || workspace_bytes < need) {
-    st::set_error("LM beam search: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    return ST_EWORKSPACE;
-  }
   if (logits->batch == 0) return ST_OK;
+  const int per_launch = candidates < kLaunchCandidates ? candidates : kLaunchCandidates;
+  const int B = logits->batch;
   RowMap map{(long)logits->t_pitch * logits->c_pitch, (long)logits->halo * logits->c_pitch, logits->c_pitch};
-  float* lp_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + beam_pool_bytes(logits->batch, logits->frames, beam_width));
-  hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), logits->batch), dim3(256), 0, st::as_stream(stream),
+  float* lp_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + beam_pool_bytes(B * per_launch, logits->frames, beam_width));
+  // the log-softmax rows once: every candidate reads the same rows
+  hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), B), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
-  const LmParams lmp{copy->view, lm_weight, word_count_weight, valid_word_count_weight, oov_score};
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
-  st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform,
-            copy->view.order);
+  st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d candidates=%d", beam_width > 64 ? "wide" : "wave", beam_width,
+            input_transform, copy->view.order, candidates);
+  for (int p0 = 0; p0 < candidates; p0 += kLaunchCandidates) {
+    const int n = candidates - p0 < kLaunchCandidates ? candidates - p0 : kLaunchCandidates;
+    LmArgs lma{};
+    lma.v = copy->view;
+    lma.oov_score = oov_score;
+    for (int p = 0; p < n; ++p)
+      for (int k = 0; k < 3; ++k) lma.w[p][k] = weights[3 * (p0 + p) + k];
+    int32_t* ids_p = ids + (size_t)p0 * B * max_out;
 #define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
-  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
-                     logits->frames, logits->channels, seq_lens, beam_width,                                         \
-                     reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
-                     out_lens, log_prob, lmp)
-  if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
-  else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
-  else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
-  else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
-  else ST_LAUNCH_BEAM(32, 64);
+    hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true>), dim3(B, n), dim3(64), 0, st::as_stream(stream), lp_rows, \
+                       logits->frames, logits->channels, seq_lens, beam_width,                                       \
+                       reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids_p, max_out,    \
+                       out_lens + (size_t)p0 * B, log_prob + (size_t)p0 * B, lma)
+    if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
+    else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
+    else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
+    else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
+    else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
-  return st::check_launch("ctc_beam_search_lm");
+    const int rc = st::check_launch("ctc_beam_search_lm");
+    if (rc != ST_OK) return rc;
+  }
+  return ST_OK;
+}
+
+// the single-candidate search is the candidates search with one triple (the same instantiation, the same launch shape)
+int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
+                                 float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                 int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
+  return st_ctc_beam_search_decode_lm_candidates(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, ids, max_out,
+                                                 out_lens, log_prob, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

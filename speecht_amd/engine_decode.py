@@ -3,6 +3,7 @@ search with a word n-gram scorer, synchronous and
 with their outputs on the way to pinned host memory (`inference.transcribe` overlaps them with the next batches)."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -43,6 +44,41 @@ class _PendingBeamDecode:
     ids = s['ids_h'][:self._batch * self._t_out].numpy().reshape(self._batch, self._t_out)
     return ([ids[b, :lens[b]].tolist() for b in range(self._batch)],
             s['score_h'][:self._batch].numpy().reshape(-1, 1).copy())
+
+
+# the largest workspace lm_beam_search_decode_candidates gives one call: 16 candidates x 64 utterances x 500 frames at beam 100
+# hold 410 MB of node pools, so a generation of that size runs in one call
+CANDIDATE_WORKSPACE_BYTES = 1 << 30
+
+
+class CandidateDecodes:
+  """Outputs of ``lm_beam_search_decode_candidates`` for P weight triples on B utterances: ``ids`` [P, B, T] int32, ``lens``
+  [P, B] int32 (a prefix longer than T keeps its true length), ``log_prob`` [P, B] float32 -- device tensors of the engine's
+  stream -- and ``host()``: one (list of id lists, log_prob [B, 1]) per candidate, like ``lm_beam_search_decode``."""
+
+  def __init__(self, ids, lens, log_prob, stream):
+    self.ids, self.lens, self.log_prob, self._stream = ids, lens, log_prob, stream
+    self._host = None
+
+  def __len__(self):
+    return self.ids.shape[0]
+
+  def _sync(self):
+    if self._stream is not None:                     # (an engine on a stream of its own: the copies below run on the current one)
+      self._stream.synchronize()
+
+  def lens_host(self):
+    self._sync()
+    return self.lens.cpu().numpy()
+
+  def host(self):
+    if self._host is None:
+      self._sync()
+      ids, lens, lp = self.ids.cpu().numpy(), self.lens.cpu().numpy(), self.log_prob.cpu().numpy()
+      T = ids.shape[2]
+      self._host = [([ids[p, b, :min(lens[p, b], T)].tolist() for b in range(ids.shape[1])], lp[p].reshape(-1, 1).copy())
+                    for p in range(ids.shape[0])]
+    return self._host
 
 
 def beam_input_transform(name):
@@ -138,6 +174,41 @@ class DecodeMixin:
     lens = self.dec_lens.cpu().numpy()
     ids = self.dec_ids.view(-1, self.t_out).cpu().numpy()
     return [ids[b, :lens[b]].tolist() for b in range(len(lens))], self.dec_score.cpu().numpy().reshape(-1, 1)
+
+  def lm_beam_search_decode_candidates(self, lm, weights, beam_width=100, input_transform='log10_softmax', oov_score=-1000.0,
+                                       max_workspace_bytes=CANDIDATE_WORKSPACE_BYTES):
+    """``lm_beam_search_decode`` for several weight triples on the same logits (the LM weight search's generation):
+    ``weights`` is a sequence of (lm_weight, word_count_weight, valid_word_count_weight).  The log-softmax rows are computed once
+    per call and one launch decodes every (candidate, utterance) pair (st_ctc_beam_search_decode_lm_candidates).  Candidates
+    are split into calls whose workspace stays under ``max_workspace_bytes`` (at least one candidate per call); the split does
+    not change any result: candidate p's outputs are bit-identical to ``lm_beam_search_decode`` with p's weights.
+    -> `CandidateDecodes`: the device outputs (ids [P, B, T], lens [P, B], log_prob [P, B]) and, on demand, a host view."""
+    lib = _lib.load()
+    w = np.asarray(weights, dtype=np.float32).reshape(-1, 3)
+    P, B, T = len(w), self.dec_lens.numel(), self.t_out
+    if P < 1:
+      raise ValueError('lm_beam_search_decode_candidates: at least one weight triple')
+    if not np.all(np.isfinite(w)):
+      raise ValueError('lm_beam_search_decode_candidates: weights must be finite')
+    chunk = P
+    while chunk > 1 and lib.st_ctc_beam_lm_candidates_ws(B, T, int(beam_width), chunk) > max_workspace_bytes:
+      chunk = (chunk + 1) // 2
+    need = lib.st_ctc_beam_lm_candidates_ws(B, T, int(beam_width), chunk)
+    ws = self._storage.view('beam_ws', need // 4 + 16, torch.int32)[0]
+    ids = torch.zeros(P * B * T, dtype=torch.int32, device=self.device)
+    lens = torch.empty(P * B, dtype=torch.int32, device=self.device)
+    logp = torch.empty(P * B, dtype=torch.float32, device=self.device)
+    handle = lm.device_handle(self.device)
+    code = beam_input_transform(input_transform)
+    self._wait_uploads()
+    for p0 in range(0, P, chunk):
+      n = min(chunk, P - p0)
+      wc = np.ascontiguousarray(w[p0:p0 + n])
+      call('st_ctc_beam_search_decode_lm_candidates', self.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle,
+           wc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n, float(oov_score),
+           ctypes.c_void_p(ids.data_ptr() + 4 * p0 * B * T), T, ctypes.c_void_p(lens.data_ptr() + 4 * p0 * B),
+           ctypes.c_void_p(logp.data_ptr() + 4 * p0 * B), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    return CandidateDecodes(ids.view(P, B, T), lens.view(P, B), logp.view(P, B), self._stream)
 
   def lm_beam_search_decode_async(self, lm, beam_width=100, decode_stream=None, input_transform='log10_softmax', lm_weight=0.8,
                                   word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0):

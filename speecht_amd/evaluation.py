@@ -26,10 +26,16 @@ class EvalStatistics:
 
   def track_decoding(self, decoded_str, expected_str):
     expected_tokens, decoded_tokens = expected_str.split(), decoded_str.split()
-    self.letter_edit_distance = editdistance.eval(expected_str, decoded_str)
-    self.word_edit_distance = editdistance.eval(expected_tokens, decoded_tokens)
-    self.letter_error_rate = self.letter_edit_distance / len(expected_str)
-    self.word_error_rate = self.word_edit_distance / len(expected_tokens)
+    self.track_distances(editdistance.eval(expected_str, decoded_str), editdistance.eval(expected_tokens, decoded_tokens),
+                         len(expected_str), len(expected_tokens))
+
+  def track_distances(self, letter_edit_distance, word_edit_distance, expected_letters, expected_words):
+    """``track_decoding`` from the distances themselves (the LM weight search computes them on the device): the same
+    assignments, rates and sums in the same order."""
+    self.letter_edit_distance = letter_edit_distance
+    self.word_edit_distance = word_edit_distance
+    self.letter_error_rate = self.letter_edit_distance / expected_letters
+    self.word_error_rate = self.word_edit_distance / expected_words
     for name in self._FIELDS:
       setattr(self, 'sum_' + name, getattr(self, 'sum_' + name) + getattr(self, name))
     self.decodings_counter += 1
