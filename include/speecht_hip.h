@@ -515,6 +515,21 @@ int st_mfcc_f32(const float* audio, const int64_t* sample_offsets, int n_utts, i
                 const int64_t* frame_offsets, int64_t total_frames, float* out, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- kaiser_best resampling (librosa.load's implicit resample, preprocessing.py:169) ----------
+ * resampy's band-limited interpolation (filter kaiser_best) + librosa's fix_length for a batch of utterances of mixed source
+ * rates: `in` holds the concatenated float32 mono samples, utterance u at [in_offsets[u], in_offsets[u+1]) with source rate
+ * rates[u] (int32); out utterance u at [out_offsets[u], out_offsets[u+1]) at rate sr_new.  The host plans every length
+ * (audio_io.plan_resample: target = ceil(n * sr_new / sr_orig) and out_valid[u] = min(int(n * ratio), target) samples
+ * interpolated, zeros after them); an utterance with rates[u] == sr_new is copied bit for bit.  win: the float64 right half
+ * window (audio_io._kaiser_best_filter, win_len = 32 769 entries).  Tap selection and weights are the float64 expressions of
+ * csrc/resample_map.h, shared with the host form; accumulation in float64.  All of these are device pointers.
+ * st_resample_kaiser_host: the same computation on host pointers, float64 out (tests without a GPU). */
+int st_resample_kaiser_f32(const float* in, const int64_t* in_offsets, int n_utts, const int32_t* rates, int sr_new,
+                           const int64_t* out_offsets, const int64_t* out_valid, int64_t total_out, const double* win,
+                           int64_t win_len, float* out, void* stream);
+int st_resample_kaiser_host(const float* in, const int64_t* in_offsets, int n_utts, const int32_t* rates, int sr_new,
+                            const int64_t* out_offsets, const int64_t* out_valid, const double* win, int64_t win_len, double* out);
+
 /* ---- helpers -------------------------------------------------------------------------- */
 int st_fill_f32(float* dst, float value, size_t n, void* stream);
 /* zero the halo rows of a padded NWC tensor (needed when a buffer is re-described for a new shape) */

@@ -170,6 +170,9 @@ _SIGNATURES = {
     'st_mfcc_ws': (c_size_t, [c_int, c_int64, c_int, c_int]),
     'st_mfcc_f32': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                             c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_resample_kaiser_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                       c_void_p, c_void_p]),
+    'st_resample_kaiser_host': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'st_fill_f32': (c_int, [c_void_p, c_float, c_size_t, c_void_p]),
     'st_zero_halos_f32': (c_int, [_T3P, c_void_p]),
     'st_zero_regions': (c_int, [c_void_p, c_int, c_void_p]),

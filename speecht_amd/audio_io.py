@@ -287,13 +287,83 @@ def resample_kaiser_best(y, sr_orig, sr_new):
   return out
 
 
+def resample_lengths(n, sr_orig, sr_new):
+  """(samples resample_kaiser_best produces, length after librosa's fix_length) for n samples at sr_orig -> sr_new, as the
+  float64 expressions of the host path compute them: int(n * ratio) and ceil(n * sr_new / sr_orig).  Equal rates: (n, n),
+  nothing is resampled.  (n * ratio is not exact for 22 050 / 16 000: the two are not one formula.)"""
+  if sr_orig == sr_new:
+    return n, n
+  return int(n * (float(sr_new) / float(sr_orig))), int(math.ceil(n * float(sr_new) / sr_orig))
+
+
+def plan_resample(lengths, rates, sr_new):
+  """Output layout of a resampling batch: (out_offsets int64 [n + 1], valid int64 [n]).  Utterance u fills
+  [out_offsets[u], out_offsets[u + 1]) -- its fix_length target -- with valid[u] interpolated samples, then zeros."""
+  n_out, target = zip(*(resample_lengths(int(n), int(sr), sr_new) for n, sr in zip(lengths, rates))) if len(lengths) else ((), ())
+  offsets = np.zeros(len(lengths) + 1, dtype=np.int64)
+  offsets[1:] = np.cumsum(np.asarray(target, dtype=np.int64))
+  return offsets, np.minimum(np.asarray(n_out, dtype=np.int64), np.asarray(target, dtype=np.int64))
+
+
+_device_filters = {}
+
+
+def _device_filter(dev):
+  """The kaiser_best window as a float64 device tensor, uploaded once per device."""
+  import torch
+  key = str(dev)
+  if key not in _device_filters:
+    win, _ = _kaiser_best_filter()
+    _device_filters[key] = torch.as_tensor(np.ascontiguousarray(win, dtype=np.float64)).to(dev)
+  return _device_filters[key]
+
+
+def resample_kaiser_best_device(signals, rates, sr_new, device='cuda:0'):
+  """resample_kaiser_best + fix_length (what librosa_load does after decoding) for a batch of float32 mono signals of their
+  own source rates, in one launch of st_resample_kaiser_f32.  Returns (device float32 buffer of the concatenated outputs,
+  out_offsets int64 [n + 1] on the host); the buffer is ready on the current stream of ``device``.  A signal already at
+  ``sr_new`` is copied unchanged."""
+  import ctypes
+  import torch
+  from . import _lib
+  dev = torch.device(device)
+  lens = np.array([len(s) for s in signals], dtype=np.int64)
+  if len(lens) == 0:
+    raise ValueError('resample_kaiser_best_device: no signals')
+  rates = np.asarray(rates, dtype=np.int64)
+  if rates.shape != lens.shape or rates.min() <= 0 or int(sr_new) <= 0 or rates.max() >= 2 ** 31:
+    raise ValueError('resample_kaiser_best_device: one positive rate per signal expected, got {}'.format(rates.tolist()))
+  out_offsets, valid = plan_resample(lens, rates, int(sr_new))
+  in_offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+  audio = torch.as_tensor(np.concatenate([np.asarray(s, dtype=np.float32) for s in signals])).to(dev)
+  meta = torch.as_tensor(np.concatenate([in_offsets, out_offsets, valid])).to(dev)
+  d_rates = torch.as_tensor(rates.astype(np.int32)).to(dev)
+  n = len(lens)
+  total = int(out_offsets[-1])
+  out = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+  win = _device_filter(dev)
+  P = lambda t: ctypes.c_void_p(t.data_ptr())
+  base = meta.data_ptr()
+  _lib.call('st_resample_kaiser_f32', P(audio), ctypes.c_void_p(base), n, P(d_rates), int(sr_new),
+            ctypes.c_void_p(base + 8 * (n + 1)), ctypes.c_void_p(base + 16 * (n + 1)), total, P(win), win.numel(), P(out),
+            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+  return out[:total], out_offsets
+
+
+def resample_kaiser_best_batch(signals, rates, sr_new, device='cuda:0'):
+  """resample_kaiser_best_device, read back: a list of float32 arrays (librosa_load's resampled signals)."""
+  out, offsets = resample_kaiser_best_device(signals, rates, sr_new, device)
+  host = out.cpu().numpy()
+  return [host[offsets[i]:offsets[i + 1]] for i in range(len(signals))]
+
+
 def librosa_load(path, sr=22050):
   """``librosa.load(path)`` as the reference calls it (preprocessing.py:169): decode, mono, resample to
   ``sr`` (None keeps the native rate), float32 in [-1, 1).  FLAC only; see preprocessing.load_audio for wav."""
   samples, rate, bps = decode_flac(path)
   y = samples.astype(np.float64).mean(axis=1) / float(1 << (bps - 1))
   if sr is not None and sr != rate:
-    target = int(math.ceil(y.shape[0] * float(sr) / rate))             # librosa: fix_length(resampled, ceil(n * ratio))
+    target = resample_lengths(y.shape[0], rate, sr)[1]
     z = resample_kaiser_best(y, rate, sr)
     y = np.concatenate([z, np.zeros(max(0, target - z.shape[0]))])[:target]
     rate = sr

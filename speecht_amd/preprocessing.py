@@ -41,29 +41,48 @@ def mel_filterbank(samplerate, n_fft, n_mels):
 def calc_power_spectrogram_batch(audio_list, samplerate, n_mels=128, n_fft=512, hop_length=160, device='cuda:0'):
   """Features for several utterances in one launch pair; returns a list of [time, n_mels] float32
   arrays.  Utterances are concatenated in HBM; no padding, no per-utterance launches."""
+  audio, s_off = _upload_audio(audio_list, device)
+  return power_spectrogram_device(audio, s_off, samplerate, n_mels, n_fft, hop_length)
+
+
+def _upload_audio(audio_list, device):
   import torch
-  from . import _lib
-  dev = torch.device(device)
   lens = np.array([len(a) for a in audio_list], dtype=np.int64)
+  s_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+  audio = torch.as_tensor(np.concatenate([np.asarray(a, dtype=np.float32) for a in audio_list])).to(torch.device(device))
+  return audio, s_off
+
+
+def _frame_plan(sample_offsets, n_fft, hop_length):
+  lens = np.diff(np.asarray(sample_offsets, dtype=np.int64))
   if lens.min() <= n_fft // 2:
     raise ValueError('utterances must be longer than n_fft/2 samples (reflect padding)')
-  s_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-  frames = 1 + lens // hop_length
-  f_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+  f_off = np.concatenate([[0], np.cumsum(1 + lens // hop_length)]).astype(np.int64)
+  return lens, f_off
+
+
+def power_spectrogram_device(audio, sample_offsets, samplerate, n_mels=128, n_fft=512, hop_length=160):
+  """calc_power_spectrogram_batch on audio already in HBM: ``audio`` a float32 device tensor holding the concatenated
+  utterances, utterance i at [sample_offsets[i], sample_offsets[i + 1]) (host int64 array; the layout
+  audio_io.resample_kaiser_best_device returns).  Only the [time, n_mels] features come back to the host."""
+  import torch
+  from . import _lib
+  dev = audio.device
+  lens, f_off = _frame_plan(sample_offsets, n_fft, hop_length)
+  s_off = np.asarray(sample_offsets, dtype=np.int64)
   total = int(f_off[-1])
-  audio = torch.as_tensor(np.concatenate([np.asarray(a, dtype=np.float32) for a in audio_list])).to(dev)
   basis = torch.as_tensor(mel_filterbank(float(samplerate), n_fft, n_mels).astype(np.float32)).contiguous().to(dev)
   d_soff, d_foff = torch.as_tensor(s_off).to(dev), torch.as_tensor(f_off).to(dev)
   out = torch.empty(total * n_mels, dtype=torch.float32, device=dev)
   lib = _lib.load()
-  ws_bytes = lib.st_melspec_ws(len(audio_list), total, n_mels)
+  ws_bytes = lib.st_melspec_ws(len(lens), total, n_mels)
   ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
   P = lambda t: ctypes.c_void_p(t.data_ptr())
-  _lib.call('st_melspec_f32', P(audio), P(d_soff), len(audio_list), int(lens.max()), P(basis), n_mels, n_fft,
+  _lib.call('st_melspec_f32', P(audio), P(d_soff), len(lens), int(lens.max()), P(basis), n_mels, n_fft,
             hop_length, P(d_foff), total, P(out), P(ws), ws.numel() * 4,
             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
   host = out.view(total, n_mels).cpu().numpy()
-  return [host[f_off[i]:f_off[i + 1]] for i in range(len(audio_list))]
+  return [host[f_off[i]:f_off[i + 1]] for i in range(len(lens))]
 
 
 def normalize(values):
@@ -81,28 +100,31 @@ def calc_power_spectrogram(audio_data, samplerate, n_mels=128, n_fft=512, hop_le
 def calc_mfccs_batch(audio_list, samplerate, n_mfcc=13, n_fft=512, hop_length=160, device='cuda:0'):
   """MFCC + delta + delta-delta features for several utterances in one launch sequence; returns a list
   of [time, 3 * n_mfcc] float32 arrays (each block z-normalised per utterance)."""
+  audio, s_off = _upload_audio(audio_list, device)
+  return mfccs_device(audio, s_off, samplerate, n_mfcc, n_fft, hop_length)
+
+
+def mfccs_device(audio, sample_offsets, samplerate, n_mfcc=13, n_fft=512, hop_length=160):
+  """calc_mfccs_batch on audio already in HBM (the layout of power_spectrogram_device); only the [time, 3 * n_mfcc]
+  features come back to the host."""
   import torch
   from . import _lib
   n_mels = 128                                   # librosa.feature.mfcc's melspectrogram default
-  dev = torch.device(device)
-  lens = np.array([len(a) for a in audio_list], dtype=np.int64)
-  if lens.min() <= n_fft // 2:
-    raise ValueError('utterances must be longer than n_fft/2 samples (reflect padding)')
-  s_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-  f_off = np.concatenate([[0], np.cumsum(1 + lens // hop_length)]).astype(np.int64)
+  dev = audio.device
+  lens, f_off = _frame_plan(sample_offsets, n_fft, hop_length)
+  s_off = np.asarray(sample_offsets, dtype=np.int64)
   total = int(f_off[-1])
-  audio = torch.as_tensor(np.concatenate([np.asarray(a, dtype=np.float32) for a in audio_list])).to(dev)
   basis = torch.as_tensor(mel_filterbank(float(samplerate), n_fft, n_mels).astype(np.float32)).contiguous().to(dev)
   d_soff, d_foff = torch.as_tensor(s_off).to(dev), torch.as_tensor(f_off).to(dev)
   out = torch.empty(total * 3 * n_mfcc, dtype=torch.float32, device=dev)
-  ws_bytes = _lib.load().st_mfcc_ws(len(audio_list), total, n_mels, n_mfcc)
+  ws_bytes = _lib.load().st_mfcc_ws(len(lens), total, n_mels, n_mfcc)
   ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
   P = lambda t: ctypes.c_void_p(t.data_ptr())
-  _lib.call('st_mfcc_f32', P(audio), P(d_soff), len(audio_list), int(lens.max()), P(basis), n_mels, n_mfcc, n_fft,
+  _lib.call('st_mfcc_f32', P(audio), P(d_soff), len(lens), int(lens.max()), P(basis), n_mels, n_mfcc, n_fft,
             hop_length, P(d_foff), total, P(out), P(ws), ws.numel() * 4,
             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
   host = out.view(total, 3 * n_mfcc).cpu().numpy()
-  return [host[f_off[i]:f_off[i + 1]] for i in range(len(audio_list))]
+  return [host[f_off[i]:f_off[i + 1]] for i in range(len(lens))]
 
 
 def calc_mfccs(audio_data, samplerate, n_mfcc=13, n_fft=512, hop_length=160):
@@ -163,17 +185,30 @@ class SpeechCorpusReader:
       audio_id = self._extract_audio_id(path)
       yield audio_id, preprocess_fnc(samples, rate), self._transcript_dict[audio_id]
 
-  def store_samples(self, directory, preprocess_fnc, audio_loader=None, pattern='*.flac', batch=32):
+  def store_samples(self, directory, preprocess_fnc, audio_loader=None, pattern='*.flac', batch=32, device_resample=False,
+                    device='cuda:0'):
     """Preprocess every audio file of ``<data>/<directory>`` and cache it as .npz.  The device
     extractor processes ``batch`` utterances per launch instead of the reference's process pool
-    (preprocessing.py:229-241)."""
+    (preprocessing.py:229-241).  ``device_resample``: decode each chunk at its native rate (``audio_loader`` is not used),
+    then resample it to what ``load_audio`` delivers (FLAC: 22 050 Hz; wav / npy: their own rate) and compute the features on
+    ``device`` in one batch."""
     if audio_loader is None:
       audio_loader = load_audio
+    if device_resample and preprocess_fnc not in (calc_power_spectrogram, calc_mfccs):
+      raise ValueError('device_resample computes calc_power_spectrogram or calc_mfccs features only')
     out_directory = self._get_directory(preprocess_fnc, directory)
     os.makedirs(out_directory, exist_ok=True)
     files = list(iglob_recursive(self._data_directory + '/' + directory, pattern))
     for i in range(0, len(files), batch):
       chunk = files[i:i + batch]
+      if device_resample:
+        from . import transcription
+        loaded = [transcription.load_native(f) for f in chunk]
+        feats = transcription.device_features([a for a, _ in loaded], [sr for _, sr in loaded],
+                                              'power' if preprocess_fnc == calc_power_spectrogram else 'mfcc',
+                                              LIBROSA_RATE if pattern.endswith('.flac') else 'native', device)
+        self._store(out_directory, chunk, feats)
+        continue
       loaded = [audio_loader(f) for f in chunk]
       rates = {sr for _, sr in loaded}
       if preprocess_fnc == calc_power_spectrogram and len(rates) == 1:
@@ -182,9 +217,12 @@ class SpeechCorpusReader:
         feats = calc_mfccs_batch([a for a, _ in loaded], rates.pop())
       else:
         feats = [preprocess_fnc(a, sr) for a, sr in loaded]
-      for f, feat in zip(chunk, feats):
-        audio_id = self._extract_audio_id(f)
-        np.savez(out_directory + '/' + audio_id, audio_fragments=feat, transcript=self._transcript_dict[audio_id])
+      self._store(out_directory, chunk, feats)
+
+  def _store(self, out_directory, chunk, feats):
+    for f, feat in zip(chunk, feats):
+      audio_id = self._extract_audio_id(f)
+      np.savez(out_directory + '/' + audio_id, audio_fragments=feat, transcript=self._transcript_dict[audio_id])
 
   def load_samples(self, directory, max_size=False, loop_infinitely=False, limit_count=0, feature_type='mfcc', shuffle_seed=None):
     """Iterator over (audio_fragments, transcript), same semantics as preprocessing.py:243-279.
@@ -212,6 +250,9 @@ class SpeechCorpusReader:
       if not loop_infinitely:
         break
       shuffle(files)
+
+
+LIBROSA_RATE = 22050          # librosa.load's default rate: what load_audio resamples FLAC to
 
 
 def load_audio(path):
@@ -266,4 +307,6 @@ class Preprocessing:
           continue
         print('Preprocessing {} data'.format(title))
         for pattern in self.AUDIO_PATTERNS:
-          corpus_reader.store_samples(split, preprocess_fnc, audio_loader=load_audio, pattern=pattern)
+          corpus_reader.store_samples(split, preprocess_fnc, audio_loader=load_audio, pattern=pattern,
+                                      device_resample=getattr(self.flags, 'device_resample', False),
+                                      device=getattr(self.flags, 'device', 'cuda:0'))

@@ -1,0 +1,185 @@
+"""Audio files to text: `speecht-cli transcribe` and its Python API.
+
+Decoding the container stays on the host (audio_io: FLAC / 16-bit wav / npy, at the file's own rate).  Everything after it
+runs on the device: librosa.load's resampling to the model's rate (the kaiser_best kernel, audio_io.resample_kaiser_best_device),
+the features (power spectrogram or MFCCs, preprocessing.power_spectrogram_device / mfccs_device), the network and the decoder
+(inference.transcribe) -- the audio goes to the device once and only the features come back.
+
+Batch semantics: nothing in the network is masked, so the logits near an utterance's end depend on the padded length of the
+batch it is in.  The default ``batch_size=1`` runs every file as one [1, T, C] batch without padding -- what the reference's
+`record` does with its single utterance.  ``batch_size > 1`` buckets files by length for throughput; transcripts near the ends
+of the shorter files of a bucket may then differ from the ``batch_size=1`` ones.
+"""
+import contextlib
+import json
+import os
+import sys
+import time
+
+from . import audio_io, inference, preprocessing
+
+AUDIO_EXTENSIONS = ('.flac', '.wav')          # what a directory is searched for
+FEATURE_WIDTH = {'power': 128, 'mfcc': 39}
+N_FFT = 512
+FEATURE_BATCH = 64                            # utterances per resample + feature launch sequence
+
+
+class TranscriptionError(ValueError):
+  """A file that cannot be transcribed: unreadable, or too short for the features."""
+
+
+def expand_paths(paths):
+  """PATH arguments -> audio files in order: a file stays as given, a directory becomes its *.flac and *.wav files, searched
+  recursively, in sorted order."""
+  files = []
+  for p in paths:
+    if os.path.isdir(p):
+      found = []
+      for root, _, names in os.walk(p):
+        found += [os.path.join(root, n) for n in names if os.path.splitext(n)[1].lower() in AUDIO_EXTENSIONS]
+      files += sorted(found)
+    else:
+      files.append(p)
+  return files
+
+
+def load_native(path):
+  """(float32 mono samples, native rate): preprocessing.load_audio without the host resampler."""
+  if not os.path.isfile(path):
+    raise TranscriptionError('{}: no such file'.format(path))
+  ext = os.path.splitext(path)[1].lower()
+  try:
+    if ext == '.flac':
+      return audio_io.librosa_load(path, sr=None)
+    if ext in ('.wav', '.npy'):
+      return preprocessing.load_audio(path)
+  except Exception as e:                      # a corrupt file is reported with its path; the other files go on
+    raise TranscriptionError('{}: cannot decode: {}'.format(path, e)) from e
+  raise TranscriptionError('{}: unsupported audio file type {} (expected .flac, 16-bit .wav or .npy)'.format(
+      path, ext or '(none)'))
+
+
+def _target_rate(rate, sample_rate):
+  return rate if sample_rate in (None, 'native') else int(sample_rate)
+
+
+def check_length(n, rate, sample_rate, name='utterance'):
+  """Raise TranscriptionError if n samples at ``rate`` are too short for the features after resampling (<= n_fft / 2)."""
+  target = _target_rate(rate, sample_rate)
+  length = audio_io.resample_lengths(int(n), int(rate), target)[1]
+  if length <= N_FFT // 2:
+    raise TranscriptionError('{}: too short: {} samples at {} Hz (the features need more than {})'.format(
+        name, length, target, N_FFT // 2))
+
+
+def device_features(signals, rates, feature_type='power', sample_rate=22050, device='cuda:0'):
+  """Features of float32 mono signals at their own rates: resampled to ``sample_rate`` (None / 'native': kept at their own
+  rate) and turned into [T, 128] power spectrograms or [T, 39] MFCCs on the device, FEATURE_BATCH signals per launch
+  sequence (signals of one target rate share a launch).  Returns a list of host arrays in input order."""
+  if feature_type not in FEATURE_WIDTH:
+    raise ValueError('feature_type must be power or mfcc, got {!r}'.format(feature_type))
+  extract = preprocessing.power_spectrogram_device if feature_type == 'power' else preprocessing.mfccs_device
+  for i, (s, r) in enumerate(zip(signals, rates)):
+    check_length(len(s), r, sample_rate, 'utterance {}'.format(i))
+  targets = [_target_rate(r, sample_rate) for r in rates]
+  feats = [None] * len(signals)
+  for target in sorted(set(targets)):
+    idx = [i for i, t in enumerate(targets) if t == target]
+    for k in range(0, len(idx), FEATURE_BATCH):
+      part = idx[k:k + FEATURE_BATCH]
+      audio, offsets = audio_io.resample_kaiser_best_device([signals[i] for i in part], [rates[i] for i in part], target, device)
+      for i, f in zip(part, extract(audio, offsets, target)):
+        feats[i] = f
+  return feats
+
+
+def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=22050, batch_size=1, **decode):
+  """Transcribe float32 mono signals in [-1, 1] at the given source rates -> (list of id lists, list of strings).
+
+  Resampling (to ``sample_rate``, default 22 050 Hz as librosa.load; None or 'native' keeps each signal's rate) and the
+  features run on the engine's device; the features must match the engine's input width (power: 128, mfcc: 39).
+  ``decode``: inference.transcribe's decoding arguments -- none (greedy), ``beam_width``, or ``language_model`` with
+  ``lm_options``.
+
+  ``batch_size=1`` (default): every signal is one [1, T, C] batch without padding, the semantics of the reference's `record`.
+  ``batch_size > 1``: signals are bucketed by length into padded batches for throughput; nothing in the network is masked,
+  so transcripts near the ends of the shorter signals of a batch may differ from the ``batch_size=1`` ones."""
+  feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
+  return inference.transcribe(engine, feats, batch_size=batch_size, **decode)
+
+
+def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, **decode):
+  """Transcribe audio files (.flac, 16-bit .wav, .npy taken as 16 kHz) -> a list, in ``paths`` order, of dicts
+  {path, seconds, text, ids, error}: ``error`` is the message for a file that cannot be read or is too short (its text and
+  ids are None); the other files are transcribed as transcribe_audio does (same arguments, same batch semantics).
+  ``timings``: a dict that receives the seconds spent in host decoding ('decode_host'), resampling and features
+  ('features') and the network with the decoder ('transcribe')."""
+  results = []
+  signals, rates, ok = [], [], []
+  t0 = time.perf_counter()
+  for path in paths:
+    entry = dict(path=path, seconds=None, text=None, ids=None, error=None)
+    results.append(entry)
+    try:
+      samples, rate = load_native(path)
+      entry['seconds'] = len(samples) / float(rate)
+      check_length(len(samples), rate, sample_rate, path)
+    except TranscriptionError as e:
+      entry['error'] = str(e)
+      continue
+    signals.append(samples)
+    rates.append(rate)
+    ok.append(entry)
+  t1 = time.perf_counter()
+  if ok:
+    feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
+    t2 = time.perf_counter()
+    ids, texts = inference.transcribe(engine, feats, batch_size=batch_size, **decode)
+    for entry, i, t in zip(ok, ids, texts):
+      entry['ids'], entry['text'] = i, t
+  else:
+    t2 = t1
+  if timings is not None:
+    timings.update(decode_host=t1 - t0, features=t2 - t1, transcribe=time.perf_counter() - t2)
+  return results
+
+
+def run_cli(flags):
+  """`speecht-cli transcribe`: prints path<TAB>transcript per file in input order (and JSON lines to --output); a file that
+  cannot be transcribed is reported on stderr and makes the exit status 1.  Creates no train / data / log directory."""
+  from .speech_input import SingleInputLoader
+  from .speech_model import Session, create_default_model
+  paths = expand_paths(flags.paths)
+  if not paths:
+    print('transcribe: no audio files found in {}'.format(' '.join(flags.paths)), file=sys.stderr)
+    return 1
+  input_size = FEATURE_WIDTH[flags.feature_type]
+  with contextlib.redirect_stdout(sys.stderr):          # stdout carries the transcripts only
+    model = create_default_model(flags, input_size, SingleInputLoader(input_size))
+  decode = {}
+  if model.language_model is not None:
+    decode = dict(language_model=model.language_model, beam_width=model.beam_width,
+                  lm_options=dict(input_transform=model.beam_input, lm_weight=model.lm_weight,
+                                  word_count_weight=model.word_count_weight,
+                                  valid_word_count_weight=model.valid_word_count_weight))
+  elif model.beam_width:
+    decode = dict(beam_width=model.beam_width)
+  with Session(flags.device) as sess:
+    with contextlib.redirect_stdout(sys.stderr):
+      model.restore(sess, flags.run_train_dir)          # FileNotFoundError('No checkpoint for evaluation found'), as evaluate
+    results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, **decode)
+  out = open(flags.output, 'w') if flags.output else None
+  status = 0
+  try:
+    for r in results:
+      if r['error'] is not None:
+        print('transcribe: {}'.format(r['error']), file=sys.stderr)
+        status = 1
+        continue
+      print('{}\t{}'.format(r['path'], r['text']), flush=True)
+      if out:
+        out.write(json.dumps(dict(path=r['path'], seconds=r['seconds'], text=r['text'])) + '\n')
+  finally:
+    if out:
+      out.close()
+  return status
