@@ -15,24 +15,13 @@ import numpy as np
 import pytest
 
 from oracle import w2l_oracle as O
+from tests import grad_parity as GP
 from tests import workloads as WL
 
 torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
-ULP = 2.0 ** -8
-
-
-def scaled_err(a, b):
-  s = float(np.max(np.abs(b))) + 1e-30
-  d = np.abs(np.asarray(a, np.float64) - b) / s
-  return float(d.max()), float(d.mean())
-
-
-def plane(t3, buf):
-  """[B,T,C] float64 copy of the valid region of a bf16 (or fp32) buffer laid out like the padded NWC tensor t3."""
-  v = buf.view(t3.batch, t3.t_pitch, t3.c_pitch)[:, t3.halo:t3.halo + t3.frames, :t3.channels]
-  return v.float().cpu().numpy().astype(np.float64)
+ULP, scaled_err = GP.ULP, GP.scaled_err
 
 
 def test_config3_rank_shard_bf16_training_step_vs_bf16_storage_oracle():
@@ -52,7 +41,7 @@ def test_config3_rank_shard_bf16_training_step_vs_bf16_storage_oracle():
   from speecht_amd.engine import Wav2LetterEngine
   layers = WL.w2l_layers(80)
   params = WL.xavier_params(layers, seed=42, dtype=np.float32)
-  B, L = 32, len(layers)
+  B = 32
   x, seq, labels = WL.make_batch([1001] * B, 80, seed=103)            # rank 3's shard of bench.py's global batch
   x = x.astype(np.float32)
   eng = Wav2LetterEngine(layers, device='cuda:0', conv_mode='bf16')
@@ -95,66 +84,8 @@ def test_config3_rank_shard_bf16_training_step_vs_bf16_storage_oracle():
     assert mxF < 64 * ULP and meanF < 8 * ULP and mxb < 64 * ULP, (i, mxF, meanF, mxb)
   del acts, ref_grads
 
-  # ---- kernel by kernel on the device's stored operands ----
-  # (a stored value is the fp32 accumulation rounded to bf16, the expectation the float64 one: where the exact value sits
-  # within ~1e-7 of a rounding boundary the two may land on neighbouring bf16 values -- one spacing, which in the top
-  # binade of the tensor is up to 2 ULP of the tensor's maximum; the mean bound says it is a handful of elements)
-  t0 = time.time()
-  Xs = [plane(eng.X[i], eng.Xb[i]) for i in range(L)]                 # stored bf16 inputs of every layer
-  dZs = [plane(eng.dZ[i], eng.dZb[i]) for i in range(L)]              # stored bf16 gradients wrt every layer's output
-  for i, ((F, b), (W, s, cin, cout, relu)) in enumerate(zip(p64, layers)):
-    if i in spectral:
-      # the frequency-domain layer against ITS storage model on the stored operands: spectra of the stored input, of the stored
-      # gradient and of the fp32 master filters rounded to bf16, everything else exact (an element of a spectrum within fp32
-      # rounding of a bf16 boundary may land on the other side than in float64: slightly looser means than the W-tap layers')
-      y, dx, dF, db = O.block_dft_conv(Xs[i], F, b, relu, dz=dZs[i], store=O.bf16_round)
-    else:
-      y = O.conv1d_same_fwd(Xs[i], O.bf16_round(F), b, s, relu)
-      dx, dF, db = O.conv1d_same_bwd(Xs[i], O.bf16_round(F), None, dZs[i], s, relu=False, need_dx=(i > 0))
-    mean_tol = 0.05 if i in spectral else 0.01
-    if i in spectral:
-      # ... and against the DIRECT form on the same stored operands (the storage model above must not define the
-      # accuracy loss of bf16 spectra away).  What bf16 spectra cost relative to the W-tap bf16 kernel, which rounds only its
-      # output: the oracle's two forms differ by max 1.5 / mean 0.06 ulp (forward), 1.5 / 0.12 ulp (back-prop) and 2.5e-3 of
-      # the maximum (filter gradient, 0.6 ulp) on random data of this layer's shape class; the bounds leave a factor ~3.
-      yd = O.conv1d_same_fwd(Xs[i], O.bf16_round(F), b, s, relu)
-      dxd, dFd, dbd = O.conv1d_same_bwd(Xs[i], O.bf16_round(F), None, dZs[i], s, relu=False, need_dx=True)
-      mx, mean = scaled_err(Xs[i + 1], O.bf16_round(yd))
-      print('spectral L%d vs DIRECT form: forward max %.2f ulp mean %.3f ulp' % (i, mx / ULP, mean / ULP))
-      assert mx <= 4 * ULP and mean < 0.25 * ULP, ('forward vs direct form', i, mx / ULP, mean / ULP)
-      dxm = dxd * (Xs[i] > 0) if layers[i - 1][4] else dxd
-      mx, mean = scaled_err(dZs[i - 1], O.bf16_round(dxm))
-      print('spectral L%d vs DIRECT form: back-prop max %.2f ulp mean %.3f ulp' % (i, mx / ULP, mean / ULP))
-      assert mx <= 4 * ULP and mean < 0.4 * ULP, ('back-prop vs direct form', i, mx / ULP, mean / ULP)
-      mxF, _ = scaled_err(grads[i][0], dFd)
-      mxb, _ = scaled_err(grads[i][1], dbd)
-      print('spectral L%d vs DIRECT form: filter gradient %.1e, bias gradient %.1e of max' % (i, mxF, mxb))
-      assert mxF < 8e-3 and mxb < 2e-4, ('filter/bias gradient vs direct form', i, mxF, mxb)
-      del yd, dxd, dFd, dxm
-    if i + 1 < L:
-      mx, mean = scaled_err(Xs[i + 1], O.bf16_round(y))
-      assert mx <= 2.01 * ULP and mean < mean_tol * ULP, ('forward', i, mx / ULP, mean / ULP)
-    else:
-      mx, _ = scaled_err(plane(eng.X[L], eng.X[L].buf), y)            # logits stay fp32
-      assert mx < 1e-5, ('logits from stored X10', mx)
-    # filter / bias gradient of layer i from its stored operands
-    mxF, _ = scaled_err(grads[i][0], dF)
-    mxb, _ = scaled_err(grads[i][1], db)
-    assert mxF < (1e-3 if i in spectral else 2e-4) and mxb < 2e-4, ('filter/bias gradient', i, mxF, mxb)
-    # gradient handed to the layer below: mask of the stored activation, rounded to bf16 when written
-    if i > 0:
-      if layers[i - 1][4]:
-        dx = dx * (Xs[i] > 0)
-      mx, mean = scaled_err(dZs[i - 1], O.bf16_round(dx))
-      assert mx <= 2.01 * ULP and mean < mean_tol * ULP, ('back-prop to the input', i, mx / ULP, mean / ULP)
-    print('kernel-level L%d ok (filters %.1e, bias %.1e of max)' % (i, mxF, mxb))
-  # the bf16 copy of d loss / d logits and the fp32 CTC gradient it was rounded from
-  mx, _ = scaled_err(dZs[L - 1], O.bf16_round(plane(eng.dZ[L - 1], eng.dZ[L - 1].buf)))
-  assert mx == 0.0
-  dl_ref = np.transpose(O.ctc_loss_and_grad(got.astype(np.float64), labels, seq // 2)[1], (1, 0, 2)) / (8 * B)
-  mx, _ = scaled_err(plane(eng.dZ[L - 1], eng.dZ[L - 1].buf), dl_ref)
-  assert mx < 2e-4, mx
-  print('kernel-by-kernel checks on the stored operands: %.1f s' % (time.time() - t0))
+  # ---- kernel by kernel on the device's stored operands (tests/grad_parity.py) ----
+  GP.stored_operand_checks(eng, p64, layers, grads, labels, seq, 1.0 / (8 * B), spectral)
 
 
 def test_config4_rank_shard_long_form_forward_and_decoders():

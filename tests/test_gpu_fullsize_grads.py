@@ -9,12 +9,13 @@ The launch trace of the library is asserted so that the test cannot silently tak
 
 Tolerances: logits <= 1e-4 absolute, loss <= 1e-4 relative, d loss / d logits and every
 gradient tensor <= 2e-4 of its own max -- kernel by kernel on the device's operands AND end to end against an
-independent float64 evaluation with the ReLU pattern pinned to the device's (``compare``)."""
+independent float64 evaluation with the ReLU pattern pinned to the device's (``compare``, tests/grad_parity.py)."""
 import time
 
 import numpy as np
 import pytest
 
+from tests import grad_parity as GP
 from tests import torch_ref as TR
 from tests import workloads as WL
 
@@ -35,86 +36,10 @@ def case():
   t0 = time.time()
   ref = TR.loss_and_grads(x32, seq, labels, params, layers, dtype=torch.float64)
   print('float64 CPU reference of the full-size step: %.1f s' % (time.time() - t0))
-  return dict(layers=layers, params=params, x=x32, seq=seq, labels=labels, ref=ref)
+  return dict(GP.make_case(layers, params, x32, seq, labels), ref=ref)
 
 
-def run_step(case, mode, fft_conv=False):
-  from speecht_amd._lib import launch_trace
-  from speecht_amd.engine import Wav2LetterEngine
-  eng = Wav2LetterEngine(case['layers'], device='cuda:0', conv_mode=mode, fft_conv=fft_conv)
-  eng.set_weights(case['params'])
-  eng.load_batch(case['x'], case['seq'])
-  eng.set_labels(case['labels'])
-  with launch_trace() as tr:
-    eng.forward()
-    eng.ctc_loss_grad(1.0 / len(FRAMES))
-    eng.backward()
-  torch.cuda.synchronize()
-  eng.check_ctc_status()
-  return eng, tr.lines
-
-
-def rel_err(g, r):
-  return float(np.max(np.abs(g - r)) / np.max(np.abs(r)))
-
-
-def compare(eng, ref, case, grad_tol=2e-4):
-  """Three comparisons, from the most independent to the most exact:
-
-  1. logits, per-utterance losses and d avg_loss / d logits against the float64 autograd reference;
-  2. the BACKWARD KERNELS at full size: all 22 gradient tensors against float64 back-prop evaluated on the
-     device's own stored activations and its own dlogits (tests/torch_ref.backward_from_acts) -- the exact linear
-     map the kernels must reproduce, tolerance 2e-4 of each tensor's max;
-  3. END TO END, all 22 tensors at the same 2e-4: against a second float64 evaluation of the whole step (its own
-     forward activations from the inputs, its own CTC, autograd) whose ReLU pattern is pinned to the one the device
-     took (tests/torch_ref.loss_and_grads(relu_masks=...)).  The step has one discontinuity -- a ReLU input within
-     fp32 rounding of zero lands on the other side in float64 (1-10 of 4-32 million elements per layer; the flipped
-     unit's whole gradient appears or vanishes and the ill-conditioned lower layers amplify it) -- and pinning the
-     pattern removes exactly that and nothing else: the pinned pre-activations differ from the free ones by < 1e-6
-     at the flipped elements (asserted through the logits), every other number is independent of the device.
-     The un-pinned end-to-end figures are printed for the record."""
-  logits = eng.logits_time_major().cpu().numpy()
-  assert logits.shape == ref['logits'].shape == (501, 32, 29)
-  # frames beyond an utterance's own length are computed too (nothing is masked, SURVEY F7): compare all
-  err = float(np.max(np.abs(logits - ref['logits'])))
-  assert err < 1e-4, err
-  np.testing.assert_allclose(eng.loss.cpu().numpy(), ref['loss'], rtol=1e-4)
-  dl = eng.dZ[-1].interior().cpu().numpy().astype(np.float64)
-  dl_err = rel_err(dl, ref['dlogits'])
-  assert dl_err < 2e-4, dl_err
-  acts = [eng.X[i].interior().cpu().numpy() for i in range(len(eng.layers) + 1)]
-  flips = [int(np.sum((acts[i] > 0) != (ref['acts'][i] > 0))) for i in range(1, len(eng.layers))]   # ReLU outputs
-  got = eng.get_grads()
-  exact, _ = TR.backward_from_acts(acts, case['params'], case['layers'], dl)
-  t0 = time.time()
-  pinned = TR.loss_and_grads(case['x'], case['seq'], case['labels'], case['params'], case['layers'], dtype=torch.float64,
-                             relu_masks=TR.relu_masks_of(acts, case['layers']))
-  pin_secs = time.time() - t0
-  # the pinned evaluation is the same function as the free one except at the flipped units, whose pre-activations are
-  # within rounding of zero: logits and losses agree far below the parity tolerance
-  pin_shift = float(np.max(np.abs(pinned['logits'] - ref['logits'])))
-  assert pin_shift < 1e-5, pin_shift
-  assert float(np.max(np.abs(logits - pinned['logits']))) < 1e-4
-  np.testing.assert_allclose(eng.loss.cpu().numpy(), pinned['loss'], rtol=1e-4)
-  kernel_report, e2e_report, free_report, failed = [], [], [], []
-  for i, ((gF, gb), (xF, xb), (pF, pb), (rF, rb)) in enumerate(zip(got, exact, pinned['grads'], ref['grads'])):
-    for name, g, x, p, r in (('filters', gF, xF, pF, rF), ('bias', gb, xb, pb, rb)):
-      assert g.shape == x.shape == p.shape == r.shape
-      k, e, f = rel_err(g, x), rel_err(g, p), rel_err(g, r)
-      kernel_report.append('L%d %s %.1e' % (i, name, k))
-      e2e_report.append('L%d %s %.1e' % (i, name, e))
-      free_report.append('L%d %s %.1e' % (i, name, f))
-      if not k < grad_tol:
-        failed.append('kernel L%d %s %.2e' % (i, name, k))
-      if not e < grad_tol:
-        failed.append('end-to-end (ReLU pattern pinned) L%d %s %.2e' % (i, name, e))
-  print('dlogits error %.2e of max; ReLU sign flips vs float64 per layer output: %s' % (dl_err, flips))
-  print('backward kernels vs float64 back-prop on the device activations: ' + '; '.join(kernel_report))
-  print('end to end vs float64 autograd with the device\'s ReLU pattern (%.1f s, logits moved %.1e by the pinning): '
-        % (pin_secs, pin_shift) + '; '.join(e2e_report))
-  print('for the record, end to end vs the free float64 autograd (flipped units included): ' + '; '.join(free_report))
-  assert not failed, failed
-  return err, dl_err
+run_step, compare = GP.run_step, GP.compare
 
 
 def test_fullsize_fp32_gradients_match_float64_reference(case):
