@@ -413,6 +413,18 @@ int st_global_norm_clip_adam_gated_f32(float* params, const float* grads, float*
                                        float clip_norm, float lr_t, float beta1, float beta2, float eps,
                                        float* stats, const float* gate, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* Counted form: the number of updates applied lives on the device, so that a skipped update (gate, non-finite norm) can never
+ * advance the bias correction.  counts (device, 2 x uint32): counts[0] = updates applied so far, counts[1] = updates skipped
+ * because the global norm was not finite.  The update uses t = counts[0] + 1, lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+ * computed in double (the host formula, rounded to float once), and the moments use (float)beta1 / (float)beta2.  Afterwards
+ * counts[0] += 1 if the update was applied, counts[1] += 1 if the norm was not finite; a gated update moves neither.  stats
+ * (device, 3 floats, or NULL) receives {global_norm, scale, lr_t}; gate as in the gated form (NULL: ungated).  The update itself
+ * is the gated form's arithmetic: given the same lr_t, the two write the same bits.  Workspace: st_global_norm_ws(n) bytes (the
+ * other forms need NORM_BLOCKS floats of it only). */
+int st_global_norm_clip_adam_counted_f32(float* params, const float* grads, float* m, float* v, size_t n,
+                                         float clip_norm, double lr, double beta1, double beta2, float eps,
+                                         float* stats, const float* gate, uint32_t* counts, void* workspace,
+                                         size_t workspace_bytes, void* stream);
 /* norm only (stats[0] = ||g||, stats[1] = clip/max(norm,clip)); used for reporting */
 int st_global_norm_f32(const float* grads, size_t n, float clip_norm, float* stats,
                        void* workspace, size_t workspace_bytes, void* stream);

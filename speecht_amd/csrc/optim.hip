@@ -57,13 +57,16 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict
   }
 }
 
+// RATE_IN_MEMORY: lr_t is read from *lr_t_ptr (adam_rate_kernel wrote it there, on the device) instead of the argument.  Either
+// way it is one uniform value, and the arithmetic below is the same code: both forms give the same bits for the same lr_t.
+template <bool RATE_IN_MEMORY>
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
                                                         const float* __restrict__ partial, float clip, float lr_t_value,
                                                         float b1, float b2, float eps, float* __restrict__ stats,
-                                                        const float* __restrict__ gate) {
+                                                        const float* __restrict__ gate, const float* __restrict__ lr_t_ptr) {
   __shared__ float red[4];
-  const float lr_t = lr_t_value;
+  const float lr_t = RATE_IN_MEMORY ? *lr_t_ptr : lr_t_value;
   const float gn = sqrtf(total_sumsq(partial, red));
   const float scale = clip / fmaxf(gn, clip);
   if (blockIdx.x == 0 && threadIdx.x == 0 && stats) { stats[0] = gn; stats[1] = scale; }
@@ -97,6 +100,30 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
     m[i] = mm; v[i] = vv;
     p[i] -= lr_t * mm / (sqrtf(vv) + eps);
   }
+}
+
+// The counted form's rate, one thread ahead of clip_adam_kernel: update t = counts[0] + 1 at
+// lr * sqrt(1 - beta2^t) / (1 - beta1^t), in double like the host formula it replaces (tf.train.AdamOptimizer), rounded to float
+// once.  Written to the workspace slot behind the norm partials (and to stats[2] for the caller).
+__global__ void adam_rate_kernel(const uint32_t* __restrict__ counts, double lr, double b1, double b2, float* __restrict__ lr_t,
+                                 float* __restrict__ stats) {
+  if (threadIdx.x != 0) return;
+  const double t = (double)counts[0] + 1.0;
+  const float r = (float)(lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)));
+  lr_t[0] = r;
+  if (stats) stats[2] = r;
+}
+
+// The counted form's bookkeeping, one workgroup behind clip_adam_kernel: the same norm out of the same partials (same order, same
+// bits), the same two exits.  counts[0] += 1 when the update was applied, counts[1] += 1 when the norm was not finite; a gated
+// update (CTC rejected the batch) moves neither.
+__global__ __launch_bounds__(256) void adam_count_kernel(const float* __restrict__ partial, const float* __restrict__ gate,
+                                                         uint32_t* __restrict__ counts) {
+  __shared__ float red[4];
+  const float gn = sqrtf(total_sumsq(partial, red));
+  if (threadIdx.x != 0 || (gate && gate[0] != 0.f)) return;
+  if (gn <= 3.0e38f) counts[0] += 1u;
+  else counts[1] += 1u;
 }
 
 // gate[0] = number of utterances CTC refused; with `loss_hi`: gate[1] = sum_b (hi_b + lo_b) * loss_scale, summed in double in a
@@ -137,11 +164,12 @@ int st_ctc_status_gate_loss_f32(const int32_t* status, int batch, const float* l
   return st::check_launch("status_gate_loss");
 }
 
-size_t st_global_norm_ws(size_t n) { (void)n; return NORM_BLOCKS * sizeof(float); }
+// the norm partials, then (counted form) a slot for the rate; the other forms need the partials only
+size_t st_global_norm_ws(size_t n) { (void)n; return (NORM_BLOCKS + 64) * sizeof(float); }
 
 int st_global_norm_f32(const float* grads, size_t n, float clip_norm, float* stats, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(grads && stats && workspace && workspace_bytes >= st_global_norm_ws(n), "global_norm: bad args");
+  ST_REQUIRE(grads && stats && workspace && workspace_bytes >= NORM_BLOCKS * sizeof(float), "global_norm: bad args");
   ST_REQUIRE(((uintptr_t)grads & 15) == 0, "global_norm: buffer must be 16-byte aligned");
   hipStream_t s = st::as_stream(stream);
   float* partial = reinterpret_cast<float*>(workspace);
@@ -160,16 +188,34 @@ int st_global_norm_clip_adam_f32(float* params, const float* grads, float* m, fl
 int st_global_norm_clip_adam_gated_f32(float* params, const float* grads, float* m, float* v, size_t n, float clip_norm,
                                        float lr_t, float beta1, float beta2, float eps, float* stats, const float* gate,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(params && grads && m && v && workspace && workspace_bytes >= st_global_norm_ws(n), "clip_adam: bad args");
+  ST_REQUIRE(params && grads && m && v && workspace && workspace_bytes >= NORM_BLOCKS * sizeof(float), "clip_adam: bad args");
   ST_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
              "clip_adam: buffers must be 16-byte aligned");
   hipStream_t s = st::as_stream(stream);
   float* partial = reinterpret_cast<float*>(workspace);
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(NORM_BLOCKS), dim3(256), 0, s, grads, n, partial);
   const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n / 4 + 255) / 256, 2048));
-  hipLaunchKernelGGL(clip_adam_kernel, dim3(blocks), dim3(256), 0, s, params, grads, m, v, n, partial, clip_norm,
-                     lr_t, beta1, beta2, eps, stats, gate);
+  hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(blocks), dim3(256), 0, s, params, grads, m, v, n, partial, clip_norm,
+                     lr_t, beta1, beta2, eps, stats, gate, (const float*)nullptr);
   return st::check_launch("clip_adam");
+}
+
+int st_global_norm_clip_adam_counted_f32(float* params, const float* grads, float* m, float* v, size_t n, float clip_norm,
+                                         double lr, double beta1, double beta2, float eps, float* stats, const float* gate,
+                                         uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(params && grads && m && v && counts && workspace && workspace_bytes >= st_global_norm_ws(n), "clip_adam_counted: bad args");
+  ST_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
+             "clip_adam_counted: buffers must be 16-byte aligned");
+  hipStream_t s = st::as_stream(stream);
+  float* partial = reinterpret_cast<float*>(workspace);
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3(NORM_BLOCKS), dim3(256), 0, s, grads, n, partial);
+  const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n / 4 + 255) / 256, 2048));
+  float* rate = partial + NORM_BLOCKS;                 // (st_global_norm_ws: one slot behind the partials)
+  hipLaunchKernelGGL(adam_rate_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)counts, lr, beta1, beta2, rate, stats);
+  hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(blocks), dim3(256), 0, s, params, grads, m, v, n, partial, clip_norm, 0.f,
+                     (float)beta1, (float)beta2, eps, stats, gate, (const float*)rate);
+  hipLaunchKernelGGL(adam_count_kernel, dim3(1), dim3(256), 0, s, partial, gate, counts);
+  return st::check_launch("clip_adam_counted");
 }
 
 }  // extern "C"

@@ -82,10 +82,17 @@ class Wav2LetterEngine(DecodeMixin):
     self.packed_t = [None] + [torch.zeros(l.kt_pad * l.nt_pad, dtype=torch.float32, device=self.device)
                               for l in self.layers[1:]]
     self._packed_t_fresh = False
-    self.stats = torch.zeros(2, dtype=torch.float32, device=self.device)
+    # the update's device words: stats {global norm, clip scale, lr_t} and the update counts {applied, skipped because the norm
+    # was not finite} (st_global_norm_clip_adam_counted_f32) -- one buffer, so that the loss read-back brings them with one copy
+    self._update_words = torch.zeros(8, dtype=torch.int32, device=self.device)
+    self.stats = self._update_words[:4].view(torch.float32)
+    self.update_counts = self._update_words[4:6]
     self.norm_ws = torch.zeros(_lib.load().st_global_norm_ws(self.n_flat) // 4, dtype=torch.float32,
                                device=self.device)
-    self.step_count = 0
+    # host mirrors of the update counts, and how many updates were enqueued in all / before the last read-back of the counts
+    self._applied_seen, self.updates_skipped, self.last_skip_norm = 0, 0, None
+    self._updates_enqueued, self._updates_covered, self._count_version = 0, 0, 0
+    self._tuning_epoch = _lib.TUNING_EPOCH[0]
     self._shape = None
     self._storage = _Storage(self.device)
     self.ctc_ws = None
@@ -160,7 +167,45 @@ class Wav2LetterEngine(DecodeMixin):
     self.step_count = int(step)
 
   def get_adam_state(self):
+    self.sync_update_counts()
     return self._unpack(self.adam_m), self._unpack(self.adam_v)
+
+  # ---- the number of updates applied -------------------------------------------------------------------------------
+  # It lives on the device (`update_counts`), next to the gate: the update kernel takes its bias correction from it and counts only
+  # the updates it really applies -- a batch CTC rejected or a gradient whose global norm is not finite leaves it where it was.  The
+  # host reads it back with the losses (`fetch_losses_begin`: no wait of its own) and, when updates have been enqueued since that
+  # read-back, on demand (`sync_update_counts`, which waits for the stream).
+
+  @property
+  def step_count(self):
+    """Updates applied so far (Adam's t of the last one).  Waits for the device when an update is still unaccounted for."""
+    if self._updates_covered != self._updates_enqueued:
+      self.sync_update_counts()
+    return self._applied_seen
+
+  @step_count.setter
+  def step_count(self, value):
+    """Sets the device count (ordered behind whatever the stream holds) and its mirror."""
+    stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+    with torch.cuda.stream(stream):
+      self.update_counts[:1].fill_(int(value))
+    self._applied_seen = int(value)
+    self._updates_covered = self._updates_enqueued
+    self._count_version += 1                       # (a read-back enqueued before this write must not overwrite the mirror)
+
+  def sync_update_counts(self):
+    """Read the update counts (and the last update's norm) back now: waits for everything enqueued on the engine's stream."""
+    stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+    with torch.cuda.stream(stream):
+      words = self._update_words.cpu()
+    self._updates_covered = self._updates_enqueued
+    self._take_update_words(words)
+
+  def _take_update_words(self, words):
+    applied, skipped = int(words[4]), int(words[5])
+    if skipped != self.updates_skipped:
+      self.last_skip_norm = float(words[:1].view(torch.float32)[0])
+    self._applied_seen, self.updates_skipped = applied, skipped
 
   def mark_weights_changed(self):
     """Call after writing ``self.params`` directly: derived operand copies are rebuilt on next use."""
@@ -270,6 +315,16 @@ class Wav2LetterEngine(DecodeMixin):
                                   mode=self.mode.shape_token())
 
   def _ensure_shape(self, batch, frames):
+    epoch = _lib.TUNING_EPOCH[0]
+    if epoch != self._tuning_epoch:
+      # a knob was flipped (set_tuning): the knobs choose operand layouts (no_g3: the filter spectra's planes) and policies that
+      # may size workspaces, so the current shape is described anew (cached descriptions are keyed by the epoch) and every operand
+      # derived from the weights is rebuilt, whatever its buffer's size says
+      self._tuning_epoch = epoch
+      self._shape = None
+      self.mark_weights_changed()
+      self.__dict__.pop('_fft_table_key', None)
+      self.__dict__.pop('_fftb_table_key', None)
     if self._shape == (batch, frames):
       return
     if self._reenter_shape(batch, frames):
@@ -577,12 +632,6 @@ class Wav2LetterEngine(DecodeMixin):
     wanted = (lambda i: True) if hook_layers is None else (lambda i: i in hook_layers)
     return self.mode.backward(on_layer_done, wanted)
 
-  def _adam_rate(self, lr, beta1, beta2):
-    """The bias-corrected rate of the NEXT update (tf.train.AdamOptimizer: lr * sqrt(1 - beta2^t) / (1 - beta1^t)); counts it."""
-    self.step_count += 1
-    t = self.step_count
-    return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-
   def _refresh_after_update(self):
     """The operands the NEXT forward pass derives from the weights: filter spectra of the frequency-domain layers / the bf16 filter
     copies -- the bottom layer's on the compute stream, the others on the side stream with an event each."""
@@ -590,14 +639,14 @@ class Wav2LetterEngine(DecodeMixin):
       self.mode.refresh_after_update()
 
   def apply_update(self, lr, max_grad_norm=5.0, beta1=0.9, beta2=0.999, eps=1e-3):
-    """clip_by_global_norm + tf.train.AdamOptimizer(epsilon=1e-3) (speech_model.py:77-82)."""
-    lr_t = self._adam_rate(lr, beta1, beta2)
-    # gated on the device: a step whose batch CTC rejected (on any rank) leaves params / m / v untouched
-    call('st_global_norm_clip_adam_gated_f32', self._ptr(self.params), self._ptr(self.grads), self._ptr(self.adam_m),
-         self._ptr(self.adam_v), self.n_flat, float(max_grad_norm), float(lr_t), beta1, beta2, eps,
-         self._ptr(self.stats), self._ptr(self.gate), self._ptr(self.norm_ws), self.norm_ws.numel() * 4,
-         self.stream_ptr)
-    self._updates_in_flight = getattr(self, '_updates_in_flight', 0) + 1
+    """clip_by_global_norm + tf.train.AdamOptimizer(epsilon=1e-3) (speech_model.py:77-82).  The bias correction's t is 1 + the
+    device's count of updates applied; a step whose batch CTC rejected (on any rank) or whose global norm is not finite leaves
+    params / m / v and that count untouched (the latter is counted in ``updates_skipped`` once read back)."""
+    call('st_global_norm_clip_adam_counted_f32', self._ptr(self.params), self._ptr(self.grads), self._ptr(self.adam_m),
+         self._ptr(self.adam_v), self.n_flat, float(max_grad_norm), float(lr), float(beta1), float(beta2), eps,
+         self._ptr(self.stats), self._ptr(self.gate), self._ptr(self.update_counts), self._ptr(self.norm_ws),
+         self.norm_ws.numel() * 4, self.stream_ptr)
+    self._updates_enqueued += 1
     self.mark_weights_changed()
     self._refresh_after_update()
 
@@ -620,8 +669,8 @@ class Wav2LetterEngine(DecodeMixin):
     if not hasattr(self, '_loss_host') or self._loss_host[0].numel() < 2 * B:
       self._loss_host = (torch.empty(max(2 * B, 128), dtype=torch.float32, pin_memory=True),
                          torch.empty(max(B, 64), dtype=torch.int32, pin_memory=True), torch.cuda.Event(),
-                         torch.empty(16, dtype=torch.float32, pin_memory=True))
-    loss_h, status_h, event, gate_h = self._loss_host
+                         torch.empty(16, dtype=torch.float32, pin_memory=True), torch.empty(8, dtype=torch.int32, pin_memory=True))
+    loss_h, status_h, event, gate_h, words_h = self._loss_host
     if stream is None:
       stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
     lost_h = self._streamk_lost_async(stream)
@@ -629,22 +678,22 @@ class Wav2LetterEngine(DecodeMixin):
       loss_h[:2 * B].copy_(self.loss_pair, non_blocking=True)
       status_h[:B].copy_(self.ctc_status, non_blocking=True)
       gate_h[:2].copy_(self.gate_slots, non_blocking=True)
+      words_h.copy_(self._update_words, non_blocking=True)      # the update counts as of the updates enqueued so far
       event.record(stream)
-    return (B, lost_h)
+    return (B, lost_h, (self._updates_enqueued, self._count_version))
 
   def fetch_losses_end(self, handle, precise=False):
     """Wait for the copies of `fetch_losses_begin`, check the status words (raises like `fetch_losses`), return the losses."""
-    B, lost_h = handle
-    loss_h, status_h, event, gate_h = self._loss_host
+    B, lost_h, (covered, version) = handle
+    loss_h, status_h, event, gate_h, words_h = self._loss_host
     event.synchronize()
+    if version == self._count_version and covered >= self._updates_covered:
+      self._updates_covered = covered
+      self._take_update_words(words_h)
     self._check_streamk_lost(lost_h)
     st = status_h[:B].numpy()
-    skipped = getattr(self, '_updates_in_flight', 0)
-    self._updates_in_flight = 0
     if st.any() or float(gate_h[0]) != 0.0:
-      # the gated Adam kernel enqueued behind this CTC evaluation was a no-op: take its step count back so that
-      # the bias correction stays in step with the updates that really happened
-      self.step_count -= min(skipped, 1)
+      # (the gated Adam kernel enqueued behind this CTC evaluation was a no-op: it did not count itself)
       if (st == 2).any():
         raise ValueError('label ids must lie in [0, {}) (blank = {}); offending utterances: {}'.format(
             self.num_classes - 1, self.num_classes - 1, np.nonzero(st == 2)[0].tolist()))

@@ -9,6 +9,7 @@ hand-written HIP kernels through ``engine.Wav2LetterEngine``.  ``sess`` is an op
 """
 import json
 import os
+import warnings
 
 import numpy as np
 
@@ -89,6 +90,8 @@ class _Saver:
     bundles instead (``save_tf``)."""
     if getattr(self.model, 'checkpoint_format', 'npz') == 'tf':
       return self.save_tf(sess, save_path, global_step)
+    if hasattr(self.model, 'settle_updates'):
+      self.model.settle_updates()                  # global_step and the engine's count: updates applied, none still in flight
     step = global_step.eval() if hasattr(global_step, 'eval') else global_step
     path = '{}-{}'.format(save_path, step) if step is not None else save_path
     if getattr(self.model, '_rank', 0) != 0:
@@ -129,6 +132,8 @@ class _Saver:
     model.  Restoring into the reference itself is the intent and follows from TF 1.x naming rules, but has not been
     tried against a TensorFlow installation (none is available here)."""
     from . import tf_checkpoint as tfc
+    if hasattr(self.model, 'settle_updates'):
+      self.model.settle_updates()                  # global_step and the engine's count: updates applied, none still in flight
     step = global_step.eval() if hasattr(global_step, 'eval') else global_step
     path = '{}-{}'.format(save_path, step) if step is not None else save_path
     if getattr(self.model, '_rank', 0) != 0:
@@ -259,6 +264,7 @@ class SpeechModel:
     self._reducer = None
     self._world = 1
     self._rank = 0
+    self._skips_seen = 0
 
   # ---- graph-building protocol ---------------------------------------------------------------
   def _convolution(self, value, filter_width, stride, input_channels, out_channels, apply_non_linearity=True):
@@ -359,6 +365,28 @@ class SpeechModel:
         self._early = eng.fetch_losses_begin(stream=stream)
       self._reducer.after_first_bucket = after_first_bucket
 
+  def _take_skipped_updates(self, eng):
+    """global_step counts applied updates only.  An update whose gradients' global norm was not finite is skipped on the device
+    (st_global_norm_clip_adam_counted_f32) and the host learns of it from a later read-back: take the steps it counted back."""
+    skipped = getattr(eng, 'updates_skipped', 0)
+    new = skipped - self._skips_seen
+    self._skips_seen = skipped
+    if new > 0:
+      last = self.global_step.value
+      self.global_step.value -= new
+      warnings.warn('update of training step {} skipped: the global gradient norm was {} (not finite); weights, Adam state and '
+                    'global_step stay as they were ({} update(s) skipped in all)'.format(
+                        last if new == 1 else '{}-{}'.format(last - new + 1, last), getattr(eng, 'last_skip_norm', None), skipped),
+                    RuntimeWarning, stacklevel=3)
+
+  def settle_updates(self):
+    """Wait for the updates enqueued so far and bring global_step in line with the updates the device really applied (checkpoints
+    call this; a training step learns of a skipped update one step later, without waiting)."""
+    eng = self.engine
+    if eng is not None and hasattr(eng, 'sync_update_counts'):
+      eng.sync_update_counts()
+      self._take_skipped_updates(eng)
+
   def step(self, sess, loss=True, update=True, decode=False, return_label=False, summary=False, feed_dict=None):
     """One evaluation of the path.  Returns, in this order and only when requested:
     avg_loss, decoded, label, update (None), summary  (speech_model.py:197-235)."""
@@ -398,6 +426,8 @@ class SpeechModel:
         early = self._early if self._early is not None else eng.fetch_losses_begin()
       losses = eng.fetch_losses_end(early, precise=True)
       avg_loss = np.float32(losses.mean())     # mean of -log p in float64, returned as TF's float32
+      # the read-back above was enqueued before this step's update: it reports the updates of earlier steps
+      self._take_skipped_updates(eng)
       if update:
         self.global_step.value += 1
       if self._world > 1:
