@@ -43,8 +43,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int BKB = 32;           // bf16 elements of reduction per LDS stage (2 MFMA k-steps)
 constexpr int NT_ = 256;
@@ -323,10 +321,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nn_bf16_kernel(X6Params p) 
     const int op = pc / (NP * PPW), pl = (pc / PPW) % NP, i = pc % PPW;
     if (op == 0) {
       const __bf16* g = FAST ? aptr[pl][i] + k0 : asrc[i] + pl * p.a_plane + min(k0 + slot8[i], ktail);
-      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(As + (buf * NP + pl) * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)g, (st::lptr_t)(As + (buf * NP + pl) * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
     } else {
       const __bf16* g = FAST ? bptr[pl][i] + k0 : bsrc[i] + pl * p.b_plane + min(k0 + slot8[i], p.Kp - 8);
-      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(Bs + (buf * NP + pl) * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)g, (st::lptr_t)(Bs + (buf * NP + pl) * PL + (wave * RW + i * RPP) * BK), 16, 0, 0);
     }
   };
 
@@ -563,8 +561,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nn_bf16_kernel(X6Params p) 
   }
 }
 
-int npad_of(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)st::round_up(cout, 128)); }
-
 // out[i] = sum_s slabs[s][i]
 __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ slabs, int n_slabs, size_t n4,
                                                        float* __restrict__ out) {
@@ -735,7 +731,7 @@ int conv_fwd(const st_tensor3* x, const void* x_planes, const void* w_planes, co
   p.A = reinterpret_cast<const __bf16*>(x_planes);
   p.a_plane = (size_t)x->batch * x->t_pitch * x->c_pitch;
   p.amap = map_of(*x, x->halo - pad_left, stride, y->frames);
-  p.Np = npad_of(y->channels);
+  p.Np = st::npad_of(y->channels);
   p.Kvalid = width * x->c_pitch;
   p.Kp = (int)st::round_up(p.Kvalid, 32);
   p.B = reinterpret_cast<const __bf16*>(w_planes);
@@ -773,8 +769,8 @@ int conv_fwd(const st_tensor3* x, const void* x_planes, const void* w_planes, co
 // the idle CUs.  Tap-inner convolutions split over 64-channel chunks (every slice walks all taps), 1x1 layers
 // over slices of >= 4 stages.
 int fwd_splits(const st_tensor3& x, const st_tensor3& y, int width) {
-  const long tiles = (long)st::ceil_div(y.batch * y.frames, 128) * st::ceil_div(npad_of(y.channels), 128);
-  if (tiles >= 128 || npad_of(y.channels) % 128) return 1;
+  const long tiles = (long)st::ceil_div(y.batch * y.frames, 128) * st::ceil_div(st::npad_of(y.channels), 128);
+  if (tiles >= 128 || st::npad_of(y.channels) % 128) return 1;
   const int chunks = st::ceil_div(x.c_pitch, 64);
   const long slices = width > 1 ? chunks : chunks / 4;
   return (int)std::max(1L, std::min<long>(256 / tiles, slices));
@@ -783,7 +779,7 @@ int fwd_splits(const st_tensor3& x, const st_tensor3& y, int width) {
 // channel-chunk split of a tap-inner convolution whose tile grid cannot fill the chip (back-prop through L8:
 // 252 tiles, 1000 stages each): 1 = no split
 int bwd_data_splits(const st_tensor3& dz, const st_tensor3& dx, int width) {
-  const long tiles = (long)st::ceil_div(dx.batch * dx.frames, 128) * st::ceil_div(npad_of(dx.channels), 128);
+  const long tiles = (long)st::ceil_div(dx.batch * dx.frames, 128) * st::ceil_div(st::npad_of(dx.channels), 128);
   const int chunks = st::ceil_div(dz.c_pitch, 64);
   if (tiles >= 384 || (long)chunks * width < 128) return 1;
   return (int)std::max(1L, std::min<long>(st::ceil_div(768, (int)tiles), chunks / 4));
@@ -798,7 +794,7 @@ int conv_bwd_data(const st_tensor3* dz, const void* dz_planes, const void* wt_pl
   p.A = reinterpret_cast<const __bf16*>(dz_planes);
   p.a_plane = (size_t)dz->batch * dz->t_pitch * dz->c_pitch;
   p.amap = map_of(*dz, dz->halo - lead, 1, dx->frames);
-  p.Np = npad_of(dx->channels);
+  p.Np = st::npad_of(dx->channels);
   p.Kvalid = width * dz->c_pitch;
   p.Kp = (int)st::round_up(p.Kvalid, 32);
   p.B = reinterpret_cast<const __bf16*>(wt_planes);
@@ -855,7 +851,7 @@ int conv_bwd_filter(const void* xt_planes, size_t xt_plane, long xt_phase_stride
   p.amap.phase_shift = phases == 2 ? 1 : 0;
   p.amap.phase_mask = phases - 1;
   p.amap.phase_stride = xt_phase_stride;
-  p.Np = npad_of(cout);
+  p.Np = st::npad_of(cout);
   p.Kvalid = (int)red;
   p.Kp = (int)pitch;
   p.B = reinterpret_cast<const __bf16*>(dzt_planes);
@@ -891,7 +887,7 @@ WgradPlan wgrad_plan(const st_tensor3& x, const st_tensor3& dz, int width, int s
   const int x_rows = st::ceil_div(x.t_pitch - x_first_row, stride);
   w.tq = (int)st::round_up(std::max(x_rows, dz.frames), 32);
   w.red = (long)x.batch * w.tq;
-  w.n_pad = npad_of(dz.channels);
+  w.n_pad = st::npad_of(dz.channels);
   w.pitch = w.red;      // a padded row pitch (64..520 elements, against power-of-two strides) measured 4-14 % slower
   w.xt_phase_elems = (size_t)x.c_pitch * w.pitch + 4096;         // slack: the last taps read past the last row
   w.xt_bytes = st::round_up(w.xt_phase_elems * stride * 2, 256);
@@ -1045,7 +1041,7 @@ int st_exp_conv1d_fwd_bf16x6(const st_tensor3* x, const void* x_planes, const vo
   ST_REQUIRE(x && y && x_planes && w_planes && y->base, "conv bf16x6: null argument");
   ST_REQUIRE(x->halo >= pad_left && y->frames == st::ceil_div(x->frames, stride) && x->c_pitch % 16 == 0,
              "conv bf16x6: bad geometry");
-  ST_REQUIRE(npad_of(y->channels) % 128 == 0, "conv bf16x6: n_pad must be a multiple of 128");
+  ST_REQUIRE(st::npad_of(y->channels) % 128 == 0, "conv bf16x6: n_pad must be a multiple of 128");
   return conv_fwd<3>(x, x_planes, w_planes, bias, width, stride, pad_left, relu, y, y->base, y_planes,
                      st::as_stream(stream));
 }
@@ -1055,7 +1051,7 @@ int st_exp_conv1d_fwd_bf16x6(const st_tensor3* x, const void* x_planes, const vo
 size_t st_exp_conv1d_bwd_data_bf16x6_ws(const st_tensor3* dz, const st_tensor3* dx, int width) {
   if (!dz || !dx) return 0;
   const int splits = bwd_data_splits(*dz, *dx, width);
-  return splits > 1 ? (size_t)splits * dx->batch * dx->frames * npad_of(dx->channels) * sizeof(float) : 0;
+  return splits > 1 ? (size_t)splits * dx->batch * dx->frames * st::npad_of(dx->channels) * sizeof(float) : 0;
 }
 
 int st_exp_conv1d_bwd_data_bf16x6(const st_tensor3* dz, const void* dz_planes, const void* wt_planes, int width,
@@ -1064,7 +1060,7 @@ int st_exp_conv1d_bwd_data_bf16x6(const st_tensor3* dz, const void* dz_planes, c
   ST_REQUIRE(dz && dx && dz_planes && wt_planes && dx->base, "conv bwd bf16x6: null argument");
   const int lead = width - 1 - pad_left;
   ST_REQUIRE(lead >= 0 && dz->halo >= lead && dz->frames == dx->frames && dz->batch == dx->batch, "conv bwd bf16x6: bad geometry");
-  ST_REQUIRE(npad_of(dx->channels) % 128 == 0, "conv bwd bf16x6: n_pad must be a multiple of 128");
+  ST_REQUIRE(st::npad_of(dx->channels) % 128 == 0, "conv bwd bf16x6: n_pad must be a multiple of 128");
   // few output tiles and a long reduction (back-prop through L8): split over channel chunks when a workspace is given
   int splits = bwd_data_splits(*dz, *dx, width);
   if (!workspace || workspace_bytes < st_exp_conv1d_bwd_data_bf16x6_ws(dz, dx, width)) splits = 1;
@@ -1089,7 +1085,7 @@ int st_exp_conv1d_bwd_filter_bf16x6(const void* xt_planes, const void* dzt_plane
                                     int cin_pitch, int x_first_row, int cout, float* dpacked, void* stream) {
   ST_REQUIRE(xt_planes && dzt_planes && dpacked && tq % 32 == 0 && cin_pitch % 16 == 0, "bwd_filter bf16x6: bad args");
   const long red = (long)batch * tq;
-  ST_REQUIRE(npad_of(cout) % 128 == 0 && red < (1L << 31), "bwd_filter bf16x6: unsupported shape");
+  ST_REQUIRE(st::npad_of(cout) % 128 == 0 && red < (1L << 31), "bwd_filter bf16x6: unsupported shape");
   return conv_bwd_filter<3>(xt_planes, (size_t)cin_pitch * red + 4096, 0, 1, dzt_planes, batch, tq, width, cin_pitch,
                             x_first_row, cout, dpacked, 1, nullptr, st::as_stream(stream));
 }
@@ -1116,7 +1112,7 @@ int st_filters_bwd_bf16(const float* packed, int width, int cin, int cout, int c
   ST_REQUIRE(packed && wtt && width >= 1 && cin >= 1 && cout >= 1 && cin_pitch >= cin && cout_pitch >= cout &&
                  cout_pitch % 16 == 0 && cin_pitch % 16 == 0,
              "st_filters_bwd_bf16: bad args");
-  const int n_pad = npad_of(cout);                                   // column pitch of the packed filters
+  const int n_pad = st::npad_of(cout);                               // column pitch of the packed filters
   const int kt_pad = (int)st::round_up((size_t)width * cout_pitch, 32);
   const long total = (long)width * cin * (cout_pitch / 4);
   hipLaunchKernelGGL(filters_bwd_bf16_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0,
@@ -1128,7 +1124,7 @@ int st_filters_bwd_bf16(const float* packed, int width, int cin, int cout, int c
 size_t st_conv1d_fwd_bf16_ws(const st_tensor3* x, const st_tensor3* y, int width) {
   if (!x || !y) return 0;
   const int splits = fwd_splits(*x, *y, width);
-  return splits > 1 ? (size_t)splits * y->batch * y->frames * npad_of(y->channels) * sizeof(float) : 0;
+  return splits > 1 ? (size_t)splits * y->batch * y->frames * st::npad_of(y->channels) * sizeof(float) : 0;
 }
 
 int st_conv1d_nwc_fwd_ws_bf16(const st_tensor3* x, const void* x_bf16, const void* wt_bf16, const float* bias, int width,
@@ -1157,7 +1153,7 @@ int st_conv1d_nwc_fwd_bf16(const st_tensor3* x, const void* x_bf16, const void* 
 size_t st_conv1d_bwd_data_bf16_ws(const st_tensor3* dz, const st_tensor3* dx, int width) {
   if (!dz || !dx) return 0;
   const int splits = bwd_data_splits(*dz, *dx, width);
-  return splits > 1 ? (size_t)splits * dx->batch * dx->frames * npad_of(dx->channels) * sizeof(float) : 0;
+  return splits > 1 ? (size_t)splits * dx->batch * dx->frames * st::npad_of(dx->channels) * sizeof(float) : 0;
 }
 
 int st_conv1d_nwc_bwd_data_bf16(const st_tensor3* dz, const void* dz_bf16, const void* wtt_bf16, int width, int pad_left,

@@ -57,7 +57,6 @@ __host__ __device__ inline int fused_column(int q, int hh, int n, int pad_left) 
   return (q - 32) < right ? V + pad_left + (q - 32) : -1;
 }
 
-int npad_of(int c) { return c <= 32 ? 32 : (c <= 64 ? 64 : (int)st::round_up(c, 128)); }
 // spectra of a tensor with channel pitch cp keep `half_of(cp)` columns for the real and for the imaginary parts: a
 // multiple of 64, so that [re | im] rows tile the filter-gradient kernel (128 columns) whatever the pitch
 int half_of(int cp) { return (int)st::round_up(cp, 64); }
@@ -955,11 +954,6 @@ __global__ __launch_bounds__(256) void bias_from_spectra_kernel(const float* __r
   }
 }
 
-bool tensor_ok(const st_tensor3* t) {
-  return t && t->base && t->batch > 0 && t->frames > 0 && t->channels > 0 && t->halo >= 0 && t->c_pitch % 16 == 0 &&
-         t->c_pitch >= t->channels && t->t_pitch >= t->halo + t->frames;
-}
-
 RowsIn rows_in(const st_tensor3& t) {
   RowsIn r;
   r.base_b = nullptr;
@@ -1037,7 +1031,7 @@ bool width_ok(int width) { return width >= 2 && V + width - 1 <= KP; }
 // the same rows with the four-product kernels.  st_set_tuning("no_g3", 1): the four-product form everywhere (A/B runs, parity
 // of the two forms) -- set before the filter spectra are built.
 constexpr int G3_MIN_WIDTH = 2 * FUSE_HALO + 2;
-bool zf3_form(int width, int cout) { return width >= G3_MIN_WIDTH && npad_of(cout) >= 512 && st::tuning(st::TUNE_NO_G3) == 0; }
+bool zf3_form(int width, int cout) { return width >= G3_MIN_WIDTH && st::npad_of(cout) >= 512 && st::tuning(st::TUNE_NO_G3) == 0; }
 bool g3_form(int width, int cin_pitch, int cout) { return zf3_form(width, cout) && half_of(cin_pitch) % 128 == 0; }
 // the filter gradient's lag products as separate real / imaginary products over half-length rows (see bwd_filter): needs the
 // spectra halves to tile the filter-gradient kernel (128 columns)
@@ -1183,17 +1177,17 @@ int st_conv1d_fft_tables_f32(int width, int pad_left, float* tables, size_t tabl
 size_t st_conv1d_fft_filter_floats(int width, int cin_pitch, int cout) {
   if (!width_ok(width)) return 0;
   const size_t bins = (V + width - 1) / 2 + 1;
-  return bins * 2 * half_of(cin_pitch) * 2 * npad_of(cout);
+  return bins * 2 * half_of(cin_pitch) * 2 * st::npad_of(cout);
 }
 
 int st_conv1d_fft_filters_f32(const float* packed, int width, int cin, int cout, int cin_pitch, const float* tables, float* gfwd,
                               void* stream) {
   ST_REQUIRE(width_ok(width) && cin_pitch % 16 == 0 && tables && packed && gfwd, "fft filters: bad argument");
-  ST_REQUIRE(npad_of(cout) % 128 == 0, "fft filters: the output channels must pack to a multiple of 128");
+  ST_REQUIRE(st::npad_of(cout) % 128 == 0, "fft filters: the output channels must pack to a multiple of 128");
   hipStream_t s = st::as_stream(stream);
   const int n = V + width - 1, bins = n / 2 + 1;
   const f32x2* tw = reinterpret_cast<const f32x2*>(tables + T_FW);
-  const int npo = npad_of(cout);
+  const int npo = st::npad_of(cout);
   // compile-time widths for the layers of the model (taps in registers); any other width runs the generic form
 #define ST_FFT_WIDTH_DISPATCH(KERNEL, ...)                                                                   \
   do {                                                                                                       \
@@ -1229,14 +1223,14 @@ size_t st_conv1d_fft_zf_floats(const st_tensor3* dz, int width) {
   const Plan p = make_plan(width, dz->frames, dz->batch);
   // (three parts per row, [Z_r + Z_i | Z_r | Z_i], where the layer's gradient spectra take the three-product layout: zf3_form --
   // sized for it whatever the tuning knob says)
-  const bool three = width >= G3_MIN_WIDTH && npad_of(dz->channels) >= 512;
-  return (size_t)p.bins * p.rows_pad * (three ? 3 : 2) * npad_of(dz->channels);
+  const bool three = width >= G3_MIN_WIDTH && st::npad_of(dz->channels) >= 512;
+  return (size_t)p.bins * p.rows_pad * (three ? 3 : 2) * st::npad_of(dz->channels);
 }
 
 size_t st_conv1d_fft_ws(const st_tensor3* x, const st_tensor3* y, int width) {
   if (!x || !y || !width_ok(width)) return 0;
   const Plan p = make_plan(width, y->frames, y->batch);
-  const size_t nf = 2 * (size_t)npad_of(y->channels), ka = 2 * (size_t)half_of(x->c_pitch), nb = ka;
+  const size_t nf = 2 * (size_t)st::npad_of(y->channels), ka = 2 * (size_t)half_of(x->c_pitch), nb = ka;
   const size_t yf = (size_t)p.bins * p.rows_pad * nf, xf = (size_t)p.bins * p.rows_pad * nb, qf = (size_t)p.bins * ka * nf;
   // [stream-K area of the per-bin products (control words + partial tiles, st_common.h) | spectra of the call's output]
   return (st::SK_WS_FLOATS + std::max(yf, std::max(xf, qf)) + 64) * sizeof(float);
@@ -1250,13 +1244,13 @@ int st_conv1d_nwc_fwd_fft_chain_f32(const st_tensor3* x, const float* gfwd, cons
                                     const st_tensor3* y, const float* tables, float* sf, int sf_ready, const float* next_tables,
                                     float* next_sf, int next_width, int next_pad_left, int* next_sf_written, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(y) && gfwd && sf && workspace && tables && width_ok(width), "conv fft fwd: bad argument");
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(y) && gfwd && sf && workspace && tables && width_ok(width), "conv fft fwd: bad argument");
   ST_REQUIRE(x->batch == y->batch && x->frames == y->frames && pad_left >= 0 && pad_left < width, "conv fft fwd: stride-1 SAME layers only");
-  ST_REQUIRE(npad_of(y->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(x, y, width), "conv fft fwd: workspace / shape");
+  ST_REQUIRE(st::npad_of(y->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(x, y, width), "conv fft fwd: workspace / shape");
   if (next_sf_written) *next_sf_written = 0;
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, y->frames, y->batch, ROWS_F32);
-  const int ka = 2 * half_of(x->c_pitch), npo = npad_of(y->channels), nf = 2 * npo;
+  const int ka = 2 * half_of(x->c_pitch), npo = st::npad_of(y->channels), nf = 2 * npo;
   float* const sk = reinterpret_cast<float*>(workspace);
   float* yf = sk + st::SK_WS_FLOATS;
   const int half = half_of(x->c_pitch);
@@ -1313,17 +1307,17 @@ int st_conv1d_nwc_fwd_fft_f32(const st_tensor3* x, const float* gfwd, const floa
 }
 
 int st_conv1d_fft_dz_spectra_f32(const st_tensor3* dz, int width, const float* tables, float* zf, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tables && zf && width_ok(width) && npad_of(dz->channels) % 128 == 0, "conv fft dz spectra: bad argument");
+  ST_REQUIRE(st::tensor_ok(dz) && tables && zf && width_ok(width) && st::npad_of(dz->channels) % 128 == 0, "conv fft dz spectra: bad argument");
   const Plan p = make_plan(width, dz->frames, dz->batch, ROWS_F32);
-  launch_dft(*dz, nullptr, p, tables + T_FZ, 0, V, npad_of(dz->channels), zf, nullptr, 0, 0, nullptr, st::as_stream(stream), 0, nullptr,
+  launch_dft(*dz, nullptr, p, tables + T_FZ, 0, V, st::npad_of(dz->channels), zf, nullptr, 0, 0, nullptr, st::as_stream(stream), 0, nullptr,
              zf3_form(width, dz->channels) ? 5 : 0);
   return st::check_launch("conv fft dz spectra");
 }
 
 int st_conv1d_fft_bias_grad_f32(const st_tensor3* dz, int width, const float* zf, float* dbias, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && zf && dbias && width_ok(width) && npad_of(dz->channels) % 128 == 0, "conv fft bias grad: bad argument");
+  ST_REQUIRE(st::tensor_ok(dz) && zf && dbias && width_ok(width) && st::npad_of(dz->channels) % 128 == 0, "conv fft bias grad: bad argument");
   const Plan p = make_plan(width, dz->frames, dz->batch, ROWS_F32);
-  const int np = npad_of(dz->channels);
+  const int np = st::npad_of(dz->channels);
   const bool zf3 = zf3_form(width, dz->channels);              // rows [Z_r + Z_i | Z_r | Z_i]: bin 0's real parts one part in
   hipLaunchKernelGGL(bias_from_spectra_kernel, dim3(st::ceil_div(np, 32)), dim3(256), 0, st::as_stream(stream), zf + (zf3 ? np : 0), p.rows,
                      (zf3 ? 3 : 2) * np, dz->channels, np, dbias);
@@ -1339,19 +1333,19 @@ int st_conv1d_nwc_bwd_data_fft_chain_f32(const st_tensor3* dz, const float* zf, 
                                          const st_tensor3* act, const st_tensor3* dx, const float* tables, const float* below_tables,
                                          float* below_zf, int below_width, int* below_zf_written, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tensor_ok(dx) && zf && gfwd && workspace && tables && width_ok(width), "conv fft bwd_data: bad argument");
+  ST_REQUIRE(st::tensor_ok(dz) && st::tensor_ok(dx) && zf && gfwd && workspace && tables && width_ok(width), "conv fft bwd_data: bad argument");
   ST_REQUIRE(dz->batch == dx->batch && dz->frames == dx->frames && pad_left >= 0 && pad_left < width, "conv fft bwd_data: stride-1 layers only");
-  ST_REQUIRE(npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(dx, dz, width), "conv fft bwd_data: workspace / shape");
-  if (act) ST_REQUIRE(tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames && act->c_pitch >= dx->c_pitch,
+  ST_REQUIRE(st::npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(dx, dz, width), "conv fft bwd_data: workspace / shape");
+  if (act) ST_REQUIRE(st::tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames && act->c_pitch >= dx->c_pitch,
                       "conv fft bwd_data: mask tensor mismatch");
   if (below_zf_written) *below_zf_written = 0;
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, dz->frames, dz->batch, ROWS_F32);
   // X[bin] = Z[bin] (rows x 2 npo) * gfwd[bin]^T (2 npo x 2 cph): the forward spectra read as a transposed operand
-  const int kz = 2 * npad_of(dz->channels), cph = half_of(dx->c_pitch), nb = 2 * cph;
+  const int kz = 2 * st::npad_of(dz->channels), cph = half_of(dx->c_pitch), nb = 2 * cph;
   float* const sk = reinterpret_cast<float*>(workspace);
   float* xf = sk + st::SK_WS_FLOATS;
-  const int npz = npad_of(dz->channels);
+  const int npz = st::npad_of(dz->channels);
   const bool zf3 = zf3_form(width, dz->channels);
   if (g3_form(width, dx->c_pitch, dz->channels)) {
     // X = Z G in three products, the filter planes read transposed in place:
@@ -1373,8 +1367,8 @@ int st_conv1d_nwc_bwd_data_fft_chain_f32(const st_tensor3* dz, const float* zf, 
                            st::tuning(st::TUNE_NO_FUSED_TRANSFORMS) == 0;
   if (window_form) {
     // the layer below's dz spectra ride along when its zf rows are laid out like this call's columns
-    const bool below = below_tables && below_zf && width_ok(below_width) && npad_of(dx->channels) % 128 == 0 &&
-                       npad_of(dx->channels) == cph && 32 * nchunks == cph && !zf3_form(below_width, dx->channels);
+    const bool below = below_tables && below_zf && width_ok(below_width) && st::npad_of(dx->channels) % 128 == 0 &&
+                       st::npad_of(dx->channels) == cph && 32 * nchunks == cph && !zf3_form(below_width, dx->channels);
     const Plan pb = make_plan(below ? below_width : width, dx->frames, dx->batch, ROWS_F32);
     // gflop: the whole-window inverse (2 * HP k-steps, three 32-row tiles), then the 32 k-steps of the layer below's zero-padded
     // forward transform (three tiles); mb: this layer's dx spectra and the ReLU mask in, dx and the layer below's dz spectra out
@@ -1419,9 +1413,9 @@ size_t st_conv1d_fft_filter_plane_elems(int width, int cin_pitch, int cout) { re
 int st_conv1d_fft_filters_planes(const float* packed, int width, int cin, int cout, int cin_pitch, const float* tables, void* g_planes,
                                  void* gt_planes, int planes, void* stream) {
   ST_REQUIRE(width_ok(width) && cin_pitch % 16 == 0 && tables && packed && g_planes && gt_planes && planes_ok(planes), "fft filter planes: bad argument");
-  ST_REQUIRE(npad_of(cout) % 128 == 0, "fft filter planes: the output channels must pack to a multiple of 128");
+  ST_REQUIRE(st::npad_of(cout) % 128 == 0, "fft filter planes: the output channels must pack to a multiple of 128");
   hipStream_t s = st::as_stream(stream);
-  const int n = V + width - 1, bins = n / 2 + 1, npo = npad_of(cout), cph = half_of(cin_pitch);
+  const int n = V + width - 1, bins = n / 2 + 1, npo = st::npad_of(cout), cph = half_of(cin_pitch);
   const f32x2* tw = reinterpret_cast<const f32x2*>(tables + T_FW);
   const size_t plane = (size_t)bins * 2 * cph * 2 * npo;
   const int gx = st::ceil_div(npo, 256), gy = cph;
@@ -1440,7 +1434,7 @@ int st_conv1d_fft_filters_planes(const float* packed, int width, int cin, int co
 size_t st_conv1d_fft_planes_ws(const st_tensor3* x, const st_tensor3* y, int width, int planes) {
   if (!x || !y || !width_ok(width) || !planes_ok(planes)) return 0;
   const Plan p = make_plan(width, y->frames, y->batch);
-  const size_t nf = 2 * (size_t)npad_of(y->channels), ka = 2 * (size_t)half_of(x->c_pitch);
+  const size_t nf = 2 * (size_t)st::npad_of(y->channels), ka = 2 * (size_t)half_of(x->c_pitch);
   const size_t red = (size_t)p.bins * p.rows_pad;
   // [stream-K area (unused here, kept for a common layout) | fp32 product spectra: max(yf, xf, qf) | reduction-major bf16 copies
   //  of both spectra for the lag products, `planes` each]
@@ -1452,15 +1446,15 @@ size_t st_conv1d_fft_planes_ws(const st_tensor3* x, const st_tensor3* y, int wid
 int st_conv1d_nwc_fwd_fft_planes(const st_tensor3* x, const void* x_bf16, const void* gt_planes, const float* bias, int width,
                                  int pad_left, int relu, const st_tensor3* y, void* y_bf16, const float* tables, void* sf_planes,
                                  int planes, void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(y) && gt_planes && sf_planes && workspace && tables && width_ok(width) && planes_ok(planes),
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(y) && gt_planes && sf_planes && workspace && tables && width_ok(width) && planes_ok(planes),
              "conv fft planes fwd: bad argument");
   ST_REQUIRE((planes == 1) == (x_bf16 != nullptr) && (planes == 1) == (y_bf16 != nullptr),
              "conv fft planes fwd: one plane goes with bf16 tensors, three planes with fp32 tensors");
   ST_REQUIRE(x->batch == y->batch && x->frames == y->frames && pad_left >= 0 && pad_left < width, "conv fft planes fwd: stride-1 SAME layers only");
-  ST_REQUIRE(npad_of(y->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(x, y, width, planes), "conv fft planes fwd: workspace / shape");
+  ST_REQUIRE(st::npad_of(y->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(x, y, width, planes), "conv fft planes fwd: workspace / shape");
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, y->frames, y->batch);
-  const int ka = 2 * half_of(x->c_pitch), npo = npad_of(y->channels), nf = 2 * npo;
+  const int ka = 2 * half_of(x->c_pitch), npo = st::npad_of(y->channels), nf = 2 * npo;
   const size_t s_plane = (size_t)p.bins * p.rows_pad * ka, g_plane = (size_t)p.bins * ka * nf;
   float* yf = reinterpret_cast<float*>(workspace) + st::SK_WS_FLOATS;
   launch_dft(*x, x_bf16, p, tables + T_FS, -pad_left, p.n, half_of(x->c_pitch), nullptr, sf_planes, planes, s_plane, nullptr, s);
@@ -1476,10 +1470,10 @@ int st_conv1d_nwc_fwd_fft_planes(const st_tensor3* x, const void* x_bf16, const 
 
 int st_conv1d_fft_dz_spectra_planes(const st_tensor3* dz, const void* dz_bf16, int width, const float* tables, void* zf_planes,
                                     int planes, float* dc, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tables && zf_planes && width_ok(width) && planes_ok(planes) && npad_of(dz->channels) % 128 == 0 &&
+  ST_REQUIRE(st::tensor_ok(dz) && tables && zf_planes && width_ok(width) && planes_ok(planes) && st::npad_of(dz->channels) % 128 == 0 &&
                  (planes == 1) == (dz_bf16 != nullptr), "conv fft planes dz spectra: bad argument");
   const Plan p = make_plan(width, dz->frames, dz->batch);
-  const int npo = npad_of(dz->channels);
+  const int npo = st::npad_of(dz->channels);
   launch_dft(*dz, dz_bf16, p, tables + T_FZ, 0, V, npo, nullptr, zf_planes, planes, (size_t)p.bins * p.rows_pad * 2 * npo, dc,
              st::as_stream(stream));
   return st::check_launch("conv fft planes dz spectra");
@@ -1496,17 +1490,17 @@ int st_conv1d_fft_bias_grad_dc_f32(const float* dc, int rows, int channels, int 
 int st_conv1d_nwc_bwd_data_fft_planes(const st_tensor3* dz, const void* zf_planes, const void* g_planes, int width, int pad_left,
                                       const st_tensor3* act, const void* act_bf16, const st_tensor3* dx, void* dx_bf16,
                                       const float* tables, int planes, void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tensor_ok(dx) && zf_planes && g_planes && workspace && tables && width_ok(width) && planes_ok(planes),
+  ST_REQUIRE(st::tensor_ok(dz) && st::tensor_ok(dx) && zf_planes && g_planes && workspace && tables && width_ok(width) && planes_ok(planes),
              "conv fft planes bwd_data: bad argument");
   ST_REQUIRE(dz->batch == dx->batch && dz->frames == dx->frames && pad_left >= 0 && pad_left < width, "conv fft planes bwd_data: stride-1 layers only");
   ST_REQUIRE((planes == 1) == (dx_bf16 != nullptr) && (!act || (planes == 1) == (act_bf16 != nullptr)),
              "conv fft planes bwd_data: one plane goes with bf16 tensors, three planes with fp32 tensors");
-  ST_REQUIRE(npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(dx, dz, width, planes), "conv fft planes bwd_data: workspace / shape");
-  if (act) ST_REQUIRE(tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames && act->c_pitch >= dx->c_pitch,
+  ST_REQUIRE(st::npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(dx, dz, width, planes), "conv fft planes bwd_data: workspace / shape");
+  if (act) ST_REQUIRE(st::tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames && act->c_pitch >= dx->c_pitch,
                       "conv fft planes bwd_data: mask tensor mismatch");
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, dz->frames, dz->batch);
-  const int kz = 2 * npad_of(dz->channels), cph = half_of(dx->c_pitch), nb = 2 * cph;
+  const int kz = 2 * st::npad_of(dz->channels), cph = half_of(dx->c_pitch), nb = 2 * cph;
   float* xf = reinterpret_cast<float*>(workspace) + st::SK_WS_FLOATS;
   // X[bin] = Z[bin] (rows x kz) * gfwd[bin]^T (kz x nb): gfwd itself is the k-contiguous operand
   if (int e = st::gemm_bf16_bins(planes, zf_planes, (size_t)p.bins * p.rows_pad * kz, kz, (long)p.rows_pad * kz, g_planes, (size_t)p.bins * nb * kz,
@@ -1525,14 +1519,14 @@ int st_conv1d_nwc_bwd_data_fft_planes(const st_tensor3* dz, const void* zf_plane
 int st_conv1d_nwc_bwd_filter_fft_planes(const st_tensor3* x, const st_tensor3* dz, const void* sf_planes, const void* zf_planes, int width,
                                         const float* tables, float* dpacked, int planes, void* workspace, size_t workspace_bytes,
                                         void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(dz) && sf_planes && zf_planes && dpacked && workspace && tables && width_ok(width) && planes_ok(planes),
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(dz) && sf_planes && zf_planes && dpacked && workspace && tables && width_ok(width) && planes_ok(planes),
              "conv fft planes bwd_filter: bad argument");
   ST_REQUIRE(x->batch == dz->batch && x->frames == dz->frames, "conv fft planes bwd_filter: stride-1 layers only");
-  ST_REQUIRE(npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(x, dz, width, planes), "conv fft planes bwd_filter: workspace / shape");
+  ST_REQUIRE(st::npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_planes_ws(x, dz, width, planes), "conv fft planes bwd_filter: workspace / shape");
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, dz->frames, dz->batch);
   const f32x2* tw = reinterpret_cast<const f32x2*>(tables + T_FW);
-  const int half = half_of(x->c_pitch), ka = 2 * half, npo = npad_of(dz->channels), nf = 2 * npo;
+  const int half = half_of(x->c_pitch), ka = 2 * half, npo = st::npad_of(dz->channels), nf = 2 * npo;
   const long red = (long)p.bins * p.rows_pad;
   const size_t prod = std::max((size_t)p.bins * p.rows_pad * nf, (size_t)p.bins * ka * nf);
   float* qf = reinterpret_cast<float*>(workspace) + st::SK_WS_FLOATS;
@@ -1577,13 +1571,13 @@ int st_conv1d_nwc_bwd_filter_fft_planes(const st_tensor3* x, const st_tensor3* d
 
 int st_conv1d_nwc_bwd_filter_fft_f32(const st_tensor3* x, const st_tensor3* dz, const float* sf, const float* zf, int width,
                                      const float* tables, float* dpacked, void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(dz) && sf && zf && dpacked && workspace && tables && width_ok(width), "conv fft bwd_filter: bad argument");
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(dz) && sf && zf && dpacked && workspace && tables && width_ok(width), "conv fft bwd_filter: bad argument");
   ST_REQUIRE(x->batch == dz->batch && x->frames == dz->frames, "conv fft bwd_filter: stride-1 layers only");
-  ST_REQUIRE(npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(x, dz, width), "conv fft bwd_filter: workspace / shape");
+  ST_REQUIRE(st::npad_of(dz->channels) % 128 == 0 && workspace_bytes >= st_conv1d_fft_ws(x, dz, width), "conv fft bwd_filter: workspace / shape");
   hipStream_t s = st::as_stream(stream);
   const Plan p = make_plan(width, dz->frames, dz->batch, ROWS_F32);
   const f32x2* tw = reinterpret_cast<const f32x2*>(tables + T_FW);
-  const int half = half_of(x->c_pitch), ka = 2 * half, npo = npad_of(dz->channels), nf = 2 * npo;
+  const int half = half_of(x->c_pitch), ka = 2 * half, npo = st::npad_of(dz->channels), nf = 2 * npo;
   float* qf = reinterpret_cast<float*>(workspace) + st::SK_WS_FLOATS;
   const long s_bin = 2L * p.rows_pad * ka;                      // [S | rotated copy] per bin (st_conv1d_fft_sf_floats)
   const bool zf3 = zf3_form(width, dz->channels);

@@ -77,8 +77,6 @@ struct NNParams {
 // All LDS lives in ONE array (a second __shared__ object makes hipcc drain the DMA queue before
 // every fragment read).
 // ------------------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // LDS-DMA with scalar base + 32-bit per-lane byte offset (no VALU address math per piece).
 // hipcc does not model the M0 write or the outstanding load: the issuing wave drains with
@@ -102,6 +100,124 @@ template <> __device__ __forceinline__ float vget<1>(const float& v, int) { retu
 template <int N> __device__ __forceinline__ void vset(typename FVec<N>::type& v, int i, float x) { v[i] = x; }
 template <> __device__ __forceinline__ void vset<1>(float& v, int, float x) { v = x; }
 
+// XOR swizzle of a [rows][BK] stage: LDS row `row`, 16-byte slot p holds source slot p ^ ((row >> 1) & 7).  swz_slot4: the
+// source slot (in floats) that DMA lane `lane` fetches for row `row` (lane & 7 is its physical slot)
+__device__ __forceinline__ int swz_slot4(int lane, int row) { return ((lane & 7) ^ ((row >> 1) & 7)) * 4; }
+// swz_frag: the offset of the fragment of k-quad q in row `row` (logical slot 2q + h, h = lane >> 5)
+__device__ __forceinline__ int swz_frag(int row, int q, int h) { return row * BK + (((2 * q + h) ^ ((row >> 1) & 7)) * 4); }
+
+// The staged k-tile of the NN kernels (gemm_nn_kernel, gemm_nn_bins_kernel, gemm_nn_g3_kernel): A staged [BM][32] with the
+// XOR swizzle, B staged [32][BN] linear, or with BT transposed [BN][32] and swizzled like A.  A kernel owns the tile mapping
+// and how a DMA piece is addressed; run() reads the fragments of LDS slot CUR, runs the 4 x 16 MFMAs into `acc` and, when
+// MORE, issues the DMA pieces of the next tile into slot CUR ^ 1 through the kernel's dma_piece(pc, buf).
+// CUR and MORE are compile-time: a steady-state loop of stage pairs is then one basic block per pair -- no uniform branches
+// cutting hipcc's MFMA / ds_read / DMA interleave, LDS addresses folded into instruction offsets.
+template <int BM, int BN, int WMW, int WNW, bool BT>
+struct NNStage {
+  static constexpr int WTM = BM / WMW, WTN = BN / WNW;
+  static constexpr int MT = WTM / 32, NT = WTN / 32;
+  static constexpr int A_DMA = BM / 32;            // DMA instructions per wave for the [BM][32] A stage
+  static constexpr int B_DMA = BN / 32;            // ... for the [32][BN] B stage
+  static constexpr int N_DMA = A_DMA + B_DMA;
+  static constexpr int A_SZ = BM * BK, B_SZ = BK * BN;
+  typedef typename FVec<NT>::type bvec;
+
+  // a_frag / bt_frag: swz_frag offsets of the wave's first A / Bt fragment row; b_frag: the lane's plain B fragment.
+  // nq < 4: a tile holding only 16 valid channels runs half the MFMA quads.
+  template <int CUR, bool MORE, typename Dma, typename... Next>
+  static __device__ __forceinline__ void run(const float* As, const float* Bs, const int (&a_frag)[4], const int (&bt_frag)[4],
+                                             int b_frag, f32x16 (&acc)[MT][NT], int nq, Dma& dma_piece, Next... next) {
+    const float* as = As + CUR * A_SZ;
+    const float* bs = Bs + CUR * B_SZ + (BT ? 0 : b_frag);
+    // Software-pipelined fragment reads: the reads of k-quad q+1 are issued BEFORE the 16 MFMAs of
+    // quad q (sched_barrier pins the order; hipcc otherwise sinks the reads behind the MFMAs to
+    // save registers and then stalls on LDS latency four times per tile).
+    f32x4 af[4][MT];
+    bvec bf[4][4];
+    f32x4 bft[4][NT];
+    auto read_frags = [&](int q) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i) af[q][i] = *reinterpret_cast<const f32x4*>(as + a_frag[q] + i * 32 * BK);
+      if (BT) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) bft[q][n] = *reinterpret_cast<const f32x4*>(bs + bt_frag[q] + n * 32 * BK);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bf[q][j] = *reinterpret_cast<const bvec*>(bs + (8 * q + j) * BN);
+      }
+    };
+    read_frags(0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      // The DMA of the next tile is issued in slices between the MFMA quads: a burst of 8 DMA
+      // instructions stalls the wave's issue long enough to drain the matrix pipe, two (~60 cycles
+      // each) hide in the shadow of the MFMAs in flight.  (One per 4 MFMAs with more sched_barriers
+      // measured slower: the pinning then also blocks hipcc's own ds_read/MFMA interleave.)
+      if (MORE) {
+#pragma unroll
+        for (int pc = q; pc < N_DMA; pc += 4) dma_piece(pc, next..., CUR ^ 1);
+      }
+      if (q < 3) read_frags(q + 1);
+      if (q < nq) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+              acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][i][j], BT ? bft[q][n][j] : vget<NT>(bf[q][j], n), acc[i][n], 0, 0, 0);
+      }
+      // interleave request: one ds_read behind each of the first MFMAs, then the address VALU and
+      // one DMA behind later MFMAs (each MFMA shadows ~64 issue cycles)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x006, 8, 0);
+        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();                         // also drains this wave's DMA (vmcnt) before anyone reads it
+  }
+};
+
+// Batched launches: bin = 8 * set + xcd -- all tiles of one bin run on ONE XCD, whose L2 then holds that bin's operands (a bin's
+// filter matrix is 8 MB: spread over the XCDs every L2 would stream all of them).  Row tiles fastest, so the workgroups sharing
+// a filter panel sit next to each other.  False past the last bin.
+__device__ __forceinline__ bool bin_tile(int tiles_m, int tiles_n, int batches, int& bin, int& tile_m, int& tile_n) {
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+  const int per_bin = tiles_m * tiles_n;
+  const int set = local / per_bin, t = local - set * per_bin;
+  bin = set * 8 + xcd;
+  tile_n = t / tiles_m;
+  tile_m = t - tile_n * tiles_m;
+  return bin < batches;
+}
+
+// nk k-tiles through LDS slots 0, 1, 0, ...: stage(integral_constant<int, CUR>, bool_constant<MORE>) per tile, in pairs
+template <typename Stage> __device__ __forceinline__ void nn_stage_pairs(int nk, Stage& stage) {
+  using std::integral_constant;
+  using std::true_type;
+  using std::false_type;
+  int kt = 0;
+  for (; kt + 2 < nk; kt += 2) {             // steady state: both tiles have a successor
+    stage(integral_constant<int, 0>{}, true_type{});
+    stage(integral_constant<int, 1>{}, true_type{});
+  }
+  if (kt + 2 == nk) {
+    stage(integral_constant<int, 0>{}, true_type{});
+    stage(integral_constant<int, 1>{}, false_type{});
+  } else if (kt + 1 == nk) {
+    stage(integral_constant<int, 0>{}, false_type{});
+  }
+}
+
 // FAST: every k-tile is whole (channel pitch and reduction length multiples of 32), so the DMA source of a
 // piece is a per-lane pointer plus the uniform k0 -- no clamps, one 64-bit add per piece.
 // BT (needs FAST, one tap): the filter operand is given TRANSPOSED, Bt[n][k] with k contiguous -- back-prop to the input of a
@@ -112,14 +228,11 @@ template <> __device__ __forceinline__ void vset<1>(float& v, int, float x) { v 
 // read are consecutive LDS rows (conflict-free like A's), and the epilogue addresses its columns one by one.
 template <int BM, int BN, int WMW, int WNW, int EPI, bool FAST = false, bool BT = false>
 __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
-  constexpr bool SGB = true;
   static_assert(!BT || FAST, "the transposed-operand variant exists for whole k-tiles only");
-  constexpr int WTM = BM / WMW, WTN = BN / WNW;
-  constexpr int MT = WTM / 32, NT = WTN / 32;
-  constexpr int A_DMA = BM / 32;            // DMA instructions per wave for the [BM][32] A stage
-  constexpr int B_DMA = BN / 32;            // ... for the [32][BN] B stage
+  typedef NNStage<BM, BN, WMW, WNW, BT> S;
+  constexpr int WTM = S::WTM, WTN = S::WTN, MT = S::MT, NT = S::NT;
+  constexpr int A_DMA = S::A_DMA, B_DMA = S::B_DMA, N_DMA = S::N_DMA, A_SZ = S::A_SZ, B_SZ = S::B_SZ;
   constexpr int B_LPR = BN / 4;             // lanes per B row
-  constexpr int A_SZ = BM * BK, B_SZ = BK * BN;
   static_assert(WMW * WNW == 4 && MT >= 1 && (NT == 1 || NT == 2 || NT == 4) && A_DMA >= 1 && B_DMA >= 1, "tile config");
   typedef typename FVec<NT>::type bvec;
 
@@ -141,9 +254,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
   const float* __restrict__ Bbase = p.Bm;
   float* __restrict__ Cbase = p.C;
   if (p.batches > 0) {
-    // Batched mode: bin = 8 * set + xcd -- all tiles of one bin run on ONE XCD, whose L2 then holds that bin's
-    // operands (a bin's filter matrix is 8 MB: spread over the XCDs every L2 would stream all of them).
-    // Row tiles fastest, so the workgroups sharing a filter panel sit next to each other.
+    // Batched mode: bin = 8 * set + xcd (see bin_tile, written out here: the helper perturbs this kernel's schedule)
     const int per_bin = p.tiles_m * p.tiles_n;
     const int set = local / per_bin, t = local - set * per_bin;
     const int bin = set * 8 + xcd;
@@ -186,17 +297,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
   for (int i = 0; i < A_DMA; ++i) {
     const int row = (wave * A_DMA + i) * 8 + (lane >> 3);
     asrc[i] = Abase + a_off[row];
-    aslot4[i] = (((lane & 7) ^ ((row >> 1) & 7))) * 4;
+    aslot4[i] = swz_slot4(lane, row);
   }
-  const float* bsrc[B_DMA];
-#pragma unroll
-  for (int i = 0; i < B_DMA; ++i) {
-    bsrc[i] = Bbase + n0 + (lane % B_LPR) * 4;
-  }
+  const float* const bsrc = Bbase + n0 + (lane % B_LPR) * 4;
   const int ktail = p.Kvalid - 4;   // last float4 inside the valid reduction range
 
   const int kplast = p.Kp - 1;
-  constexpr int N_DMA = A_DMA + B_DMA;
   // DMA piece `pc` (compile-time) of the tile starting at reduction index k0: pieces [0, A_DMA) are
   // 8-row groups of the im2col operand, the rest 1-KiB groups of filter rows.
   // (The scalar-base inline-asm DMA of the filter-gradient kernel measured SLOWER here, 123 vs 128
@@ -210,9 +316,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
   for (int i = 0; i < B_DMA; ++i) {
     if (BT) {            // rows of Bt like rows of A: instruction i covers tile rows (wave * B_DMA + i) * 8 .. +8 (clamped into Bt)
       const int row = (wave * B_DMA + i) * 8 + (lane >> 3);
-      bptr[i] = Bbase + (long)min(n0 + row, p.bt_rows - 1) * p.bt_ld + (((lane & 7) ^ ((row >> 1) & 7))) * 4;
+      bptr[i] = Bbase + (long)min(n0 + row, p.bt_rows - 1) * p.bt_ld + swz_slot4(lane, row);
     } else {
-      bptr[i] = bsrc[i] + (long)((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * p.Np;
+      bptr[i] = bsrc + (long)((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * p.Np;
     }
   }
   auto dma_piece = [&](int pc, int k0, int buf) {
@@ -220,12 +326,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
       const int i = pc < A_DMA ? pc : 0;
       // reduction tail: clamp so the read stays inside the row span (values there are unused)
       const float* g = FAST ? aptr[i] + k0 : asrc[i] + min(k0 + aslot4[i], ktail);
-      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(As + buf * A_SZ + (wave * A_DMA + pc) * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)g, (st::lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
     } else {
       const int i = pc - A_DMA < B_DMA ? pc - A_DMA : 0;
       const int krow = min(k0 + (wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR, kplast);
-      const float* g = BT ? bptr[i] + k0 : (FAST ? bptr[i] + (long)k0 * p.Np : bsrc[i] + (long)krow * p.Np);
-      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
+      const float* g = BT ? bptr[i] + k0 : (FAST ? bptr[i] + (long)k0 * p.Np : bsrc + (long)krow * p.Np);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)g, (st::lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
     }
   };
   auto dma = [&](int k0, int buf) {
@@ -233,29 +339,21 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
     for (int pc = 0; pc < N_DMA; ++pc) dma_piece(pc, k0, buf);
   };
 
-  f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x16 acc[MT][NT] = {};
 
   // fragment addresses: A row = wm*WTM + mt*32 + l31, logical slot 2q+h, XOR-swizzled
   int a_frag[4];
   {
     const int row = wm * WTM + l31;
-    const int sw = (row >> 1) & 7;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) a_frag[q] = swz_frag(row, q, h);
   }
   const int b_frag = (4 * h) * BN + wn * WTN + NT * l31;
   int bt_frag[4];        // BT: fragment of column tile n = bt_frag[q] + n * 32 * BK (row = wn * WTN + n * 32 + l31; same swizzle for every n)
   {
     const int row = wn * WTN + l31;
-    const int sw = (row >> 1) & 7;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) bt_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) bt_frag[q] = swz_frag(row, q, h);
   }
 
   // Reduction order.  k = tap * cp + channel.  With more than one tap the k-tiles are walked
@@ -282,89 +380,17 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_kernel(NNParams p) {
   // One k-tile.  CUR (LDS slot) and MORE (is there a next tile to stage) are compile-time: in the FAST
   // variant the steady-state loop below is then one basic block per pair of tiles -- no uniform branches
   // cutting hipcc's MFMA / ds_read / DMA interleave, LDS addresses folded into instruction offsets.
+  // one k-tile (FAST: the steady state below is one basic block per pair of tiles)
   auto stage = [&](auto cur_c, auto more_c) {
-    constexpr int CUR = decltype(cur_c)::value;
-    constexpr bool MORE = decltype(more_c)::value;
     const int nq = FAST ? 4 : tile_nq(tap, chunk);
     // next tile
     int ntap = tap, nchunk = chunk;
     if (tap_inner) { if (++ntap == p.taps) { ntap = 0; ++nchunk; } } else { ++nchunk; }
     const int nk0 = tile_k0(ntap, nchunk);
     tap = ntap; chunk = nchunk;
-    const float* as = As + CUR * A_SZ;
-    const float* bs = Bs + CUR * B_SZ + (BT ? 0 : b_frag);
-    // Software-pipelined fragment reads: the reads of k-quad q+1 are issued BEFORE the 16 MFMAs of
-    // quad q (sched_barrier pins the order; hipcc otherwise sinks the reads behind the MFMAs to
-    // save registers and then stalls on LDS latency four times per tile).
-    f32x4 af[4][MT];
-    bvec bf[4][4];
-    f32x4 bft[4][NT];
-    auto read_frags = [&](int q) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) af[q][i] = *reinterpret_cast<const f32x4*>(as + a_frag[q] + i * 32 * BK);
-      if (BT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) bft[q][n] = *reinterpret_cast<const f32x4*>(bs + bt_frag[q] + n * 32 * BK);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bf[q][j] = *reinterpret_cast<const bvec*>(bs + (8 * q + j) * BN);
-      }
-    };
-    read_frags(0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      // The DMA of the next tile is issued in slices between the MFMA quads: a burst of 8 DMA
-      // instructions stalls the wave's issue long enough to drain the matrix pipe, two (~60 cycles
-      // each) hide in the shadow of the MFMAs in flight.  (One per 4 MFMAs with more sched_barriers
-      // measured slower: the pinning then also blocks hipcc's own ds_read/MFMA interleave.)
-      if (MORE) {
-#pragma unroll
-        for (int pc = q; pc < N_DMA; pc += 4) dma_piece(pc, nk0, CUR ^ 1);
-      }
-      if (q < 3) read_frags(q + 1);
-      if (q < nq) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-              acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][i][j], BT ? bft[q][n][j] : vget<NT>(bf[q][j], n), acc[i][n], 0, 0, 0);
-      }
-      if (SGB) {
-        // interleave request: one ds_read behind each of the first MFMAs, then the address VALU and
-        // one DMA behind later MFMAs (each MFMA shadows ~64 issue cycles)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x006, 8, 0);
-          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();                         // also drains this wave's DMA (vmcnt) before anyone reads it
+    S::template run<decltype(cur_c)::value, decltype(more_c)::value>(As, Bs, a_frag, bt_frag, b_frag, acc, nq, dma_piece, nk0);
   };
-  using std::integral_constant;
-  using std::true_type;
-  using std::false_type;
-  int kt = 0;
-  for (; kt + 2 < nk; kt += 2) {             // steady state: both tiles have a successor
-    stage(integral_constant<int, 0>{}, true_type{});
-    stage(integral_constant<int, 1>{}, true_type{});
-  }
-  if (kt + 2 == nk) {
-    stage(integral_constant<int, 0>{}, true_type{});
-    stage(integral_constant<int, 1>{}, false_type{});
-  } else if (kt + 1 == nk) {
-    stage(integral_constant<int, 0>{}, false_type{});
-  }
+  nn_stage_pairs(nk, stage);
 
   if constexpr (BT) {
     // epilogue of the transposed-operand variant: column tile n of this lane is column n * 32 + l31 of the wave's block
@@ -544,11 +570,10 @@ struct BinsParams {
 // (gbwd = gfwd^T); staged and read like the A operand, a lane's two columns 32 apart (see gemm_nn_kernel).
 template <int BM, int BN, int WMW, int WNW, int MINW, bool BT>
 __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams p) {
-  constexpr int WTM = BM / WMW, WTN = BN / WNW;
-  constexpr int MT = WTM / 32, NT = WTN / 32;
-  constexpr int A_DMA = BM / 32, B_DMA = BN / 32, B_LPR = BN / 4;
-  constexpr int A_SZ = BM * BK, B_SZ = BK * BN;
-  constexpr int N_DMA = A_DMA + B_DMA;
+  typedef NNStage<BM, BN, WMW, WNW, BT> S;
+  constexpr int WTM = S::WTM, WTN = S::WTN, MT = S::MT, NT = S::NT;
+  constexpr int A_DMA = S::A_DMA, B_DMA = S::B_DMA, N_DMA = S::N_DMA, A_SZ = S::A_SZ, B_SZ = S::B_SZ;
+  constexpr int B_LPR = BN / 4;
   static_assert(WMW * WNW == 4 && MT >= 1 && NT == 2 && A_DMA >= 1 && B_DMA >= 1, "tile config");
   typedef typename FVec<NT>::type bvec;
   typedef unsigned long long u64;
@@ -580,14 +605,14 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
 #pragma unroll
   for (int i = 0; i < A_DMA; ++i) {
     const int row = (wave * A_DMA + i) * 8 + (lane >> 3);
-    a_lane[i] = row * (int)p.lda + (((lane & 7) ^ ((row >> 1) & 7))) * 4;           // (BM rows of a bin: fits an int)
+    a_lane[i] = row * (int)p.lda + swz_slot4(lane, row);                                // (BM rows of a bin: fits an int)
   }
   int b_lane[B_DMA];
 #pragma unroll
   for (int i = 0; i < B_DMA; ++i) {
     if (BT) {
       const int row = (wave * B_DMA + i) * 8 + (lane >> 3);
-      b_lane[i] = row * (int)p.ldb + (((lane & 7) ^ ((row >> 1) & 7))) * 4;                             // (BN rows of Bt)
+      b_lane[i] = row * (int)p.ldb + swz_slot4(lane, row);                                                  // (BN rows of Bt)
     } else {
       b_lane[i] = ((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * (int)p.ldb + (lane % B_LPR) * 4;   // (32 rows of B)
     }
@@ -595,16 +620,14 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
   int bt_frag[4];
   {
     const int row = wn * WTN + l31;
-    const int sw = (row >> 1) & 7;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) bt_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) bt_frag[q] = swz_frag(row, q, h);
   }
   int a_frag[4];
   {
     const int row = wm * WTM + l31;
-    const int sw = (row >> 1) & 7;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) a_frag[q] = swz_frag(row, q, h);
   }
   const int b_frag = (4 * h) * BN + wn * WTN + NT * l31;
   const int tcol = wn * WTN + NT * l31;                      // this lane's first column inside the tile (the partial tiles'
@@ -627,20 +650,14 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
     auto dma_piece = [&](int pcx, int k0, int buf) {
       if (pcx < A_DMA) {
         const int i = pcx < A_DMA ? pcx : 0;
-        __builtin_amdgcn_global_load_lds((gptr_t)(aptr[i] + k0), (lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((st::gptr_t)(aptr[i] + k0), (st::lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
       } else {
         const int i = pcx - A_DMA < B_DMA ? pcx - A_DMA : 0;
-        __builtin_amdgcn_global_load_lds((gptr_t)(BT ? bptr[i] + k0 : bptr[i] + (long)k0 * p.ldb), (lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((st::gptr_t)(BT ? bptr[i] + k0 : bptr[i] + (long)k0 * p.ldb), (st::lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
       }
     };
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MT][NT] = {};
 
     int k0 = pc.kt0 * BK;                                    // reduction index of the tile being COMPUTED
 #pragma unroll
@@ -648,72 +665,12 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
     __syncthreads();                                         // (drains the DMA; the previous piece's stores too)
 
     auto stage = [&](auto cur_c, auto more_c) {
-      constexpr int CUR = decltype(cur_c)::value;
-      constexpr bool MORE = decltype(more_c)::value;
       const int nk0 = k0 + BK;
       k0 = nk0;
-      const float* as = As + CUR * A_SZ;
-      const float* bs = Bs + CUR * B_SZ + (BT ? 0 : b_frag);
-      f32x4 af[4][MT];
-      bvec bf[4][4];
-      f32x4 bft[4][NT];
-      auto read_frags = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) af[q][i] = *reinterpret_cast<const f32x4*>(as + a_frag[q] + i * 32 * BK);
-        if (BT) {
-#pragma unroll
-          for (int n = 0; n < NT; ++n) bft[q][n] = *reinterpret_cast<const f32x4*>(bs + bt_frag[q] + n * 32 * BK);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bf[q][j] = *reinterpret_cast<const bvec*>(bs + (8 * q + j) * BN);
-        }
-      };
-      read_frags(0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (MORE) {
-#pragma unroll
-          for (int pcx = q; pcx < N_DMA; pcx += 4) dma_piece(pcx, nk0, CUR ^ 1);
-        }
-        if (q < 3) read_frags(q + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-              acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][i][j], BT ? bft[q][n][j] : vget<NT>(bf[q][j], n), acc[i][n], 0, 0, 0);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x006, 8, 0);
-          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __syncthreads();
+      S::template run<decltype(cur_c)::value, decltype(more_c)::value>(As, Bs, a_frag, bt_frag, b_frag, acc, 4, dma_piece, nk0);
     };
-    using std::integral_constant;
-    using std::true_type;
-    using std::false_type;
     const int nk = pc.kt1 - pc.kt0;
-    int kt = 0;
-    for (; kt + 2 < nk; kt += 2) {
-      stage(integral_constant<int, 0>{}, true_type{});
-      stage(integral_constant<int, 1>{}, true_type{});
-    }
-    if (kt + 2 == nk) {
-      stage(integral_constant<int, 0>{}, true_type{});
-      stage(integral_constant<int, 1>{}, false_type{});
-    } else if (kt + 1 == nk) {
-      stage(integral_constant<int, 0>{}, false_type{});
-    }
+    nn_stage_pairs(nk, stage);
 
     if (pc.kt0 > 0) {
       // a piece that does not hold the tile's start (always the first piece of this run): publish the partial tile --
@@ -829,11 +786,10 @@ __global__ __launch_bounds__(256) void g3_zero_out_kernel(float* __restrict__ C,
 template <int BM, bool BT>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nn_g3_kernel(G3Params p) {
   constexpr int BN = 128, WMW = 2, WNW = 2;
-  constexpr int WTM = BM / WMW, WTN = BN / WNW;
-  constexpr int MT = WTM / 32, NT = WTN / 32;
-  constexpr int A_DMA = BM / 32, B_DMA = BN / 32, B_LPR = BN / 4;
-  constexpr int A_SZ = BM * BK, B_SZ = BK * BN;
-  constexpr int N_DMA = A_DMA + B_DMA;
+  typedef NNStage<BM, BN, WMW, WNW, BT> S;
+  constexpr int WTM = S::WTM, WTN = S::WTN, MT = S::MT, NT = S::NT;
+  constexpr int A_DMA = S::A_DMA, B_DMA = S::B_DMA, N_DMA = S::N_DMA, A_SZ = S::A_SZ, B_SZ = S::B_SZ;
+  constexpr int B_LPR = BN / 4;
   static_assert(MT >= 1 && NT == 2, "tile config");
   typedef typename FVec<NT>::type bvec;
 
@@ -841,13 +797,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nn_g3_kernel(G3Params p) {
   float* const As = smem;
   float* const Bs = smem + 2 * A_SZ;
 
-  // one bin per XCD at a time (its operands stay in that L2), row tiles fastest (see gemm_nn_kernel's batched mode)
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int per_bin = p.tiles_m * p.tiles_n;
-  const int set = local / per_bin, t = local - set * per_bin;
-  const int bin = set * 8 + xcd;
-  if (bin >= p.batches) return;
-  const int tile_n = t / p.tiles_m, tile_m = t - tile_n * p.tiles_m;
+  int bin, tile_m, tile_n;                       // one bin per XCD at a time (its operands stay in that L2): see bin_tile
+  if (!bin_tile(p.tiles_m, p.tiles_n, p.batches, bin, tile_m, tile_n)) return;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   const int tid = threadIdx.x;
@@ -864,13 +815,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nn_g3_kernel(G3Params p) {
 #pragma unroll
   for (int i = 0; i < A_DMA; ++i) {
     const int row = (wave * A_DMA + i) * 8 + (lane >> 3);
-    aptr[i] = Ab + (long)min(m0 + row, p.M - 1) * p.lda + (((lane & 7) ^ ((row >> 1) & 7))) * 4;   // rows past M: re-read, never stored
+    aptr[i] = Ab + (long)min(m0 + row, p.M - 1) * p.lda + swz_slot4(lane, row);   // rows past M: re-read, never stored
   }
 #pragma unroll
   for (int i = 0; i < B_DMA; ++i) {
     if (BT) {
       const int row = (wave * B_DMA + i) * 8 + (lane >> 3);
-      bptr[i] = Bb + (long)(n0 + row) * p.ldb + (((lane & 7) ^ ((row >> 1) & 7))) * 4;
+      bptr[i] = Bb + (long)(n0 + row) * p.ldb + swz_slot4(lane, row);
     } else {
       bptr[i] = Bb + (long)((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * p.ldb + n0 + (lane % B_LPR) * 4;
     }
@@ -879,34 +830,28 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nn_g3_kernel(G3Params p) {
   auto dma_piece = [&](int pcx, long ao, long bo, int buf) {
     if (pcx < A_DMA) {
       const int i = pcx < A_DMA ? pcx : 0;
-      __builtin_amdgcn_global_load_lds((gptr_t)(aptr[i] + ao), (lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)(aptr[i] + ao), (st::lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
     } else {
       const int i = pcx - A_DMA < B_DMA ? pcx - A_DMA : 0;
-      __builtin_amdgcn_global_load_lds((gptr_t)(bptr[i] + bo), (lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)(bptr[i] + bo), (st::lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
     }
   };
   const long bstep = BT ? (long)BK : (long)BK * p.ldb;         // a k-tile further inside a plane
 
   int a_frag[4], bt_frag[4];
   {
-    const int row = wm * WTM + l31, sw = (row >> 1) & 7;
+    const int row = wm * WTM + l31;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) a_frag[q] = swz_frag(row, q, h);
   }
   {
-    const int row = wn * WTN + l31, sw = (row >> 1) & 7;
+    const int row = wn * WTN + l31;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) bt_frag[q] = row * BK + (((2 * q + h) ^ sw) * 4);
+    for (int q = 0; q < 4; ++q) bt_frag[q] = swz_frag(row, q, h);
   }
   const int b_frag = (4 * h) * BN + wn * WTN + NT * l31;
 
-  f32x16 acc[MT][NT], acc2[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x16 acc[MT][NT] = {}, acc2[MT][NT];
 
 #pragma unroll
   for (int pcx = 0; pcx < N_DMA; ++pcx) dma_piece(pcx, p.a_off[0], p.b_off[0], 0);
@@ -914,54 +859,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nn_g3_kernel(G3Params p) {
 
   // one k-tile into `tgt`; (nao, nbo): offsets of the tile to stage meanwhile
   auto stage = [&](auto cur_c, auto more_c, f32x16 (&tgt)[MT][NT], long nao, long nbo) __attribute__((always_inline)) {
-    constexpr int CUR = decltype(cur_c)::value;
-    constexpr bool MORE = decltype(more_c)::value;
-    const float* as = As + CUR * A_SZ;
-    const float* bs = Bs + CUR * B_SZ + (BT ? 0 : b_frag);
-    f32x4 af[4][MT];
-    bvec bf[4][4];
-    f32x4 bft[4][NT];
-    auto read_frags = [&](int q) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) af[q][i] = *reinterpret_cast<const f32x4*>(as + a_frag[q] + i * 32 * BK);
-      if (BT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) bft[q][n] = *reinterpret_cast<const f32x4*>(bs + bt_frag[q] + n * 32 * BK);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bf[q][j] = *reinterpret_cast<const bvec*>(bs + (8 * q + j) * BN);
-      }
-    };
-    read_frags(0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (MORE) {
-#pragma unroll
-        for (int pcx = q; pcx < N_DMA; pcx += 4) dma_piece(pcx, nao, nbo, CUR ^ 1);
-      }
-      if (q < 3) read_frags(q + 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int n = 0; n < NT; ++n)
-            tgt[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][i][j], BT ? bft[q][n][j] : vget<NT>(bf[q][j], n), tgt[i][n], 0, 0, 0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x006, 8, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();                         // also drains this wave's DMA (vmcnt) before anyone reads it
+    S::template run<decltype(cur_c)::value, decltype(more_c)::value>(As, Bs, a_frag, bt_frag, b_frag, tgt, 4, dma_piece, nao, nbo);
   };
   using std::integral_constant;
   using std::true_type;
@@ -1090,13 +988,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TNParams p) {
   const int l31 = lane & 31, h = lane >> 5;
   const int wk = wave / WNW, wn = wave % WNW;
 
-  f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x16 acc[MT][NT] = {};
 
   const int nstages = (m_end - m_begin + BMR - 1) / BMR;
 
@@ -1148,7 +1040,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TNParams p) {
         const float* g = isA ? Ab + p.amap.off(m) + acol : Zb + p.zmap.off(m) + zcol;
         if (mb + r >= m_end) g = g_zero_row;            // rows past the split end contribute zero
         float* dst = isA ? As + buf * A_SZ + pc * 256 : Zs + buf * Z_SZ + pc * 256;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((st::gptr_t)g, (st::lptr_t)dst, 16, 0, 0);
       }
     }
   };
@@ -1253,14 +1145,8 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_g3_kernel(TN3Params p) 
   float* const As = smem;
   float* const Zs = smem + 2 * A_SZ;
 
-  // all tiles of a bin on one XCD (blockIdx.x = 8 * (set * tiles + tile) + xcd, bin = 8 * set + xcd): the bin's two operands
-  // are read by its 32 tiles out of that L2
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int per_bin = p.tiles_k * p.tiles_n;
-  const int set = local / per_bin, t = local - set * per_bin;
-  const int bin = set * 8 + xcd;
-  if (bin >= p.batches) return;
-  const int tile_n = t / p.tiles_k, tile_k = t - tile_n * p.tiles_k;
+  int bin, tile_k, tile_n;                       // all tiles of a bin on one XCD, read out of its L2: see bin_tile
+  if (!bin_tile(p.tiles_k, p.tiles_n, p.batches, bin, tile_k, tile_n)) return;
   const int k0 = tile_k * BKO, n0 = tile_n * BN;
 
   const int tid = threadIdx.x;
@@ -1520,8 +1406,6 @@ __global__ void fill_kernel(float* dst, float v, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) dst[i] = v;
 }
-
-int npad_of(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)st::round_up(cout, 128)); }
 
 RowMap make_map(const st_tensor3& t, int first_row, int frame_stride, int frames) {
   RowMap m;
@@ -1863,15 +1747,6 @@ int st::gemm_tn_g3_batched(const float* A, long lda, long a_batch, const long a_
   return st::check_launch("gemm_tn_g3_batched");
 }
 
-namespace {
-
-bool tensor_ok(const st_tensor3* t) {
-  return t && t->base && t->batch > 0 && t->frames > 0 && t->channels > 0 && t->halo >= 0 &&
-         t->c_pitch % 16 == 0 && t->c_pitch >= t->channels && t->t_pitch >= t->halo + t->frames;
-}
-
-}  // namespace
-
 static int bwd_data_impl(const st_tensor3* dz, const float* packed_t, bool forward_filters, int width, int pad_left,
                          const st_tensor3* act, const st_tensor3* dx, float* dbias_dx, void* workspace,
                          size_t workspace_bytes, void* stream);
@@ -1913,7 +1788,7 @@ int st_packed_dims(int width, int cin_pitch, int cout, int* k_valid, int* k_pad,
   int kv = width * cin_pitch;
   if (k_valid) *k_valid = kv;
   if (k_pad) *k_pad = (int)st::round_up(kv, BK);
-  if (n_pad) *n_pad = npad_of(cout);
+  if (n_pad) *n_pad = st::npad_of(cout);
   return ST_OK;
 }
 
@@ -1934,7 +1809,7 @@ int st_zero_regions(const void* regions_device, int n_regions, void* stream) {
 }
 
 int st_zero_halos_f32(const st_tensor3* t, void* stream) {
-  ST_REQUIRE(tensor_ok(t), "st_zero_halos_f32: bad tensor descriptor");
+  ST_REQUIRE(st::tensor_ok(t), "st_zero_halos_f32: bad tensor descriptor");
   const int halo_rows = t->t_pitch - t->frames;
   if (halo_rows == 0) return ST_OK;
   const long total = (long)halo_rows * (t->c_pitch / 4);
@@ -1972,7 +1847,7 @@ int st_filters_flip_transpose_f32(const float* packed, int width, int cin, int c
                                   int cout_pitch, float* packed_t, void* stream) {
   ST_REQUIRE(packed && packed_t && cin <= cin_pitch && cout <= cout_pitch && cout_pitch % 16 == 0,
              "st_filters_flip_transpose_f32: bad args");
-  int np = npad_of(cout);
+  int np = st::npad_of(cout);
   int kvt, kpt, npt;
   if (int e = st_packed_dims(width, cout_pitch, cin, &kvt, &kpt, &npt)) return e;
   const int pad_rows = kpt - width * cout_pitch;          // < 32 rows of k-padding
@@ -1984,7 +1859,7 @@ int st_filters_flip_transpose_f32(const float* packed, int width, int cin, int c
 
 size_t st_conv1d_fwd_ws(const st_tensor3* x, const st_tensor3* y, int width) {
   if (!x || !y) return 0;
-  const int np = npad_of(y->channels);
+  const int np = st::npad_of(y->channels);
   const int M = y->batch * y->frames;
   const int nk = width > 1 ? st::ceil_div(x->c_pitch, BK) * width : st::ceil_div(x->c_pitch, BK);
   const int splits = fwd_splits(M, np, nk);
@@ -1999,7 +1874,7 @@ int st_conv1d_nwc_fwd_f32(const st_tensor3* x, const float* packed, const float*
 int st_conv1d_nwc_fwd_ws_f32(const st_tensor3* x, const float* packed, const float* bias, int width,
                              int stride, int pad_left, int relu, const st_tensor3* y, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(y) && packed, "conv fwd: bad tensor descriptor");
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(y) && packed, "conv fwd: bad tensor descriptor");
   ST_REQUIRE(width > 0 && stride > 0 && pad_left >= 0 && x->batch == y->batch, "conv fwd: bad shape");
   ST_REQUIRE(y->frames == st::ceil_div(x->frames, stride), "conv fwd: y.frames != ceil(x.frames/stride)");
   ST_REQUIRE(x->halo >= pad_left, "conv fwd: x.halo %d < pad_left %d", x->halo, pad_left);
@@ -2009,7 +1884,7 @@ int st_conv1d_nwc_fwd_ws_f32(const st_tensor3* x, const float* packed, const flo
   p.A = x->base;
   p.amap = make_map(*x, x->halo - pad_left, stride, y->frames);
   p.Bm = packed;
-  p.Np = npad_of(y->channels);
+  p.Np = st::npad_of(y->channels);
   p.C = y->base;
   p.cmap = make_map(*y, y->halo, 1, y->frames);
   p.bias = bias;
@@ -2033,7 +1908,7 @@ int st_conv1d_nwc_fwd_ws_f32(const st_tensor3* x, const float* packed, const flo
 
 size_t st_conv1d_bwd_data_ws(const st_tensor3* dz, const st_tensor3* dx, int width) {
   if (!dz || !dx) return 0;
-  const int np = npad_of(dx->channels), kp = (int)st::round_up((size_t)width * dz->c_pitch, BK);
+  const int np = st::npad_of(dx->channels), kp = (int)st::round_up((size_t)width * dz->c_pitch, BK);
   const int M = dx->batch * dx->frames;
   const int splits = nn_splits(M, np, kp);
   return splits > 1 ? (size_t)splits * M * np * sizeof(float) : 0;
@@ -2047,7 +1922,7 @@ int st_conv1d_nwc_bwd_data_f32(const st_tensor3* dz, const float* packed_t, int 
 
 size_t st_conv1d_bwd_data_bias_ws(const st_tensor3* dz, const st_tensor3* dx, int width) {
   if (!dz || !dx) return 0;
-  const int np = npad_of(dx->channels);
+  const int np = st::npad_of(dx->channels);
   const size_t rows = (size_t)std::max(st::ceil_div(dx->batch * dx->frames, 64) * 4, dx->batch * st::ceil_div(dx->frames, COLSUM_ROWS));
   return st::round_up(st_conv1d_bwd_data_ws(dz, dx, width), 256) + rows * np * sizeof(float) + 256;
 }
@@ -2060,8 +1935,8 @@ int st_conv1d_nwc_bwd_data_bias_f32(const st_tensor3* dz, const float* packed_t,
 
 int st_conv1d_1tap_bwd_data_bias_f32(const st_tensor3* dz, const float* packed, const st_tensor3* act, const st_tensor3* dx,
                                      float* dbias_dx, void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tensor_ok(dx) && dz->c_pitch % 32 == 0 && npad_of(dx->channels) % 128 == 0 &&
-                 npad_of(dz->channels) >= dz->c_pitch,
+  ST_REQUIRE(st::tensor_ok(dz) && st::tensor_ok(dx) && dz->c_pitch % 32 == 0 && st::npad_of(dx->channels) % 128 == 0 &&
+                 st::npad_of(dz->channels) >= dz->c_pitch,
              "conv 1-tap bwd_data: needs a channel pitch of dz that is a multiple of 32 and an input width that packs to 128s");
   return bwd_data_impl(dz, packed, true, 1, 0, act, dx, dbias_dx, workspace, workspace_bytes, stream);
 }
@@ -2073,19 +1948,19 @@ int st_conv1d_1tap_bwd_data_bias_f32(const st_tensor3* dz, const float* packed, 
 static int bwd_data_impl(const st_tensor3* dz, const float* packed_t, bool forward_filters, int width, int pad_left,
                          const st_tensor3* act, const st_tensor3* dx, float* dbias_dx, void* workspace,
                          size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && tensor_ok(dx) && packed_t, "conv bwd_data: bad tensor descriptor");
+  ST_REQUIRE(st::tensor_ok(dz) && st::tensor_ok(dx) && packed_t, "conv bwd_data: bad tensor descriptor");
   ST_REQUIRE(dz->batch == dx->batch && dz->frames == dx->frames, "conv bwd_data: stride-1 layers only");
   const int lead = width - 1 - pad_left;   // zero rows needed in front of dz frame 0
   ST_REQUIRE(lead >= 0 && dz->halo >= lead, "conv bwd_data: dz.halo %d < %d", dz->halo, lead);
   ST_REQUIRE(dz->frames + pad_left <= dz->t_pitch - dz->halo, "conv bwd_data: trailing halo of dz too small");
-  if (act) ST_REQUIRE(tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames &&
-                      act->c_pitch >= std::min(dx->c_pitch, npad_of(dx->channels)),
+  if (act) ST_REQUIRE(st::tensor_ok(act) && act->batch == dx->batch && act->frames == dx->frames &&
+                      act->c_pitch >= std::min(dx->c_pitch, st::npad_of(dx->channels)),
                       "conv bwd_data: mask tensor mismatch");
   NNParams p{};
   p.A = dz->base;
   p.amap = make_map(*dz, dz->halo - lead, 1, dx->frames);
   p.Bm = packed_t;
-  p.Np = npad_of(dx->channels);
+  p.Np = st::npad_of(dx->channels);
   p.C = dx->base;
   p.cmap = make_map(*dx, dx->halo, 1, dx->frames);
   if (act) {
@@ -2099,7 +1974,7 @@ static int bwd_data_impl(const st_tensor3* dz, const float* packed_t, bool forwa
   p.taps = width;
   p.cp = dz->c_pitch;
   if (forward_filters) {                       // Bt[n = input channel][k = output channel]: rows of the forward operand
-    p.bt_ld = npad_of(dz->channels);
+    p.bt_ld = st::npad_of(dz->channels);
     p.bt_rows = dx->c_pitch;
   }
   // long reductions on few output tiles (L8: K = 64000, N = 256) are split over K; needs the workspace
@@ -2157,13 +2032,13 @@ static int bwd_filter_splits(int M, int kp, int np) {
 
 size_t st_bias_grad_ws(const st_tensor3* dz) {
   if (!dz) return 0;
-  return (size_t)dz->batch * st::ceil_div(dz->frames, COLSUM_ROWS) * npad_of(dz->channels) * sizeof(float) + 256;
+  return (size_t)dz->batch * st::ceil_div(dz->frames, COLSUM_ROWS) * st::npad_of(dz->channels) * sizeof(float) + 256;
 }
 
 int st_bias_grad_f32(const st_tensor3* dz, float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(dz) && dbias && workspace && workspace_bytes >= st_bias_grad_ws(dz), "bias_grad: bad args");
+  ST_REQUIRE(st::tensor_ok(dz) && dbias && workspace && workspace_bytes >= st_bias_grad_ws(dz), "bias_grad: bad args");
   hipStream_t s = st::as_stream(stream);
-  const int np = npad_of(dz->channels);
+  const int np = st::npad_of(dz->channels);
   const int chunks = st::ceil_div(dz->frames, COLSUM_ROWS);
   float* partial = reinterpret_cast<float*>(workspace);
   const RowMap zmap = make_map(*dz, dz->halo, 1, dz->frames);
@@ -2175,7 +2050,7 @@ int st_bias_grad_f32(const st_tensor3* dz, float* dbias, void* workspace, size_t
 
 size_t st_conv1d_bwd_filter_ws(const st_tensor3* x, const st_tensor3* dz, int width) {
   if (!x || !dz) return 0;
-  int kp = (int)st::round_up((size_t)width * x->c_pitch, BK), np = npad_of(dz->channels);
+  int kp = (int)st::round_up((size_t)width * x->c_pitch, BK), np = st::npad_of(dz->channels);
   int M = dz->batch * dz->frames;
   int splits = bwd_filter_splits(M, kp, np);
   size_t slabs = splits > 1 ? (size_t)splits * kp * np * sizeof(float) : 0;
@@ -2186,7 +2061,7 @@ size_t st_conv1d_bwd_filter_ws(const st_tensor3* x, const st_tensor3* dz, int wi
 int st_conv1d_nwc_bwd_filter_f32(const st_tensor3* x, const st_tensor3* dz, int width, int stride,
                                  int pad_left, float* dpacked, float* dbias, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  ST_REQUIRE(tensor_ok(x) && tensor_ok(dz) && dpacked, "conv bwd_filter: bad tensor descriptor");
+  ST_REQUIRE(st::tensor_ok(x) && st::tensor_ok(dz) && dpacked, "conv bwd_filter: bad tensor descriptor");
   ST_REQUIRE(x->batch == dz->batch && dz->frames == st::ceil_div(x->frames, stride), "conv bwd_filter: bad shape");
   ST_REQUIRE(x->halo >= pad_left && (dz->frames - 1) * stride + width - pad_left <= x->t_pitch - x->halo,
              "conv bwd_filter: halo of x too small");
@@ -2200,7 +2075,7 @@ int st_conv1d_nwc_bwd_filter_f32(const st_tensor3* x, const st_tensor3* dz, int 
   p.M = dz->batch * dz->frames;
   p.Kvalid = width * x->c_pitch;
   p.Kp = (int)st::round_up(p.Kvalid, BK);
-  p.Np = npad_of(dz->channels);
+  p.Np = st::npad_of(dz->channels);
   p.z_cols = std::min(dz->c_pitch, p.Np);
   const int splits = bwd_filter_splits(p.M, p.Kp, p.Np);
   p.rows_per_split = (int)st::round_up(st::ceil_div(p.M, splits), 32);

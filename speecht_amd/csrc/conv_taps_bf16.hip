@@ -32,8 +32,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int TM = 128, TN = 128, TK = 64, CP = 256;
 constexpr int ST = 5;                                // filter ring depth
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void conv_taps_bf16_kernel(TapsParams p) {
       const int row = 2 * piece + prow;
       const long g = min(max(p.a_row0 + q0 + row, 0L), p.a_rows - 1);
       const unsigned short* src = p.A + g * CP + ((pch ^ (row & 15)) << 3);
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + piece * 512), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)src, (st::lptr_t)(smem + piece * 512), 16, 0, 0);
     }
   }
   // a filter stage: 16 pieces of eight channels x 128 bytes, wave v takes pieces 4 v .. 4 v + 3; lane i writes physical chunk
@@ -105,8 +103,8 @@ __global__ __launch_bounds__(256, 1) void conv_taps_bf16_kernel(TapsParams p) {
   auto issue = [&](int kt, int slot) {
 #pragma unroll
     for (int pi = 0; pi < 4; ++pi)
-      __builtin_amdgcn_global_load_lds((gptr_t)(bsrc[pi] + (long)kt * TK),
-                                       (lptr_t)(smem + (A_BYTES + slot * B_STAGE) / 2 + (wave * 4 + pi) * 512), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((st::gptr_t)(bsrc[pi] + (long)kt * TK),
+                                       (st::lptr_t)(smem + (A_BYTES + slot * B_STAGE) / 2 + (wave * 4 + pi) * 512), 16, 0, 0);
   };
 
   // fragment addresses.  Panel: row = 64 wm + 32 i + (lane & 31) + tap, chunk = 8 kc + 2 kk + h; filter stage: channel
@@ -252,14 +250,12 @@ __global__ __launch_bounds__(256, 1) void conv_taps_bf16_kernel(TapsParams p) {
   }
 }
 
-int npad_of(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)st::round_up(cout, 128)); }
-
 }  // namespace
 
 // operand `a` (plane a_plane) -> result `y` (plane y_plane): tap w of output frame t reads operand frame t + w - lead.
 bool st::conv_taps_bf16_eligible(const st_tensor3& a, const st_tensor3& y, int width, int lead, const st_tensor3* act) {
   if (st::tuning(st::TUNE_BF16_TAPS_PANEL) == 1) return false;
-  const int np = npad_of(y.channels);
+  const int np = st::npad_of(y.channels);
   if (a.c_pitch != CP || width < 2 || width > MAX_TAPS || np % TN || y.c_pitch % 16) return false;
   if (a.t_pitch != y.t_pitch || a.batch != y.batch || a.frames != y.frames || a.halo < lead) return false;
   if (act && (act->t_pitch != y.t_pitch || act->batch != y.batch || act->c_pitch < std::min(y.c_pitch, np))) return false;
@@ -287,7 +283,7 @@ int st::conv_taps_bf16(const st_tensor3& a, const void* a_plane, const void* fil
   p.width = width;
   p.c_cp = y.c_pitch;
   p.m_cp = act ? act->c_pitch : 0;
-  const int np = npad_of(y.channels);
+  const int np = st::npad_of(y.channels);
   p.n_store = std::min(y.c_pitch, np);
   p.relu = relu;
   p.tiles_m = (int)st::ceil_div(p.Q, (long)TM);

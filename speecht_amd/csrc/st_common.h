@@ -97,10 +97,22 @@ inline int check_launch(const char* what) {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// column pitch of packed filters and their products for `cout` output channels
+inline int npad_of(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)round_up(cout, 128)); }
+
+inline bool tensor_ok(const st_tensor3* t) {
+  return t && t->base && t->batch > 0 && t->frames > 0 && t->channels > 0 && t->halo >= 0 && t->c_pitch % 16 == 0 &&
+         t->c_pitch >= t->channels && t->t_pitch >= t->halo + t->frames;
+}
+
 // float offset of row (b, t) of a padded NWC tensor
 inline long row_offset(const st_tensor3& x, int b, int t) {
   return ((long)b * x.t_pitch + x.halo + t) * (long)x.c_pitch;
 }
+
+// operand types of the LDS-DMA builtin (__builtin_amdgcn_global_load_lds): global source, LDS destination
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -35,8 +35,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int TM = 128, TN = 128, TK = 32;         // tile: input channels x output channels x reduction rows per stage
 constexpr int STAGE_ELEMS = TK * 128;              // bf16 elements of one operand's stage (32 rows x 256 bytes)
@@ -158,10 +156,10 @@ __global__ __launch_bounds__(256, ST <= 4 ? 2 : 1) void wgrad_tr_bf16_kernel(TrP
     const unsigned short* b = bsrc + (long)kt * b_stage;
     unsigned short* la = As + buf * STAGE_ELEMS + wave * 8 * 128;
     unsigned short* lb = Bs + buf * STAGE_ELEMS + wave * 8 * 128;
-    __builtin_amdgcn_global_load_lds((gptr_t)a, (lptr_t)la, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr_t)(a + a_piece), (lptr_t)(la + 4 * 128), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr_t)b, (lptr_t)lb, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr_t)(b + b_piece), (lptr_t)(lb + 4 * 128), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((st::gptr_t)a, (st::lptr_t)la, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((st::gptr_t)(a + a_piece), (st::lptr_t)(la + 4 * 128), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((st::gptr_t)b, (st::lptr_t)lb, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((st::gptr_t)(b + b_piece), (st::lptr_t)(lb + 4 * 128), 16, 0, 0);
   };
 
   // fragment addresses (bytes inside a stage): 16-lane group g = lane >> 4 reads rows 8 (g >> 1) + 4 h + (l >> 2), l = lane & 15,
@@ -380,8 +378,6 @@ __global__ __launch_bounds__(256) void wgrad_tr_finish_kernel(const float* __res
   }
 }
 
-int npad_of(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)st::round_up(cout, 128)); }
-
 struct TrPlan {
   long z_row0, x_row0, rows;
   int stages, splits, stages_per_split, n_pad, mtiles_per_tap, tiles_m, tiles_n, chunks;
@@ -390,7 +386,7 @@ struct TrPlan {
 
 TrPlan tr_plan(const st_tensor3& x, const st_tensor3& dz, int width, int pad_left) {
   TrPlan t{};
-  t.n_pad = npad_of(dz.channels);
+  t.n_pad = st::npad_of(dz.channels);
   t.z_row0 = dz.halo;                                                     // the first real gradient row
   t.x_row0 = (long)dz.halo + (x.halo - pad_left) - dz.halo;               // its input row for tap 0
   t.rows = (long)(dz.batch - 1) * dz.t_pitch + dz.frames;                 // up to the last real gradient row
@@ -430,7 +426,7 @@ bool tr_eligible(const st_tensor3* x, const st_tensor3* dz, int width, int strid
   const long plane_rows = (long)x->batch * x->t_pitch;
   const long rows = (long)(dz->batch - 1) * dz->t_pitch + dz->frames;
   const long staged = cdiv(rows, TK) * TK;                                                 // rows the stages cover
-  const int n_pad = npad_of(dz->channels);
+  const int n_pad = st::npad_of(dz->channels);
   const long x_over = cdiv(x->c_pitch, TM) * TM - x->c_pitch, z_over = cdiv(n_pad, TN) * TN - dz->c_pitch;
   const long x_spill = x_over > 0 ? cdiv(x_over, x->c_pitch) : 0, z_spill = z_over > 0 ? cdiv(z_over, dz->c_pitch) : 0;
   const long x_last = (long)(x->halo - pad_left) + (width - 1) + staged - 1 + x_spill;     // furthest input row read
