@@ -90,7 +90,7 @@ def score_candidates(label, decodes, pair_by_row=False, device=True):
   dist = np.full((len(flat), 2), -1, dtype=np.int32)
   if flat:
     dev = decodes.ids.device
-    stream = decodes._stream if decodes._stream is not None else torch.cuda.current_stream(dev)
+    stream = decodes.stream
     with torch.cuda.stream(stream):
       d_mat = torch.as_tensor(mat).to(dev, non_blocking=False)
       d_lab_lens = torch.as_tensor(lab_lens).to(dev)

@@ -171,7 +171,7 @@ class GradientAllReducer:
   selects it without code changes.
   """
 
-  def __init__(self, flat_grads, layer_offsets, group=None, force=False, transport=None, compute_stream=None):
+  def __init__(self, flat_grads, layer_offsets, group=None, force=False, transport=None):
     self.flat = flat_grads
     self.group = group
     self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -184,7 +184,6 @@ class GradientAllReducer:
     self.buckets = default_buckets(sizes, layer_offsets)
     self._ready_at = {lo: (s, e) for lo, s, e in self.buckets}
     self._pending = []
-    self._compute_stream = compute_stream
     # called once per step right after the FIRST bucket (the top layers' slice, which also carries the update gate and the
     # mean-loss slot) has been handed to the all-reduce, with a function `wait(stream)` that makes `stream` wait for that
     # bucket's reduction only: SpeechModel.step reads the reduced slots back from there, long before back-prop ends
@@ -209,7 +208,9 @@ class GradientAllReducer:
     return role_stream(self.flat.device, 'collective')
 
   def _stream(self):
-    return self._compute_stream if self._compute_stream is not None else torch.cuda.current_stream(self.flat.device)
+    """The stream back-prop is enqueued on: torch's current one (an engine on a stream of its own runs under
+    ``torch.cuda.stream(engine.stream)``)."""
+    return torch.cuda.current_stream(self.flat.device)
 
   def on_layer_done(self, i):
     if not self.active or i not in self._ready_at:

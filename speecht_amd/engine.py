@@ -8,6 +8,10 @@ padded NWC activation tensors (engine_buffers.py), the role streams and the side
 input side (H2D staging, label uploads), CTC, clip + Adam, loss read-back and the decoders
 (engine_decode.py).  What differs between fp32, bf16x6 and bf16 -- derived operands and the forward / backward launch
 sequences -- lives in speecht_amd/modes/ behind `self.mode`.
+
+Where state lives: what outlives a shape and the modes share (weights, optimizer state, streams, host slots) is an attribute of the
+engine, created in `__init__`; what is a function of (batch, frames, knobs) alone is ONE `ShapeState` (engine_buffers.py) in
+`self.shape`, swapped as a whole when a shape comes round again; what belongs to one arithmetic is an attribute of the mode object.
 """
 import ctypes
 import math
@@ -18,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import Tensor3, call
-from .engine_buffers import DevTensor3, LayerSpec, _round_up, _StagedHostBatch, _Storage, channel_pitch, same_padding   # noqa: F401
+from .engine_buffers import DevTensor3, LayerSpec, ShapeState, _round_up, _StagedHostBatch, _Storage, channel_pitch, same_padding   # noqa: F401
 from .engine_decode import DecodeMixin, _PendingBeamDecode, _PendingDecode, beam_input_transform, merge_repeated_labels   # noqa: F401
 from .engine_streams import decoder_stream_pair, decoder_streams, role_stream   # noqa: F401
 from .modes import make_mode
@@ -81,7 +85,6 @@ class Wav2LetterEngine(DecodeMixin):
     self.gate_slots = self.reduce_buffer[self.n_flat:self.n_flat + 2]
     self.packed_t = [None] + [torch.zeros(l.kt_pad * l.nt_pad, dtype=torch.float32, device=self.device)
                               for l in self.layers[1:]]
-    self._packed_t_fresh = False
     # the update's device words: stats {global norm, clip scale, lr_t} and the update counts {applied, skipped because the norm
     # was not finite} (st_global_norm_clip_adam_counted_f32) -- one buffer, so that the loss read-back brings them with one copy
     self._update_words = torch.zeros(8, dtype=torch.int32, device=self.device)
@@ -93,34 +96,52 @@ class Wav2LetterEngine(DecodeMixin):
     self._applied_seen, self.updates_skipped, self.last_skip_norm = 0, 0, None
     self._updates_enqueued, self._updates_covered, self._count_version = 0, 0, 0
     self._tuning_epoch = _lib.TUNING_EPOCH[0]
-    self._shape = None
     self._storage = _Storage(self.device)
+    self.shape = None                              # the current (batch, frames)'s ShapeState; None before the first batch
+    self._shape_cache = {}                         # (batch, frames) -> ShapeState of the shapes seen before
     self.ctc_ws = None
-    self._wplanes_fresh = False
-    self._wtplanes_fresh = False
-    self._gfwd_fresh = False
-    self.fft = {}
-    self.fftb = {}
-    self.mode = make_mode(self)                    # the arithmetic mode's buffers and launch sequences (speecht_amd/modes/)
+    # the input side: H2D staging slots, the pinned ring of the int32 uploads and their copy stream (streams made on first use)
+    self._h2d, self._pin_ring, self._pin_turn = None, [[None, None] for _ in range(8)], 0
+    self._up_stream, self._uploads = None, []
+    self.max_label_len, self._rejected_labels, self.defer_label_errors = 0, [], False
+    # the side streams of `_on_side_stream` and the event each one's last chain ended with; forward graphs by (shape, generation)
+    self._side = self._side2 = self._side_done = self._side2_done = None
+    self._graphs, self._graph_seen = {}, set()
+    # pinned host buffers of the loss read-back; the decoders' host slots and stream (engine_decode.py)
+    self._loss_host, self._dec_host, self._dec_turn = None, [None, None], 0
+    self._beam_slots, self._beam_turn, self._decode_stream = [], 0, None
+    self.mode = make_mode(self)                    # the arithmetic mode's own state and launch sequences (speecht_amd/modes/)
     # lost stream-K hand-offs are counted per process by the library; this engine reports the ones after its creation
     seen = ctypes.c_uint32(0)
     call('st_streamk_lost_count', ctypes.byref(seen))
     self._sk_lost = [torch.zeros(1, dtype=torch.int32, pin_memory=True), int(seen.value)]
 
   def __getattr__(self, name):
-    """Mode-level helpers (`_use_fft`, `_transposed_in_place`, `_refresh_fft_filters`, ...) stay reachable on the engine: tests,
-    bench.py and the profiling scripts call a few of them.  Only reached when the engine itself has no such attribute."""
-    mode = self.__dict__.get('mode')
-    if mode is not None and not name.startswith('__') and hasattr(type(mode), name):
-      return getattr(mode, name)
+    """For OUTSIDE readers only (tests, bench.py, the profiling scripts): `eng.X`, `eng.fft`, `eng.Wb`, `eng._use_fft`, ... are
+    looked up in the current ShapeState, then in its mode part, then on the mode.  Read-only, and slow -- it runs after normal
+    look-up has failed; the package itself names `self.shape.X`, `self.mode.Wb` explicitly."""
+    d = self.__dict__                              # (not `self.shape`: that would come back here before __init__ has set it)
+    shape, mode = d.get('shape'), d.get('mode')
+    if not name.startswith('__'):
+      for owner in (shape, shape.mode if shape is not None else None, mode):
+        if owner is not None and hasattr(owner, name):
+          return getattr(owner, name)
     raise AttributeError("'{}' object has no attribute '{}'".format(type(self).__name__, name))
 
   # ---- plumbing --------------------------------------------------------------------------
 
   @property
+  def stream(self):
+    """Where the engine enqueues: its own stream (or the side stream `_on_side_stream` has swapped in), else torch's current one."""
+    return self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+
+  @property
   def stream_ptr(self):
-    s = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    return ctypes.c_void_p(s.cuda_stream)
+    return ctypes.c_void_p(self.stream.cuda_stream)
+
+  @property
+  def _shape(self):
+    return self.shape and (self.shape.batch, self.shape.frames)
 
   def _slice(self, flat, i):
     fo, bo = self.offsets[i]
@@ -186,8 +207,7 @@ class Wav2LetterEngine(DecodeMixin):
   @step_count.setter
   def step_count(self, value):
     """Sets the device count (ordered behind whatever the stream holds) and its mirror."""
-    stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    with torch.cuda.stream(stream):
+    with torch.cuda.stream(self.stream):
       self.update_counts[:1].fill_(int(value))
     self._applied_seen = int(value)
     self._updates_covered = self._updates_enqueued
@@ -195,8 +215,7 @@ class Wav2LetterEngine(DecodeMixin):
 
   def sync_update_counts(self):
     """Read the update counts (and the last update's norm) back now: waits for everything enqueued on the engine's stream."""
-    stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    with torch.cuda.stream(stream):
+    with torch.cuda.stream(self.stream):
       words = self._update_words.cpu()
     self._updates_covered = self._updates_enqueued
     self._take_update_words(words)
@@ -209,10 +228,7 @@ class Wav2LetterEngine(DecodeMixin):
 
   def mark_weights_changed(self):
     """Call after writing ``self.params`` directly: derived operand copies are rebuilt on next use."""
-    self._packed_t_fresh = False
-    self._wplanes_fresh = False
-    self._wtplanes_fresh = False
-    self._gfwd_fresh = False
+    self.mode.weights_changed()
 
   def _unpack(self, flat):
     out = []
@@ -241,7 +257,8 @@ class Wav2LetterEngine(DecodeMixin):
 
   # ---- activation buffers ------------------------------------------------------------------
 
-  def _tensor(self, name, batch, frames, channels, halo_l, halo_r, clear=False):
+  def _tensor(self, ranges, name, batch, frames, channels, halo_l, halo_r, clear=False):
+    """A padded NWC view on the named storage; the bytes to zero when the shape is re-entered are appended to ``ranges``."""
     storage, fresh = self._storage.view(name, DevTensor3.numel(batch, frames, channels, halo_l, halo_r))
     t = DevTensor3(storage, batch, frames, channels, halo_l, halo_r)
     # what has to happen whenever the shape is (re-)entered on storage another shape has written: the other shape's interiors
@@ -251,31 +268,27 @@ class Wav2LetterEngine(DecodeMixin):
         t.buf.zero_()
       else:
         call('st_zero_halos_f32', t.ref, self.stream_ptr)
-    log = self.__dict__.get('_describe_log')
-    if log is not None:
-      # (byte ranges: the whole view, or the halo rows -- the rows behind utterance b and in front of b + 1 are one range)
-      base, row = t.buf.data_ptr(), t.c_pitch * 4
-      if clear:
-        log.append((base, t.buf.numel() * 4))
-      else:
-        tail = t.t_pitch - t.halo - t.frames
-        for b in range(t.batch + 1):
-          lo = b * t.t_pitch - (tail if b > 0 else 0)
-          hi = b * t.t_pitch + (t.halo if b < t.batch else 0)
-          if hi > lo:
-            log.append((base + lo * row, (hi - lo) * row))
+    # (byte ranges: the whole view, or the halo rows -- the rows behind utterance b and in front of b + 1 are one range)
+    base, row = t.buf.data_ptr(), t.c_pitch * 4
+    if clear:
+      ranges.append((base, t.buf.numel() * 4))
+    else:
+      tail = t.t_pitch - t.halo - t.frames
+      for b in range(t.batch + 1):
+        lo = b * t.t_pitch - (tail if b > 0 else 0)
+        hi = b * t.t_pitch + (t.halo if b < t.batch else 0)
+        if hi > lo:
+          ranges.append((base + lo * row, (hi - lo) * row))
     return t
 
   # ---- shapes seen before -----------------------------------------------------------------------------------------
   # The reference pads every batch to its own longest member (speech_input.py:37-45): (B, max_T) changes nearly every step, and a
   # training run walks the same few hundred shapes over and over.  Describing a shape is ~60 C calls (geometry, workspace sizes,
   # plans) and as many Python objects -- 0.55 ms of host time in fp32, 1.0 ms with bf16 activations, where it is what bounds the
-  # step (2.4 ms of kernels, enqueued in 1.0 ms).  A description is therefore kept per (B, T): re-entering a shape puts the cached
-  # descriptors back, re-zeroes what another shape's interiors may have overwritten (halo rows, the input tensor, the bf16
-  # planes: ONE launch over a device table of byte ranges, st_zero_regions) and re-evaluates only what depends on the shape left behind (the modes' `reenter`: stale filter spectra when the set
+  # step (2.4 ms of kernels, enqueued in 1.0 ms).  A description -- one ShapeState (engine_buffers.py) -- is therefore kept per
+  # (B, T): re-entering a shape makes that object `self.shape` again, re-zeroes what another shape's interiors may have
+  # overwritten (halo rows, the input tensor, the bf16 planes: ONE launch over a device table of byte ranges, st_zero_regions) and re-evaluates only what depends on the shape left behind (the modes' `reenter`: stale filter spectra when the set
   # of frequency-domain layers changed, transform tables).  Entries die with the storage generation they were described on.
-  _SHAPE_ATTRS = ('X', 'dZ', 'geo', 't_out', 'loss_pair', 'loss', 'loss_lo', 'ctc_status', 'dec_ids', 'dec_lens', 'dec_score')
-
   def _shape_knobs(self):
     env = os.environ.get
     return (self.fft_conv, self.fft_min_width, self.fft_min_rows, self.fft_min_rows_narrow, self.fft_first_layer,
@@ -283,36 +296,33 @@ class Wav2LetterEngine(DecodeMixin):
             env('ST_BF16_WGRAD_TR'))
 
   def _reenter_shape(self, batch, frames):
-    """Put a cached description of (batch, frames) back; False when there is none (or it is stale)."""
-    cache = self.__dict__.get('_shape_cache')
-    entry = cache.get((batch, frames)) if cache else None
-    if entry is None or entry['generation'] != self._storage.generation or entry['knobs'] != self._shape_knobs():
+    """Make a cached description of (batch, frames) the current one; False when there is none (or it is stale)."""
+    entry = self._shape_cache.get((batch, frames))
+    if entry is None or entry.generation != self._storage.generation or entry.knobs != self._shape_knobs():
       return False
-    self.__dict__.update(entry['state'])
-    table, count = entry['zero']
+    self.shape = entry
+    table, count = entry.zero
     if count:
       call('st_zero_regions', self._ptr(table), count, self.stream_ptr)
-    self.mode.reenter(entry['mode'])
-    self._shape = (batch, frames)
+    self.mode.reenter(entry)
     return True
 
-  def _remember_shape(self, batch, frames, ranges):
-    if not self.mode.shape_attrs or os.environ.get('ST_SHAPE_CACHE', '1') == '0':
+  def _remember_shape(self, sh):
+    if not self.mode.cache_shapes or os.environ.get('ST_SHAPE_CACHE', '1') == '0':
       return
-    cache = self.__dict__.setdefault('_shape_cache', {})
-    generation = self._storage.generation
-    if any(e['generation'] != generation for e in cache.values()) or len(cache) >= 4096:
+    cache = self._shape_cache
+    sh.generation, sh.knobs = self._storage.generation, self._shape_knobs()
+    if any(e.generation != sh.generation for e in cache.values()) or len(cache) >= 4096:
       cache.clear()                                  # (their views may point into buffers that have been replaced since)
-    state = {k: self.__dict__[k] for k in self._SHAPE_ATTRS + tuple(self.mode.shape_attrs) if k in self.__dict__}
     # the byte ranges to zero on re-entry as a device table, long ranges in pieces of 1 MB (one workgroup each: st_zero_regions)
     pieces = []
-    for address, nbytes in ranges:
+    for address, nbytes in sh.ranges:
       assert address % 16 == 0 and nbytes % 16 == 0, (address, nbytes)
       for off in range(0, nbytes, 1 << 20):
         pieces.append((address + off, min(1 << 20, nbytes - off)))
     table = torch.from_numpy(np.asarray(pieces, dtype=np.uint64).reshape(-1, 2).view(np.int64)).to(self.device) if pieces else None
-    cache[(batch, frames)] = dict(state=state, zero=(table, len(pieces)), generation=generation, knobs=self._shape_knobs(),
-                                  mode=self.mode.shape_token())
+    sh.zero, sh.ranges = (table, len(pieces)), None
+    cache[(sh.batch, sh.frames)] = sh
 
   def _ensure_shape(self, batch, frames):
     epoch = _lib.TUNING_EPOCH[0]
@@ -321,31 +331,28 @@ class Wav2LetterEngine(DecodeMixin):
       # may size workspaces, so the current shape is described anew (cached descriptions are keyed by the epoch) and every operand
       # derived from the weights is rebuilt, whatever its buffer's size says
       self._tuning_epoch = epoch
-      self._shape = None
+      self.shape = None
       self.mark_weights_changed()
-      self.__dict__.pop('_fft_table_key', None)
-      self.__dict__.pop('_fftb_table_key', None)
-    if self._shape == (batch, frames):
+      self.mode.forget_tables()
+    sh = self.shape
+    if sh is not None and sh.batch == batch and sh.frames == frames:
       return
     if self._reenter_shape(batch, frames):
       return
-    self._describe_log = ranges = []
-    try:
-      self._describe_shape(batch, frames)
-    finally:
-      self._describe_log = None
-    self._remember_shape(batch, frames, ranges)
+    self.shape = sh = self._describe_shape(batch, frames)
+    self._remember_shape(sh)
 
   def _describe_shape(self, batch, frames):
-    dev = self.device
-    self.X, self.dZ = [], []
+    """A new ShapeState for (batch, frames): views on the named storage (halo rows cleared where another shape has written it)
+    and the mode's part from its `alloc`.  Assigns nothing on the engine."""
+    sh = ShapeState(batch, frames)
     t = frames
     geo = []
     for l in self.layers:
       t_out, pl, pr = same_padding(t, l.width, l.stride)
       geo.append((t, t_out, pl, pr))
       t = t_out
-    self.geo = geo
+    sh.geo = geo
     for i, l in enumerate(self.layers):
       t_in, t_out, pl, pr = geo[i]
       halo_l, halo_r = pl, max(pr, (t_out - 1) * l.stride + l.width - pl - t_in)
@@ -355,23 +362,23 @@ class Wav2LetterEngine(DecodeMixin):
         halo_l += halo_l & 1
         halo_r += (halo_l + t_in + halo_r) & 1
       # X[0]'s pad channels are not written by any kernel: clear the whole view on re-use
-      self.X.append(self._tensor('X%d' % i, batch, t_in, l.cin, halo_l, halo_r, clear=(i == 0)))
+      sh.X.append(self._tensor(sh.ranges, 'X%d' % i, batch, t_in, l.cin, halo_l, halo_r, clear=(i == 0)))
       # gradient wrt this layer's pre-activation output; halo for its own back-prop-to-input conv
-      self.dZ.append(self._tensor('dZ%d' % i, batch, t_out, l.cout, l.width - 1 - pl, pl))
+      sh.dZ.append(self._tensor(sh.ranges, 'dZ%d' % i, batch, t_out, l.cout, l.width - 1 - pl, pl))
     last = self.layers[-1]
-    self.X.append(self._tensor('X%d' % len(self.layers), batch, geo[-1][1], last.cout, 0, 0))   # logits [B, T', C]
-    self.t_out = geo[-1][1]
+    sh.X.append(self._tensor(sh.ranges, 'X%d' % len(self.layers), batch, geo[-1][1], last.cout, 0, 0))   # logits [B, T', C]
+    sh.t_out = geo[-1][1]
     # per-utterance CTC losses as (hi, lo) float pairs: `loss` is the fp32 value (what tf.nn.ctc_loss returns), `loss_lo` what
     # fp32 cannot hold of -log p at that magnitude (st_ctc_loss_grad_hilo_f32); one buffer, so one copy brings both back
     loss_buf = self._storage.view('loss', 2 * batch)[0]
-    self.loss_pair = loss_buf[:2 * batch]
-    self.loss, self.loss_lo = loss_buf[:batch], loss_buf[batch:2 * batch]
-    self.ctc_status = self._storage.view('ctc_status', batch, torch.int32)[0][:batch]
-    self.dec_ids = self._storage.view('dec_ids', batch * self.t_out, torch.int32)[0][:batch * self.t_out]
-    self.dec_lens = self._storage.view('dec_lens', batch, torch.int32)[0][:batch]
-    self.dec_score = self._storage.view('dec_score', batch)[0][:batch]
-    self.mode.alloc(batch)                         # what this arithmetic needs beyond the shared buffers
-    self._shape = (batch, frames)
+    sh.loss_pair = loss_buf[:2 * batch]
+    sh.loss, sh.loss_lo = loss_buf[:batch], loss_buf[batch:2 * batch]
+    sh.ctc_status = self._storage.view('ctc_status', batch, torch.int32)[0][:batch]
+    sh.dec_ids = self._storage.view('dec_ids', batch * sh.t_out, torch.int32)[0][:batch * sh.t_out]
+    sh.dec_lens = self._storage.view('dec_lens', batch, torch.int32)[0][:batch]
+    sh.dec_score = self._storage.view('dec_score', batch)[0][:batch]
+    sh.mode = self.mode.alloc(sh)                  # what this arithmetic needs beyond the shared buffers
+    return sh
 
   def reserve(self, batch, max_frames, min_frames=None, step=64):
     """Size every named device buffer for training batches of up to ``batch`` x ``max_frames`` BEFORE the first step: the
@@ -384,17 +391,15 @@ class Wav2LetterEngine(DecodeMixin):
     for frames in ladder:
       self._ensure_shape(int(batch), frames)
 
-  def _planes(self, name, numel, n=3, slack=0):
+  def _planes(self, ranges, name, numel, n=3, slack=0):
     """n zeroed bf16 planes of `numel` elements each (whole buffer cleared when re-used).  ``slack``: that many further zero
     elements stay allocated behind the (single) plane -- readable zeros for kernels that run past the last row
-    (st_conv1d_nwc_bwd_filter_tr_bf16); the returned view does not include them."""
+    (st_conv1d_nwc_bwd_filter_tr_bf16); the returned view does not include them.  The bytes to zero on re-entry go to ``ranges``."""
     buf, fresh = self._storage.view(name, n * numel + slack, torch.bfloat16)
     v = buf[:n * numel + slack]
     if not fresh:
       v.zero_()
-    log = self.__dict__.get('_describe_log')
-    if log is not None:
-      log.append((v.data_ptr(), -(-v.numel() * 2 // 16) * 16))      # (whole 16-byte units: the storage is allocated in larger ones)
+    ranges.append((v.data_ptr(), -(-v.numel() * 2 // 16) * 16))        # (whole 16-byte units: the storage is allocated in larger ones)
     return v[:n * numel]
 
   # ---- the path ----------------------------------------------------------------------------
@@ -403,7 +408,7 @@ class Wav2LetterEngine(DecodeMixin):
     """inputs: [B, T, input_size] (numpy or torch, any float dtype, or a ``speech_input.StagedBatch`` that the
     input pipeline already copied to the device); seq_lens: [B] unpadded frames."""
     if hasattr(inputs, 'event') and hasattr(inputs, 'tensor'):
-      stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+      stream = self.stream
       stream.wait_event(inputs.event)              # H2D ran on the pipeline's copy stream
       inputs.tensor.record_stream(stream)          # keep the allocator from recycling it under the copy below
       staged, inputs = inputs, inputs.tensor
@@ -413,10 +418,10 @@ class Wav2LetterEngine(DecodeMixin):
     B, T, C = x.shape
     assert C == self.layers[0].cin, 'input_size mismatch'
     self._ensure_shape(B, T)
-    self.X[0].interior().copy_(x.to(torch.float32), non_blocking=True)
+    self.shape.X[0].interior().copy_(x.to(torch.float32), non_blocking=True)
     if staged is not None and hasattr(staged, 'consumed'):
       staged.taken = True
-      staged.consumed.record(self._stream if self._stream is not None else torch.cuda.current_stream(self.device))
+      staged.consumed.record(self.stream)
     self.seq_lens_host = np.asarray(seq_lens, dtype=np.int64)
     # the reference feeds sequence_lengths // 2 to CTC and the decoder (speech_model.py:74,114)
     self.ctc_lens = self._upload_i32((self.seq_lens_host // 2).astype(np.int32))
@@ -426,7 +431,7 @@ class Wav2LetterEngine(DecodeMixin):
     an intermediate host copy) on the engine's copy stream into one of two staging buffers in HBM.  Returns a
     handle for ``load_batch``; the copy of batch k+1 overlaps the kernels of batch k.  A staging buffer is
     re-used only after the compute stream has consumed it (event recorded by ``load_batch``)."""
-    if not hasattr(self, '_h2d'):
+    if self._h2d is None:
       self._h2d = dict(stream=role_stream(self.device, 'h2d'), slots=[None, None], turn=0)
     h = self._h2d
     x = torch.as_tensor(x_host)
@@ -468,8 +473,6 @@ class Wav2LetterEngine(DecodeMixin):
     """Small int32 host array -> device through a ring of pinned slots.  A hipMemcpyAsync from pageable memory
     only returns once the stream's earlier kernels have finished, which would stall the thread that enqueues
     the next batch behind the previous batch's forward; from pinned memory the copy is a stream operation."""
-    if not hasattr(self, '_pin_ring'):
-      self._pin_ring, self._pin_turn = [[None, None] for _ in range(8)], 0
     slot = self._pin_ring[self._pin_turn % len(self._pin_ring)]
     self._pin_turn += 1
     n = int(values.shape[0])
@@ -480,9 +483,9 @@ class Wav2LetterEngine(DecodeMixin):
     slot[0][:n].copy_(torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32)))
     # on the copy stream: the consumers (CTC, the decoders) come a whole forward pass later and wait for the event
     # there (`_wait_uploads`); on the compute stream three such copies cost the start of every step ~40 us
-    main = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    if not hasattr(self, '_up_stream'):
-      self._up_stream, self._uploads = role_stream(self.device, 'upload'), []
+    main = self.stream
+    if self._up_stream is None:
+      self._up_stream = role_stream(self.device, 'upload')
     with torch.cuda.stream(self._up_stream):
       dev = torch.empty(n, dtype=torch.int32, device=self.device)
       dev.copy_(slot[0][:n], non_blocking=True)
@@ -495,9 +498,9 @@ class Wav2LetterEngine(DecodeMixin):
 
   def _wait_uploads(self):
     """The compute stream waits for the int32 uploads (lengths, labels) issued since the last call."""
-    ups = getattr(self, '_uploads', None)
+    ups = self._uploads
     if ups:
-      (self._stream if self._stream is not None else torch.cuda.current_stream(self.device)).wait_event(ups[-1])
+      self.stream.wait_event(ups[-1])
       del ups[:]
 
   def forward(self):
@@ -510,8 +513,6 @@ class Wav2LetterEngine(DecodeMixin):
     inference) the eleven kernels are launch-bound and the CPU cost of enqueueing them is the latency.
     Buffers, weights and the batch are read through the same device pointers on replay, so new inputs
     (``load_batch`` with the same shape) and in-place weight updates are picked up; a new shape captures anew."""
-    if not hasattr(self, '_graphs'):
-      self._graphs, self._graph_seen = {}, set()
     self.mode.prepare_forward_graph()              # derived operands are rebuilt, outside events waited for, outside the graph
     key = (self._shape, self._storage.generation)
     graph = self._graphs.get(key)
@@ -535,7 +536,7 @@ class Wav2LetterEngine(DecodeMixin):
 
   def logits_time_major(self):
     """[T', B, C] like tf.transpose(outputs, (1, 0, 2)) (speech_model.py:295)."""
-    return self.X[-1].interior().permute(1, 0, 2)
+    return self.shape.X[-1].interior().permute(1, 0, 2)
 
   def set_labels(self, label_list):
     lens = [len(l) for l in label_list]
@@ -549,7 +550,7 @@ class Wav2LetterEngine(DecodeMixin):
     self._rejected_labels = []
     if ids.size > 1 and (int(ids.min()) < 0 or int(ids.max()) >= self.num_classes - 1):
       bad = [b for b, l in enumerate(label_list) if len(l) and (min(l) < 0 or max(l) >= self.num_classes - 1)]
-      if not getattr(self, 'defer_label_errors', False):
+      if not self.defer_label_errors:
         raise ValueError('label ids must lie in [0, {}) (blank = {}); offending utterances: {}'.format(
             self.num_classes - 1, self.num_classes - 1, bad))
       # Data-parallel training (set by SpeechModel.enable_data_parallel): raising here, on this rank only, would leave
@@ -571,10 +572,10 @@ class Wav2LetterEngine(DecodeMixin):
     compute stream wait for both.  Used to put small HBM-bound operand preparation next to the CTC recursion, which is
     a latency chain of 500 dependent steps on 64 wavefronts and leaves the rest of the chip idle, and independent
     chains of the backward pass next to each other."""
-    main = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    if getattr(self, '_side', None) is None:
+    main = self.stream
+    if self._side is None:
       self._side = role_stream(self.device, 'side')
-    if second and getattr(self, '_side2', None) is None:
+    if second and self._side2 is None:
       self._side2 = role_stream(self.device, 'side2')
     stream = self._side2 if second else self._side
     fork = torch.cuda.Event()
@@ -593,15 +594,18 @@ class Wav2LetterEngine(DecodeMixin):
       self._side_done = done
 
   def _join_side_stream(self, second_only=False):
-    main = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-    for name in (('_side2_done',) if second_only else ('_side_done', '_side2_done')):
-      done = getattr(self, name, None)
-      if done is not None:
-        main.wait_event(done)
-        setattr(self, name, None)
+    main = self.stream
+    if self._side_done is not None and not second_only:
+      main.wait_event(self._side_done)
+      self._side_done = None
+    if self._side2_done is not None:
+      main.wait_event(self._side2_done)
+      self._side2_done = None
 
   def ctc_loss_grad(self, grad_scale):
-    B, T = self.X[-1].batch, self.X[-1].frames
+    sh = self.shape
+    logits = sh.X[-1]
+    B, T = logits.batch, logits.frames
     lib = _lib.load()
     need = lib.st_ctc_ws(B, T, self.max_label_len)
     if need == 0:
@@ -612,14 +616,13 @@ class Wav2LetterEngine(DecodeMixin):
     # the CTC recursion runs (a latency chain of 500 dependent steps on 64 wavefronts: the rest of the chip is idle)
     self.mode.refresh_under_ctc()
     self._wait_uploads()
-    call('st_ctc_loss_grad_hilo_f32', self.X[-1].ref, self._ptr(self.label_ids), self._ptr(self.label_offs),
-         self._ptr(self.ctc_lens), self.max_label_len, float(grad_scale), self._ptr(self.loss), self._ptr(self.loss_lo), self.dZ[-1].ref,
-         self._ptr(self.ctc_status), self._ptr(self.ctc_ws), self.ctc_ws.numel() * 4, self.stream_ptr)
-    if getattr(self, '_rejected_labels', None):            # labels refused on the host (deferred mode): status 2
-      stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
-      with torch.cuda.stream(stream):
-        self.ctc_status.index_fill_(0, torch.as_tensor(self._rejected_labels, dtype=torch.int64).to(self.device, non_blocking=True), 2)
-    call('st_ctc_status_gate_loss_f32', self._ptr(self.ctc_status), B, self._ptr(self.loss), self._ptr(self.loss_lo), float(grad_scale),
+    call('st_ctc_loss_grad_hilo_f32', logits.ref, self._ptr(self.label_ids), self._ptr(self.label_offs),
+         self._ptr(self.ctc_lens), self.max_label_len, float(grad_scale), self._ptr(sh.loss), self._ptr(sh.loss_lo), sh.dZ[-1].ref,
+         self._ptr(sh.ctc_status), self._ptr(self.ctc_ws), self.ctc_ws.numel() * 4, self.stream_ptr)
+    if self._rejected_labels:                              # labels refused on the host (deferred mode): status 2
+      with torch.cuda.stream(self.stream):
+        sh.ctc_status.index_fill_(0, torch.as_tensor(self._rejected_labels, dtype=torch.int64).to(self.device, non_blocking=True), 2)
+    call('st_ctc_status_gate_loss_f32', self._ptr(sh.ctc_status), B, self._ptr(sh.loss), self._ptr(sh.loss_lo), float(grad_scale),
          self._ptr(self.gate), self.stream_ptr)
 
   def backward(self, on_layer_done=None, hook_layers=None):
@@ -632,12 +635,6 @@ class Wav2LetterEngine(DecodeMixin):
     wanted = (lambda i: True) if hook_layers is None else (lambda i: i in hook_layers)
     return self.mode.backward(on_layer_done, wanted)
 
-  def _refresh_after_update(self):
-    """The operands the NEXT forward pass derives from the weights: filter spectra of the frequency-domain layers / the bf16 filter
-    copies -- the bottom layer's on the compute stream, the others on the side stream with an event each."""
-    if self._shape is not None:
-      self.mode.refresh_after_update()
-
   def apply_update(self, lr, max_grad_norm=5.0, beta1=0.9, beta2=0.999, eps=1e-3):
     """clip_by_global_norm + tf.train.AdamOptimizer(epsilon=1e-3) (speech_model.py:77-82).  The bias correction's t is 1 + the
     device's count of updates applied; a step whose batch CTC rejected (on any rank) or whose global norm is not finite leaves
@@ -648,7 +645,10 @@ class Wav2LetterEngine(DecodeMixin):
          self.norm_ws.numel() * 4, self.stream_ptr)
     self._updates_enqueued += 1
     self.mark_weights_changed()
-    self._refresh_after_update()
+    # the operands the NEXT forward pass derives from the weights: filter spectra of the frequency-domain layers / the bf16 filter
+    # copies -- the bottom layer's on the compute stream, the others on the side stream with an event each
+    if self.shape is not None:
+      self.mode.refresh_after_update()
 
   def fetch_losses(self, precise=False):
     """Per-utterance CTC losses [B] on the host, after checking the status words: both arrays come back in one
@@ -665,18 +665,19 @@ class Wav2LetterEngine(DecodeMixin):
     backward pass.  ``stream``: read back on that stream instead of the compute stream (data parallelism: the gate and the mean
     loss are final once the FIRST gradient bucket is reduced -- the caller makes ``stream`` wait for that bucket and nothing else,
     `GradientAllReducer.after_first_bucket`)."""
-    B = self.loss.numel()
-    if not hasattr(self, '_loss_host') or self._loss_host[0].numel() < 2 * B:
+    sh = self.shape
+    B = sh.loss.numel()
+    if self._loss_host is None or self._loss_host[0].numel() < 2 * B:
       self._loss_host = (torch.empty(max(2 * B, 128), dtype=torch.float32, pin_memory=True),
                          torch.empty(max(B, 64), dtype=torch.int32, pin_memory=True), torch.cuda.Event(),
                          torch.empty(16, dtype=torch.float32, pin_memory=True), torch.empty(8, dtype=torch.int32, pin_memory=True))
     loss_h, status_h, event, gate_h, words_h = self._loss_host
     if stream is None:
-      stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+      stream = self.stream
     lost_h = self._streamk_lost_async(stream)
     with torch.cuda.stream(stream):
-      loss_h[:2 * B].copy_(self.loss_pair, non_blocking=True)
-      status_h[:B].copy_(self.ctc_status, non_blocking=True)
+      loss_h[:2 * B].copy_(sh.loss_pair, non_blocking=True)
+      status_h[:B].copy_(sh.ctc_status, non_blocking=True)
       gate_h[:2].copy_(self.gate_slots, non_blocking=True)
       words_h.copy_(self._update_words, non_blocking=True)      # the update counts as of the updates enqueued so far
       event.record(stream)
@@ -725,11 +726,11 @@ class Wav2LetterEngine(DecodeMixin):
 
   def losses_precise(self):
     """float64 losses (hi + lo) straight from the device buffers, no status check (tests, bench parity)."""
-    pair = self.loss_pair.cpu().numpy().astype(np.float64)
-    B = self.loss.numel()
+    pair = self.shape.loss_pair.cpu().numpy().astype(np.float64)
+    B = self.shape.batch
     return pair[:B] + pair[B:]
 
   def check_ctc_status(self):
-    st = self.ctc_status.cpu().numpy()
+    st = self.shape.ctc_status.cpu().numpy()
     if st.any():
       raise ValueError('Not enough time for target transition sequence (utterances {})'.format(np.nonzero(st)[0].tolist()))

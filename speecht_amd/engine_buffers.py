@@ -57,6 +57,23 @@ class DevTensor3:
     return v[:, self.halo:self.halo + self.frames, :self.channels]
 
 
+class ShapeState:
+  """Everything an engine holds that is a function of (batch, frames, knobs) alone: the activation / gradient views, the layer
+  geometry, the loss and decoder outputs, and -- in ``mode`` -- what the arithmetic mode adds in its `alloc` (the engine never
+  looks into it).  Built by `Wav2LetterEngine._describe_shape`; the current one is ``engine.shape``, the ones seen before are in
+  the shape cache and come back whole, so no per-shape value can be left over from the shape before."""
+  __slots__ = ('batch', 'frames', 'X', 'dZ', 'geo', 't_out', 'loss_pair', 'loss', 'loss_lo', 'ctc_status', 'dec_ids', 'dec_lens',
+               'dec_score', 'mode', 'ranges', 'zero', 'generation', 'knobs')
+
+  def __init__(self, batch, frames):
+    self.batch, self.frames = batch, frames
+    self.X, self.dZ, self.mode = [], [], None
+    # byte ranges (address, bytes) that another shape's interiors may overwrite, logged while the views are made
+    # (`Wav2LetterEngine._tensor` / `_planes`); a cached state keeps them as a device table (table, count) in ``zero``
+    self.ranges = []
+    self.zero = (None, 0)
+
+
 class _Storage:
   """Grow-only named device buffers: real training batches change (B, max_T) every step, so the
   activation buffers are re-described per shape instead of re-allocated; only the halo rows have to

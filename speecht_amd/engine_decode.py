@@ -53,19 +53,18 @@ CANDIDATE_WORKSPACE_BYTES = 1 << 30
 
 class CandidateDecodes:
   """Outputs of ``lm_beam_search_decode_candidates`` for P weight triples on B utterances: ``ids`` [P, B, T] int32, ``lens``
-  [P, B] int32 (a prefix longer than T keeps its true length), ``log_prob`` [P, B] float32 -- device tensors of the engine's
-  stream -- and ``host()``: one (list of id lists, log_prob [B, 1]) per candidate, like ``lm_beam_search_decode``."""
+  [P, B] int32 (a prefix longer than T keeps its true length), ``log_prob`` [P, B] float32 -- device tensors of ``stream``, the
+  stream the engine decoded on -- and ``host()``: one (list of id lists, log_prob [B, 1]) per candidate, like ``lm_beam_search_decode``."""
 
   def __init__(self, ids, lens, log_prob, stream):
-    self.ids, self.lens, self.log_prob, self._stream = ids, lens, log_prob, stream
+    self.ids, self.lens, self.log_prob, self.stream = ids, lens, log_prob, stream
     self._host = None
 
   def __len__(self):
     return self.ids.shape[0]
 
   def _sync(self):
-    if self._stream is not None:                     # (an engine on a stream of its own: the copies below run on the current one)
-      self._stream.synchronize()
+    self.stream.synchronize()                        # (the copies of the callers run on the current stream, maybe another one)
 
   def lens_host(self):
     self._sync()
@@ -98,27 +97,28 @@ def merge_repeated_labels(seq):
 
 
 class DecodeMixin:
-  """The decoding entry points of `Wav2LetterEngine` (they read the logits X[-1] and the lengths the batch was loaded with)."""
+  """The decoding entry points of `Wav2LetterEngine` (they read the logits X[-1] and the decoder outputs of the current ShapeState
+  and the lengths the batch was loaded with; their host slots and stream are made in the engine's `__init__`)."""
 
   def greedy_decode(self, merge_repeated=True):
     """tf.nn.ctc_greedy_decoder (speech_model.py:113-115) -> (list of id lists, neg_sum_logits [B,1])."""
+    sh = self.shape
     self._wait_uploads()
-    call('st_ctc_greedy_decode', self.X[-1].ref, self._ptr(self.ctc_lens), int(merge_repeated),
-         self._ptr(self.dec_ids), self.t_out, self._ptr(self.dec_lens), self._ptr(self.dec_score), self.stream_ptr)
-    lens = self.dec_lens.cpu().numpy()
-    ids = self.dec_ids.view(-1, self.t_out).cpu().numpy()
-    return [ids[b, :lens[b]].tolist() for b in range(len(lens))], self.dec_score.cpu().numpy().reshape(-1, 1)
+    call('st_ctc_greedy_decode', sh.X[-1].ref, self._ptr(self.ctc_lens), int(merge_repeated),
+         self._ptr(sh.dec_ids), sh.t_out, self._ptr(sh.dec_lens), self._ptr(sh.dec_score), self.stream_ptr)
+    lens = sh.dec_lens.cpu().numpy()
+    ids = sh.dec_ids.view(-1, sh.t_out).cpu().numpy()
+    return [ids[b, :lens[b]].tolist() for b in range(len(lens))], sh.dec_score.cpu().numpy().reshape(-1, 1)
 
   def greedy_decode_async(self, merge_repeated=True):
     """``greedy_decode`` without the host synchronisation: launches the decoder and the D2H copies of its
     outputs into pinned host buffers and returns a handle; ``handle.result()`` waits for that batch only.  Lets
     a caller enqueue the next batch's forward before it reads this batch's transcripts (inference.transcribe)."""
+    sh = self.shape
     self._wait_uploads()
-    call('st_ctc_greedy_decode', self.X[-1].ref, self._ptr(self.ctc_lens), int(merge_repeated),
-         self._ptr(self.dec_ids), self.t_out, self._ptr(self.dec_lens), self._ptr(self.dec_score), self.stream_ptr)
-    B, n = self.dec_lens.numel(), self.dec_ids.numel()
-    if not hasattr(self, '_dec_host'):
-      self._dec_host, self._dec_turn = [None, None], 0
+    call('st_ctc_greedy_decode', sh.X[-1].ref, self._ptr(self.ctc_lens), int(merge_repeated),
+         self._ptr(sh.dec_ids), sh.t_out, self._ptr(sh.dec_lens), self._ptr(sh.dec_score), self.stream_ptr)
+    B, n = sh.dec_lens.numel(), sh.dec_ids.numel()
     self._dec_turn ^= 1
     slot = self._dec_host[self._dec_turn]
     if slot is None or slot[0].numel() < n or slot[1].numel() < B:
@@ -127,12 +127,12 @@ class DecodeMixin:
       slot = [torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True),
               torch.empty(max(B, 1), dtype=torch.int32, pin_memory=True), torch.cuda.Event()]
       self._dec_host[self._dec_turn] = slot
-    stream = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+    stream = self.stream
     with torch.cuda.stream(stream):
-      slot[0][:n].copy_(self.dec_ids, non_blocking=True)
-      slot[1][:B].copy_(self.dec_lens, non_blocking=True)
+      slot[0][:n].copy_(sh.dec_ids, non_blocking=True)
+      slot[1][:B].copy_(sh.dec_lens, non_blocking=True)
       slot[2].record(stream)
-    return _PendingDecode(slot, B, self.t_out)
+    return _PendingDecode(slot, B, sh.t_out)
 
   def beam_search_decode(self, beam_width=16, input_transform=None, merge_repeated=False):
     """LM-free CTC prefix beam search, top path (stock tf.nn.ctc_beam_search_decoder semantics; the
@@ -141,19 +141,20 @@ class DecodeMixin:
     searches on log10(softmax(logits) + 1e-8), the reference's decoder input (speech_model.py:102); ``merge_repeated``
     (reference: False, speech_model.py:110) collapses repeated labels of the returned prefix the way TF's decoder does."""
     lib = _lib.load()
-    B = self.dec_lens.numel()
-    need = lib.st_ctc_beam_ws(B, self.t_out, int(beam_width))
+    sh = self.shape
+    B = sh.dec_lens.numel()
+    need = lib.st_ctc_beam_ws(B, sh.t_out, int(beam_width))
     ws = self._storage.view('beam_ws', need // 4 + 16, torch.int32)[0]
     self._wait_uploads()
-    call('st_ctc_beam_search_decode_ex', self.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), beam_input_transform(input_transform),
-         self._ptr(self.dec_ids), self.t_out, self._ptr(self.dec_lens), self._ptr(self.dec_score),
+    call('st_ctc_beam_search_decode_ex', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), beam_input_transform(input_transform),
+         self._ptr(sh.dec_ids), sh.t_out, self._ptr(sh.dec_lens), self._ptr(sh.dec_score),
          self._ptr(ws), ws.numel() * 4, self.stream_ptr)
-    lens = self.dec_lens.cpu().numpy()
-    ids = self.dec_ids.view(-1, self.t_out).cpu().numpy()
+    lens = sh.dec_lens.cpu().numpy()
+    ids = sh.dec_ids.view(-1, sh.t_out).cpu().numpy()
     out = [ids[b, :lens[b]].tolist() for b in range(len(lens))]
     if merge_repeated:
       out = [merge_repeated_labels(seq) for seq in out]
-    return out, self.dec_score.cpu().numpy().reshape(-1, 1)
+    return out, sh.dec_score.cpu().numpy().reshape(-1, 1)
 
   def lm_beam_search_decode(self, lm, beam_width=100, input_transform='log10_softmax', lm_weight=0.8, word_count_weight=0.0,
                             valid_word_count_weight=2.3, oov_score=-1000.0):
@@ -162,18 +163,19 @@ class DecodeMixin:
     ARPA model (`language_model.LanguageModel`) in place of its KenLM scorer; semantics: tests/lm_oracle.py.
     -> (list of id lists, log_prob [B,1]); log_prob includes the LM terms."""
     lib = _lib.load()
-    B = self.dec_lens.numel()
-    need = lib.st_ctc_beam_ws(B, self.t_out, int(beam_width))
+    sh = self.shape
+    B = sh.dec_lens.numel()
+    need = lib.st_ctc_beam_ws(B, sh.t_out, int(beam_width))
     ws = self._storage.view('beam_ws', need // 4 + 16, torch.int32)[0]
     handle = lm.device_handle(self.device)
     self._wait_uploads()
-    call('st_ctc_beam_search_decode_lm', self.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), beam_input_transform(input_transform),
+    call('st_ctc_beam_search_decode_lm', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), beam_input_transform(input_transform),
          handle, float(lm_weight), float(word_count_weight), float(valid_word_count_weight), float(oov_score),
-         self._ptr(self.dec_ids), self.t_out, self._ptr(self.dec_lens), self._ptr(self.dec_score),
+         self._ptr(sh.dec_ids), sh.t_out, self._ptr(sh.dec_lens), self._ptr(sh.dec_score),
          self._ptr(ws), ws.numel() * 4, self.stream_ptr)
-    lens = self.dec_lens.cpu().numpy()
-    ids = self.dec_ids.view(-1, self.t_out).cpu().numpy()
-    return [ids[b, :lens[b]].tolist() for b in range(len(lens))], self.dec_score.cpu().numpy().reshape(-1, 1)
+    lens = sh.dec_lens.cpu().numpy()
+    ids = sh.dec_ids.view(-1, sh.t_out).cpu().numpy()
+    return [ids[b, :lens[b]].tolist() for b in range(len(lens))], sh.dec_score.cpu().numpy().reshape(-1, 1)
 
   def lm_beam_search_decode_candidates(self, lm, weights, beam_width=100, input_transform='log10_softmax', oov_score=-1000.0,
                                        max_workspace_bytes=CANDIDATE_WORKSPACE_BYTES):
@@ -185,7 +187,8 @@ class DecodeMixin:
     -> `CandidateDecodes`: the device outputs (ids [P, B, T], lens [P, B], log_prob [P, B]) and, on demand, a host view."""
     lib = _lib.load()
     w = np.asarray(weights, dtype=np.float32).reshape(-1, 3)
-    P, B, T = len(w), self.dec_lens.numel(), self.t_out
+    sh = self.shape
+    P, B, T = len(w), sh.dec_lens.numel(), sh.t_out
     if P < 1:
       raise ValueError('lm_beam_search_decode_candidates: at least one weight triple')
     if not np.all(np.isfinite(w)):
@@ -204,11 +207,11 @@ class DecodeMixin:
     for p0 in range(0, P, chunk):
       n = min(chunk, P - p0)
       wc = np.ascontiguousarray(w[p0:p0 + n])
-      call('st_ctc_beam_search_decode_lm_candidates', self.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle,
+      call('st_ctc_beam_search_decode_lm_candidates', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle,
            wc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n, float(oov_score),
            ctypes.c_void_p(ids.data_ptr() + 4 * p0 * B * T), T, ctypes.c_void_p(lens.data_ptr() + 4 * p0 * B),
            ctypes.c_void_p(logp.data_ptr() + 4 * p0 * B), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
-    return CandidateDecodes(ids.view(P, B, T), lens.view(P, B), logp.view(P, B), self._stream)
+    return CandidateDecodes(ids.view(P, B, T), lens.view(P, B), logp.view(P, B), self.stream)
 
   def lm_beam_search_decode_async(self, lm, beam_width=100, decode_stream=None, input_transform='log10_softmax', lm_weight=0.8,
                                   word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0):
@@ -238,13 +241,13 @@ class DecodeMixin:
   def _beam_decode_async(self, beam_width, decode_stream, launch):
     """The slot ring of the asynchronous beam searches; `launch` issues the search itself on the decoder stream."""
     lib = _lib.load()
-    B, T = self.dec_lens.numel(), self.t_out
-    xl = self.X[-1]
+    B, T = self.shape.dec_lens.numel(), self.shape.t_out
+    xl = self.shape.X[-1]
     need = lib.st_ctc_beam_ws(B, T, int(beam_width))
     streams = list(decode_stream) if isinstance(decode_stream, (list, tuple)) else [decode_stream]
     # one slot more than decoder streams: the forward pass fills a slot while every stream searches one
-    if not hasattr(self, '_beam_slots') or len(self._beam_slots) != len(streams) + 1:
-      for old in getattr(self, '_beam_slots', []):
+    if len(self._beam_slots) != len(streams) + 1:
+      for old in self._beam_slots:
         if old is not None:
           old['event'].synchronize()
       self._beam_slots, self._beam_turn = [None] * (len(streams) + 1), 0
@@ -252,9 +255,9 @@ class DecodeMixin:
     which = self._beam_turn % len(self._beam_slots)
     slot = self._beam_slots[which]
     decode_stream = streams[self._beam_turn % len(streams)]
-    main = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
+    main = self.stream
     if decode_stream is None:
-      if getattr(self, '_decode_stream', None) is None:
+      if self._decode_stream is None:
         self._decode_stream = torch.cuda.Stream(self.device)
       decode_stream = self._decode_stream
     if slot is None or slot['logits'].numel() < xl.buf.numel() or slot['ids'].numel() < B * T or slot['ws'].numel() * 4 < need or \

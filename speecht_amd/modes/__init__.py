@@ -4,8 +4,10 @@
   bf16x6   the same with the wide 1 x 1 layers as fp32-accurate three-piece bf16 products (experimental, opt-in)
   bf16     bf16 activations and activation gradients, fp32 masters / accumulation / CTC / Adam (BASELINE configs[3])
 
-A mode object holds no tensors of its own: it reads and writes the attributes of the engine it belongs to (`self.e`), so
-`eng.fft`, `eng.Xb`, ... stay where tests, bench.py and the profiling scripts look for them.
+A mode object owns the state of its arithmetic that outlives a shape (derived weight copies such as `Wb`, freshness flags, events,
+transform-table keys: all created in its `__init__`); what it needs per (batch, frames) is the object its `alloc` returns, kept by
+the engine in `ShapeState.mode` (`fft`, `Xb`, `wgrad_ws`, ...).  Outside readers still find `eng.fft`, `eng.Xb`, `eng.Wb` through the
+engine's read-only `__getattr__`; code in the package names `engine.shape.mode.fft` / `engine.mode.Wb`.
 """
 from .bf16 import Bf16Mode
 from .bf16x6 import Bf16x6Mode

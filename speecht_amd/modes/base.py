@@ -2,29 +2,32 @@
 
 
 class ModeBase:
-  """A mode = the buffers derived from the weights and the activations that only this arithmetic needs, plus the launch
-  sequences of the forward and the backward pass.  State lives in the engine core -- shared buffers, streams, freshness flags,
-  and the mode's own tensors too (`e.fft`, `e.Xb`, ...: where tests, bench.py and the profiling scripts look for them): a mode
-  holds a reference to its engine, `self.e`, and nothing else."""
+  """A mode = the operands derived from the weights and the activations that only this arithmetic needs, plus the launch
+  sequences of the forward and the backward pass.  Its state has two homes: what outlives a shape (derived weight copies, their
+  freshness flags and events, which transform tables lie in the buffers) is an attribute of the mode object, created in its
+  `__init__`; what is a function of the shape is the object `alloc` returns, which the engine keeps in `ShapeState.mode` and never
+  looks into.  The shared buffers, streams and events are the engine's (`self.e`)."""
+  cache_shapes = True             # False: `alloc` decides things that are not functions of the shape -- described anew every time
+  fft = fftb = {}                 # (what `engine.fft` / `engine.fftb` show an outside reader where the mode has no such layers)
 
   def __init__(self, engine):
     self.e = engine
 
   # ---- the interface -------------------------------------------------------------------------------------------
-  # Engine attributes `alloc` assigns that are functions of the shape alone: the engine keeps them per (B, T) and puts them back
-  # when a shape comes round again (`Wav2LetterEngine._reenter_shape`) instead of calling `alloc`.  Empty: never cached.
-  shape_attrs = ()
+  def alloc(self, sh):
+    """This mode's part of the ShapeState under construction (X, dZ, geo exist; `sh` is not the engine's current shape yet).
+    Byte ranges another shape may overwrite are logged in `sh.ranges`."""
+    raise NotImplementedError
 
-  def shape_token(self):
-    """What `reenter` needs to know about the shape just described (kept with the cached description)."""
-    return None
-
-  def reenter(self, token):
+  def reenter(self, sh):
     """A cached shape is current again: redo what `alloc` does that depends on the shape LEFT BEHIND (freshness flags)."""
 
-  def alloc(self, batch):
-    """Buffers of this mode for the shape `_ensure_shape` has just described (X, dZ, geo exist)."""
+  def weights_changed(self):
+    """The weights were written (an update, `set_weights`): everything derived from them is stale."""
     raise NotImplementedError
+
+  def forget_tables(self):
+    """A tuning knob was flipped: the transform tables in the layers' buffers are rebuilt by the next description."""
 
   def forward(self):
     raise NotImplementedError

@@ -1,7 +1,7 @@
 """An engine's per-shape state at full width, where every production step runs in the frequency domain.
 
 Real training changes (B, max_T) nearly every step.  A shape seen before is re-entered from a cached description
-(Wav2LetterEngine._reenter_shape: the attributes of _SHAPE_ATTRS and mode.shape_attrs put back, the logged byte ranges
+(Wav2LetterEngine._reenter_shape: the cached ShapeState object made `engine.shape` again, the logged byte ranges
 re-zeroed, freshness re-evaluated by the mode); a tuning knob flipped on a live engine makes it describe the shape anew and
 rebuild every operand derived from the weights.  Either way every step must equal, bit for bit, the same step on an engine
 built fresh from the same params, m, v and step count.  The walks use the model's own widths (250 / 2000 channels, non-zero
@@ -153,15 +153,15 @@ def test_full_width_walk_bf16(dev):
     assert f['W-tap 32-tap layer'] == (not f['32-tap layer spectral']), (name, f)
 
 
-# ---- the re-entry whitelist ------------------------------------------------------------------------------------------------
+# ---- per-shape state lives in ONE object ---------------------------------------------------------------------------------
 
-# engine attributes a description changes on purpose that re-entry does NOT put back from the cache, because it recomputes them
+# what a description may change on the engine and on the mode: the current ShapeState, the cache, and the mode's cross-shape
+# state that a transition between shapes recomputes on purpose
 RECOMPUTED = {
-    '_shape',              # set by _reenter_shape itself
+    'shape',               # the current ShapeState (everything that is a function of the shape is inside it)
     '_shape_cache',        # the cache (a new entry)
-    '_describe_log',       # byte ranges to zero, kept in the cache entry as a device table
     '_fft_prev', '_fftb_prev',                                 # the frequency-domain set left behind: `_fft_transition` compares
-    '_fft_table_key', '_fftb_table_key',                       # whose tables lie in each layer's buffer: checked against the token
+    '_fft_table_key', '_fftb_table_key',                       # whose tables lie in each layer's buffer: checked against the state's keys
     '_gfwd_fresh', '_packed_t_fresh', '_wplanes_fresh', '_wtplanes_fresh',   # freshness flags, re-evaluated by the transitions
 }
 
@@ -183,21 +183,32 @@ def changed(before, after):
 
 @pytest.mark.parametrize('mode', ['fp32', 'bf16'])
 def test_every_per_shape_attribute_is_cached_or_recomputed(dev, mode):
-  """Describe two shapes on the frequency-domain path on one engine: every engine or mode attribute the second description
-  changed is put back by re-entry (_SHAPE_ATTRS, mode.shape_attrs) or recomputed on purpose (RECOMPUTED).  A new per-shape
-  attribute must be classified before this passes."""
+  """Describe two shapes on the frequency-domain path on one engine: the only engine or mode attributes the second description
+  changed are `shape`, the cache and what a transition recomputes on purpose (RECOMPUTED) -- a per-shape value kept anywhere
+  but in the ShapeState fails this.  Going back to the first shape makes the very object described first current again."""
   layers = WL.w2l_layers(80)
   eng = make_engine(layers, dev, mode)
   eng.set_weights(WL.xavier_params(layers, seed=42, dtype=np.float32))
+  # (buffers at their final size first, as in `run_walk`: a buffer that grows drops every cached description)
+  for _ in range(2):
+    for name in ('D', 'E'):
+      eng._ensure_shape(len(SHAPES[name]), max(SHAPES[name]))
+  eng._shape_cache.clear()
+  generation = eng._storage.generation
   eng._ensure_shape(len(SHAPES['D']), max(SHAPES['D']))
   assert 8 in (eng.fft if mode != 'bf16' else eng.fftb)
+  first, first_x0, first_part = eng.shape, eng.shape.X[0].buf.data_ptr(), eng.shape.mode
   before, mode_before = snapshot(eng.__dict__), snapshot(eng.mode.__dict__)
   eng._ensure_shape(len(SHAPES['E']), max(SHAPES['E']))
   assert 8 in (eng.fft if mode != 'bf16' else eng.fftb)
-  allowed = set(eng._SHAPE_ATTRS) | set(eng.mode.shape_attrs) | RECOMPUTED
+  allowed = RECOMPUTED
   diff = changed(before, snapshot(eng.__dict__)) | changed(mode_before, snapshot(eng.mode.__dict__))
   assert diff, 'nothing changed between two shapes: the snapshot is broken'
   assert diff <= allowed, sorted(diff - allowed)
+  assert eng.shape is not first
+  eng._ensure_shape(len(SHAPES['D']), max(SHAPES['D']))
+  assert eng.shape is first and eng._storage.generation == generation
+  assert eng.shape.X[0].buf.data_ptr() == first_x0 and eng.shape.mode is first_part
 
 
 # ---- knobs flipped on a live engine ----------------------------------------------------------------------------------------
