@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- utterances/sec of one Wav2Letter TRAINING step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   (N > 1 without WORLD_SIZE in the environment: re-launches itself under torch.distributed.run, one rank per
   GPU over RCCL; under an external torch.distributed.run it just joins the job)
 
@@ -14,10 +14,16 @@ SURVEY 8(d) counts into it: the H2D copy of the padded feature batch from pinned
 double-buffered, so batch k+1 travels while batch k computes) and the upload of the labels.
 Weak scaling: every rank processes its own 32 utterances; value = N*32 / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus a summary of `roofline` (dominant kernel, HIP
-event timing) and `cpu_baseline` (the numpy oracle timed on the host cores, N=1 only).  The line stays short (RESULT_LINE
-says what it keeps) so that a reader holding only the tail of the output still gets it whole; the full record (every side
-measurement, the roofline's per-kernel rows) goes to stderr as one line starting with `bench.py: full record `.
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, then ONE JSON line on rank 0 with
+the contract's keys (metric, value, unit, higher_is_better, dtype, ms_per_step) and what describes the run.
+
+--full adds, after the timed steps' outputs are written, everything else the benchmark measures and checks: parity of the
+logits and the CTC loss against the float64 oracle on the bench inputs (before the warm-up, asserted: exit 3), the replicas'
+digest and the compute / exchange split for N > 1 (exit 4), the other precisions (`alt_bf16x6`, `alt_bf16`), host cost,
+communication probe and model, `roofline` (dominant kernel, HIP event timing), mel features, BASELINE configs[2] and [4]
+and `cpu_baseline` (N=1 only); a summary of them joins the line.  The line stays short (RESULT_LINE says what it
+keeps) so that a reader holding only the tail of the output still gets it whole; the full record (every side measurement, the
+roofline's per-kernel rows) goes to stderr as one line starting with `bench.py: full record `.
 
 --dump-outputs DIR writes what the timed path computed in its last step (losses, logits, a seeded sample of the updated
 weights and of the gradients) to DIR/<name>.npy, so that two builds can be compared output for output on the same inputs.
@@ -884,13 +890,15 @@ def main():
   ap.add_argument('--batch', type=int, default=32, help='utterances per GPU')
   ap.add_argument('--seconds', type=float, default=10.0)
   ap.add_argument('--mels', type=int, default=80)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-alt', action='store_true', help='skip the bf16 side measurement (configs[3] arithmetic on this GPU)')
-  ap.add_argument('--alt-bf16x6', action='store_true', help='(accepted for old command lines: the bf16x6 side measurement is part of the default run)')
-  ap.add_argument('--no-alt-bf16x6', action='store_true', help='skip the bf16x6 side measurement (its launches share kernel symbols with the '
+  ap.add_argument('--full', action='store_true', help='after the timed steps, also everything else the benchmark measures and checks: parity '
+                  'against the float64 oracle (asserted), roofline, other precisions and configurations, data-parallel split, CPU baselines')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+  ap.add_argument('--no-alt', action='store_true', help='with --full: skip the bf16 side measurement (configs[3] arithmetic on this GPU)')
+  ap.add_argument('--alt-bf16x6', action='store_true', help='(accepted for old command lines: the bf16x6 side measurement is part of a --full run)')
+  ap.add_argument('--no-alt-bf16x6', action='store_true', help='with --full: skip the bf16x6 side measurement (its launches share kernel symbols with the '
                   'fp32 step; the profiled runs of scripts/gpu_profile_round.sh use --no-alt / --steps-only anyway)')
-  ap.add_argument('--steps-only', action='store_true', help='warm-up + timed steps and a minimal line: no parity pass, roofline, mel, '
-                  'alt modes or CPU baseline (the command the PMC passes of scripts/gpu_profile_round.sh run: every launch is a step\'s)')
+  ap.add_argument('--steps-only', action='store_true', help='what a run without --full does, with a minimal line (the command the PMC passes '
+                  'of scripts/gpu_profile_round.sh run: every launch is a step\'s)')
   ap.add_argument('--self-launch', action='store_true', help='go through torch.distributed.run even for --gpus 1 (self-test of the launcher path)')
   ap.add_argument('--force-allreduce', action='store_true', help='run the RCCL all-reduce path even on 1 rank (self-test)')
   ap.add_argument('--conv-mode', choices=('fp32', 'bf16x6', 'bf16'), default=None,
@@ -904,6 +912,8 @@ def main():
   args = ap.parse_args()
   if args.steps < 1 or args.warmup < 0:
     ap.error('--steps must be >= 1 and --warmup >= 0')
+  if args.full and args.steps_only:
+    ap.error('--full and --steps-only exclude each other')
   for kv in args.tune:
     from speecht_amd._lib import set_tuning
     set_tuning(kv.split('=')[0], int(kv.split('=')[1]))
@@ -941,11 +951,11 @@ def main():
   # parity on the bench inputs twice: with NON-ZERO biases U(-0.05, 0.05) first (zero biases hide F7 -- the padded
   # region then stays zero through every layer), then with the zero-bias fresh-training weights the timed steps start from
   parity_b = None
-  if rank == 0 and not args.steps_only:
+  if rank == 0 and args.full:
     eng.set_weights(WL.xavier_params(layers, seed=42, bias_range=0.05, dtype=np.float32))
     parity_b = parity_on_bench_inputs(eng, x, seq_lens, labels)
   eng.set_weights(WL.xavier_params(layers, seed=42, bias_range=0.0, dtype=np.float32))   # same replica everywhere
-  parity = parity_on_bench_inputs(eng, x, seq_lens, labels) if (rank == 0 and not args.steps_only) else None
+  parity = parity_on_bench_inputs(eng, x, seq_lens, labels) if (rank == 0 and args.full) else None
   for pr in (parity, parity_b):
     if pr is not None and eng.conv_mode == 'bf16':
       pr['asserted'], pr['passed'] = None, None        # bf16 storage: parity is tests/test_gpu_bf16.py's (bf16 ulps), not 1e-4
@@ -1022,6 +1032,7 @@ def main():
     dist.all_gather(every, t)
     rank_ms = [float(e[0]) / args.steps * 1e3 for e in every]
     elapsed = max(float(e[0]) for e in every)
+  if world > 1 and args.full:
     # data-parallel invariant: every rank applied the same averaged gradient to the same weights, so the
     # replicas must still be bit-identical (checked outside the timed region: two small all-reduces)
     p64 = eng.params.double()
@@ -1073,7 +1084,7 @@ def main():
                       library_comm=reducer.comm.count() if reducer.comm is not None else None, transport=reducer.transport,
                       library_comm_spans_job=(reducer.comm.count() == world) if reducer.comm is not None else None,
                       fallback=transport_note)
-    if world > 1 and not replicas_identical:
+    if world > 1 and args.full and not replicas_identical:
       if rank == 0:
         print('bench.py: the replicas are NOT bit-identical after %d data-parallel steps (rccl_ranks %s): the exchange is '
               'broken, no result line is printed' % (args.warmup + args.steps, json.dumps(ranks_info)), file=sys.stderr)
@@ -1108,91 +1119,92 @@ def main():
                                                                            [args.batch, args.seconds, args.mels])),
                    'global_batch': global_batch, 'frames': frames, 'parallelism': 'dp%d' % world,
                    'allreduce': reducer.transport if reducer else None},
-        'final_avg_loss': round(loss, 4),
-        'ctc_loss_delta': parity['ctc_loss_delta'], 'max_logit_err': parity['max_logit_err'],
-        'ctc_loss_delta_kind': 'absolute, ASSERTED < 1e-4: |hi + lo - oracle| of the kernel\'s (hi, lo) loss pair; the fp32 hi part alone '
-                               '(what TF returns) is ctc_loss_delta_fp32_output in `parity`',
-        'ctc_loss_delta_rel': parity['ctc_loss_delta_rel'], 'parity': parity, 'parity_nonzero_bias': parity_b,
-        'replicas_identical': replicas_identical, 'rccl_ranks': ranks_info,
-        'per_rank_ms_per_step': [round(v, 3) for v in rank_ms], 'comm': comm,
+        'final_avg_loss': round(loss, 4), 'rccl_ranks': ranks_info, 'per_rank_ms_per_step': [round(v, 3) for v in rank_ms],
         'step_tflops_algorithmic': round(step_gflop / ms, 2),
         'step_tflops_note': ('W-tap FLOPs of the reference formulation (SURVEY 8(d): 71.4 GFLOP per utterance) / step time; '
                              'nine of the eleven layers run in the frequency domain with 3-10x fewer multiplications, so this is an '
                              'equivalent rate, not a hardware rate (the hardware rate is roofline.achieved)')
                             if (eng.fft and eng.fft_conv) else None,
     }
-    # The side measurements come BEFORE the roofline passes: those launch through hipExtLaunchKernel with start / stop events,
-    # which switches the process's HSA queues into profiling mode for good -- every later dispatch carries a completion
-    # signal.  The 7 ms fp32 step does not notice; steps of many short launches do (measured round 4, scripts/exp/
-    # alt_timing_probe.py: bf16 2.66 -> 2.86 ms, bf16x6 6.46 -> 7.11 ms when timed after those passes).
-    if world == 1 and reducer is None and eng.conv_mode == 'fp32':
-      out['comm_probe_world1'] = comm_probe_world1(eng, feed, lr, global_batch, args.steps, ahead)
-    if world == 1 and reducer is None and not args.no_alt:
-      out['comm_model_8gpu'] = comm_model(eng, feed, lr, global_batch, ms)
-      out['host_cost'] = host_cost(eng, feed, lr, global_batch, args.steps, ahead)
-    if world == 1 and eng.conv_mode == 'fp32' and not args.no_alt:
-      # Side measurements on the same box and inputs, NOT the headline:
-      #  * bf16x6 (experimental): fp32 operands split exactly into 3 bf16 pieces, 6 cross terms on the bf16
-      #    matrix pipe, fp32 accumulate; passes the same parity tests as the fp32 path.
-      #  * bf16: BASELINE configs[3]'s arithmetic ("bf16 activations / fp32 CTC") on one GPU -- reduced
-      #    precision by design, parity against the oracle's bf16 storage model (tests/test_gpu_bf16.py).
-      alts = [('alt_bf16x6', 'bf16x6', 'f32 tensors; the 2000 x 2000 layer\'s three products with every operand split exactly into 3 bf16 pieces, '
-               '6 bf16 MFMA terms, f32 accumulate (the other layers as in the headline)',
-               'opt-in (ST_CONV_MODE=bf16x6): fp32-level accuracy (same parity tests and tolerances as the headline path) on the '
-               'bf16 matrix pipe; reported beside the headline, which stays on the fp32 MFMA instruction'),
-              ('alt_bf16', 'bf16', 'bf16 activations + activation gradients, f32 masters/accumulate/logits/CTC/Adam',
-               'configs[3] arithmetic on 1 GPU (ST_CONV_MODE=bf16); reduced precision, not the headline value')]
-      for key, mode, dtype, note in alts:
-        if mode == 'bf16x6' and args.no_alt_bf16x6:
-          continue
-        alt = Wav2LetterEngine(layers, device=dev, conv_mode=mode)
-        alt.params.copy_(eng.params)
-        alt.mark_weights_changed()
-        alt_feed = HostFeed(alt, x, seq_lens, labels)
-        for _ in range(args.warmup):
-          train_step(alt, alt_feed, None, lr, global_batch)
-        torch.cuda.synchronize()
-        # timed like the headline loop: at most `ahead` steps in flight (an unbounded burst after a sync runs its first
-        # steps slow -- it made this 3.1 ms step read 3.5 ms)
-        alt_marks = [torch.cuda.Event() for _ in range(args.steps)]
-        t1 = time.perf_counter()
-        for k in range(args.steps):
-          if ahead and k >= ahead:
-            alt_marks[k - ahead].synchronize()
-          train_step(alt, alt_feed, None, lr, global_batch)
-          alt_marks[k].record()
-        torch.cuda.synchronize()
-        alt_ms = (time.perf_counter() - t1) / args.steps * 1e3
-        out[key] = {'value': round(args.batch / alt_ms * 1e3, 2), 'unit': 'utterances/s', 'ms_per_step': round(alt_ms, 3),
-                    'step_tflops_algorithmic': round(step_gflop / alt_ms, 2),
-                    'final_avg_loss': round(float(alt.loss.mean()), 4), 'dtype': dtype, 'note': note}
-        if mode == 'bf16':
-          # the comm model first (plain events), the roofline pass last: its timed launches switch the queues to profiling mode
-          out[key]['host_cost'] = host_cost(alt, alt_feed, lr, global_batch, args.steps, ahead)
-          out[key]['comm_probe_world1'] = comm_probe_world1(alt, alt_feed, lr, global_batch, args.steps, ahead)
-          out[key]['comm_model_8gpu'] = comm_model(alt, alt_feed, lr, global_batch, alt_ms)
-          out[key]['roofline'] = roofline_bf16_in_step(alt, lambda: train_step(alt, alt_feed, None, lr, global_batch), alt_ms)
-        del alt
-        torch.cuda.empty_cache()
-    # (rank 0 alone runs these profiled steps: without the exchange when there are other ranks)
-    step_fn = lambda: train_step(eng, feed, reducer if world == 1 else None, lr, global_batch)
-    out['roofline'], step_hw = measure_dominant_kernel(eng, args.batch, step_fn, ms)
-    if step_hw:
-      out.update(step_hw)
-    if out['roofline'] and eng.conv_mode != 'bf16':
-      attach_pmc_profiles(out['roofline'])
-    if world == 1:
-      out['mel_features'] = measure_mel(dev, args.batch, args.seconds, args.mels)
-      if not args.no_alt:
-        out['mel_features_batch512'] = measure_mel(dev, 512, args.seconds, args.mels)    # (a preprocessing job's batch: launch costs amortised)
-    if world == 1 and not args.no_alt and args.mels == 80:
-      # the other single-GPU configurations of BASELINE.json, a few seconds each, each with an oracle check of its own
-      out['configs2_inference'] = config2_rate(dev, layers)
-      out['configs4_decode'] = config4_rate(dev, layers)
-    if world == 1 and not args.no_cpu_baseline:
-      # two CPU restatements of the reference path on this box's host cores; the faster one is `cpu_baseline`
-      out['cpu_baseline'] = cpu_baseline_torch(args.mels, frames, args.batch)
-      out['cpu_baseline_numpy_oracle'] = cpu_baseline(args.mels, frames)
+    if args.full:
+      out.update({
+          'ctc_loss_delta': parity['ctc_loss_delta'], 'max_logit_err': parity['max_logit_err'],
+          'ctc_loss_delta_kind': 'absolute, ASSERTED < 1e-4: |hi + lo - oracle| of the kernel\'s (hi, lo) loss pair; the fp32 hi part alone '
+                                 '(what TF returns) is ctc_loss_delta_fp32_output in `parity`',
+          'ctc_loss_delta_rel': parity['ctc_loss_delta_rel'], 'parity': parity, 'parity_nonzero_bias': parity_b,
+          'replicas_identical': replicas_identical, 'comm': comm})
+      # The side measurements come BEFORE the roofline passes: those launch through hipExtLaunchKernel with start / stop events,
+      # which switches the process's HSA queues into profiling mode for good -- every later dispatch carries a completion
+      # signal.  The 7 ms fp32 step does not notice; steps of many short launches do (measured round 4, scripts/exp/
+      # alt_timing_probe.py: bf16 2.66 -> 2.86 ms, bf16x6 6.46 -> 7.11 ms when timed after those passes).
+      if world == 1 and reducer is None and eng.conv_mode == 'fp32':
+        out['comm_probe_world1'] = comm_probe_world1(eng, feed, lr, global_batch, args.steps, ahead)
+      if world == 1 and reducer is None and not args.no_alt:
+        out['comm_model_8gpu'] = comm_model(eng, feed, lr, global_batch, ms)
+        out['host_cost'] = host_cost(eng, feed, lr, global_batch, args.steps, ahead)
+      if world == 1 and eng.conv_mode == 'fp32' and not args.no_alt:
+        # Side measurements on the same box and inputs, NOT the headline:
+        #  * bf16x6 (experimental): fp32 operands split exactly into 3 bf16 pieces, 6 cross terms on the bf16
+        #    matrix pipe, fp32 accumulate; passes the same parity tests as the fp32 path.
+        #  * bf16: BASELINE configs[3]'s arithmetic ("bf16 activations / fp32 CTC") on one GPU -- reduced
+        #    precision by design, parity against the oracle's bf16 storage model (tests/test_gpu_bf16.py).
+        alts = [('alt_bf16x6', 'bf16x6', 'f32 tensors; the 2000 x 2000 layer\'s three products with every operand split exactly into 3 bf16 pieces, '
+                 '6 bf16 MFMA terms, f32 accumulate (the other layers as in the headline)',
+                 'opt-in (ST_CONV_MODE=bf16x6): fp32-level accuracy (same parity tests and tolerances as the headline path) on the '
+                 'bf16 matrix pipe; reported beside the headline, which stays on the fp32 MFMA instruction'),
+                ('alt_bf16', 'bf16', 'bf16 activations + activation gradients, f32 masters/accumulate/logits/CTC/Adam',
+                 'configs[3] arithmetic on 1 GPU (ST_CONV_MODE=bf16); reduced precision, not the headline value')]
+        for key, mode, dtype, note in alts:
+          if mode == 'bf16x6' and args.no_alt_bf16x6:
+            continue
+          alt = Wav2LetterEngine(layers, device=dev, conv_mode=mode)
+          alt.params.copy_(eng.params)
+          alt.mark_weights_changed()
+          alt_feed = HostFeed(alt, x, seq_lens, labels)
+          for _ in range(args.warmup):
+            train_step(alt, alt_feed, None, lr, global_batch)
+          torch.cuda.synchronize()
+          # timed like the headline loop: at most `ahead` steps in flight (an unbounded burst after a sync runs its first
+          # steps slow -- it made this 3.1 ms step read 3.5 ms)
+          alt_marks = [torch.cuda.Event() for _ in range(args.steps)]
+          t1 = time.perf_counter()
+          for k in range(args.steps):
+            if ahead and k >= ahead:
+              alt_marks[k - ahead].synchronize()
+            train_step(alt, alt_feed, None, lr, global_batch)
+            alt_marks[k].record()
+          torch.cuda.synchronize()
+          alt_ms = (time.perf_counter() - t1) / args.steps * 1e3
+          out[key] = {'value': round(args.batch / alt_ms * 1e3, 2), 'unit': 'utterances/s', 'ms_per_step': round(alt_ms, 3),
+                      'step_tflops_algorithmic': round(step_gflop / alt_ms, 2),
+                      'final_avg_loss': round(float(alt.loss.mean()), 4), 'dtype': dtype, 'note': note}
+          if mode == 'bf16':
+            # the comm model first (plain events), the roofline pass last: its timed launches switch the queues to profiling mode
+            out[key]['host_cost'] = host_cost(alt, alt_feed, lr, global_batch, args.steps, ahead)
+            out[key]['comm_probe_world1'] = comm_probe_world1(alt, alt_feed, lr, global_batch, args.steps, ahead)
+            out[key]['comm_model_8gpu'] = comm_model(alt, alt_feed, lr, global_batch, alt_ms)
+            out[key]['roofline'] = roofline_bf16_in_step(alt, lambda: train_step(alt, alt_feed, None, lr, global_batch), alt_ms)
+          del alt
+          torch.cuda.empty_cache()
+      # (rank 0 alone runs these profiled steps: without the exchange when there are other ranks)
+      step_fn = lambda: train_step(eng, feed, reducer if world == 1 else None, lr, global_batch)
+      out['roofline'], step_hw = measure_dominant_kernel(eng, args.batch, step_fn, ms)
+      if step_hw:
+        out.update(step_hw)
+      if out['roofline'] and eng.conv_mode != 'bf16':
+        attach_pmc_profiles(out['roofline'])
+      if world == 1:
+        out['mel_features'] = measure_mel(dev, args.batch, args.seconds, args.mels)
+        if not args.no_alt:
+          out['mel_features_batch512'] = measure_mel(dev, 512, args.seconds, args.mels)    # (a preprocessing job's batch: launch costs amortised)
+      if world == 1 and not args.no_alt and args.mels == 80:
+        # the other single-GPU configurations of BASELINE.json, a few seconds each, each with an oracle check of its own
+        out['configs2_inference'] = config2_rate(dev, layers)
+        out['configs4_decode'] = config4_rate(dev, layers)
+      if world == 1 and not args.no_cpu_baseline:
+        # two CPU restatements of the reference path on this box's host cores; the faster one is `cpu_baseline`
+        out['cpu_baseline'] = cpu_baseline_torch(args.mels, frames, args.batch)
+        out['cpu_baseline_numpy_oracle'] = cpu_baseline(args.mels, frames)
     print('bench.py: full record ' + json.dumps(out), file=sys.stderr)
     sys.stderr.flush()
     print(json.dumps(pick(out, RESULT_LINE)))

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: gpu_bench_summary.sh <tag> [bench.py args]: one bench.py run -> gpurun_out/<tag>.json + a short summary of its roofline
 TAG="$1"; shift
+set -- --full "$@"      # the summary below reads the roofline, which only a --full run measures
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 timeout 600 python bench.py "$@" > gpurun_out/$TAG.json 2> gpurun_out/$TAG.err

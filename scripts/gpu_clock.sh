@@ -6,7 +6,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
 OUT=$ROOT/gpurun_out/clock_$MODE
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT -o c -- python $ROOT/bench.py --steps 6 --warmup 2 --no-alt --no-cpu-baseline --conv-mode $MODE > $OUT/run.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT -o c -- python $ROOT/bench.py --steps 6 --warmup 2 --full --no-alt --no-cpu-baseline --conv-mode $MODE > $OUT/run.log 2>&1
 cd $ROOT
 python - "$OUT" <<'PY'
 import csv, glob, os, sys, collections

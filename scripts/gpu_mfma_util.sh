@@ -3,10 +3,11 @@
 # SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over the SIMDs (MI355X_MICROARCH.md: = 64 x N_mfma for
 # v_mfma_f32_32x32x2_f32); utilisation = busy / (kernel duration x 2.4 GHz x 1024 SIMDs).
 export TMPDIR=/tmp
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/mfma
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT -o m -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline > $OUT/run.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT -o m -- python $ROOT/bench.py --steps 2 --warmup 1 --full --no-alt --no-cpu-baseline > $OUT/run.log 2>&1
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
 import csv, glob, json, os, collections

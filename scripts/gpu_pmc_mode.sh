@@ -8,7 +8,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
 OUT=$ROOT/gpurun_out/pmc_$MODE
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline --conv-mode $MODE"
+CMD="python $ROOT/bench.py --steps 2 --warmup 1 --full --no-alt --no-cpu-baseline --conv-mode $MODE"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT/a -o a -- $CMD > $OUT/a.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16 --kernel-trace --output-format csv -d $OUT/b -o b -- $CMD > $OUT/b.log 2>&1
 cd $ROOT

@@ -1,8 +1,8 @@
 #!/bin/bash
 # The measured artefacts profiles/ holds for a round, all from ONE build (stamped with build.source_digest()):
 #   (order of execution: 3, 4, then 1, 2 -- the bench line quotes the PMC files of ITS build)
-#   1. the default bench line (what the driver runs)                       -> gpurun_out/round/bench.json
-#   2. rocprofv3 --kernel-trace --stats of `bench.py --no-alt --no-cpu-baseline` -> kernel_stats.csv, step_timeline.txt
+#   1. the bench line of a --full run (every side measurement)            -> bench.json
+#   2. rocprofv3 --kernel-trace --stats of `bench.py --full --no-alt --no-cpu-baseline` -> kernel_stats.csv, step_timeline.txt
 #   3. PMC passes over `bench.py --steps-only` (every launch belongs to a training step), counters + kernel-trace only,
 #      FETCH_SIZE and WRITE_SIZE in separate passes (MI355X_MICROARCH.md: 3 + 2 of the 4 TCC slots), read side doubled
 #      (gfx950: FETCH_SIZE tallies 128-B requests at 64 B)                  -> traffic.json (per kernel and per step)
@@ -107,7 +107,7 @@ PY
 # the bench quotes profiles/traffic.json / mfma_util.json only when their digest is the digest of the sources it runs: put the
 # files just collected where it looks (on this box's copy; scripts/copy_round_profiles.sh does the same for the repository)
 cp $OUT/traffic.json $OUT/mfma_util.json $ROOT/profiles/
-S0=$SECONDS; python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench.py default run: $((SECONDS - S0)) s wall" | tee $OUT/bench_wall.txt
+S0=$SECONDS; python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench.py --full run: $((SECONDS - S0)) s wall" | tee $OUT/bench_wall.txt
 # rocprofv3 --kernel-trace --stats twice: (a) over `bench.py --steps-only` -- every launch under a symbol is a training step's,
 # the file the in-step roofline of the bench line is checked against (kernel_stats_steps_only.csv: average duration of the
 # dominant symbol = roofline.avg_launch_ms); (b) over the bench command itself (isolated-measurement launches included)
@@ -115,7 +115,7 @@ bash scripts/gpu_prof.sh round${TAG}_prof_steps python bench.py --steps-only --s
 python scripts/step_timeline.py $(find gpurun_out/round${TAG}_prof_steps -name '*kernel_trace.csv' | head -1) > $OUT/step_timeline.txt 2>/dev/null
 cp $(find gpurun_out/round${TAG}_prof_steps -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_steps_only.csv
 grep '^{' gpurun_out/round${TAG}_prof_steps/stdout.log > $OUT/bench_steps_only_under_rocprof.json
-bash scripts/gpu_prof.sh round${TAG}_prof python bench.py --no-alt --no-cpu-baseline | head -40 > $OUT/kernel_top.txt
+bash scripts/gpu_prof.sh round${TAG}_prof python bench.py --full --no-alt --no-cpu-baseline | head -40 > $OUT/kernel_top.txt
 cp $(find gpurun_out/round${TAG}_prof -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv
 grep '^{' gpurun_out/round${TAG}_prof/stdout.log > $OUT/bench_under_rocprof.json
 python - <<PY

@@ -1,9 +1,9 @@
 #!/bin/bash
-# the whole GPU suite, then the default bench line (what the driver runs at round end)
+# the whole GPU suite, then the benchmark with --full (the summary below reads its side measurements)
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/suite; mkdir -p $O
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | grep -v "^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -12 | tee $O/pytest_gpu.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | grep '^{' > $O/bench.json
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $O/bench.err | grep '^{' > $O/bench.json
 python - "$O/bench.err" <<'PY'
 import json, sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('bench.py: full record ')][-1][len('bench.py: full record '):])

@@ -4,11 +4,12 @@
 # sys/hip tracing.  FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of the bytes
 # of wide (16 B/lane) coalesced reads, so the read side is doubled.  Writes profiles/traffic.json.
 export TMPDIR=/tmp
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/traffic
 mkdir -p $OUT
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o t -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline > $OUT/$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o t -- python $ROOT/bench.py --steps 2 --warmup 1 --full --no-alt --no-cpu-baseline > $OUT/$C.log 2>&1
 done
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
@@ -39,7 +40,7 @@ for k, d in vals.items():
     fetch = d['FETCH_SIZE'][0] / max(d['FETCH_SIZE'][1], 1) * 1024 * 2      # gfx950 correction (MI355X_MICROARCH.md, HBM section)
     write = d['WRITE_SIZE'][0] / max(d['WRITE_SIZE'][1], 1) * 1024
     by[k] = dict(launches=d['FETCH_SIZE'][1], fetch_bytes_per_launch=fetch, write_bytes_per_launch=write, bytes_per_launch=fetch + write)
-out = dict(by_kernel=by, command='bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline',
+out = dict(by_kernel=by, command='bench.py --steps 2 --warmup 1 --full --no-alt --no-cpu-baseline',
            note='FETCH_SIZE x 1024 x 2 (gfx950 wide-read correction) + WRITE_SIZE x 1024, averaged over all launches of the symbol '
                 '(the training steps and the roofline-measurement launches of the same command: the same launch mix)')
 json.dump(out, open(os.path.join(root, 'gpurun_out/traffic/traffic.json'), 'w'), indent=1)

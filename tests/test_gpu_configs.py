@@ -124,7 +124,7 @@ def test_config4_rank_shard_long_form_forward_and_decoders():
 
 
 def test_bench_self_launch_two_ranks_share_one_gpu():
-  """`python bench.py --gpus 2` exactly as the driver invokes it (no torch.distributed environment): bench.py
+  """`python bench.py --gpus 2 --full` with no torch.distributed environment, as a caller starts it: bench.py
   re-launches itself under torch.distributed.run.  On a 1-GPU box the two ranks share cuda:0 and use gloo
   (test knobs ST_SHARE_GPU / ST_DIST_BACKEND); the control flow, the bucketed exchange hooks, the max-over-ranks
   timing and the one JSON line are the production ones."""
@@ -139,7 +139,7 @@ def test_bench_self_launch_two_ranks_share_one_gpu():
   for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
   r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                      '--batch', '4', '--seconds', '2', '--no-alt', '--no-cpu-baseline'],
+                      '--batch', '4', '--seconds', '2', '--full', '--no-alt', '--no-cpu-baseline'],
                      env=env, cwd=root, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -150,3 +150,44 @@ def test_bench_self_launch_two_ranks_share_one_gpu():
   assert len(out['per_rank_ms_per_step']) == 2 and out['comm']['allreduce_alone_ms'] > 0
   assert out['max_logit_err'] < 1e-4 and out['parity']['max_logit_err_rel'] < 2e-5 and out['parity']['ctc_loss_delta_rel'] < 1e-4
   assert out['parity_nonzero_bias']['passed'] is True
+
+
+def test_bench_plain_run_prints_the_headline_alone_and_dumps_outputs(tmp_path):
+  """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps, the dump and the line.
+  The line carries the contract's keys and what describes the run, nothing of what --full measures or checks; the
+  dumped arrays are the ones --full dumps (the parity passes before the warm-up leave no trace in the timed steps)."""
+  import json
+  import os
+  import subprocess
+  import sys
+  if not torch.cuda.is_available():
+    pytest.skip('no GPU')
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = dict(os.environ)
+  for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+    env.pop(k, None)
+
+  def run(name, extra):
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+                        '--seconds', '2', '--dump-outputs', str(tmp_path / name)] + extra,
+                       env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    record = [l for l in r.stderr.splitlines() if l.startswith('bench.py: full record ')]
+    assert len(record) == 1, r.stderr[-4000:]
+    return json.loads(lines[0]), json.loads(record[0][len('bench.py: full record '):])
+
+  out, record = run('plain', [])
+  assert out['metric'].startswith('utterances/sec') and out['unit'] == 'utterances/s' and out['higher_is_better'] is True
+  assert out['dtype'] == 'f32' and out['n_gpus'] == 1 and out['steps'] == 3 and out['warmup'] == 1
+  assert out['ms_per_step'] > 0 and out['value'] == pytest.approx(4 / out['ms_per_step'] * 1e3, rel=1e-3)
+  moved = ('parity', 'parity_nonzero_bias', 'max_logit_err', 'ctc_loss_delta', 'roofline', 'alt_bf16', 'alt_bf16x6', 'comm',
+           'comm_probe_world1', 'comm_model_8gpu', 'host_cost', 'mel_features', 'configs2_inference', 'configs4_decode',
+           'cpu_baseline', 'cpu_baseline_numpy_oracle', 'replicas_identical', 'step_hw_frac')
+  assert not [k for k in moved if k in out or k in record], (sorted(out), sorted(record))
+  full, _ = run('full', ['--full', '--no-alt', '--no-cpu-baseline'])
+  assert full['parity']['passed'] is True and full['roofline']['frac'] > 0
+  for name in ('loss', 'loss_f64', 'logits', 'weights', 'grads'):
+    a, b = np.load(str(tmp_path / 'plain' / (name + '.npy'))), np.load(str(tmp_path / 'full' / (name + '.npy')))
+    assert a.shape == b.shape and np.array_equal(a, b), name

@@ -223,7 +223,7 @@ def test_bucket_exchange_waits_for_side_stream_filter_gradients(tmp_path, mode):
 
 
 def test_bench_rccl_transport_through_the_self_launch_path_at_world_one():
-  """`python bench.py --gpus 1 --self-launch --force-allreduce --allreduce rccl`: torch.distributed.run starts the one
+  """`python bench.py --gpus 1 --full --self-launch --force-allreduce --allreduce rccl`: torch.distributed.run starts the one
   rank, the library's communicator is created from the broadcast id, every bucket goes through st_allreduce_buckets_f32,
   and the line says who exchanged: torch.distributed's world size AND the communicator's own rank count."""
   if not torch.cuda.is_available():
@@ -232,8 +232,8 @@ def test_bench_rccl_transport_through_the_self_launch_path_at_world_one():
   for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--self-launch', '--force-allreduce',
-                      '--allreduce', 'rccl', '--steps', '3', '--warmup', '1', '--batch', '4', '--seconds', '2', '--no-alt',
-                      '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                      '--allreduce', 'rccl', '--steps', '3', '--warmup', '1', '--batch', '4', '--seconds', '2', '--full',
+                      '--no-alt', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
   assert len(lines) == 1, r.stdout
