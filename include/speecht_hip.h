@@ -316,6 +316,41 @@ int st_ctc_greedy_decode(const st_tensor3* logits, const int32_t* seq_lens, int 
                          int32_t* ids, int max_out, int32_t* out_lens, float* neg_sum_logits,
                          void* stream);
 
+/* ---- Forced alignment: the best-path (Viterbi) CTC alignment of given labels (csrc/ctc_align.hip) ----
+ * Conventions of st_ctc_loss_grad_f32: logits [B, T', C] padded NWC, blank = C-1, C <= 32, labels CSR, labels up to 511
+ * (max_label_len picks the same states-per-lane dispatch), enqueues only, never allocates.
+ *
+ * Semantics (the float64 specification is tests/align_oracle.py).  The lattice of utterance b has U = 2L+1 states: even
+ * states are blanks, odd state u is label (u-1)/2.  A path assigns one state to each of the seq_lens[b] frames; it
+ *  - starts in state 0 or 1 and ends in state U-1 or U-2,
+ *  - moves by 0 (stay), 1 (advance) or 2 (skip) states per frame, the skip only from a label to a DIFFERENT label,
+ *  - and the one returned maximises sum_t ln softmax(logits[t])[class of the state at t].
+ * Ties go to the smaller move: stay, then advance, then skip (decided at the later frame, over the best scores of the three
+ * predecessors); a tie at the end goes to the last label state.  L = 0 is valid: every frame is blank, spans is empty.
+ * Logits may be -inf for single classes; if that leaves no path of finite score, score = -inf and spans / states are
+ * unspecified (status stays 0).
+ *
+ * Outputs: spans [label_offsets[B]][2] = first frame, one past the last frame spent in that label's state;
+ * states [B][frames] (may be null) = label index at each frame, -1 = blank, -2 = frame >= seq_lens[b];
+ * score [B] = ln p(best path), rounded to float from the double the lattice is kept in;
+ * status [B] != 0: the label does not fit (seq_lens[b] < L + adjacent repeats, seq_lens[b] outside 0..frames, or L beyond
+ * what max_label_len was dispatched for) -- then score = -inf, the utterance's spans are {-1, -1} and all its states -2.
+ * Every output is written with ordinary vector stores.
+ *
+ * Workspace (16-byte aligned): st_ctc_align_ws = batch * frames * (32 * 8 + 64 * 4) + batch * 4 + 512 bytes for
+ * 0 <= max_label_len <= 511 and batch, frames > 0 (else 0): the ln-softmax rows in double, one 256-byte back-pointer row per
+ * frame (2 bits per state, one uint32 per lane) and the end states.
+ *
+ * st_ctc_align_host: the same recursion (shared arithmetic, csrc/ctc_align_core.h: identical paths, ties included) on HOST
+ * pointers, logits as a dense [batch][frames][classes] array; needs no device. */
+size_t st_ctc_align_ws(int batch, int frames, int max_label_len);
+int st_ctc_align_f32(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets,
+                     const int32_t* seq_lens, int max_label_len, int32_t* spans, int32_t* states, float* score,
+                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_align_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,
+                      const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, int32_t* spans,
+                      int32_t* states, float* score, int32_t* status, void* workspace, size_t workspace_bytes);
+
 /* ---- LM-free CTC prefix beam search, top path (BASELINE config 5) -----
  * The reference only reaches a beam search through its KenLM TensorFlow fork
  * (speech_model.py:101-111: beam_width=100, merge_repeated=False, top_paths=1); this is the stock

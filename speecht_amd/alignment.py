@@ -1,0 +1,227 @@
+"""Forced alignment: when each word of a known transcript was said -- `speecht-cli align` and its Python API -- and the word
+times of `speecht-cli transcribe --timestamps`.
+
+The alignment itself is the best CTC path of the transcript's ids against the network's logits (`engine.align`,
+st_ctc_align_f32; semantics and tie rules: include/speecht_hip.h).  This module turns its per-character frame spans into words
+and seconds and runs it over audio files as `transcription.transcribe_files` runs the decoders.
+
+What a time means: one output frame of the network covers ``2 * hop_length`` samples (the features hop by ``hop_length`` = 160
+samples and the first layer strides by 2), so frame f is reported as ``f * 2 * hop_length / sample_rate`` seconds.  That is a
+NOMINAL time: the network's receptive field is wide (hundreds of milliseconds), a frame's logits depend on audio well before
+and after its nominal position, and CTC training does not tie a character's peak to its acoustic onset.
+"""
+import contextlib
+import json
+import os
+import sys
+import time
+
+from . import inference, transcription, vocabulary
+
+HOP_LENGTH = 160                      # preprocessing.power_spectrogram_device / mfccs_device
+TRANSCRIPT_SUFFIX = '.trans.txt'
+
+
+def char_spans(ids, spans):
+  """-> list of (character, first frame, end frame) for every id."""
+  return [(vocabulary.id_to_letter(i), int(s[0]), int(s[1])) for i, s in zip(ids, spans)]
+
+
+def word_spans(ids, spans):
+  """Words are maximal runs of ids other than space: -> list of (word, first frame of its first character, end frame of its
+  last character).  Leading, trailing and repeated spaces produce no words."""
+  words, start = [], None
+  ids = list(ids)
+  for k, i in enumerate(ids + [vocabulary.SPACE_ID]):
+    if i != vocabulary.SPACE_ID:
+      if start is None:
+        start = k
+    elif start is not None:
+      words.append((vocabulary.ids_to_sentence(ids[start:k]), int(spans[start][0]), int(spans[k - 1][1])))
+      start = None
+  return words
+
+
+def frames_to_seconds(frame, sample_rate, hop_length=HOP_LENGTH, duration=None):
+  """Nominal time of output frame ``frame`` (see the module text): ``frame * 2 * hop_length / sample_rate`` seconds, clipped
+  to [0, duration] when the file's duration is given."""
+  t = max(float(frame) * 2.0 * hop_length / float(sample_rate), 0.0)
+  return t if duration is None else min(t, float(duration))
+
+
+def timed_words(ids, spans, sample_rate, duration=None, chars=False):
+  """The JSON form: [{word, start, end}] in seconds (``chars``: of the single characters, as {char, start, end})."""
+  sec = lambda f: round(frames_to_seconds(f, sample_rate, HOP_LENGTH, duration), 4)
+  if chars:
+    return [dict(char=c, start=sec(a), end=sec(b)) for c, a, b in char_spans(ids, spans)]
+  return [dict(word=w, start=sec(a), end=sec(b)) for w, a, b in word_spans(ids, spans)]
+
+
+def read_transcripts(path):
+  """A LibriSpeech-style transcript file, ``<id> <text>`` per line -> {id: text}; parsed as preprocessing.SpeechCorpusReader
+  parses it (split at the first space), blank lines skipped, an id without text maps to ''."""
+  out = {}
+  with open(path, 'r') as f:
+    for line in f:
+      line = line.rstrip('\n').rstrip('\r')
+      if not line.strip():
+        continue
+      parts = line.split(' ', 1)
+      out[parts[0]] = parts[1] if len(parts) > 1 else ''
+  return out
+
+
+def find_transcripts(paths, transcripts_file=None):
+  """{audio path: transcript text or None}: from ``transcripts_file`` when given, else from the *.trans.txt files in each audio
+  file's own directory; the key is the file's stem."""
+  tables = {}
+
+  def table(directory):
+    if directory not in tables:
+      merged = {}
+      try:
+        names = sorted(n for n in os.listdir(directory or '.') if n.endswith(TRANSCRIPT_SUFFIX))
+      except OSError:
+        names = []
+      for n in names:
+        merged.update(read_transcripts(os.path.join(directory or '.', n)))
+      tables[directory] = merged
+    return tables[directory]
+
+  given = read_transcripts(transcripts_file) if transcripts_file else None
+  out = {}
+  for p in paths:
+    stem = os.path.splitext(os.path.basename(p))[0]
+    out[p] = (given if given is not None else table(os.path.dirname(p))).get(stem)
+  return out
+
+
+def transcript_ids(text):
+  """Ids of a transcript as the corpus reader makes them (vocabulary.sentence_to_ids after lower-casing); raises
+  TranscriptionError for a character outside the vocabulary."""
+  ids = vocabulary.sentence_to_ids(text.lower())
+  bad = sorted({ch for ch, i in zip(text.lower(), ids) if not 0 <= i < vocabulary.SIZE})
+  if bad:
+    raise transcription.TranscriptionError('transcript has characters outside the vocabulary: {}'.format(' '.join(map(repr, bad))))
+  return ids
+
+
+def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None):
+  """Align audio files with their transcripts -> a list, in ``paths`` order, of dicts
+  {path, seconds, sample_rate, text, ids, spans, score, frames, error}.  ``transcripts``: {path: text} (`find_transcripts`) or
+  a list parallel to ``paths``; None = no transcript.  ``error`` is the message for a file that is unreadable, too short, has no
+  transcript, or whose transcript does not fit its frames or the vocabulary (spans is None then); the other files go on.
+  ``spans``: [L, 2] output frames per id; ``frames``: output frames of the utterance; ``sample_rate``: the rate the features
+  were computed at (what `frames_to_seconds` needs).  Batch semantics as `transcription.transcribe_files`."""
+  texts = [transcripts.get(p) for p in paths] if isinstance(transcripts, dict) else list(transcripts)
+  if len(texts) != len(paths):
+    raise ValueError('align_files: {} paths and {} transcripts'.format(len(paths), len(texts)))
+  results, signals, rates, ok = [], [], [], []
+  t0 = time.perf_counter()
+  for path, text in zip(paths, texts):
+    entry = dict(path=path, seconds=None, sample_rate=None, text=None, ids=None, spans=None, score=None, frames=None, error=None)
+    results.append(entry)
+    try:
+      samples, rate = transcription.load_native(path)
+      entry['seconds'] = len(samples) / float(rate)
+      entry['sample_rate'] = transcription._target_rate(rate, sample_rate)
+      transcription.check_length(len(samples), rate, sample_rate, path)
+      if text is None:
+        raise transcription.TranscriptionError('{}: no transcript'.format(path))
+      try:
+        entry['ids'] = transcript_ids(text)
+      except transcription.TranscriptionError as e:
+        raise transcription.TranscriptionError('{}: {}'.format(path, e)) from e
+      entry['text'] = text.lower()
+      if len(entry['ids']) > MAX_LABELS:
+        raise transcription.TranscriptionError('{}: transcript of {} characters is too long to align (max {})'.format(
+            path, len(entry['ids']), MAX_LABELS))
+    except transcription.TranscriptionError as e:
+      entry['error'] = str(e)
+      continue
+    signals.append(samples)
+    rates.append(rate)
+    ok.append(entry)
+  t1 = time.perf_counter()
+  if ok:
+    feats = transcription.device_features(signals, rates, feature_type, sample_rate, engine.device)
+    t2 = time.perf_counter()
+    spans, scores, status = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size)
+    for entry, f, sp, sc, st in zip(ok, feats, spans, scores, status):
+      entry['frames'] = output_frames(f.shape[0])
+      if st != 0:
+        entry['error'] = '{}: transcript does not fit: {} characters (repeats need a frame between them) on {} output frames'.format(
+            entry['path'], len(entry['ids']), entry['frames'])
+      else:
+        entry['spans'], entry['score'] = sp, sc
+  else:
+    t2 = t1
+  if timings is not None:
+    timings.update(decode_host=t1 - t0, features=t2 - t1, align=time.perf_counter() - t2)
+  return results
+
+
+MAX_LABELS = 511                      # engine_decode.MAX_ALIGN_LABELS (kept here so that this module imports without torch)
+
+
+def output_frames(feature_frames):
+  """Output frames of the network for ``feature_frames`` input frames: what the engine hands CTC and the decoders
+  (sequence_lengths // 2, speech_model.py:74)."""
+  return int(feature_frames) // 2
+
+
+def result_json(entry, chars=False):
+  """The --output line of an aligned (or transcribed with --timestamps) file."""
+  rate, dur = entry['sample_rate'], entry['seconds']
+  out = dict(path=entry['path'], seconds=dur, text=entry['text'])
+  if entry.get('score') is not None:
+    out['score'] = entry['score']
+    out['score_per_frame'] = entry['score'] / max(entry['frames'], 1)
+  out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur)
+  if chars:
+    out['chars'] = timed_words(entry['ids'], entry['spans'], rate, dur, chars=True)
+  return out
+
+
+def print_words(entry, file=None):
+  """One line per word: path<TAB>start<TAB>end<TAB>word."""
+  for w in timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds']):
+    print('{}\t{:.3f}\t{:.3f}\t{}'.format(entry['path'], w['start'], w['end'], w['word']), file=file or sys.stdout, flush=True)
+
+
+def run_cli(flags):
+  """`speecht-cli align`: prints path<TAB>start<TAB>end<TAB>word per word in input order (and JSON lines to --output); a file that
+  cannot be aligned is reported on stderr and makes the exit status 1.  Creates no train / data / log directory."""
+  from .speech_input import SingleInputLoader
+  from .speech_model import Session, create_default_model
+  paths = transcription.expand_paths(flags.paths)
+  if not paths:
+    print('align: no audio files found in {}'.format(' '.join(flags.paths)), file=sys.stderr)
+    return 1
+  try:
+    transcripts = find_transcripts(paths, flags.transcripts)
+  except OSError as e:
+    print('align: cannot read transcripts: {}'.format(e), file=sys.stderr)
+    return 1
+  input_size = transcription.FEATURE_WIDTH[flags.feature_type]
+  with contextlib.redirect_stdout(sys.stderr):          # stdout carries the word lines only
+    model = create_default_model(flags, input_size, SingleInputLoader(input_size))
+  with Session(flags.device) as sess:
+    with contextlib.redirect_stdout(sys.stderr):
+      model.restore(sess, flags.run_train_dir)
+    results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size)
+  out = open(flags.output, 'w') if flags.output else None
+  status = 0
+  try:
+    for r in results:
+      if r['error'] is not None:
+        print('align: {}'.format(r['error']), file=sys.stderr)
+        status = 1
+        continue
+      print_words(r)
+      if out:
+        out.write(json.dumps(result_json(r, chars=flags.chars)) + '\n')
+  finally:
+    if out:
+      out.close()
+  return status

@@ -1,6 +1,7 @@
 """Decoders of the engine (speech_model.py:101-115): greedy CTC decoding, the LM-free prefix beam search and the prefix beam
 search with a word n-gram scorer, synchronous and
-with their outputs on the way to pinned host memory (`inference.transcribe` overlaps them with the next batches)."""
+with their outputs on the way to pinned host memory (`inference.transcribe` overlaps them with the next batches) -- and `align`,
+the forced alignment of given labels against the same logits."""
 import ctypes
 
 import numpy as np
@@ -49,6 +50,9 @@ class _PendingBeamDecode:
 # the largest workspace lm_beam_search_decode_candidates gives one call: 16 candidates x 64 utterances x 500 frames at beam 100
 # hold 410 MB of node pools, so a generation of that size runs in one call
 CANDIDATE_WORKSPACE_BYTES = 1 << 30
+
+
+MAX_ALIGN_LABELS = 511          # labels per utterance of st_ctc_align_f32 (the 16-states-per-lane lattice of st_ctc_loss_grad_f32)
 
 
 class CandidateDecodes:
@@ -155,6 +159,45 @@ class DecodeMixin:
     if merge_repeated:
       out = [merge_repeated_labels(seq) for seq in out]
     return out, sh.dec_score.cpu().numpy().reshape(-1, 1)
+
+  def align(self, labels, return_states=False):
+    """Forced alignment (st_ctc_align_f32; semantics: include/speecht_hip.h, tests/align_oracle.py): the best CTC path of the
+    given id lists, one per utterance of the batch, against the logits of the current shape
+    -> (list of [L_b, 2] int32 arrays: first frame and one past the last frame of each label, score [B, 1] = ln p(best path),
+    status [B]: != 0 where the label does not fit its utterance's frames -- then score = -inf and the spans are -1).
+    ``return_states``: a fourth element, [B, T'] int32, the label index of every frame (-1 blank, -2 beyond the utterance).
+    Labels hold ids in [0, num_classes - 1) and at most MAX_ALIGN_LABELS of them."""
+    lib = _lib.load()
+    sh = self.shape
+    xl = sh.X[-1]
+    B, T = xl.batch, xl.frames
+    if len(labels) != B:
+      raise ValueError('align: {} label sequences for a batch of {}'.format(len(labels), B))
+    lens = [len(l) for l in labels]
+    offs = np.zeros(B + 1, dtype=np.int32)
+    offs[1:] = np.cumsum(lens)
+    N, max_len = int(offs[-1]), int(max(lens + [0]))
+    if max_len > MAX_ALIGN_LABELS:
+      raise ValueError('align: label of length {} is too long for the alignment kernel (max {})'.format(max_len, MAX_ALIGN_LABELS))
+    ids = np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in labels] + [np.zeros(1, np.int32)])
+    # the kernel indexes LDS rows with the id: it must never see one outside the classes
+    if N and (int(ids.min()) < 0 or int(ids.max()) >= self.num_classes - 1):
+      raise ValueError('align: label ids must lie in [0, {}) (blank = {})'.format(self.num_classes - 1, self.num_classes - 1))
+    need = lib.st_ctc_align_ws(B, T, max_len)
+    ws = self._storage.view('align_ws', need // 4 + 16, torch.int32)[0]
+    # outputs in one buffer, one copy back: spans [N][2] | states [B][T] | status [B] | score [B] (float bits)
+    out = self._storage.view('align_out', 2 * N + B * T + 2 * B, torch.int32)[0]
+    at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+    d_ids, d_offs = self._upload_i32(ids), self._upload_i32(offs)
+    self._wait_uploads()
+    call('st_ctc_align_f32', xl.ref, self._ptr(d_ids), self._ptr(d_offs), self._ptr(self.ctc_lens), max_len,
+         at(0), at(2 * N), at(2 * N + B * T + B), at(2 * N + B * T), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    with torch.cuda.stream(self.stream):
+      host = out[:2 * N + B * T + 2 * B].cpu().numpy()
+    spans = host[:2 * N].reshape(N, 2)
+    res = ([spans[offs[b]:offs[b + 1]].copy() for b in range(B)],
+           host[2 * N + B * T + B:].view(np.float32).reshape(-1, 1).copy(), host[2 * N + B * T:2 * N + B * T + B].copy())
+    return res + (host[2 * N:2 * N + B * T].reshape(B, T).copy(),) if return_states else res
 
   def lm_beam_search_decode(self, lm, beam_width=100, input_transform='log10_softmax', lm_weight=0.8, word_count_weight=0.0,
                             valid_word_count_weight=2.3, oov_score=-1000.0):

@@ -44,7 +44,8 @@ DEFAULT_PIPELINE = True
 BEAM_DECODERS = 2
 
 
-def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None):
+def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None,
+               timestamps=False):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -59,11 +60,20 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
 
   ``language_model`` (a `language_model.LanguageModel` or a path to an ARPA model): the LM-scored beam search instead, the
   reference's decoder (beam 100 unless ``beam_width`` says otherwise; ``lm_options``: keyword arguments of
-  ``engine.lm_beam_search_decode`` -- input_transform, lm_weight, word_count_weight, valid_word_count_weight, oov_score)."""
+  ``engine.lm_beam_search_decode`` -- input_transform, lm_weight, word_count_weight, valid_word_count_weight, oov_score).
+
+  ``timestamps=True``: a third element, one [L, 2] int32 array per utterance -- the first output frame and one past the last
+  output frame of every decoded id on the best CTC path of those ids (``engine.align``; `alignment.word_spans` and
+  `alignment.frames_to_seconds` turn them into word times).  Whichever decoder ran, its ids are aligned against the logits of
+  their batch before the next batch overwrites them, so the batches run one after the other (the serial loop: same launches
+  on the same data, hence the same ids as without timestamps).  An utterance that decodes to more than
+  ``engine_decode.MAX_ALIGN_LABELS`` ids gets None.  With ``timestamps=False`` nothing changes."""
   if not features:
-    return [], []
+    return ([], [], []) if timestamps else ([], [])
   if pipeline is None:
     pipeline = DEFAULT_PIPELINE
+  if timestamps:
+    pipeline = False
   lm_opts = dict(lm_options or {})
   if language_model is not None:
     from .language_model import LanguageModel
@@ -83,6 +93,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
 
   lengths, buckets = _plan(features, batch_size, bucket)
   ids_out = [None] * len(features)
+  spans_out = [None] * len(features)
   if not pipeline:
     for idx in buckets:
       max_t = max(lengths[i] for i in idx)
@@ -94,7 +105,12 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
       ids = decode_sync()
       for row, i in enumerate(idx):
         ids_out[i] = ids[row]
-    return ids_out, [vocabulary.ids_to_sentence(s) for s in ids_out]
+      if timestamps:
+        spans = _align_current(engine, ids)[0]
+        for row, i in enumerate(idx):
+          spans_out[i] = spans[row]
+    texts = [vocabulary.ids_to_sentence(s) for s in ids_out]
+    return (ids_out, texts, spans_out) if timestamps else (ids_out, texts)
 
   def collect(handle, idx):
     res = handle.result()
@@ -133,6 +149,47 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
       if beam_width:
         torch.cuda.synchronize(engine.device)    # nothing of this call is left on the masked streams
   return ids_out, [vocabulary.ids_to_sentence(s) for s in ids_out]
+
+
+def _align_current(engine, labels):
+  """``engine.align`` on the batch the engine holds, with labels the kernel cannot take (longer than MAX_ALIGN_LABELS) left out:
+  their spans are None, their score -inf and their status 1."""
+  from .engine_decode import MAX_ALIGN_LABELS
+  long = [len(l) > MAX_ALIGN_LABELS for l in labels]
+  spans, score, status = engine.align([[] if skip else l for l, skip in zip(labels, long)])
+  for row, skip in enumerate(long):
+    if skip:
+      spans[row], score[row, 0], status[row] = None, -np.inf, 1
+  return spans, score, status
+
+
+def align(engine, features, labels, batch_size=1, bucket=True):
+  """Forced alignment of known transcripts: features as for `transcribe`, ``labels`` one id list per utterance
+  -> (spans, scores, status) in input order: spans[i] an [L_i, 2] int32 array (first output frame, one past the last output
+  frame of each id on the best CTC path), scores[i] = ln p(that path), status[i] != 0 where the transcript does not fit the
+  utterance's output frames (its spans are -1; None for a transcript of more than MAX_ALIGN_LABELS ids).
+
+  Batched as `transcribe` batches.  ``batch_size=1`` is the default for the reason `transcription` gives: nothing in the
+  network is masked, so the logits near the end of an utterance depend on the padded length of its batch, and with them the
+  times of its last words."""
+  if len(features) != len(labels):
+    raise ValueError('align: {} feature arrays and {} label sequences'.format(len(features), len(labels)))
+  n = len(features)
+  spans_out, score_out, status_out = [None] * n, [float('-inf')] * n, [1] * n
+  if not features:
+    return spans_out, score_out, status_out
+  lengths, buckets = _plan(features, batch_size, bucket)
+  for idx in buckets:
+    max_t = max(lengths[i] for i in idx)
+    x = np.zeros((len(idx), max_t, features[0].shape[1]), dtype=np.float32)
+    for row, i in enumerate(idx):
+      x[row, :lengths[i]] = features[i]
+    engine.load_batch(x, [lengths[i] for i in idx])
+    engine.forward()
+    spans, score, status = _align_current(engine, [labels[i] for i in idx])
+    for row, i in enumerate(idx):
+      spans_out[i], score_out[i], status_out[i] = spans[row], float(score[row, 0]), int(status[row])
+  return spans_out, score_out, status_out
 
 
 _STREAMS = {}      # device -> the stagers' copy stream

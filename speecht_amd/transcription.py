@@ -108,10 +108,12 @@ def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=2
   return inference.transcribe(engine, feats, batch_size=batch_size, **decode)
 
 
-def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, **decode):
+def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, timestamps=False, **decode):
   """Transcribe audio files (.flac, 16-bit .wav, .npy taken as 16 kHz) -> a list, in ``paths`` order, of dicts
   {path, seconds, text, ids, error}: ``error`` is the message for a file that cannot be read or is too short (its text and
   ids are None); the other files are transcribed as transcribe_audio does (same arguments, same batch semantics).
+  ``timestamps=True`` adds ``spans`` ([L, 2] output frames per id, inference.transcribe; None when the text is too long to align),
+  ``frames`` and ``sample_rate`` (the rate of the features), which `alignment.timed_words` turns into word times.
   ``timings``: a dict that receives the seconds spent in host decoding ('decode_host'), resampling and features
   ('features') and the network with the decoder ('transcribe')."""
   results = []
@@ -134,9 +136,12 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   if ok:
     feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
-    ids, texts = inference.transcribe(engine, feats, batch_size=batch_size, **decode)
-    for entry, i, t in zip(ok, ids, texts):
+    res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, **decode)
+    for entry, i, t in zip(ok, res[0], res[1]):
       entry['ids'], entry['text'] = i, t
+    if timestamps:
+      for entry, f, rate, sp in zip(ok, feats, rates, res[2]):
+        entry.update(spans=sp, frames=f.shape[0] // 2, sample_rate=_target_rate(rate, sample_rate))
   else:
     t2 = t1
   if timings is not None:
@@ -167,7 +172,9 @@ def run_cli(flags):
   with Session(flags.device) as sess:
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)          # FileNotFoundError('No checkpoint for evaluation found'), as evaluate
-    results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, **decode)
+    timestamps = bool(getattr(flags, 'timestamps', False))
+    results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, timestamps=timestamps,
+                               **decode)
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:
@@ -177,8 +184,13 @@ def run_cli(flags):
         status = 1
         continue
       print('{}\t{}'.format(r['path'], r['text']), flush=True)
+      line = dict(path=r['path'], seconds=r['seconds'], text=r['text'])
+      if timestamps and r['spans'] is not None:
+        from . import alignment
+        alignment.print_words(r)
+        line['words'] = alignment.timed_words(r['ids'], r['spans'], r['sample_rate'], r['seconds'])
       if out:
-        out.write(json.dumps(dict(path=r['path'], seconds=r['seconds'], text=r['text'])) + '\n')
+        out.write(json.dumps(line) + '\n')
   finally:
     if out:
       out.close()
