@@ -295,7 +295,14 @@ int st_conv1d_nwc_bwd_filter_f32(const st_tensor3* x, const st_tensor3* dz, int 
  * (0 for t >= seq_lens[b]); status[b] != 0 when the label does not fit ("Not enough time for
  * target transition sequence") -- then loss = +inf and grad = 0.  The forward-backward lattice is kept as mantissa * 2^exponent
  * with an integer exponent per state (not in log space): exact range, no transcendental on the sequential chain; a class more than
- * 2^-30000 below its frame's best counts as impossible.  Workspace: st_ctc_ws bytes (log-softmax, emission factors, two lattices). */
+ * 2^-30000 below its frame's best counts as impossible.  Workspace: st_ctc_ws bytes (log-softmax, emission factors, two lattices).
+ * The two tensors may differ in halo, t_pitch and c_pitch (logits: c_pitch >= 32).  Of the logits only columns < C of frames
+ * 0 .. frames-1 are read -- never a pitch column, a halo row or a row beyond the frames -- and what rows t >= seq_lens[b] hold
+ * changes no output bit (the log-softmax does run over those rows, into scratch nobody reads).  Of grad,
+ * columns 0 .. min(c_pitch, 32) - 1 of every frame 0 .. frames-1 are written: zeros in columns >= C, in rows t >= seq_lens[b]
+ * and in every row of a refused utterance; columns >= 32, halo rows and rows beyond the frames are left untouched.  An empty
+ * label over seq_lens[b] = 0 frames is valid: loss exactly 0.  Every utterance's result is independent of the rest of the
+ * batch and the same bits from run to run. */
 size_t st_ctc_ws(int batch, int frames, int max_label_len);
 int st_ctc_loss_grad_f32(const st_tensor3* logits, const int32_t* label_ids,
                          const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len,
@@ -311,7 +318,9 @@ int st_ctc_loss_grad_hilo_f32(const st_tensor3* logits, const int32_t* label_ids
                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K14: tf.nn.ctc_greedy_decoder(merge_repeated) (speech_model.py:113-115) ------------
- * ids [B][max_out] int32 (max_out >= frames), out_lens [B], neg_sum_logits [B]. */
+ * ids [B][max_out] int32 (max_out >= frames), out_lens [B], neg_sum_logits [B].  Row b of ids is written in its first
+ * out_lens[b] entries only, the rest is left untouched.  With a max_out smaller than an utterance's output, out_lens[b] still
+ * is the full count and the first max_out ids are written.  Logits are read in columns < C of frames t < seq_lens[b] alone. */
 int st_ctc_greedy_decode(const st_tensor3* logits, const int32_t* seq_lens, int merge_repeated,
                          int32_t* ids, int max_out, int32_t* out_lens, float* neg_sum_logits,
                          void* stream);
