@@ -293,7 +293,9 @@ int st_conv1d_nwc_bwd_filter_f32(const st_tensor3* x, const st_tensor3* dz, int 
  * [B+1], label_ids [label_offsets[B]].  seq_lens[b] = frames to use (reference passes
  * sequence_lengths // 2).  Outputs: loss[b] = -log p(l|x); grad = grad_scale * dloss/dlogits
  * (0 for t >= seq_lens[b]); status[b] != 0 when the label does not fit ("Not enough time for
- * target transition sequence") -- then loss = +inf and grad = 0.  The forward-backward lattice is kept as mantissa * 2^exponent
+ * target transition sequence": seq_lens[b] < L + adjacent repeats, seq_lens[b] outside 0..frames, L beyond what max_label_len
+ * was dispatched for, or a negative L, i.e. label_offsets that do not increase) -- then loss = +inf and grad = 0.  A negative
+ * max_label_len counts as 0.  The forward-backward lattice is kept as mantissa * 2^exponent
  * with an integer exponent per state (not in log space): exact range, no transcendental on the sequential chain; a class more than
  * 2^-30000 below its frame's best counts as impossible.  Workspace: st_ctc_ws bytes (log-softmax, emission factors, two lattices).
  * The two tensors may differ in halo, t_pitch and c_pitch (logits: c_pitch >= 32).  Of the logits only columns < C of frames
@@ -342,8 +344,8 @@ int st_ctc_greedy_decode(const st_tensor3* logits, const int32_t* seq_lens, int 
  * Outputs: spans [label_offsets[B]][2] = first frame, one past the last frame spent in that label's state;
  * states [B][frames] (may be null) = label index at each frame, -1 = blank, -2 = frame >= seq_lens[b];
  * score [B] = ln p(best path), rounded to float from the double the lattice is kept in;
- * status [B] != 0: the label does not fit (seq_lens[b] < L + adjacent repeats, seq_lens[b] outside 0..frames, or L beyond
- * what max_label_len was dispatched for) -- then score = -inf, the utterance's spans are {-1, -1} and all its states -2.
+ * status [B] != 0: the label does not fit (seq_lens[b] < L + adjacent repeats, seq_lens[b] outside 0..frames, L beyond
+ * what max_label_len was dispatched for, or a negative L: the rule of st_ctc_loss_grad_f32, csrc/ctc_lattice.h) -- then score = -inf, the utterance's spans are {-1, -1} and all its states -2.
  * Every output is written with ordinary vector stores.
  *
  * Workspace (16-byte aligned): st_ctc_align_ws = batch * frames * (32 * 8 + 64 * 4) + batch * 4 + 512 bytes for

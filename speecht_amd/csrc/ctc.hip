@@ -13,29 +13,25 @@
 //     2L+1 lattice states are dealt KPL-contiguous per lane, so a whole time step is register
 //     arithmetic plus four cross-lane shifts (DPP) -- no LDS round trip, no barrier on the 500-1500
 //     step critical path.  Emission factors are staged through LDS in 64-frame chunks, prefetched
-//     one chunk ahead.  alpha and beta run concurrently on different CUs.
+//     one chunk ahead.  alpha and beta run concurrently on different CUs.  The dispatch list, the refusal
+//     rule, the chunk stage and the DPP move are ctc_lattice.h's, shared with ctc_align.hip.
 //  3. ctc_grad: fully parallel over (b, t): occupancy per class from alpha+beta with a fixed
 //     summation order (per-class position lists), so results are run-to-run deterministic.
 #include <algorithm>
 
+#include "ctc_lattice.h"
 #include "st_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using st::RowMap;
+using st::dpp_shift;
+constexpr int SHR1 = st::DPP_WAVE_SHR1, SHL1 = st::DPP_WAVE_SHL1;
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int CP = 32;        // class pitch of the log-softmax scratch
-constexpr int TC = 64;        // frames per LDS emission chunk
+constexpr int TC = st::LATTICE_TC;   // frames per LDS emission chunk
 #define NEG_INF (-__builtin_inff())
-
-struct RowMap2 {   // (b, t) -> float offset
-  long batch_stride;
-  long row0;
-  int row_stride;
-  __device__ __forceinline__ long off(int b, int t) const {
-    return (long)b * batch_stride + row0 + (long)t * row_stride;
-  }
-};
 
 // ---- scaled arithmetic --------------------------------------------------------------------------
 // A lattice value is m * 2^e: m a float in [0.5, 1) (0: no path reaches the state), e an int of its own PER STATE.
@@ -50,18 +46,8 @@ struct RowMap2 {   // (b, t) -> float offset
 constexpr int EZ = -(1 << 28);           // exponent of a zero state: below anything a path reaches, differences stay in int range
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// cross-lane moves on the VALU (DPP), no LDS round trip; lanes without a source keep `fill`
-template <int CTRL>
-__device__ __forceinline__ int dpp_movei(int v, int fill) {
-  return __builtin_amdgcn_update_dpp(fill, v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_movef(float v, float fill) {
-  return __builtin_bit_cast(float, dpp_movei<CTRL>(__builtin_bit_cast(int, v), __builtin_bit_cast(int, fill)));
-}
 // (by value: __builtin_bit_cast applied directly to a vector ELEMENT reads element 0 -- clang takes the vector's address)
 __device__ __forceinline__ int ibits(float x) { return __builtin_bit_cast(int, x); }
-constexpr int SHR1 = 0x138, SHL1 = 0x130;   // wave_shr:1 (value of the lane below), wave_shl:1 (of the lane above)
 
 // m * 2^e of the three aligned terms; zero terms (m = 0, any e) drop out, all zero -> 0 * 2^EZ
 __device__ __forceinline__ float aligned_sum3(float m0, int e0, float m1, int e1, float m2, int e2, int& E) {
@@ -79,7 +65,7 @@ constexpr float LN2 = 0.6931471805599453f;
 // frame's distribution is nearly the same (all logits ~0, log2 y ~ -4.86), so the float rounding of log2 y (2.4e-7) had the
 // same sign on all 501 frames and the loss came out 1e-4 low (measured round 4, scripts/diag_ctc_loss.py: -9.9e-5 on a loss
 // of 1 245; the recursion itself adds ~1e-6).  What remains is the float mantissa of the factor (3e-8 relative per frame).
-__global__ __launch_bounds__(256) void ctc_logsoftmax_kernel(const float* __restrict__ logits, RowMap2 map,
+__global__ __launch_bounds__(256) void ctc_logsoftmax_kernel(const float* __restrict__ logits, RowMap map,
                                                              int B, int T, int C, float* __restrict__ logy,
                                                              float* __restrict__ emis) {
   const int lane = threadIdx.x & 63, c = lane & 31;
@@ -135,10 +121,8 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
   const int Tb = seq_lens[b];
 
   // "Not enough time for target transition sequence": L + #adjacent repeats must fit in Tb
-  int rep = 0;
-  for (int i = 1 + lane; i < L; i += 64) rep += lab[i] == lab[i - 1];
-  rep = (int)st::wave_sum((float)rep);
-  const bool bad = Tb < 0 || Tb > T || L + rep > Tb || U > UP;
+  const int rep = st::lattice_repeats(lab, L, lane);
+  const bool bad = st::lattice_refused(L, rep, Tb, T, UP);
   if (bad) {
     if (!is_beta && lane == 0) status[b] = 1;
     return;
@@ -152,11 +136,9 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
   for (int j = 0; j < KPL; ++j) {
     const int u = lane * KPL + j;
     valid[j] = u < U;
-    const bool odd = (u & 1) && valid[j];
-    const int li = (u - 1) >> 1;
-    coff[j] = 2 * (odd ? lab[li] : blank);
-    if (!is_beta) skip[j] = odd && u >= 3 && lab[li] != lab[li - 1];          // may arrive from u-2
-    else skip[j] = odd && u + 2 < U && lab[li + 1] != lab[li];                  // may leave to u+2
+    coff[j] = 2 * (valid[j] ? st::lattice_class(u, lab, blank) : blank);
+    if (!is_beta) skip[j] = valid[j] && st::lattice_skip_from_below(u, lab);     // may arrive from u-2
+    else skip[j] = valid[j] && st::lattice_skip_to_above(u, U, lab);             // may leave to u+2
   }
 
   const float* ly = emis + (long)b * T * EC;
@@ -167,22 +149,10 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
     for (int j = 0; j < KPL; ++j) o[j * 64] = f32x2{m[j], __builtin_bit_cast(float, e[j])};
   };
 
-  // stage one 64-frame chunk of emissions [chunk*TC, +TC) into E[buf]; rows past T read row T-1
-  constexpr int STG = TC * EC / 4 / 64;
-  f32x4 stage[STG];
-  auto chunk_load = [&](int chunk) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i) {
-      int f = lane + 64 * i;                 // float4 index inside the chunk
-      int t = min(chunk * TC + f / (EC / 4), T - 1);
-      stage[i] = *reinterpret_cast<const f32x4*>(ly + (long)t * EC + (f % (EC / 4)) * 4);
-    }
-  };
-  auto chunk_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i)
-      *reinterpret_cast<f32x4*>(&E[buf][(lane + 64 * i) * 4]) = stage[i];
-  };
+  st::ChunkStage<float, EC> stage;   // the emission rows of chunk ch are E[ch & 1]
+  // (through lambdas: with the two called directly the frame loops of <6> and <10> come out in another order)
+  auto chunk_load = [&](int chunk) { stage.load(ly, chunk, T, lane); };
+  auto chunk_store = [&](int buf) { stage.store(E[buf], lane); };
   float sm[KPL];   // mantissa of alpha_t(u) resp. beta_t(u)
   int se[KPL];     // its exponent
   // One step of either recursion for the KPL states of a lane: out = (a + b + [skip] c) * emission, brought back to [0.5, 1);
@@ -231,10 +201,10 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
       f32x2 em[KPL];
 #pragma unroll
       for (int j = 0; j < KPL; ++j) em[j] = *reinterpret_cast<const f32x2*>(e + coff[j]);
-      const float up1m = dpp_movef<SHR1>(sm[KPL - 1], 0.f);
-      const int up1e = dpp_movei<SHR1>(se[KPL - 1], EZ);
-      const float up2m = KPL >= 2 ? dpp_movef<SHR1>(sm[KPL >= 2 ? KPL - 2 : 0], 0.f) : dpp_movef<SHR1>(up1m, 0.f);
-      const int up2e = KPL >= 2 ? dpp_movei<SHR1>(se[KPL >= 2 ? KPL - 2 : 0], EZ) : dpp_movei<SHR1>(up1e, EZ);
+      const float up1m = dpp_shift<SHR1>(sm[KPL - 1], 0.f);
+      const int up1e = dpp_shift<SHR1>(se[KPL - 1], EZ);
+      const float up2m = KPL >= 2 ? dpp_shift<SHR1>(sm[KPL >= 2 ? KPL - 2 : 0], 0.f) : dpp_shift<SHR1>(up1m, 0.f);
+      const int up2e = KPL >= 2 ? dpp_shift<SHR1>(se[KPL >= 2 ? KPL - 2 : 0], EZ) : dpp_shift<SHR1>(up1e, EZ);
       float m1[KPL], m2[KPL];
       int e1[KPL], e2[KPL];
 #pragma unroll
@@ -286,10 +256,10 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
       f32x2 em[KPL];
 #pragma unroll
       for (int j = 0; j < KPL; ++j) em[j] = *reinterpret_cast<const f32x2*>(e + coff[j]);
-      const float dn1m = dpp_movef<SHL1>(sm[0], 0.f);
-      const int dn1e = dpp_movei<SHL1>(se[0], EZ);
-      const float dn2m = KPL >= 2 ? dpp_movef<SHL1>(sm[KPL >= 2 ? 1 : 0], 0.f) : dpp_movef<SHL1>(dn1m, 0.f);
-      const int dn2e = KPL >= 2 ? dpp_movei<SHL1>(se[KPL >= 2 ? 1 : 0], EZ) : dpp_movei<SHL1>(dn1e, EZ);
+      const float dn1m = dpp_shift<SHL1>(sm[0], 0.f);
+      const int dn1e = dpp_shift<SHL1>(se[0], EZ);
+      const float dn2m = KPL >= 2 ? dpp_shift<SHL1>(sm[KPL >= 2 ? 1 : 0], 0.f) : dpp_shift<SHL1>(dn1m, 0.f);
+      const int dn2e = KPL >= 2 ? dpp_shift<SHL1>(se[KPL >= 2 ? 1 : 0], EZ) : dpp_shift<SHL1>(dn1e, EZ);
       float m1[KPL], m2[KPL], bm[KPL];
       int e1[KPL], e2[KPL], be[KPL];
 #pragma unroll
@@ -324,7 +294,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
                                                        const int* __restrict__ label_off,
                                                        const int* __restrict__ seq_lens,
                                                        const int* __restrict__ status, float scale,
-                                                       float* __restrict__ grad, RowMap2 gmap, int gcols,
+                                                       float* __restrict__ grad, RowMap gmap, int gcols,
                                                        float* __restrict__ loss, float* __restrict__ loss_lo, int lmax) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
   int* pos_off = smem;                 // [32]
@@ -420,7 +390,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
 }
 
 // greedy decode: argmax per frame, collapse repeats, drop blanks; one block per utterance
-__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ logits, RowMap2 map, int T, int C,
+__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ logits, RowMap map, int T, int C,
                                                          const int* __restrict__ seq_lens, int merge_repeated,
                                                          int* __restrict__ ids, int max_out,
                                                          int* __restrict__ out_lens, float* __restrict__ neg_sum) {
@@ -472,34 +442,12 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict
   if (tid == 0) neg_sum[b] = -fsum[0];
 }
 
-int pick_kpl(int max_label_len) {
-  static const int opts[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
-  const int U = 2 * max_label_len + 1;
-  for (int k : opts) if (k * 64 >= U) return k;
-  return -1;
-}
-
-RowMap2 make_map2(const st_tensor3& t) {
-  RowMap2 m;
-  m.batch_stride = (long)t.t_pitch * t.c_pitch;
-  m.row0 = (long)t.halo * t.c_pitch;
-  m.row_stride = t.c_pitch;
-  return m;
-}
-
-template <int KPL>
-void launch_ab(int B, hipStream_t s, const float* emis, int T, int C, const int* ids, const int* off,
-               const int* lens, float* alpha, float* beta, int* status) {
-  hipLaunchKernelGGL((ctc_alpha_beta_kernel<KPL>), dim3(B, 2), dim3(64), 0, s, emis, T, C, ids, off, lens,
-                     alpha, beta, status);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t st_ctc_ws(int batch, int frames, int max_label_len) {
-  int kpl = pick_kpl(std::max(max_label_len, 0));
+  const int kpl = st::lattice_kpl(std::max(max_label_len, 0));
   if (kpl < 0 || batch <= 0 || frames <= 0) return 0;
   size_t rows = (size_t)batch * frames;
   // log2-softmax [rows][32] | emission factors [rows][32][2] | alpha, beta: (mantissa, exponent) records [rows][kpl*64][2]
@@ -524,7 +472,7 @@ int st_ctc_loss_grad_hilo_f32(const st_tensor3* logits, const int32_t* label_ids
              "ctc: num_classes must be 2..32 with c_pitch >= 32");
   ST_REQUIRE(grad->batch == logits->batch && grad->frames == logits->frames && grad->c_pitch >= logits->channels,
              "ctc: grad tensor mismatch");
-  const int kpl = pick_kpl(max_label_len);
+  const int kpl = st::lattice_kpl(std::max(max_label_len, 0));   // (a negative max_label_len counts as 0, as in st_ctc_ws)
   ST_REQUIRE(kpl > 0, "ctc: label length %d exceeds 511", max_label_len);
   ST_REQUIRE(workspace_bytes >= st_ctc_ws(logits->batch, logits->frames, max_label_len), "ctc: workspace too small");
   hipStream_t s = st::as_stream(stream);
@@ -535,22 +483,19 @@ int st_ctc_loss_grad_hilo_f32(const st_tensor3* logits, const int32_t* label_ids
   float* alpha = emis + rows * CP * 2;             // (mantissa, exponent) records
   float* beta = alpha + rows * kpl * 64 * 2;
   hipLaunchKernelGGL(ctc_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
-                     make_map2(*logits), B, T, C, logy, emis);
-  switch (kpl) {
-#define ST_AB(K) case K: launch_ab<K>(B, s, emis, T, C, label_ids, label_offsets, seq_lens, alpha, beta, status); break;
-    ST_AB(1) ST_AB(2) ST_AB(3) ST_AB(4) ST_AB(5) ST_AB(6) ST_AB(8) ST_AB(10) ST_AB(12) ST_AB(16)
-#undef ST_AB
-  }
+                     st::row_map(*logits), B, T, C, logy, emis);
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL(ctc_alpha_beta_kernel<k()>, dim3(B, 2), dim3(64), 0, s, emis, T, C, label_ids, label_offsets, seq_lens,
+                       alpha, beta, status);
+  });
   if (int e = st::check_launch("ctc_alpha_beta")) return e;
   const int lmax = std::max(1, kpl * 32);
   const size_t shm = (32 + (size_t)lmax * 5) * sizeof(int);
-  switch (kpl) {
-#define ST_GR(K) case K: hipLaunchKernelGGL(ctc_grad_kernel<K>, dim3(st::ceil_div(T, GF), B), dim3(256), shm, s, logy, alpha, beta, \
-                                            T, C, label_ids, label_offsets, seq_lens, status, grad_scale, grad->base,            \
-                                            make_map2(*grad), std::min(grad->c_pitch, CP), loss, loss_lo, lmax); break;
-    ST_GR(1) ST_GR(2) ST_GR(3) ST_GR(4) ST_GR(5) ST_GR(6) ST_GR(8) ST_GR(10) ST_GR(12) ST_GR(16)
-#undef ST_GR
-  }
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL(ctc_grad_kernel<k()>, dim3(st::ceil_div(T, GF), B), dim3(256), shm, s, logy, alpha, beta, T, C, label_ids,
+                       label_offsets, seq_lens, status, grad_scale, grad->base, st::row_map(*grad), std::min(grad->c_pitch, CP),
+                       loss, loss_lo, lmax);
+  });
   return st::check_launch("ctc_grad");
 }
 
@@ -561,7 +506,7 @@ int st_ctc_greedy_decode(const st_tensor3* logits, const int32_t* seq_lens, int 
   ST_REQUIRE(logits->frames <= 12000, "greedy: more than 12000 frames per utterance not supported");
   const size_t shm = ((size_t)logits->frames + 512) * sizeof(int);
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(logits->batch), dim3(256), shm, st::as_stream(stream), logits->base,
-                     make_map2(*logits), logits->frames, logits->channels, seq_lens, merge_repeated, ids, max_out,
+                     st::row_map(*logits), logits->frames, logits->channels, seq_lens, merge_repeated, ids, max_out,
                      out_lens, neg_sum_logits);
   return st::check_launch("ctc_greedy");
 }

@@ -16,36 +16,20 @@
 #include <algorithm>
 
 #include "ctc_align_core.h"
+#include "ctc_lattice.h"
 #include "st_common.h"
 
 namespace {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using st::RowMap;
+constexpr int SHR1 = st::DPP_WAVE_SHR1;
 constexpr int CP = st::AL_CP;  // class pitch of the log-softmax rows
-constexpr int TC = 64;         // frames per LDS chunk
+constexpr int TC = st::LATTICE_TC;   // frames per LDS chunk
 constexpr int BPW = 64;        // back-pointer words per frame (one per lane)
 #define NEG_INF_F (-__builtin_inff())
 
-struct RowMap2 {   // (b, t) -> float offset
-  long batch_stride;
-  long row0;
-  int row_stride;
-  __device__ __forceinline__ long off(int b, int t) const {
-    return (long)b * batch_stride + row0 + (long)t * row_stride;
-  }
-};
-
-constexpr int SHR1 = 0x138;   // wave_shr:1: the value of the lane below; lane 0 keeps `fill`
-__device__ __forceinline__ double dpp_shr1(double v, double fill) {
-  const long long vb = st::al_bits(v), fb = st::al_bits(fill);
-  const int lo = __builtin_amdgcn_update_dpp((int)fb, (int)vb, SHR1, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(fb >> 32), (int)(vb >> 32), SHR1, 0xF, 0xF, false);
-  return st::al_from_bits(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // ln softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum)
-__global__ __launch_bounds__(256) void align_logsoftmax_kernel(const float* __restrict__ logits, RowMap2 map, int B, int T,
+__global__ __launch_bounds__(256) void align_logsoftmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T,
                                                                int C, double* __restrict__ ly) {
   const int lane = threadIdx.x & 63, c = lane & 31;
   const long i = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
@@ -80,13 +64,9 @@ __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restr
   const int U = 2 * L + 1;
   const int Tb = seq_lens[b];
 
-  // "Not enough time for target transition sequence": L + #adjacent repeats must fit in Tb (as ctc_alpha_beta_kernel)
-  const bool fits = L >= 0 && U <= UP;
-  int rep = 0;
-  if (fits) for (int i = 1 + lane; i < L; i += 64) rep += lab[i] == lab[i - 1];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rep += __shfl_xor(rep, o, 64);
-  const bool bad = !fits || Tb < 0 || Tb > T || L + rep > Tb;
+  // "Not enough time for target transition sequence": L + #adjacent repeats must fit in Tb
+  const int rep = st::lattice_repeats(lab, L, lane);
+  const bool bad = st::lattice_refused(L, rep, Tb, T, UP);
   if (bad || Tb == 0) {      // no frames and (checked above) an empty label: the empty path, ln p = 0
     if (lane == 0) {
       status[b] = bad ? 1 : 0;
@@ -101,29 +81,15 @@ __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restr
 #pragma unroll
   for (int j = 0; j < KPL; ++j) {
     const int u = lane * KPL + j;
-    const bool odd = (u & 1) && u < U;
-    const int li = (u - 1) >> 1;
-    cls[j] = odd ? lab[li] : blank;
-    skip[j] = odd && u >= 3 && lab[li] != lab[li - 1];
+    cls[j] = u < U ? st::lattice_class(u, lab, blank) : blank;
+    skip[j] = u < U && st::lattice_skip_from_below(u, lab);
   }
 
-  // stage one 64-frame chunk of log-softmax rows [chunk*TC, +TC) into E[buf]; rows past T read row T-1
   const double* rows = ly + (long)b * T * CP;
-  constexpr int STG = TC * CP / 2 / 64;
-  f64x2 stage[STG];
-  auto chunk_load = [&](int chunk) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i) {
-      const int f = lane + 64 * i;             // 16-byte index inside the chunk
-      const int t = min(chunk * TC + f / (CP / 2), T - 1);
-      stage[i] = *reinterpret_cast<const f64x2*>(rows + (long)t * CP + (f % (CP / 2)) * 2);
-    }
-  };
-  auto chunk_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i) *reinterpret_cast<f64x2*>(&E[buf][(lane + 64 * i) * 2]) = stage[i];
-  };
-
+  st::ChunkStage<double, CP> stage;   // the log-softmax rows of chunk ch are E[ch & 1]
+  // (through lambdas: with the two called directly align_viterbi_kernel<16> takes one VGPR more)
+  auto chunk_load = [&](int chunk) { stage.load(rows, chunk, T, lane); };
+  auto chunk_store = [&](int buf) { stage.store(E[buf], lane); };
   double a[KPL];
   chunk_load(0);
   chunk_store(0);
@@ -144,8 +110,8 @@ __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restr
       double em[KPL];
 #pragma unroll
       for (int j = 0; j < KPL; ++j) em[j] = e[cls[j]];
-      const double up1 = dpp_shr1(a[KPL - 1], ST_AL_NEG_INF);
-      const double up2 = KPL >= 2 ? dpp_shr1(a[KPL >= 2 ? KPL - 2 : 0], ST_AL_NEG_INF) : dpp_shr1(up1, ST_AL_NEG_INF);
+      const double up1 = st::dpp_shift<SHR1>(a[KPL - 1], ST_AL_NEG_INF);
+      const double up2 = st::dpp_shift<SHR1>(KPL >= 2 ? a[KPL >= 2 ? KPL - 2 : 0] : up1, ST_AL_NEG_INF);
       double n[KPL];
       unsigned int word = 0;
 #pragma unroll
@@ -201,29 +167,16 @@ __global__ __launch_bounds__(64) void align_backtrace_kernel(const unsigned int*
   if (Tb == 0) return;
 
   const unsigned int* rows = bp + (long)b * T * BPW;
-  constexpr int STG = TC * BPW / 4 / 64;
-  u32x4 stage[STG];
-  auto chunk_load = [&](int chunk) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i) {
-      const int f = lane + 64 * i;             // 16-byte index inside the chunk
-      const int t = min(chunk * TC + f / (BPW / 4), T - 1);
-      stage[i] = *reinterpret_cast<const u32x4*>(rows + (long)t * BPW + (f % (BPW / 4)) * 4);
-    }
-  };
-  auto chunk_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < STG; ++i) *reinterpret_cast<u32x4*>(&W[buf][(lane + 64 * i) * 4]) = stage[i];
-  };
+  st::ChunkStage<unsigned int, BPW> stage;   // the back-pointer rows of chunk ch are W[ch & 1]
 
   int u = end_state[b];
   const int last = (Tb - 1) / TC;
-  chunk_load(last);
-  chunk_store(last & 1);
+  stage.load(rows, last, T, lane);
+  stage.store(W[last & 1], lane);
   __syncthreads();
   for (int ch = last; ch >= 0; --ch) {
     const int buf = ch & 1;
-    if (ch > 0) chunk_load(ch - 1);
+    if (ch > 0) stage.load(rows, ch - 1, T, lane);
     const int t_lo = ch * TC, t_hi = min(Tb - 1, t_lo + TC - 1);
     // the walk: the same for every lane (LDS broadcast reads); frame 0 has no back-pointer row
     for (int t = t_hi; t >= t_lo; --t) {
@@ -253,37 +206,18 @@ __global__ __launch_bounds__(64) void align_backtrace_kernel(const unsigned int*
     }
     __syncthreads();
     if (lane == 0) path[TC] = path[0];
-    if (ch > 0) chunk_store(buf ^ 1);
+    if (ch > 0) stage.store(W[buf ^ 1], lane);
     __syncthreads();
   }
-}
-
-int pick_kpl(int max_label_len) {
-  static const int opts[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
-  if (max_label_len < 0) return -1;
-  const int U = 2 * max_label_len + 1;
-  for (int k : opts) if (k * 64 >= U) return k;
-  return -1;
-}
-
-RowMap2 make_map2(const st_tensor3& t) {
-  RowMap2 m;
-  m.batch_stride = (long)t.t_pitch * t.c_pitch;
-  m.row0 = (long)t.halo * t.c_pitch;
-  m.row_stride = t.c_pitch;
-  return m;
 }
 
 // the host form of one utterance; ly: [T][32] doubles, bp: [T][UP / 16] words, 2 bits per state
 void align_host_one(const float* logits, int T, int C, const int* lab, int L, int Tb, int UP, int* sp, int* st_out,
                     float* score, int* status, double* ly, uint32_t* bp) {
   const int U = 2 * L + 1, blank = C - 1, words = UP / 16;
-  bool bad = L < 0 || U > UP || Tb < 0 || Tb > T;
-  if (!bad) {
-    int rep = 0;
-    for (int i = 1; i < L; ++i) rep += lab[i] == lab[i - 1];
-    bad = L + rep > Tb;
-  }
+  int rep = 0;
+  if (U <= UP) for (int i = 1; i < L; ++i) rep += lab[i] == lab[i - 1];
+  const bool bad = st::lattice_refused(L, rep, Tb, T, UP);
   *status = bad ? 1 : 0;
   if (bad) {
     *score = NEG_INF_F;
@@ -302,7 +236,7 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
     const double s = st::al_row_sum(e);
     for (int c = 0; c < C; ++c) ly[(long)t * CP + c] = st::al_log_softmax(row[c], m, s);
   }
-  auto cls = [&](int u) { return (u & 1) ? lab[u >> 1] : blank; };
+  auto cls = [&](int u) { return st::lattice_class(u, lab, blank); };
   double col[2][1024];                    // the lattice columns of frames t-1 and t (U <= 1023)
   for (int u = 0; u < U; ++u) col[0][u] = u < 2 ? ly[cls(u)] : ST_AL_NEG_INF;
   for (int t = 1; t < Tb; ++t) {
@@ -311,10 +245,9 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
     uint32_t* w = bp + (long)t * words;
     for (int i = 0; i < words; ++i) w[i] = 0;
     for (int u = 0; u < U; ++u) {
-      const bool skip_ok = (u & 1) && u >= 3 && lab[u >> 1] != lab[(u >> 1) - 1];
       int move;
-      n[u] = st::al_cell(a[u], u >= 1 ? a[u - 1] : ST_AL_NEG_INF, u >= 2 ? a[u - 2] : ST_AL_NEG_INF, skip_ok,
-                         ly[(long)t * CP + cls(u)], move);
+      n[u] = st::al_cell(a[u], u >= 1 ? a[u - 1] : ST_AL_NEG_INF, u >= 2 ? a[u - 2] : ST_AL_NEG_INF,
+                         st::lattice_skip_from_below(u, lab), ly[(long)t * CP + cls(u)], move);
       w[u >> 4] |= (uint32_t)move << (2 * (u & 15));
     }
   }
@@ -342,7 +275,7 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
 extern "C" {
 
 size_t st_ctc_align_ws(int batch, int frames, int max_label_len) {
-  if (pick_kpl(max_label_len) < 0 || batch <= 0 || frames <= 0) return 0;
+  if (st::lattice_kpl(max_label_len) < 0 || batch <= 0 || frames <= 0) return 0;
   const size_t rows = (size_t)batch * frames;
   // ln-softmax rows [rows][32] double | back-pointer rows [rows][64] uint32 | end state [batch] int32
   return rows * (CP * sizeof(double) + BPW * sizeof(uint32_t)) + (size_t)batch * sizeof(int32_t) + 512;
@@ -357,7 +290,7 @@ int st_ctc_align_f32(const st_tensor3* logits, const int32_t* label_ids, const i
              "ctc_align: bad logits shape");
   ST_REQUIRE(logits->channels >= 2 && logits->channels <= CP && logits->c_pitch >= logits->channels,
              "ctc_align: num_classes must be 2..32");
-  const int kpl = pick_kpl(max_label_len);
+  const int kpl = st::lattice_kpl(max_label_len);
   ST_REQUIRE(kpl > 0, "ctc_align: label length %d outside 0..511", max_label_len);
   ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(logits->batch, logits->frames, max_label_len),
              "ctc_align: workspace too small");
@@ -369,18 +302,13 @@ int st_ctc_align_f32(const st_tensor3* logits, const int32_t* label_ids, const i
   unsigned int* bp = reinterpret_cast<unsigned int*>(ly + rows * CP);
   int* end_state = reinterpret_cast<int*>(bp + rows * BPW);
   hipLaunchKernelGGL(align_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
-                     make_map2(*logits), B, T, C, ly);
-  switch (kpl) {
-#define ST_AL(K)                                                                                                              \
-  case K:                                                                                                                     \
-    hipLaunchKernelGGL(align_viterbi_kernel<K>, dim3(B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets, seq_lens, bp,     \
-                       end_state, score, status);                                                                             \
-    hipLaunchKernelGGL(align_backtrace_kernel<K>, dim3(B), dim3(64), 0, s, bp, T, label_offsets, seq_lens, end_state, status, \
-                       spans, states);                                                                                        \
-    break;
-    ST_AL(1) ST_AL(2) ST_AL(3) ST_AL(4) ST_AL(5) ST_AL(6) ST_AL(8) ST_AL(10) ST_AL(12) ST_AL(16)
-#undef ST_AL
-  }
+                     st::row_map(*logits), B, T, C, ly);
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL(align_viterbi_kernel<k()>, dim3(B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets, seq_lens, bp,
+                       end_state, score, status);
+    hipLaunchKernelGGL(align_backtrace_kernel<k()>, dim3(B), dim3(64), 0, s, bp, T, label_offsets, seq_lens, end_state, status,
+                       spans, states);
+  });
   return st::check_launch("ctc_align");
 }
 
@@ -391,7 +319,7 @@ int st_ctc_align_host(const float* logits, int batch, int frames, int classes, c
              "ctc_align: null argument");
   ST_REQUIRE(batch > 0 && frames > 0, "ctc_align: bad logits shape");
   ST_REQUIRE(classes >= 2 && classes <= CP, "ctc_align: num_classes must be 2..32");
-  const int kpl = pick_kpl(max_label_len);
+  const int kpl = st::lattice_kpl(max_label_len);
   ST_REQUIRE(kpl > 0, "ctc_align: label length %d outside 0..511", max_label_len);
   ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(batch, frames, max_label_len), "ctc_align: workspace too small");
   ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_align: workspace must be 16-byte aligned");

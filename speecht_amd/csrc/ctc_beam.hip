@@ -23,21 +23,16 @@
 // pure function of (frame, rank), so there are no atomics and the result is deterministic.
 #include <math.h>
 
+#include "ctc_lattice.h"
 #include "lm_tables.h"
 #include "st_common.h"
 
 namespace {
 
+using st::RowMap;
 constexpr int kMaxBeam = 128;          // beams of 65..128 (the reference's operating point is 100) run the WIDE instantiation
 constexpr int kMaxClasses = 32;
 constexpr unsigned long long kRootHash = 0x243F6A8885A308D3ull;
-
-struct RowMap {   // (b, t) -> float offset into a padded NWC tensor
-  long batch_stride;
-  long row0;
-  int row_stride;
-  __device__ __forceinline__ long off(int b, int t) const { return (long)b * batch_stride + row0 + (long)t * row_stride; }
-};
 
 template <int MAXB>
 struct BeamSet {   // structure of arrays: lane r reads/writes entry r without bank conflicts
@@ -781,7 +776,7 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
     return ST_EWORKSPACE;
   }
   if (logits->batch == 0) return ST_OK;
-  RowMap map{(long)logits->t_pitch * logits->c_pitch, (long)logits->halo * logits->c_pitch, logits->c_pitch};
+  const RowMap map = st::row_map(*logits);
   float* lp_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + beam_pool_bytes(logits->batch, logits->frames, beam_width));
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), logits->batch), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
@@ -844,7 +839,7 @@ int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int3
   if (logits->batch == 0) return ST_OK;
   const int per_launch = candidates < kLaunchCandidates ? candidates : kLaunchCandidates;
   const int B = logits->batch;
-  RowMap map{(long)logits->t_pitch * logits->c_pitch, (long)logits->halo * logits->c_pitch, logits->c_pitch};
+  const RowMap map = st::row_map(*logits);
   float* lp_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + beam_pool_bytes(B * per_launch, logits->frames, beam_width));
   // the log-softmax rows once: every candidate reads the same rows
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), B), dim3(256), 0, st::as_stream(stream),

@@ -55,9 +55,10 @@ def _csr(labels):
   return np.array([i for l in labels for i in l] + [0], dtype=np.int32), offs
 
 
-def device_ctc(dev, batch, rows, layout, tail='big', max_label_len=None):
+def device_ctc(dev, batch, rows, layout, tail='big', max_label_len=None, label_offsets=None):
   """One st_ctc_loss_grad_hilo_f32 call on utterances ``rows`` of the batch -> dict(loss, lo, status, grad = the WHOLE gradient
-  buffer [B, t_pitch, c_pitch], k = states per lane that ran, from the workspace size)."""
+  buffer [B, t_pitch, c_pitch], k = states per lane that ran, from the workspace size).  ``label_offsets`` replaces the offsets
+  of the rows' concatenated labels."""
   from speecht_amd import _lib
   from speecht_amd._lib import Tensor3
   lib = _lib.load()
@@ -68,6 +69,8 @@ def device_ctc(dev, batch, rows, layout, tail='big', max_label_len=None):
   to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)
   x = to(poisoned_logits([u.logits for u in utts], T, C, lh, lc, tail))
   ids, offs = _csr([u.label for u in utts])
+  if label_offsets is not None:
+    offs = np.asarray(label_offsets, dtype=np.int32)
   d_ids, d_offs, d_lens = to(ids), to(offs), to(np.array([u.logits.shape[0] for u in utts], dtype=np.int32))
   grad = torch.full((B, _t_pitch(T, gh), gc), GRAD_SENTINEL, dtype=torch.float32, device=dev)
   loss = torch.full((B,), OUT_SENTINEL, dtype=torch.float32, device=dev)
@@ -151,6 +154,25 @@ def test_lattice_dispatch(dev, name, layout):
     worst = [max(a, b) for a, b in zip(worst, w2)]
   print('{} (k = {}, C = {}, {} frames), {}: worst loss error {:.3g} of its bound, |hi + lo - ref| {:.3g}, gradient {:.3g}, '
         'loss {:.3g} relative'.format(name, batch.k, batch.C, batch.frames, layout, *worst))
+
+
+@pytest.mark.parametrize('name', ['k1', 'k5'])
+def test_negative_label_length_is_refused(dev, name):
+  """label_offsets that do not increase give an utterance a negative label length: status 1, loss +inf, a zero gradient, and
+  the utterance beside it keeps its bits."""
+  batch = CC.batch_by_name(name)
+  layout = 'haloed-grad'
+  L = len(batch.utterances[0].label)
+  kinds = [u.kind for u in batch.utterances]
+  rows = [kinds.index('e'), 0]                                  # the empty label, then the longest: the ids are the longest's
+  res = device_ctc(dev, batch, rows, layout, label_offsets=[L, 0, L])     # lengths -L and L
+  gh, gc = LAYOUTS[layout][1]
+  assert res['status'].tolist() == [1, 0]
+  assert res['loss'][0] == np.inf and res['lo'][0] == 0
+  assert (res['grad'][0][gh:gh + batch.frames, :32] == 0).all()
+  assert (res['grad'][0][:gh] == GRAD_SENTINEL).all() and (res['grad'][0][:, 32:] == GRAD_SENTINEL).all()
+  alone = device_ctc(dev, batch, [0], layout)
+  assert alone['status'].tolist() == [0] and same_bits(res, alone, slice(1, 2), slice(0, 1))
 
 
 def test_all_ten_dispatches_and_four_class_counts(dev):
