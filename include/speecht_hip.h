@@ -588,6 +588,54 @@ int st_resample_kaiser_f32(const float* in, const int64_t* in_offsets, int n_utt
 int st_resample_kaiser_host(const float* in, const int64_t* in_offsets, int n_utts, const int32_t* rates, int sr_new,
                             const int64_t* out_offsets, const int64_t* out_valid, const double* win, int64_t win_len, double* out);
 
+/* ---- Silence segmentation: cut recordings into utterances (csrc/segment.hip) ------------------------------------------------
+ * The endpointing of the reference's `record` (record_utils.AudioRecorder: normalise the peak to 0.5, trim samples with
+ * abs(x) <= threshold from both ends, add 0.1 s of zeros on each side) applied to whole recordings.  Input layout of
+ * st_resample_kaiser_f32: concatenated float32 mono signals, offsets int64 [n + 1], rates int32 [n]; finite samples.
+ *
+ * Rules (the numpy specification, in integer and float32 arithmetic only, is tests/segment_oracle.py; the device matches it bit
+ * for bit):
+ *  1. peak_i = max |x| over signal i; thr_i = threshold2 * peak_i, one float32 product, with threshold2 = float32(2 * threshold)
+ *     (the reference's threshold after its normalisation of the peak to 0.5).  A sample is ACTIVE iff |x| > thr_i (strict).  A
+ *     signal with peak_i == 0, or without samples, has no segments.
+ *  2. Chunks of c_i = max(1, rate_i / 50) samples (20 ms; integer division): chunk k covers [k c, min((k + 1) c, n_i)) and is
+ *     active iff it holds an active sample.  Per chunk: its peak |x|, its first and its last active sample.
+ *  3. A RUN is a maximal stretch from an active chunk to an active chunk without gap_chunks (G >= 1) or more consecutive silent
+ *     chunks inside.
+ *  4. A run longer than max_chunks (M >= 2) chunks is cut from the left, repeatedly while what is left is longer than M: among the
+ *     chunks j of [start + M / 2, start + M) the one with the smallest peak (the smallest j among equals); the left piece is
+ *     [start, j), the rest starts again at the first active chunk >= j.
+ *  5. A piece becomes the samples from the first active sample of its first active chunk to one past the last active sample of
+ *     its last active chunk.
+ *  6. Gather: segment s becomes pads[s] zeros, x[start:end] * gain_s, pads[s] zeros, with gain_s = float32(0.5) / segpeak_s
+ *     (a correctly rounded float32 division, then one float32 product per sample) and segpeak_s = max |x| over the segment.
+ *
+ * Tables.  Signal i owns the GROUPS [group_offsets[i], group_offsets[i + 1]) of 64 chunks, ceil(chunks_i / 64) of them (int64
+ * [n + 1], planned by the host): chunk k of signal i is entry 64 * group_offsets[i] + k of chunk_peak / chunk_first / chunk_last
+ * (offsets inside the chunk, -1 where it is silent) and bit k % 64 of word group_offsets[i] + k / 64 of chunk_mask.  All tables
+ * hold 64 * total_groups entries (chunk_mask: total_groups words); audio and seg_ranges are 16-byte aligned.
+ *  st_segment_chunks_f32: rules 1-2 (two launches); peaks [n] receives peak_i.
+ *  st_segment_runs: rules 3-5, one wavefront per signal.  The segments of signal i are rows 64 * group_offsets[i] ... of
+ *    seg_ranges [.][2] (start, end: samples inside the signal) and seg_peaks (segpeak: the largest chunk peak of the piece, which
+ *    an active sample attains) in time order, seg_counts[i] of them -- never more than the signal has active chunks.
+ *  st_segment_gather_f32: rule 6 for n_segments segments: src_start[s] = index of the segment's first sample in `audio`,
+ *    seg_peaks[s], out_offsets int64 [n_segments + 1] with out_offsets[s + 1] - out_offsets[s] = 2 * pads[s] + length.
+ * Every output is written with ordinary vector stores; no workspace. */
+int st_segment_chunks_f32(const float* audio, const int64_t* offsets, const int32_t* rates, const int64_t* group_offsets,
+                          int n_signals, int64_t total_groups, float threshold2, float* peaks, float* chunk_peak,
+                          int32_t* chunk_first, int32_t* chunk_last, uint64_t* chunk_mask, void* stream);
+int st_segment_runs(const int64_t* offsets, const int32_t* rates, const int64_t* group_offsets, int n_signals, int gap_chunks,
+                    int max_chunks, const float* chunk_peak, const int32_t* chunk_first, const int32_t* chunk_last,
+                    const uint64_t* chunk_mask, int64_t* seg_ranges, float* seg_peaks, int32_t* seg_counts, void* stream);
+int st_segment_gather_f32(const float* audio, const int64_t* src_start, const float* seg_peaks, const int64_t* out_offsets,
+                          const int32_t* pads, int n_segments, int64_t total_out, float* out, void* stream);
+
+/* ---- Masked batches: zero the rows t >= valid[b] (t < frames) of every batch row b of a padded NWC tensor, over the whole
+ * c_pitch, in 16-byte stores.  elem_bytes 4: the float tensor at t->base; 2: a bf16 plane of the same geometry at t->base.
+ * A forward pass that does this after every layer with valid[b] = ceil(seq_len_b / strides so far) gives a batched utterance
+ * the SAME padding it would see alone (engine.forward(mask_padding=True)). */
+int st_mask_rows(const st_tensor3* t, const int32_t* valid, int elem_bytes, void* stream);
+
 /* ---- helpers -------------------------------------------------------------------------- */
 int st_fill_f32(float* dst, float value, size_t n, void* stream);
 /* zero the halo rows of a padded NWC tensor (needed when a buffer is re-described for a new shape) */

@@ -106,13 +106,14 @@ def transcript_ids(text):
   return ids
 
 
-def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None):
+def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None, mask_padding=False):
   """Align audio files with their transcripts -> a list, in ``paths`` order, of dicts
   {path, seconds, sample_rate, text, ids, spans, score, frames, error}.  ``transcripts``: {path: text} (`find_transcripts`) or
   a list parallel to ``paths``; None = no transcript.  ``error`` is the message for a file that is unreadable, too short, has no
   transcript, or whose transcript does not fit its frames or the vocabulary (spans is None then); the other files go on.
   ``spans``: [L, 2] output frames per id; ``frames``: output frames of the utterance; ``sample_rate``: the rate the features
-  were computed at (what `frames_to_seconds` needs).  Batch semantics as `transcription.transcribe_files`."""
+  were computed at (what `frames_to_seconds` needs).  Batch semantics as `transcription.transcribe_files`, ``mask_padding``
+  included: with it the spans of a file do not depend on the batch it is in."""
   texts = [transcripts.get(p) for p in paths] if isinstance(transcripts, dict) else list(transcripts)
   if len(texts) != len(paths):
     raise ValueError('align_files: {} paths and {} transcripts'.format(len(paths), len(texts)))
@@ -146,7 +147,7 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
   if ok:
     feats = transcription.device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
-    spans, scores, status = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size)
+    spans, scores, status = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size, mask_padding=mask_padding)
     for entry, f, sp, sc, st in zip(ok, feats, spans, scores, status):
       entry['frames'] = output_frames(f.shape[0])
       if st != 0:
@@ -209,7 +210,8 @@ def run_cli(flags):
   with Session(flags.device) as sess:
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)
-    results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size)
+    results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size,
+                          mask_padding=bool(getattr(flags, 'mask_padding', False)))
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:

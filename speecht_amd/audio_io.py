@@ -350,6 +350,38 @@ def resample_kaiser_best_device(signals, rates, sr_new, device='cuda:0'):
   return out[:total], out_offsets
 
 
+def resample_device(audio, in_offsets, rates, sr_new):
+  """resample_kaiser_best_device for signals that are already on the device: ``audio`` a float32 device tensor with signal i at
+  [in_offsets[i], in_offsets[i + 1]) (host int64 [n + 1]) at rate rates[i] -- what segmentation.segment_device returns.  Same
+  launch, same result: (device float32 buffer of the concatenated outputs, out_offsets int64 [n + 1] on the host)."""
+  import ctypes
+  import torch
+  from . import _lib
+  dev = audio.device
+  in_offsets = np.ascontiguousarray(in_offsets, dtype=np.int64)
+  lens = np.diff(in_offsets)
+  if len(lens) == 0:
+    raise ValueError('resample_device: no signals')
+  rates = np.asarray(rates, dtype=np.int64)
+  if rates.shape != lens.shape or rates.min() <= 0 or int(sr_new) <= 0 or rates.max() >= 2 ** 31:
+    raise ValueError('resample_device: one positive rate per signal expected, got {}'.format(rates.tolist()))
+  if lens.min() < 0 or in_offsets[0] < 0 or in_offsets[-1] > audio.numel() or audio.dtype != torch.float32 or not audio.is_contiguous():
+    raise ValueError('resample_device: offsets must ascend inside a contiguous float32 buffer')
+  out_offsets, valid = plan_resample(lens, rates, int(sr_new))
+  meta = torch.as_tensor(np.concatenate([in_offsets, out_offsets, valid])).to(dev)
+  d_rates = torch.as_tensor(rates.astype(np.int32)).to(dev)
+  n = len(lens)
+  total = int(out_offsets[-1])
+  out = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+  win = _device_filter(dev)
+  P = lambda t: ctypes.c_void_p(t.data_ptr())
+  base = meta.data_ptr()
+  _lib.call('st_resample_kaiser_f32', P(audio), ctypes.c_void_p(base), n, P(d_rates), int(sr_new),
+            ctypes.c_void_p(base + 8 * (n + 1)), ctypes.c_void_p(base + 16 * (n + 1)), total, P(win), win.numel(), P(out),
+            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+  return out[:total], out_offsets
+
+
 def resample_kaiser_best_batch(signals, rates, sr_new, device='cuda:0'):
   """resample_kaiser_best_device, read back: a list of float32 arrays (librosa_load's resampled signals)."""
   out, offsets = resample_kaiser_best_device(signals, rates, sr_new, device)

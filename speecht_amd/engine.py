@@ -503,9 +503,34 @@ class Wav2LetterEngine(DecodeMixin):
       self.stream.wait_event(ups[-1])
       del ups[:]
 
-  def forward(self):
-    """X[0] -> logits X[-1] through the eleven layers (speech_model.py:279-295), by the arithmetic mode's kernels."""
-    return self.mode.forward()
+  def forward(self, mask_padding=False):
+    """X[0] -> logits X[-1] through the eleven layers (speech_model.py:279-295), by the arithmetic mode's kernels.
+
+    ``mask_padding=True`` (inference; the reference masks nothing, so training and `evaluate` do not either): after every layer
+    but the last, the rows of each utterance past its own length -- ceil(seq_len / strides so far) -- are zeroed
+    (st_mask_rows), which is the SAME padding the utterance would see alone: its logits no longer depend on the padded length
+    of its batch.  The input rows past seq_len must be zeros, as `inference` pads them.  A mode that cannot mask raises."""
+    if not mask_padding:
+      return self.mode.forward()
+    if not self.mode.masks_padding:
+      raise _lib.SpeechtHipError('forward(mask_padding=True) is not supported by the {} mode (fp32 and bf16 are)'.format(self.conv_mode))
+    return self.mode.forward(mask_padding=True)
+
+  def _mask_lengths(self):
+    """The valid rows of every layer's output but the last for the batch `load_batch` took, as one device table
+    [layers - 1][batch] of int32: -> a function i -> pointer to the row of layer i's output.  The compute stream has waited
+    for the upload when this returns."""
+    v, rows = self.seq_lens_host.astype(np.int64), []
+    for l in self.layers[:-1]:
+      v = -(-v // l.stride)
+      rows.append(v)
+    if not rows:
+      return lambda i: None
+    table = self._upload_i32(np.concatenate(rows).astype(np.int32))
+    self._wait_uploads()
+    self._mask_table = table                       # (alive until the next masked pass: the launches below read it)
+    base, pitch = table.data_ptr(), 4 * self.shape.batch
+    return lambda i: ctypes.c_void_p(base + i * pitch)
 
   def forward_graph(self):
     """``forward()`` replayed from a HIP graph: the launch sequence of the current (batch, frames) shape is

@@ -3,9 +3,10 @@ variable-length utterances).
 
 The reference pads every batch to its longest member and masks nothing (speech_input.py:37-45,
 SURVEY F7), so the ~73 output frames before an utterance's end depend on the padded length of the
-batch it happens to be in.  Bucketing by length keeps padding -- and therefore wasted convolution
-work -- small; results for an utterance equal what the reference would produce for the SAME batch
-composition (that is what the tests check), not for an arbitrary one.
+batch it happens to be in -- unless ``mask_padding`` (``--mask-padding``) is set: then every utterance's rows past
+its own length are zeroed after every layer, and it gets the logits it would get alone.  Bucketing by length keeps
+padding -- and therefore wasted convolution work -- small; without the mask, results for an utterance equal what the
+reference would produce for the SAME batch composition (that is what the tests check), not for an arbitrary one.
 """
 import queue
 import threading
@@ -45,7 +46,7 @@ BEAM_DECODERS = 2
 
 
 def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None,
-               timestamps=False):
+               timestamps=False, mask_padding=False):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -67,7 +68,12 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   `alignment.frames_to_seconds` turn them into word times).  Whichever decoder ran, its ids are aligned against the logits of
   their batch before the next batch overwrites them, so the batches run one after the other (the serial loop: same launches
   on the same data, hence the same ids as without timestamps).  An utterance that decodes to more than
-  ``engine_decode.MAX_ALIGN_LABELS`` ids gets None.  With ``timestamps=False`` nothing changes."""
+  ``engine_decode.MAX_ALIGN_LABELS`` ids gets None.  With ``timestamps=False`` nothing changes.
+
+  ``mask_padding=True``: the forward pass masks the padding of every batch (``engine.forward(mask_padding=True)``): an utterance
+  gets the logits -- to the rounding of two summation orders -- and hence the ids and spans it gets with ``batch_size=1``,
+  whatever batch it is in.  Off by default: the launch sequence is then exactly the unmasked one."""
+  forward = (lambda: engine.forward(mask_padding=True)) if mask_padding else engine.forward
   if not features:
     return ([], [], []) if timestamps else ([], [])
   if pipeline is None:
@@ -101,7 +107,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
       for row, i in enumerate(idx):
         x[row, :lengths[i]] = features[i]
       engine.load_batch(x, [lengths[i] for i in idx])
-      engine.forward()
+      forward()
       ids = decode_sync()
       for row, i in enumerate(idx):
         ids_out[i] = ids[row]
@@ -137,7 +143,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         staged = stager.get()
         with on_compute():
           engine.load_batch(staged, [lengths[i] for i in idx])
-          engine.forward()
+          forward()
           handle = decode_async(decode_stream if beam_width else None)
         pending.append((handle, idx))
         if len(pending) > depth:
@@ -163,7 +169,7 @@ def _align_current(engine, labels):
   return spans, score, status
 
 
-def align(engine, features, labels, batch_size=1, bucket=True):
+def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=False):
   """Forced alignment of known transcripts: features as for `transcribe`, ``labels`` one id list per utterance
   -> (spans, scores, status) in input order: spans[i] an [L_i, 2] int32 array (first output frame, one past the last output
   frame of each id on the best CTC path), scores[i] = ln p(that path), status[i] != 0 where the transcript does not fit the
@@ -171,7 +177,7 @@ def align(engine, features, labels, batch_size=1, bucket=True):
 
   Batched as `transcribe` batches.  ``batch_size=1`` is the default for the reason `transcription` gives: nothing in the
   network is masked, so the logits near the end of an utterance depend on the padded length of its batch, and with them the
-  times of its last words."""
+  times of its last words -- unless ``mask_padding`` is set, which masks the padding in the forward pass as in `transcribe`."""
   if len(features) != len(labels):
     raise ValueError('align: {} feature arrays and {} label sequences'.format(len(features), len(labels)))
   n = len(features)
@@ -185,7 +191,10 @@ def align(engine, features, labels, batch_size=1, bucket=True):
     for row, i in enumerate(idx):
       x[row, :lengths[i]] = features[i]
     engine.load_batch(x, [lengths[i] for i in idx])
-    engine.forward()
+    if mask_padding:
+      engine.forward(mask_padding=True)
+    else:
+      engine.forward()
     spans, score, status = _align_current(engine, [labels[i] for i in idx])
     for row, i in enumerate(idx):
       spans_out[i], score_out[i], status_out[i] = spans[row], float(score[row, 0]), int(status[row])

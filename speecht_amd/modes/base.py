@@ -29,7 +29,12 @@ class ModeBase:
   def forget_tables(self):
     """A tuning knob was flipped: the transform tables in the layers' buffers are rebuilt by the next description."""
 
-  def forward(self):
+  masks_padding = False           # True: `forward(mask_padding=True)` is implemented (the engine raises for a mode without it)
+
+  def forward(self, mask_padding=False):
+    """``mask_padding``: zero every utterance's rows past its own length after every layer but the last
+    (`Wav2LetterEngine.forward`); the next layer must then read those time-domain rows, not operands handed over beside them.
+    Without the flag the launch sequence is exactly the unmasked one."""
     raise NotImplementedError
 
   def backward(self, on_layer_done, wanted):

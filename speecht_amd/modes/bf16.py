@@ -12,6 +12,7 @@ from .base import ModeBase
 
 
 class Bf16Mode(ModeBase):
+  masks_padding = True
 
   def __init__(self, engine):
     super().__init__(engine)
@@ -171,9 +172,12 @@ class Bf16Mode(ModeBase):
     self._wb_order = order
     self._wplanes_fresh = True
 
-  def forward(self):
+  def forward(self, mask_padding=False):
+    """``mask_padding``: the bf16 plane of every layer's output but the last is masked (st_mask_rows on 2-byte elements); no layer
+    here hands its successor anything but that plane."""
     e, ptr = self.e, self.e._ptr
     sh, s, main, L = e.shape, e.stream_ptr, e.stream, len(e.layers)
+    valid = e._mask_lengths() if mask_padding else None
     X, geo, part, Xb, fftb, Wb = sh.X, sh.geo, sh.mode, sh.mode.Xb, sh.mode.fftb, self.Wb
     ws = part.wgrad_ws_b
     ws_bytes = ws.numel() * 4 if e.split_small_batches else 0
@@ -201,9 +205,13 @@ class Bf16Mode(ModeBase):
         f = fftb[i]
         call('st_conv1d_nwc_fwd_fft_planes', X[i].ref, ptr(Xb[i]), ptr(f['gt']), pb, l.width, f['pl'], int(l.relu), X[i + 1].ref,
              ptr(Xb[i + 1]), ptr(f['tables']), ptr(f['sf']), 1, ptr(f['ws']), f['ws'].numel() * 4, s)
-        continue
-      call('st_conv1d_nwc_fwd_ws_bf16', X[i].ref, ptr(Xb[i]), ptr(Wb[i]), pb, l.width, l.stride, geo[i][2], int(l.relu),
-           X[i + 1].ref, None if last else ptr(Xb[i + 1]), ptr(X[i + 1].buf) if last else None, ptr(ws), ws_bytes, s)
+      else:
+        call('st_conv1d_nwc_fwd_ws_bf16', X[i].ref, ptr(Xb[i]), ptr(Wb[i]), pb, l.width, l.stride, geo[i][2], int(l.relu),
+             X[i + 1].ref, None if last else ptr(Xb[i + 1]), ptr(X[i + 1].buf) if last else None, ptr(ws), ws_bytes, s)
+      if mask_padding and not last:
+        y = X[i + 1]
+        plane = _lib.Tensor3(Xb[i + 1].data_ptr(), y.batch, y.frames, y.channels, y.halo, y.t_pitch, y.c_pitch)
+        call('st_mask_rows', ctypes.byref(plane), valid(i), 2, s)
 
   def backward(self, on_layer_done, wanted):
     e, ptr = self.e, self.e._ptr

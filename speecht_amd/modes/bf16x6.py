@@ -12,6 +12,7 @@ class Bf16x6Mode(Fp32Mode):
   _one_tap_in_place = False
   _flip_every_layer = True
   _top_gradient_beside = False
+  masks_padding = False             # (its plane plumbing hands operands from layer to layer beside the time-domain rows)
   cache_shapes = False              # (its weight planes are re-chosen per shape in `_alloc_planes`: described anew every time)
 
   def __init__(self, engine):

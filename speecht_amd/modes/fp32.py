@@ -16,6 +16,7 @@ from .spectral import SpectralLayers
 class Fp32Mode(SpectralLayers, ModeBase):
   _one_tap_in_place = True        # 1-tap layers back-propagate through their own packed filters read transposed
   _flip_every_layer = False       # (bf16x6: every layer's operand planes are split from a flipped / transposed copy)
+  masks_padding = True
 
   def __init__(self, engine):
     super().__init__(engine)
@@ -139,10 +140,15 @@ class Fp32Mode(SpectralLayers, ModeBase):
       for k in keys:
         del ready[k]
 
-  def forward(self):
+  def forward(self, mask_padding=False):
     """X[0] -> logits X[-1] through the eleven layers (speech_model.py:279-295): per layer the frequency-domain entry
-    point, the W-tap kernel or -- in the bf16x6 mode -- that mode's kernel, as decided per shape by `_use_fft` / `_x6_fwd`."""
+    point, the W-tap kernel or -- in the bf16x6 mode -- that mode's kernel, as decided per shape by `_use_fft` / `_x6_fwd`.
+    ``mask_padding``: every layer's output but the last is masked in the time domain (st_mask_rows), so a frequency-domain layer
+    never hands input spectra to the next one -- they would be the spectra of the unmasked rows."""
+    if mask_padding and not self.masks_padding:
+      raise _lib.SpeechtHipError('forward(mask_padding=True) is not supported by this mode')
     e, ptr, sh, s = self.e, self.e._ptr, self.e.shape, self.e.stream_ptr
+    valid, top = (e._mask_lengths(), len(e.layers) - 1) if mask_padding else (None, 0)
     X, geo, part = sh.X, sh.geo, sh.mode
     fft = part.fft if e.fft_conv else {}                   # the layers that run in the frequency domain now
     ws = part.wgrad_ws
@@ -163,7 +169,7 @@ class Fp32Mode(SpectralLayers, ModeBase):
         self._wait_gfwd(i)                               # the filter spectra may still be on their way (side stream)
         # a chain of frequency-domain layers: where the shapes allow, this layer's inverse transform hands its frames to the
         # next layer's forward transform in registers and leaves that layer's input spectra behind (`sf_ready` for its call)
-        nxt = fft.get(i + 1)
+        nxt = None if mask_padding else fft.get(i + 1)
         if nxt is not None and nxt['shift'] is not None:
           nxt = None
         written = ctypes.c_int(0)
@@ -171,10 +177,11 @@ class Fp32Mode(SpectralLayers, ModeBase):
              ptr(f['tables']), ptr(f['sf']), int(sf_ready), ptr(nxt['tables']) if nxt else None, ptr(nxt['sf']) if nxt else None,
              nxt['width'] if nxt else 0, nxt['pl'] if nxt else 0, ctypes.byref(written), ptr(f['ws']), f['ws'].numel() * 4, s)
         sf_ready = written.value == 1
-        continue
       else:
         call('st_conv1d_nwc_fwd_ws_f32', X[i].ref, ptr(pf), ptr(pb), l.width, l.stride, geo[i][2], int(l.relu), X[i + 1].ref,
              ptr(ws), ws_bytes, s)
+      if mask_padding and i < top:
+        call('st_mask_rows', X[i + 1].ref, valid(i), 4, s)
 
   def backward(self, on_layer_done, wanted):
     """Back-prop from dZ[-1] through the frequency-domain / W-tap (/ bf16x6) kernels; hooks as `Wav2LetterEngine.backward`

@@ -8,7 +8,13 @@ the features (power spectrogram or MFCCs, preprocessing.power_spectrogram_device
 Batch semantics: nothing in the network is masked, so the logits near an utterance's end depend on the padded length of the
 batch it is in.  The default ``batch_size=1`` runs every file as one [1, T, C] batch without padding -- what the reference's
 `record` does with its single utterance.  ``batch_size > 1`` buckets files by length for throughput; transcripts near the ends
-of the shorter files of a bucket may then differ from the ``batch_size=1`` ones.
+of the shorter files of a bucket may then differ from the ``batch_size=1`` ones -- unless ``mask_padding`` (``--mask-padding``)
+is set: the forward pass then zeroes every utterance's rows past its own length after every layer, and a batched utterance gets
+the logits it would get alone.
+
+Long recordings: ``segment`` (``--segment``) cuts every file into utterances at its silences on the device
+(segmentation.segment_device: the endpointing rules of the reference's `record`), transcribes the utterances like files and
+joins their texts; ``--segment --batch-size N --mask-padding`` is the combination for them.
 """
 import contextlib
 import json
@@ -16,7 +22,7 @@ import os
 import sys
 import time
 
-from . import audio_io, inference, preprocessing
+from . import audio_io, inference, preprocessing, segmentation
 
 AUDIO_EXTENSIONS = ('.flac', '.wav')          # what a directory is searched for
 FEATURE_WIDTH = {'power': 128, 'mfcc': 39}
@@ -93,7 +99,83 @@ def device_features(signals, rates, feature_type='power', sample_rate=22050, dev
   return feats
 
 
-def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=22050, batch_size=1, **decode):
+def device_features_on_device(audio, offsets, rates, feature_type='power', sample_rate=22050):
+  """device_features for signals that are already on the device (the layout segmentation.segment_device returns: ``audio`` a float32
+  device tensor, signal i at [offsets[i], offsets[i + 1]) at rates[i]): no trip through the host between the gather, the resampler
+  and the features.  A signal too short for the features gets None."""
+  if feature_type not in FEATURE_WIDTH:
+    raise ValueError('feature_type must be power or mfcc, got {!r}'.format(feature_type))
+  extract = preprocessing.power_spectrogram_device if feature_type == 'power' else preprocessing.mfccs_device
+  n = len(rates)
+  feats = [None] * n
+  targets = [_target_rate(int(r), sample_rate) for r in rates]
+
+  def long_enough(i):
+    return audio_io.resample_lengths(int(offsets[i + 1] - offsets[i]), int(rates[i]), targets[i])[1] > N_FFT // 2
+
+  i = 0
+  while i < n:
+    # consecutive signals of one target rate share a launch sequence, FEATURE_BATCH at the most (their samples are one range)
+    j = i
+    while j < n and j - i < FEATURE_BATCH and targets[j] == targets[i] and long_enough(j):
+      j += 1
+    if j == i:                                  # too short: left out
+      i += 1
+      continue
+    resampled, out_offsets = audio_io.resample_device(audio, offsets[i:j + 1], rates[i:j], targets[i])
+    for k, f in enumerate(extract(resampled, out_offsets, targets[i])):
+      feats[i + k] = f
+    i = j
+  return feats
+
+
+def _segmented(engine, signals, rates, options, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode):
+  """Segment every signal at its own rate, transcribe the utterances like files -> per signal a list of dicts {start, end (seconds
+  in the signal), text, ids} in time order; with ``timestamps`` also ``words`` ([{word, start, end}] in seconds of the signal; None
+  where the text is too long to align).  An utterance too short for the features has an empty text."""
+  table, gathered, out_offsets = segmentation.segment_audio(signals, rates, options, engine.device)
+  out = [[] for _ in signals]
+  if len(table) == 0:
+    return out
+  seg_rates = [int(rates[i]) for i in table[:, 0]]
+  feats = device_features_on_device(gathered, out_offsets, seg_rates, feature_type, sample_rate)
+  ok = [s for s, f in enumerate(feats) if f is not None]
+  res = inference.transcribe(engine, [feats[s] for s in ok], batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding,
+                             **decode) if ok else ([], [], [])
+  found = {s: k for k, s in enumerate(ok)}
+  for s, (i, a, b) in enumerate(table.tolist()):
+    rate = float(rates[i])
+    seg = dict(start=a / rate, end=b / rate, text='', ids=[])
+    if timestamps:
+      seg['words'] = []
+    if s in found:
+      k = found[s]
+      seg['ids'], seg['text'] = res[0][k], res[1][k]
+      if timestamps:
+        from . import alignment
+        spans, target = res[2][k], _target_rate(int(rates[i]), sample_rate)
+        seg['spans'], seg['frames'] = spans, feats[s].shape[0] // 2
+        if spans is None:
+          seg['words'] = None
+        else:
+          inside = alignment.timed_words(seg['ids'], spans, target, (out_offsets[s + 1] - out_offsets[s]) / rate)
+          seg['words'] = segmentation.stitch(inside, seg['start'], segmentation.pad_samples(options, rates[i]) / rate, len(signals[i]) / rate)
+    out[i].append(seg)
+  return out
+
+
+def _join_segments(segments):
+  """(ids, text) of a segmented signal: the non-empty segment texts joined by one space."""
+  from . import vocabulary
+  ids = []
+  for seg in segments:
+    if seg['text']:
+      ids += ([vocabulary.SPACE_ID] if ids else []) + list(seg['ids'])
+  return ids, ' '.join(seg['text'] for seg in segments if seg['text'])
+
+
+def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=22050, batch_size=1, mask_padding=False, segment=None,
+                     **decode):
   """Transcribe float32 mono signals in [-1, 1] at the given source rates -> (list of id lists, list of strings).
 
   Resampling (to ``sample_rate``, default 22 050 Hz as librosa.load; None or 'native' keeps each signal's rate) and the
@@ -103,19 +185,34 @@ def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=2
 
   ``batch_size=1`` (default): every signal is one [1, T, C] batch without padding, the semantics of the reference's `record`.
   ``batch_size > 1``: signals are bucketed by length into padded batches for throughput; nothing in the network is masked,
-  so transcripts near the ends of the shorter signals of a batch may differ from the ``batch_size=1`` ones."""
+  so transcripts near the ends of the shorter signals of a batch may differ from the ``batch_size=1`` ones -- unless
+  ``mask_padding`` is set (inference.transcribe).
+
+  ``segment``: a segmentation.SegmentOptions -- every signal is cut into utterances at its silences on the device, the utterances
+  are transcribed like signals, and a signal's ids / text are those of its utterances joined by one space."""
+  if segment is not None:
+    joined = [_join_segments(segs) for segs in _segmented(engine, signals, rates, segment, feature_type, sample_rate, batch_size,
+                                                          False, mask_padding, decode)]
+    return [j[0] for j in joined], [j[1] for j in joined]
   feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
-  return inference.transcribe(engine, feats, batch_size=batch_size, **decode)
+  return inference.transcribe(engine, feats, batch_size=batch_size, mask_padding=mask_padding, **decode)
 
 
-def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, timestamps=False, **decode):
+def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, timestamps=False,
+                     mask_padding=False, segment=None, **decode):
   """Transcribe audio files (.flac, 16-bit .wav, .npy taken as 16 kHz) -> a list, in ``paths`` order, of dicts
   {path, seconds, text, ids, error}: ``error`` is the message for a file that cannot be read or is too short (its text and
   ids are None); the other files are transcribed as transcribe_audio does (same arguments, same batch semantics).
   ``timestamps=True`` adds ``spans`` ([L, 2] output frames per id, inference.transcribe; None when the text is too long to align),
   ``frames`` and ``sample_rate`` (the rate of the features), which `alignment.timed_words` turns into word times.
   ``timings``: a dict that receives the seconds spent in host decoding ('decode_host'), resampling and features
-  ('features') and the network with the decoder ('transcribe')."""
+  ('features') and the network with the decoder ('transcribe').
+  ``mask_padding``: as transcribe_audio.  ``segment`` (a segmentation.SegmentOptions): every file is segmented at its own rate,
+  before resampling, and its entry gains ``segments``: [{start, end, text, ids}] in seconds of the file and time order (with
+  ``timestamps`` also ``words``, the word times in the file: segment start minus pad plus the time inside the segment, clipped to
+  the file; segments are short, so files of any length can be aligned).  ``text`` / ``ids`` are the non-empty segment texts joined
+  by one space; a file without a segment has an empty text and is no error; ``spans`` is None (the words are per segment).
+  Segmentation is timed with 'features', the rest with 'transcribe'."""
   results = []
   signals, rates, ok = [], [], []
   t0 = time.perf_counter()
@@ -133,10 +230,18 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
     rates.append(rate)
     ok.append(entry)
   t1 = time.perf_counter()
-  if ok:
+  if ok and segment is not None:
+    t2 = t1
+    per_file = _segmented(engine, signals, rates, segment, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode)
+    for entry, rate, segs in zip(ok, rates, per_file):
+      entry['segments'] = segs
+      entry['ids'], entry['text'] = _join_segments(segs)
+      if timestamps:
+        entry.update(spans=None, frames=None, sample_rate=_target_rate(rate, sample_rate))
+  elif ok:
     feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
-    res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, **decode)
+    res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding, **decode)
     for entry, i, t in zip(ok, res[0], res[1]):
       entry['ids'], entry['text'] = i, t
     if timestamps:
@@ -173,8 +278,12 @@ def run_cli(flags):
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)          # FileNotFoundError('No checkpoint for evaluation found'), as evaluate
     timestamps = bool(getattr(flags, 'timestamps', False))
+    segment = None
+    if getattr(flags, 'segment', False):
+      segment = segmentation.SegmentOptions(threshold=flags.segment_threshold, min_silence=flags.min_silence,
+                                            max_segment=flags.max_segment)
     results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, timestamps=timestamps,
-                               **decode)
+                               mask_padding=bool(getattr(flags, 'mask_padding', False)), segment=segment, **decode)
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:
@@ -185,7 +294,16 @@ def run_cli(flags):
         continue
       print('{}\t{}'.format(r['path'], r['text']), flush=True)
       line = dict(path=r['path'], seconds=r['seconds'], text=r['text'])
-      if timestamps and r['spans'] is not None:
+      if segment is not None:
+        line['segments'] = []
+        for seg in r['segments']:
+          item = dict(start=round(seg['start'], 4), end=round(seg['end'], 4), text=seg['text'])
+          if timestamps and seg['words'] is not None:
+            item['words'] = seg['words']
+            for w in seg['words']:
+              print('{}\t{:.3f}\t{:.3f}\t{}'.format(r['path'], w['start'], w['end'], w['word']), flush=True)
+          line['segments'].append(item)
+      elif timestamps and r['spans'] is not None:
         from . import alignment
         alignment.print_words(r)
         line['words'] = alignment.timed_words(r['ids'], r['spans'], r['sample_rate'], r['seconds'])
