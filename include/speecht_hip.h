@@ -362,6 +362,51 @@ int st_ctc_align_host(const float* logits, int batch, int frames, int classes, c
                       const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, int32_t* spans,
                       int32_t* states, float* score, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- Word confidences: exact CTC word posteriors of given labels (csrc/ctc_conf.hip) ----
+ * Conventions of st_ctc_align_f32: logits [B, T', C] padded NWC, blank = C-1, labels CSR, labels up to 511 (max_label_len
+ * picks the states-per-lane dispatch), seq_lens[b] frames are used, enqueues only, never allocates.  Here C <= 30 (two
+ * columns of the 32-wide softmax row carry the pseudo-label and the dead blanks; ST_EINVAL above that) and
+ * 0 <= space_id < C-1 is the id that separates words.
+ *
+ * Semantics (the float64 specification is tests/conf_oracle.py), with p_t(c) = softmax(logits[t])[c]:
+ *  - the words of a label l are its maximal runs of ids other than space_id;
+ *  - P(l) is the CTC probability of l, the sum over all alignments (exp(-loss) of st_ctc_loss_grad_f32);
+ *  - P(l*j): the ids of word j are replaced by ONE pseudo-label * and the standard lattice (2L'+1 states, blanks between
+ *    labels, a skip only between different labels) is run with two changes: the * state emits sum_{c != space_id} p_t(c),
+ *    the blank included, and the two blank states beside * are impossible (emission 0).  * differs from both neighbours.
+ *    Every alignment of l is counted once in the * path with the same word boundaries: 0 < P(l) <= P(l*j).
+ *  - log_prob[b] = ln P(l); log_conf[w] = min(0, ln P(l) - ln P(l*j)): the log of the probability that the stretch between
+ *    the word's neighbouring spaces reads that word, given that all other words read as in l, word boundaries summed out.
+ *    P(l) = 0 (single -inf logits can do that): log_prob = -inf and log_conf = -inf.
+ *  - status [B] != 0: the label is refused by the rule of st_ctc_loss_grad_f32 and st_ctc_align_f32 (csrc/ctc_lattice.h);
+ *    then log_prob = -inf and the log_conf of that utterance's words are NaN.  L = 0 is valid: log_prob = sum_t ln p_t(blank).
+ *
+ * word_spans: DEVICE [n_words][3] = utterance, first label index, one past the last, made by the host from the ids; the
+ * words of all utterances in any order, log_conf [n_words] in the same order.  A span that is not a maximal non-space run of
+ * its utterance is the caller's error: the result is unspecified, but nothing outside the outputs is written and nothing
+ * outside the inputs is read (a span outside its label, or an utterance outside the batch, gives NaN).  The same holds for
+ * ids outside 0 .. C-2.  n_words = 0 is valid (word_spans and log_conf may then be null).
+ *
+ * Arithmetic: sum-product in the linear domain, IEEE double, a state's value kept as mantissa * 2^exponent with an integer
+ * exponent per state (rescaling moves exponent bits: exact); no transcendental on the frame chain.  Every output is written
+ * with ordinary vector stores.
+ *
+ * Workspace (16-byte aligned): st_ctc_word_conf_ws = batch * frames * 32 * 8 + max_jobs * 8 + 512 bytes for
+ * 0 <= max_label_len <= 511, batch, frames > 0 and max_jobs >= batch + n_words (else 0): the softmax rows in double, written
+ * once per utterance, and ln P of every job -- one full label per utterance and one * lattice per word, one wave each.
+ *
+ * st_ctc_word_conf_host: the same recursion (shared arithmetic, csrc/ctc_conf_core.h: the same BITS) on HOST pointers,
+ * word_spans included, logits as a dense [batch][frames][classes] array; needs no device. */
+size_t st_ctc_word_conf_ws(int batch, int frames, int max_label_len, int max_jobs);
+int st_ctc_word_conf_f32(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets,
+                         const int32_t* seq_lens, int max_label_len, int space_id, const int32_t* word_spans, int n_words,
+                         double* log_prob, double* log_conf, int32_t* status, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int st_ctc_word_conf_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,
+                          const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, int space_id,
+                          const int32_t* word_spans, int n_words, double* log_prob, double* log_conf, int32_t* status,
+                          void* workspace, size_t workspace_bytes);
+
 /* ---- LM-free CTC prefix beam search, top path (BASELINE config 5) -----
  * The reference only reaches a beam search through its KenLM TensorFlow fork
  * (speech_model.py:101-111: beam_width=100, merge_repeated=False, top_paths=1); this is the stock

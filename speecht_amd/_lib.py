@@ -111,6 +111,11 @@ _SIGNATURES = {
                                  c_void_p, c_size_t, c_void_p]),
     'st_ctc_align_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_size_t]),
+    'st_ctc_word_conf_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'st_ctc_word_conf_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_word_conf_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     'st_ctc_beam_ws': (c_size_t, [c_int, c_int, c_int]),
     'st_ctc_beam_search_decode': (c_int, [_T3P, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),

@@ -27,19 +27,33 @@ def char_spans(ids, spans):
   return [(vocabulary.id_to_letter(i), int(s[0]), int(s[1])) for i, s in zip(ids, spans)]
 
 
-def word_spans(ids, spans):
-  """Words are maximal runs of ids other than space: -> list of (word, first frame of its first character, end frame of its
-  last character).  Leading, trailing and repeated spaces produce no words."""
-  words, start = [], None
-  ids = list(ids)
-  for k, i in enumerate(ids + [vocabulary.SPACE_ID]):
-    if i != vocabulary.SPACE_ID:
+def word_runs(ids, space_id=vocabulary.SPACE_ID):
+  """Words are maximal runs of ids other than space: -> list of (index of the word's first id, one past its last).  Leading,
+  trailing and repeated spaces produce no words.  (The word_spans argument of st_ctc_word_conf_f32 is made of these.)"""
+  runs, start = [], None
+  for k, i in enumerate(list(ids) + [space_id]):
+    if i != space_id:
       if start is None:
         start = k
     elif start is not None:
-      words.append((vocabulary.ids_to_sentence(ids[start:k]), int(spans[start][0]), int(spans[k - 1][1])))
+      runs.append((start, k))
       start = None
-  return words
+  return runs
+
+
+def word_spans(ids, spans):
+  """-> list of (word, first frame of its first character, end frame of its last character) for every word of `word_runs`."""
+  ids = list(ids)
+  return [(vocabulary.ids_to_sentence(ids[a:b]), int(spans[a][0]), int(spans[b - 1][1])) for a, b in word_runs(ids)]
+
+
+def confident_words(ids, confidence):
+  """The JSON form without times: [{word, confidence}], ``confidence`` one probability per word of `word_runs`."""
+  ids = list(ids)
+  runs = word_runs(ids)
+  if len(runs) != len(confidence):
+    raise ValueError('{} confidences for {} words'.format(len(confidence), len(runs)))
+  return [dict(word=vocabulary.ids_to_sentence(ids[a:b]), confidence=round(float(c), 6)) for (a, b), c in zip(runs, confidence)]
 
 
 def frames_to_seconds(frame, sample_rate, hop_length=HOP_LENGTH, duration=None):
@@ -49,12 +63,17 @@ def frames_to_seconds(frame, sample_rate, hop_length=HOP_LENGTH, duration=None):
   return t if duration is None else min(t, float(duration))
 
 
-def timed_words(ids, spans, sample_rate, duration=None, chars=False):
-  """The JSON form: [{word, start, end}] in seconds (``chars``: of the single characters, as {char, start, end})."""
+def timed_words(ids, spans, sample_rate, duration=None, chars=False, confidence=None):
+  """The JSON form: [{word, start, end}] in seconds (``chars``: of the single characters, as {char, start, end});
+  ``confidence`` (one probability per word): each word also carries `confidence`."""
   sec = lambda f: round(frames_to_seconds(f, sample_rate, HOP_LENGTH, duration), 4)
   if chars:
     return [dict(char=c, start=sec(a), end=sec(b)) for c, a, b in char_spans(ids, spans)]
-  return [dict(word=w, start=sec(a), end=sec(b)) for w, a, b in word_spans(ids, spans)]
+  words = [dict(word=w, start=sec(a), end=sec(b)) for w, a, b in word_spans(ids, spans)]
+  if confidence is not None:
+    for w, c in zip(words, confident_words(ids, confidence)):
+      w['confidence'] = c['confidence']
+  return words
 
 
 def read_transcripts(path):
@@ -106,14 +125,16 @@ def transcript_ids(text):
   return ids
 
 
-def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None, mask_padding=False):
+def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None, mask_padding=False,
+                confidence=False):
   """Align audio files with their transcripts -> a list, in ``paths`` order, of dicts
   {path, seconds, sample_rate, text, ids, spans, score, frames, error}.  ``transcripts``: {path: text} (`find_transcripts`) or
   a list parallel to ``paths``; None = no transcript.  ``error`` is the message for a file that is unreadable, too short, has no
   transcript, or whose transcript does not fit its frames or the vocabulary (spans is None then); the other files go on.
   ``spans``: [L, 2] output frames per id; ``frames``: output frames of the utterance; ``sample_rate``: the rate the features
   were computed at (what `frames_to_seconds` needs).  Batch semantics as `transcription.transcribe_files`, ``mask_padding``
-  included: with it the spans of a file do not depend on the batch it is in."""
+  included: with it the spans of a file do not depend on the batch it is in.  ``confidence=True``: every aligned entry gains
+  ``confidence`` = {'log_prob': ln P(transcript), 'words': [probability per word of the transcript]} (`inference.align`)."""
   texts = [transcripts.get(p) for p in paths] if isinstance(transcripts, dict) else list(transcripts)
   if len(texts) != len(paths):
     raise ValueError('align_files: {} paths and {} transcripts'.format(len(paths), len(texts)))
@@ -147,7 +168,13 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
   if ok:
     feats = transcription.device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
-    spans, scores, status = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size, mask_padding=mask_padding)
+    res = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size, mask_padding=mask_padding,
+                          confidence=confidence)
+    spans, scores, status = res[:3]
+    if confidence:
+      for entry, c in zip(ok, res[3]):
+        if c is not None:
+          entry['confidence'] = c
     for entry, f, sp, sc, st in zip(ok, feats, spans, scores, status):
       entry['frames'] = output_frames(f.shape[0])
       if st != 0:
@@ -178,16 +205,31 @@ def result_json(entry, chars=False):
   if entry.get('score') is not None:
     out['score'] = entry['score']
     out['score_per_frame'] = entry['score'] / max(entry['frames'], 1)
-  out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur)
+  conf = entry.get('confidence')
+  if conf is not None:
+    out['log_prob'] = conf['log_prob']
+  if entry.get('spans') is None:                       # transcribed with --confidence alone: words without times
+    out['words'] = confident_words(entry['ids'], conf['words'])
+    return out
+  out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur, confidence=conf['words'] if conf is not None else None)
   if chars:
     out['chars'] = timed_words(entry['ids'], entry['spans'], rate, dur, chars=True)
   return out
 
 
 def print_words(entry, file=None):
-  """One line per word: path<TAB>start<TAB>end<TAB>word."""
-  for w in timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds']):
-    print('{}\t{:.3f}\t{:.3f}\t{}'.format(entry['path'], w['start'], w['end'], w['word']), file=file or sys.stdout, flush=True)
+  """One line per word: path<TAB>start<TAB>end<TAB>word, and <TAB>confidence when the entry carries confidences (start and end
+  are `-` for an entry without spans)."""
+  conf = entry.get('confidence')
+  if entry.get('spans') is None:
+    words = confident_words(entry['ids'], conf['words'])
+  else:
+    words = timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds'],
+                        confidence=conf['words'] if conf is not None else None)
+  for w in words:
+    times = '{:.3f}\t{:.3f}'.format(w['start'], w['end']) if 'start' in w else '-\t-'
+    tail = '\t{:.4f}'.format(w['confidence']) if conf is not None else ''
+    print('{}\t{}\t{}{}'.format(entry['path'], times, w['word'], tail), file=file or sys.stdout, flush=True)
 
 
 def run_cli(flags):
@@ -211,7 +253,8 @@ def run_cli(flags):
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)
     results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size,
-                          mask_padding=bool(getattr(flags, 'mask_padding', False)))
+                          mask_padding=bool(getattr(flags, 'mask_padding', False)),
+                          confidence=bool(getattr(flags, 'confidence', False)))
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:

@@ -199,6 +199,54 @@ class DecodeMixin:
            host[2 * N + B * T + B:].view(np.float32).reshape(-1, 1).copy(), host[2 * N + B * T:2 * N + B * T + B].copy())
     return res + (host[2 * N:2 * N + B * T].reshape(B, T).copy(),) if return_states else res
 
+  def word_confidence(self, labels, space_id=None):
+    """Word confidences (st_ctc_word_conf_f32; semantics: include/speecht_hip.h, tests/conf_oracle.py): for the given id lists,
+    one per utterance of the batch, against the logits of the current shape
+    -> (list of float64 arrays: log_conf of each word of the utterance -- ln of the probability that the stretch between the
+    word's neighbouring spaces reads that word, the other words given, word boundaries summed out --, log_prob [B, 1] float64 =
+    ln P(label), status [B]: != 0 where the label does not fit its utterance's frames -- then log_prob = -inf and the log_conf
+    are NaN).  Words are the maximal runs of ids other than ``space_id`` (default: the vocabulary's space).
+    Labels hold ids in [0, num_classes - 1) and at most MAX_ALIGN_LABELS of them."""
+    from . import alignment, vocabulary
+    lib = _lib.load()
+    space_id = vocabulary.SPACE_ID if space_id is None else int(space_id)
+    sh = self.shape
+    xl = sh.X[-1]
+    B, T = xl.batch, xl.frames
+    if len(labels) != B:
+      raise ValueError('word_confidence: {} label sequences for a batch of {}'.format(len(labels), B))
+    lens = [len(l) for l in labels]
+    offs = np.zeros(B + 1, dtype=np.int32)
+    offs[1:] = np.cumsum(lens)
+    N, max_len = int(offs[-1]), int(max(lens + [0]))
+    if max_len > MAX_ALIGN_LABELS:
+      raise ValueError('word_confidence: label of length {} is too long for the lattice kernel (max {})'.format(max_len, MAX_ALIGN_LABELS))
+    ids = np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in labels] + [np.zeros(1, np.int32)])
+    # the kernel indexes LDS rows with the id: it must never see one outside the classes
+    if N and (int(ids.min()) < 0 or int(ids.max()) >= self.num_classes - 1):
+      raise ValueError('word_confidence: label ids must lie in [0, {}) (blank = {})'.format(self.num_classes - 1, self.num_classes - 1))
+    if not 0 <= space_id < self.num_classes - 1:
+      raise ValueError('word_confidence: space_id must lie in [0, {})'.format(self.num_classes - 1))
+    runs = [alignment.word_runs(l, space_id) for l in labels]
+    counts = [len(r) for r in runs]
+    W = int(sum(counts))
+    spans = np.array([(b, a, e) for b, r in enumerate(runs) for a, e in r] + [(0, 0, 0)], dtype=np.int32).reshape(-1)
+    need = lib.st_ctc_word_conf_ws(B, T, max_len, B + W)
+    ws = self._storage.view('conf_ws', need // 4 + 16, torch.int32)[0]
+    # outputs in one buffer, one copy back: log_conf [W] | log_prob [B] (doubles) | status [B]
+    out = self._storage.view('conf_out', 2 * (W + B) + B, torch.int32)[0]
+    at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+    d_ids, d_offs, d_spans = self._upload_i32(ids), self._upload_i32(offs), self._upload_i32(spans)
+    self._wait_uploads()
+    call('st_ctc_word_conf_f32', xl.ref, self._ptr(d_ids), self._ptr(d_offs), self._ptr(self.ctc_lens), max_len, space_id,
+         self._ptr(d_spans), W, at(2 * W), at(0), at(2 * (W + B)), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    with torch.cuda.stream(self.stream):
+      host = out[:2 * (W + B) + B].cpu().numpy()
+    conf = host[:2 * W].view(np.float64)
+    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return ([conf[first[b]:first[b + 1]].copy() for b in range(B)], host[2 * W:2 * (W + B)].view(np.float64).reshape(-1, 1).copy(),
+            host[2 * (W + B):].copy())
+
   def lm_beam_search_decode(self, lm, beam_width=100, input_transform='log10_softmax', lm_weight=0.8, word_count_weight=0.0,
                             valid_word_count_weight=2.3, oov_score=-1000.0):
     """The prefix beam search with a word n-gram scorer -- the reference's decoder (speech_model.py:84-111: beam 100,

@@ -46,7 +46,7 @@ BEAM_DECODERS = 2
 
 
 def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None,
-               timestamps=False, mask_padding=False):
+               timestamps=False, mask_padding=False, confidence=False):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -70,15 +70,21 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   on the same data, hence the same ids as without timestamps).  An utterance that decodes to more than
   ``engine_decode.MAX_ALIGN_LABELS`` ids gets None.  With ``timestamps=False`` nothing changes.
 
+  ``confidence=True``: a further element (after the spans when ``timestamps`` is also set), per utterance
+  {'log_prob': ln P(ids) under the CTC distribution, 'words': [confidence of each word of the decoded text]} -- the exact CTC
+  word posterior of ``engine.word_confidence``: the probability that the stretch between the word's neighbouring spaces reads
+  that word, given the other words.  It is computed after decoding, on the same logits, whichever decoder ran (the serial
+  loop, as with timestamps: the ids are those of a run without it); None for a hypothesis of more than MAX_ALIGN_LABELS ids.
+
   ``mask_padding=True``: the forward pass masks the padding of every batch (``engine.forward(mask_padding=True)``): an utterance
   gets the logits -- to the rounding of two summation orders -- and hence the ids and spans it gets with ``batch_size=1``,
   whatever batch it is in.  Off by default: the launch sequence is then exactly the unmasked one."""
   forward = (lambda: engine.forward(mask_padding=True)) if mask_padding else engine.forward
   if not features:
-    return ([], [], []) if timestamps else ([], [])
+    return ([], []) + (([],) if timestamps else ()) + (([],) if confidence else ())
   if pipeline is None:
     pipeline = DEFAULT_PIPELINE
-  if timestamps:
+  if timestamps or confidence:
     pipeline = False
   lm_opts = dict(lm_options or {})
   if language_model is not None:
@@ -100,6 +106,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   lengths, buckets = _plan(features, batch_size, bucket)
   ids_out = [None] * len(features)
   spans_out = [None] * len(features)
+  conf_out = [None] * len(features)
   if not pipeline:
     for idx in buckets:
       max_t = max(lengths[i] for i in idx)
@@ -115,8 +122,12 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         spans = _align_current(engine, ids)[0]
         for row, i in enumerate(idx):
           spans_out[i] = spans[row]
+      if confidence:
+        conf = _confidence_current(engine, ids)
+        for row, i in enumerate(idx):
+          conf_out[i] = conf[row]
     texts = [vocabulary.ids_to_sentence(s) for s in ids_out]
-    return (ids_out, texts, spans_out) if timestamps else (ids_out, texts)
+    return (ids_out, texts) + ((spans_out,) if timestamps else ()) + ((conf_out,) if confidence else ())
 
   def collect(handle, idx):
     res = handle.result()
@@ -169,7 +180,17 @@ def _align_current(engine, labels):
   return spans, score, status
 
 
-def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=False):
+def _confidence_current(engine, labels):
+  """``engine.word_confidence`` on the batch the engine holds -> per utterance {'log_prob': ln P(ids), 'words': [probability per
+  word]}; None for labels the kernel cannot take (longer than MAX_ALIGN_LABELS) or that do not fit their frames."""
+  from .engine_decode import MAX_ALIGN_LABELS
+  long = [len(l) > MAX_ALIGN_LABELS for l in labels]
+  conf, log_prob, status = engine.word_confidence([[] if skip else l for l, skip in zip(labels, long)])
+  return [None if skip or status[row] != 0 else dict(log_prob=float(log_prob[row, 0]), words=np.exp(conf[row]).tolist())
+          for row, skip in enumerate(long)]
+
+
+def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=False, confidence=False):
   """Forced alignment of known transcripts: features as for `transcribe`, ``labels`` one id list per utterance
   -> (spans, scores, status) in input order: spans[i] an [L_i, 2] int32 array (first output frame, one past the last output
   frame of each id on the best CTC path), scores[i] = ln p(that path), status[i] != 0 where the transcript does not fit the
@@ -177,13 +198,16 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
 
   Batched as `transcribe` batches.  ``batch_size=1`` is the default for the reason `transcription` gives: nothing in the
   network is masked, so the logits near the end of an utterance depend on the padded length of its batch, and with them the
-  times of its last words -- unless ``mask_padding`` is set, which masks the padding in the forward pass as in `transcribe`."""
+  times of its last words -- unless ``mask_padding`` is set, which masks the padding in the forward pass as in `transcribe`.
+
+  ``confidence=True``: a fourth element, per utterance {'log_prob', 'words'} as `transcribe` returns it -- the confidences of the
+  GIVEN transcript's words (None where status != 0): a low one marks a word the audio contradicts."""
   if len(features) != len(labels):
     raise ValueError('align: {} feature arrays and {} label sequences'.format(len(features), len(labels)))
   n = len(features)
-  spans_out, score_out, status_out = [None] * n, [float('-inf')] * n, [1] * n
+  spans_out, score_out, status_out, conf_out = [None] * n, [float('-inf')] * n, [1] * n, [None] * n
   if not features:
-    return spans_out, score_out, status_out
+    return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
   lengths, buckets = _plan(features, batch_size, bucket)
   for idx in buckets:
     max_t = max(lengths[i] for i in idx)
@@ -198,7 +222,11 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
     spans, score, status = _align_current(engine, [labels[i] for i in idx])
     for row, i in enumerate(idx):
       spans_out[i], score_out[i], status_out[i] = spans[row], float(score[row, 0]), int(status[row])
-  return spans_out, score_out, status_out
+    if confidence:
+      conf = _confidence_current(engine, [labels[i] for i in idx])
+      for row, i in enumerate(idx):
+        conf_out[i] = conf[row]
+  return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
 
 
 _STREAMS = {}      # device -> the stagers' copy stream

@@ -129,10 +129,13 @@ def device_features_on_device(audio, offsets, rates, feature_type='power', sampl
   return feats
 
 
-def _segmented(engine, signals, rates, options, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode):
+def _segmented(engine, signals, rates, options, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode,
+               confidence=False):
   """Segment every signal at its own rate, transcribe the utterances like files -> per signal a list of dicts {start, end (seconds
   in the signal), text, ids} in time order; with ``timestamps`` also ``words`` ([{word, start, end}] in seconds of the signal; None
-  where the text is too long to align).  An utterance too short for the features has an empty text."""
+  where the text is too long to align).  An utterance too short for the features has an empty text.  ``confidence``: also
+  ``confidence`` ({'log_prob', 'words'} of inference.transcribe, None where the text is too long or empty) and, in ``words``, each
+  word's `confidence` (without ``timestamps``: ``words`` = [{word, confidence}])."""
   table, gathered, out_offsets = segmentation.segment_audio(signals, rates, options, engine.device)
   out = [[] for _ in signals]
   if len(table) == 0:
@@ -141,16 +144,24 @@ def _segmented(engine, signals, rates, options, feature_type, sample_rate, batch
   feats = device_features_on_device(gathered, out_offsets, seg_rates, feature_type, sample_rate)
   ok = [s for s, f in enumerate(feats) if f is not None]
   res = inference.transcribe(engine, [feats[s] for s in ok], batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding,
-                             **decode) if ok else ([], [], [])
+                             **dict(decode, **(dict(confidence=True) if confidence else {}))) if ok else ([], [], [], [])
   found = {s: k for k, s in enumerate(ok)}
   for s, (i, a, b) in enumerate(table.tolist()):
     rate = float(rates[i])
     seg = dict(start=a / rate, end=b / rate, text='', ids=[])
-    if timestamps:
+    if timestamps or confidence:
       seg['words'] = []
+    if confidence:
+      seg['confidence'] = None
     if s in found:
       k = found[s]
       seg['ids'], seg['text'] = res[0][k], res[1][k]
+      conf = res[-1][k] if confidence else None
+      if confidence:
+        from . import alignment
+        seg['confidence'] = conf
+        if not timestamps:
+          seg['words'] = alignment.confident_words(seg['ids'], conf['words']) if conf is not None else None
       if timestamps:
         from . import alignment
         spans, target = res[2][k], _target_rate(int(rates[i]), sample_rate)
@@ -158,7 +169,8 @@ def _segmented(engine, signals, rates, options, feature_type, sample_rate, batch
         if spans is None:
           seg['words'] = None
         else:
-          inside = alignment.timed_words(seg['ids'], spans, target, (out_offsets[s + 1] - out_offsets[s]) / rate)
+          inside = alignment.timed_words(seg['ids'], spans, target, (out_offsets[s + 1] - out_offsets[s]) / rate,
+                                         confidence=conf['words'] if conf is not None else None)
           seg['words'] = segmentation.stitch(inside, seg['start'], segmentation.pad_samples(options, rates[i]) / rate, len(signals[i]) / rate)
     out[i].append(seg)
   return out
@@ -199,7 +211,7 @@ def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=2
 
 
 def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, timestamps=False,
-                     mask_padding=False, segment=None, **decode):
+                     mask_padding=False, segment=None, confidence=False, **decode):
   """Transcribe audio files (.flac, 16-bit .wav, .npy taken as 16 kHz) -> a list, in ``paths`` order, of dicts
   {path, seconds, text, ids, error}: ``error`` is the message for a file that cannot be read or is too short (its text and
   ids are None); the other files are transcribed as transcribe_audio does (same arguments, same batch semantics).
@@ -212,7 +224,10 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   ``timestamps`` also ``words``, the word times in the file: segment start minus pad plus the time inside the segment, clipped to
   the file; segments are short, so files of any length can be aligned).  ``text`` / ``ids`` are the non-empty segment texts joined
   by one space; a file without a segment has an empty text and is no error; ``spans`` is None (the words are per segment).
-  Segmentation is timed with 'features', the rest with 'transcribe'."""
+  Segmentation is timed with 'features', the rest with 'transcribe'.
+  ``confidence=True`` adds ``confidence``: {'log_prob', 'words': [probability per word of the text]} (inference.transcribe; None
+  when the text is too long), which `alignment.timed_words` / `alignment.confident_words` put next to each word; under ``segment``
+  it is per segment and the words of ``segments`` carry `confidence`."""
   results = []
   signals, rates, ok = [], [], []
   t0 = time.perf_counter()
@@ -232,21 +247,28 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   t1 = time.perf_counter()
   if ok and segment is not None:
     t2 = t1
-    per_file = _segmented(engine, signals, rates, segment, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode)
+    per_file = _segmented(engine, signals, rates, segment, feature_type, sample_rate, batch_size, timestamps, mask_padding, decode,
+                          confidence)
     for entry, rate, segs in zip(ok, rates, per_file):
       entry['segments'] = segs
       entry['ids'], entry['text'] = _join_segments(segs)
       if timestamps:
         entry.update(spans=None, frames=None, sample_rate=_target_rate(rate, sample_rate))
+      if confidence:
+        entry['confidence'] = None
   elif ok:
     feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
-    res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding, **decode)
+    res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding,
+                               **dict(decode, **(dict(confidence=True) if confidence else {})))
     for entry, i, t in zip(ok, res[0], res[1]):
       entry['ids'], entry['text'] = i, t
     if timestamps:
       for entry, f, rate, sp in zip(ok, feats, rates, res[2]):
         entry.update(spans=sp, frames=f.shape[0] // 2, sample_rate=_target_rate(rate, sample_rate))
+    if confidence:
+      for entry, rate, c in zip(ok, rates, res[-1]):
+        entry.update(confidence=c, sample_rate=_target_rate(rate, sample_rate))
   else:
     t2 = t1
   if timings is not None:
@@ -278,12 +300,14 @@ def run_cli(flags):
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)          # FileNotFoundError('No checkpoint for evaluation found'), as evaluate
     timestamps = bool(getattr(flags, 'timestamps', False))
+    confidence = bool(getattr(flags, 'confidence', False))
     segment = None
     if getattr(flags, 'segment', False):
       segment = segmentation.SegmentOptions(threshold=flags.segment_threshold, min_silence=flags.min_silence,
                                             max_segment=flags.max_segment)
     results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, timestamps=timestamps,
-                               mask_padding=bool(getattr(flags, 'mask_padding', False)), segment=segment, **decode)
+                               mask_padding=bool(getattr(flags, 'mask_padding', False)), segment=segment, confidence=confidence,
+                               **decode)
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:
@@ -294,19 +318,25 @@ def run_cli(flags):
         continue
       print('{}\t{}'.format(r['path'], r['text']), flush=True)
       line = dict(path=r['path'], seconds=r['seconds'], text=r['text'])
+      if confidence and r.get('confidence') is not None:
+        line['log_prob'] = r['confidence']['log_prob']
       if segment is not None:
         line['segments'] = []
         for seg in r['segments']:
           item = dict(start=round(seg['start'], 4), end=round(seg['end'], 4), text=seg['text'])
-          if timestamps and seg['words'] is not None:
+          if confidence and seg.get('confidence') is not None:
+            item['log_prob'] = seg['confidence']['log_prob']
+          if (timestamps or confidence) and seg['words'] is not None:
             item['words'] = seg['words']
             for w in seg['words']:
-              print('{}\t{:.3f}\t{:.3f}\t{}'.format(r['path'], w['start'], w['end'], w['word']), flush=True)
+              times = '{:.3f}\t{:.3f}'.format(w['start'], w['end']) if 'start' in w else '-\t-'
+              tail = '\t{:.4f}'.format(w['confidence']) if 'confidence' in w else ''
+              print('{}\t{}\t{}{}'.format(r['path'], times, w['word'], tail), flush=True)
           line['segments'].append(item)
-      elif timestamps and r['spans'] is not None:
+      elif (timestamps and r['spans'] is not None) or (confidence and r.get('confidence') is not None):
         from . import alignment
         alignment.print_words(r)
-        line['words'] = alignment.timed_words(r['ids'], r['spans'], r['sample_rate'], r['seconds'])
+        line['words'] = alignment.result_json(r)['words']
       if out:
         out.write(json.dumps(line) + '\n')
   finally:
