@@ -114,7 +114,7 @@ int st_conv1d_nwc_fwd_ws_f32(const st_tensor3* x, const float* packed, const flo
  * taps become one complex channel-contraction per frequency bin -- run as real GEMMs on the exact-fp32 MFMA kernel --
  * and the result comes back by an inverse DFT fused with the bias / ReLU / mask epilogue: for the model's 32-tap
  * 250 -> 2000 layer (speech_model.py:285; 66 % of the step's MACs) ~10x fewer multiplications than the W-tap form,
- * same fp32 arithmetic class (tests/test_gpu_fft_conv.py).  stride 1, W <= 33; the output channels must pack to a
+ * same fp32 arithmetic class (tests/test_gpu_fft_conv.py).  stride 1, 2 <= W <= 32 (a window of 63 + W frames must not have more than 48 bins); the output channels must pack to a
  * multiple of 128 (and the input channels too for back-prop to the input).  A stride-2 layer of even-ish width runs
  * through the same entry points on its polyphase view: the input read as [B][T/2][2 * c_pitch] (frame pairs as
  * channels), W/2 + 1 taps, the packed filters shifted by one c_pitch block (engine.py does this for
@@ -127,7 +127,13 @@ int st_conv1d_nwc_fwd_ws_f32(const st_tensor3* x, const float* packed, const flo
  *             the filter-gradient call
  *   zf        spectra of the gradient wrt the layer output (st_conv1d_fft_zf_floats floats), written by
  *             st_conv1d_fft_dz_spectra_f32, read by both gradient calls
- *   workspace st_conv1d_fft_ws bytes, scratch of one call, headed by st_gemm_nn_batched_ws_f32's area (one workspace per stream) */
+ *   workspace st_conv1d_fft_ws bytes, scratch of one call, headed by st_gemm_nn_batched_ws_f32's area (one workspace per stream)
+ * What the calls expect of their buffers: gfwd, sf, zf and the workspace may hold ANY content (every element that is read has been
+ * written by the call that owns it: pad rows and pad channels of the spectra as zeros); the halos of the tensors hold zeros
+ * (st_zero_halos_f32) and are not written, the interiors of y and dx are written whole, pad channels as zeros.  The filter
+ * gradient writes rows [0, width * cin_pitch) of dpacked [k_pad][n_pad], padding as zeros; rows [width * cin_pitch, k_pad) -- there
+ * are some when width * cin_pitch is no multiple of 32 -- are NOT written and stay the caller's: zero, like all padding of the
+ * packed layout (the engine's gradient buffer is zero-initialised once and nothing ever writes those rows). */
 int st_conv1d_fft_plan(int width, int frames, int batch, int* n, int* valid, int* blocks, int* bins, int* rows_pad);
 /* the per-bin products themselves: `batches` independent row-major fp32 GEMMs C[i] = A[i] * B[i] (A [m][lda], B [k][n],
  * C [m][ldc]; k a multiple of 32, n of 128; strides in floats) on the convolution MFMA kernel, bin i on XCD i % 8 */

@@ -31,7 +31,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int V = 64;                        // output frames per block
-constexpr int KP = 96;                       // padded DFT length (N = V + W - 1 <= 96) and padded 2 * bins
+constexpr int KP = 96;                       // padded DFT length (N = V + W - 1 <= 95) and padded 2 * bins
 constexpr int HB = KP / 2;                   // rows [0, HB) of a spectrum matrix are real parts, [HB, KP) imaginary
 // device tables (st_conv1d_fft_tables_f32), floats:
 constexpr int T_FS = 0;                      // forward DFT of N-frame segments          [KP][KP]
@@ -1021,7 +1021,9 @@ void launch_idft(const float* in, const float* winv, const Plan& p, int half_in,
 #undef ST_IDFT
 }
 
-bool width_ok(int width) { return width >= 2 && V + width - 1 <= KP; }
+// a window of N frames has N / 2 + 1 bins and a spectrum matrix HB rows for them: 2 .. 32 taps (33 taps: N = 96 fits KP, but its
+// Nyquist bin would be a 49th row)
+bool width_ok(int width) { return width >= 2 && V + width - 1 <= KP && (V + width - 1) / 2 + 1 <= HB; }
 // The three-product form of a layer's per-bin complex products (Gauss; conv_gemm.hip gemm_nn_g3_kernel / gemm_tn_g3_kernel): wide
 // layers only -- many output channels (the narrow layers' products run on the persistent per-bin kernel, and their launches are
 // too short for another split of the work) and more than 9 taps (the fused transforms of a chain write a neighbour layer's
@@ -1155,7 +1157,7 @@ int st_conv1d_fft_three_products(int width, int cin_pitch, int cout) {
 }
 
 int st_conv1d_fft_plan(int width, int frames, int batch, int* n, int* valid, int* blocks, int* bins, int* rows_pad) {
-  ST_REQUIRE(width_ok(width) && frames > 0 && batch > 0, "fft plan: filter width must be in [2, 33]");
+  ST_REQUIRE(width_ok(width) && frames > 0 && batch > 0, "fft plan: filter width must be in [2, 32]");
   const Plan p = make_plan(width, frames, batch);
   if (n) *n = p.n;
   if (valid) *valid = V;

@@ -111,7 +111,7 @@ class Bf16Mode(ModeBase):
     e = self.e
     l = e.layers[i]
     return (e.conv_mode == 'bf16' and e.fft_conv and os.environ.get('ST_FFT_BF16', '1') != '0' and i > 0 and
-            l.stride == 1 and 16 <= l.width <= 33 and l.n_pad % 128 == 0 and batch * t_out >= e.fft_min_rows)
+            l.stride == 1 and 16 <= l.width <= 32 and l.n_pad % 128 == 0 and batch * t_out >= e.fft_min_rows)
 
   def _fftb_transition(self, fftb, table_keys):
     """What entering a shape does that depends on the shape left behind (see SpectralLayers._fft_transition)."""

@@ -36,8 +36,8 @@ class SpectralLayers:
       return False
     if l.stride == 2:        # first layer of the model (48 taps, stride 2): 25 polyphase taps over 2 x 80 channels
       width2 = self._polyphase(i, geo)[0]
-      return i == 0 and e.fft_first_layer and e.fft_min_width <= width2 <= 33
-    return i > 0 and l.stride == 1 and e.fft_min_width <= l.width <= 33 and l.nt_pad % 128 == 0
+      return i == 0 and e.fft_first_layer and e.fft_min_width <= width2 <= 32
+    return i > 0 and l.stride == 1 and e.fft_min_width <= l.width <= 32 and l.nt_pad % 128 == 0
 
   def _alloc_fft(self, sh, part):
     """Per frequency-domain layer: the transform tables and the filter spectra in both operand layouts (functions of
