@@ -413,6 +413,56 @@ int st_ctc_word_conf_host(const float* logits, int batch, int frames, int classe
                           const int32_t* word_spans, int n_words, double* log_prob, double* log_conf, int32_t* status,
                           void* workspace, size_t workspace_bytes);
 
+/* ---- Keyword spotting: the best occurrence of given keywords in given utterances (csrc/ctc_spot.hip) ----
+ * Conventions of st_ctc_align_f32 / st_ctc_word_conf_f32: logits [B, T', C] padded NWC, blank = C-1, C <= 32, seq_lens[b]
+ * frames are used, only columns < C of frames < seq_lens[b] influence any output bit (a pitch column, a halo row or a row beyond
+ * `frames` is never read), enqueues only, never allocates.  Keywords are CSR: kw_ids, kw_offsets [n_keywords + 1], ids in
+ * 0 .. C-2 (spaces allowed: a phrase), 1 <= L <= 511; max_keyword_len picks the states-per-lane dispatch.
+ *
+ * Semantics (the float64 specification is tests/spot_oracle.py).  Per frame m_t = max_c x_t(c) and
+ * d_t(c) = (double)x_t(c) - (double)m_t: one IEEE double subtraction, <= 0, exactly 0 for the greedy class; it is the log of
+ * the ratio of the class's softmax probability to the greedy class's -- the normaliser cancels, there is no exp or log.
+ * An OCCURRENCE of keyword k over frames [s, e) is a frame path that is a CTC alignment of k, beginning on k_0 and ending on
+ * k_{L-1} (no leading or trailing blank; blanks optional between labels, compulsory between equal neighbours; repeats
+ * collapse); its score is sum_{t in [s,e)} d_t(class at t), the log-likelihood ratio of reading the keyword there against the
+ * greedy reading of the same frames.  The spot score of (utterance, keyword) is the maximum over all s < e <= seq_lens[b] and
+ * all such paths: <= 0, and == 0 exactly when the frame-wise argmax classes spell the keyword tightly somewhere.
+ *
+ * Recursion over t = 0 .. seq_lens[b]-1 on the 2L+1 CTC states; states 0 and 2L are dead (-inf).  Each state u = 1 .. 2L-1
+ * carries a value v and a start frame s, v_{-1} = -inf, s_{-1} = -1:
+ *   v_t(u) = best + d_t(class(u)), best over -- in this order, replaced only by a STRICTLY larger value --
+ *     stay v_{t-1}(u), advance v_{t-1}(u-1), skip v_{t-1}(u-2) (a label that differs from the previous label), and for u = 1
+ *     enter = 0.0 with start t;
+ *   s_t(u) = the start of the predecessor taken (t for enter; -1 when best is -inf);  end_t = v_t(2L-1), start s_t(2L-1).
+ * The result is the largest finite end_t, the LATEST t among equals (the frames on which the last character stays the argmax
+ * add exact zeros and belong to the hit): score = end_t, span = {s_t(2L-1), t+1}.  No finite end_t (a keyword that needs more
+ * frames than the utterance has): score = -inf, span = {-1, -1}, status = 0.
+ *
+ * jobs: DEVICE [n_jobs][2] = utterance, keyword, in any order, repeats allowed; one wave each.  Outputs per job: score
+ * (double), span [2], status; and, when both trace pointers are given, trace_score [n_jobs][frames] = end_t and trace_start
+ * [n_jobs][frames] = s_t(2L-1), -inf and -1 for t >= seq_lens[b].  status != 0: the utterance or the keyword index lies outside
+ * its table, L < 1 or beyond what max_keyword_len was dispatched for, kw_offsets not monotone there, or seq_lens[b] outside
+ * 0 .. frames -- then score = -inf, span = {-1, -1} and the job's trace rows are -inf / -1 throughout.  A row whose largest
+ * logit is not finite makes that job's result unspecified (single -inf logits are fine); ids outside 0 .. C-2 likewise; even
+ * then nothing outside the outputs is written and nothing outside the inputs is read.  n_jobs = 0 is valid.  Every output is
+ * written with ordinary vector stores.
+ *
+ * Workspace (16-byte aligned): st_ctc_spot_ws = batch * frames * 32 * 8 + 512 bytes for 1 <= max_keyword_len <= 511, batch,
+ * frames > 0 and n_jobs >= 0 (else 0): the rows of d in double, written once per utterance.  The start travels with the
+ * value: no back-pointer rows, no back-trace, nothing that grows with n_jobs * frames.
+ *
+ * st_ctc_spot_host: the same recursion (shared arithmetic, csrc/ctc_spot_core.h: the same BITS) on HOST pointers, jobs
+ * included, logits as a dense [batch][frames][classes] array; needs no device. */
+size_t st_ctc_spot_ws(int batch, int frames, int max_keyword_len, int n_jobs);
+int st_ctc_spot_f32(const st_tensor3* logits, const int32_t* seq_lens, const int32_t* kw_ids, const int32_t* kw_offsets,
+                    int n_keywords, int max_keyword_len, const int32_t* jobs, int n_jobs, double* score, int32_t* span,
+                    double* trace_score, int32_t* trace_start, int32_t* status, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int st_ctc_spot_host(const float* logits, int batch, int frames, int classes, const int32_t* seq_lens, const int32_t* kw_ids,
+                     const int32_t* kw_offsets, int n_keywords, int max_keyword_len, const int32_t* jobs, int n_jobs,
+                     double* score, int32_t* span, double* trace_score, int32_t* trace_start, int32_t* status, void* workspace,
+                     size_t workspace_bytes);
+
 /* ---- LM-free CTC prefix beam search, top path (BASELINE config 5) -----
  * The reference only reaches a beam search through its KenLM TensorFlow fork
  * (speech_model.py:101-111: beam_width=100, merge_repeated=False, top_paths=1); this is the stock

@@ -116,6 +116,11 @@ _SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     'st_ctc_word_conf_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    'st_ctc_spot_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'st_ctc_spot_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_spot_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     'st_ctc_beam_ws': (c_size_t, [c_int, c_int, c_int]),
     'st_ctc_beam_search_decode': (c_int, [_T3P, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),

@@ -55,6 +55,16 @@ CANDIDATE_WORKSPACE_BYTES = 1 << 30
 MAX_ALIGN_LABELS = 511          # labels per utterance of st_ctc_align_f32 (the 16-states-per-lane lattice of st_ctc_loss_grad_f32)
 
 
+MAX_SPOT_LABELS = 511           # ids per keyword of st_ctc_spot_f32 (the same lattice)
+SPOT_TRACE_BYTES = 256 << 20    # the largest trace (12 bytes per job and frame) one st_ctc_spot_f32 call of `spot` writes
+SPOT_KPLS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16)    # states per lane the lattice kernels are built for (csrc/ctc_lattice.h)
+
+
+def spot_lattice_kpl(keyword_len):
+  """The states-per-lane dispatch a keyword of that many ids needs (csrc/ctc_lattice.h, lattice_kpl): 64 * kpl >= 2 L + 1."""
+  return next(k for k in SPOT_KPLS if 64 * k >= 2 * keyword_len + 1)
+
+
 class CandidateDecodes:
   """Outputs of ``lm_beam_search_decode_candidates`` for P weight triples on B utterances: ``ids`` [P, B, T] int32, ``lens``
   [P, B] int32 (a prefix longer than T keeps its true length), ``log_prob`` [P, B] float32 -- device tensors of ``stream``, the
@@ -246,6 +256,80 @@ class DecodeMixin:
     first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     return ([conf[first[b]:first[b + 1]].copy() for b in range(B)], host[2 * W:2 * (W + B)].view(np.float64).reshape(-1, 1).copy(),
             host[2 * (W + B):].copy())
+
+  def spot(self, keywords, jobs=None, trace=False):
+    """Keyword spotting (st_ctc_spot_f32; semantics: include/speecht_hip.h, tests/spot_oracle.py): the best occurrence of each
+    keyword -- an id list, spaces allowed -- in the frames of each utterance, against the logits of the current shape.
+    ``jobs``: [n, 2] (utterance, keyword) pairs; default: every pair, utterance-major.
+    -> (score [n] float64: the log-likelihood ratio of reading the keyword on its best frames against the greedy reading of the
+    same frames, <= 0, -inf where the keyword does not fit; spans [n, 2] int32: first output frame and one past the last, -1
+    without a hit; status [n]: != 0 for a job outside the tables), in the order of ``jobs``.
+    ``trace=True``: two more arrays, [n, T'] float64 and int32 -- for every frame the best score of the occurrences that end
+    there and their first frame (-inf and -1 beyond the utterance): what `spotting.pick_hits` finds several hits in.
+
+    One call of the kernel runs one states-per-lane lattice, so the jobs are grouped by the lattice their keyword needs (one
+    long phrase does not put every short word on the 16-states-per-lane kernel) and, inside a group, ordered utterance-major:
+    neighbouring workgroups then read the same rows.  Trace calls are split over jobs so that one call's trace stays under
+    SPOT_TRACE_BYTES.  Keywords hold 1 .. MAX_SPOT_LABELS ids in [0, num_classes - 1)."""
+    lib = _lib.load()
+    sh = self.shape
+    xl = sh.X[-1]
+    B, T = xl.batch, xl.frames
+    keywords = [np.asarray(k, dtype=np.int32).reshape(-1) for k in keywords]
+    K = len(keywords)
+    for k in keywords:
+      if not 1 <= len(k) <= MAX_SPOT_LABELS:
+        raise ValueError('spot: a keyword holds 1 .. {} ids, got {}'.format(MAX_SPOT_LABELS, len(k)))
+      # the kernel indexes LDS rows with the id: it must never see one outside the classes
+      if int(k.min()) < 0 or int(k.max()) >= self.num_classes - 1:
+        raise ValueError('spot: keyword ids must lie in [0, {}) (blank = {})'.format(self.num_classes - 1, self.num_classes - 1))
+    if jobs is None:
+      jobs = np.stack(np.meshgrid(np.arange(B), np.arange(K), indexing='ij'), axis=-1)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
+    n = len(jobs)
+    score = np.full(n, -np.inf)
+    spans = np.full((n, 2), -1, dtype=np.int32)
+    status = np.ones(n, dtype=np.int32)
+    trace_score = np.full((n, T), -np.inf) if trace else None
+    trace_start = np.full((n, T), -1, dtype=np.int32) if trace else None
+    result = lambda: (score, spans, status) + ((trace_score, trace_start) if trace else ())
+    if n == 0 or K == 0:
+      return result()
+    offs = np.zeros(K + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([len(k) for k in keywords])
+    kpl_of = np.array([spot_lattice_kpl(len(k)) for k in keywords])
+    known = (jobs[:, 1] >= 0) & (jobs[:, 1] < K)
+    job_kpl = np.where(known, kpl_of[np.clip(jobs[:, 1], 0, K - 1)], SPOT_KPLS[0])      # (a job outside the tables: any lattice refuses it)
+    d_ids, d_offs = self._upload_i32(np.concatenate(keywords)), self._upload_i32(offs)
+    per_call = max(1, SPOT_TRACE_BYTES // (12 * T)) if trace else n
+    for kpl in sorted(set(job_kpl.tolist())):
+      group = np.flatnonzero(job_kpl == kpl)
+      group = group[np.argsort(jobs[group, 0], kind='stable')]
+      max_len = int(max([len(keywords[k]) for k in range(K) if kpl_of[k] == kpl]))
+      need = lib.st_ctc_spot_ws(B, T, max_len, min(per_call, len(group)))
+      ws = self._storage.view('spot_ws', need // 4 + 16, torch.int32)[0]
+      for first in range(0, len(group), per_call):
+        which = group[first:first + per_call]
+        m = len(which)
+        # outputs in one buffer, one copy back: score [m] | trace_score [m][T] (doubles) | span [m][2] | status [m] | trace_start [m][T]
+        tr = m * T if trace else 0
+        words = 2 * m + 2 * tr + 2 * m + m + tr
+        out = self._storage.view('spot_out', words + 2, torch.int32)[0]
+        at = lambda first_word: ctypes.c_void_p(out.data_ptr() + 4 * first_word)
+        d_jobs = self._upload_i32(jobs[which].reshape(-1))
+        self._wait_uploads()
+        call('st_ctc_spot_f32', xl.ref, self._ptr(self.ctc_lens), self._ptr(d_ids), self._ptr(d_offs), K, max_len, self._ptr(d_jobs), m,
+             at(0), at(2 * m + 2 * tr), at(2 * m) if trace else None, at(2 * m + 2 * tr + 3 * m) if trace else None,
+             at(2 * m + 2 * tr + 2 * m), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+        with torch.cuda.stream(self.stream):
+          host = out[:words].cpu().numpy()
+        score[which] = host[:2 * m].view(np.float64)
+        spans[which] = host[2 * m + 2 * tr:2 * m + 2 * tr + 2 * m].reshape(m, 2)
+        status[which] = host[2 * m + 2 * tr + 2 * m:2 * m + 2 * tr + 3 * m]
+        if trace:
+          trace_score[which] = host[2 * m:2 * m + 2 * tr].view(np.float64).reshape(m, T)
+          trace_start[which] = host[2 * m + 2 * tr + 3 * m:].reshape(m, T)
+    return result()
 
   def lm_beam_search_decode(self, lm, beam_width=100, input_transform='log10_softmax', lm_weight=0.8, word_count_weight=0.0,
                             valid_word_count_weight=2.3, oov_score=-1000.0):

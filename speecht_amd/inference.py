@@ -229,6 +229,44 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
   return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
 
 
+def spot(engine, features, keywords, batch_size=1, bucket=True, mask_padding=False, trace=False):
+  """Keyword spotting: features as for `transcribe`, ``keywords`` a list of id lists (`spotting.keyword_ids`), every keyword
+  searched in every utterance (``engine.spot``; semantics: include/speecht_hip.h)
+  -> (score [N, K] float64, spans [N, K, 2] int32, status [N, K]) in input order: the best occurrence of keyword k in utterance
+  i, its score the log-likelihood ratio against the greedy reading of the same output frames (<= 0; -inf and spans of -1 where
+  the keyword does not fit the utterance).  ``trace=True``: two more elements, per utterance a [K, T_i'] float64 and a
+  [K, T_i'] int32 array over its own T_i' output frames -- the best score of the occurrences ending at each frame and their
+  first frame (`spotting.pick_hits` finds several hits in them).
+
+  Batched as `align` batches, and ``batch_size=1`` is the default for the same reason: nothing in the network is masked, so the
+  logits near the end of an utterance depend on the padded length of its batch -- unless ``mask_padding`` is set."""
+  n, K = len(features), len(keywords)
+  score = np.full((n, K), -np.inf)
+  spans = np.full((n, K, 2), -1, dtype=np.int32)
+  status = np.ones((n, K), dtype=np.int32)
+  trace_score, trace_start = [None] * n, [None] * n
+  if features and K:
+    lengths, buckets = _plan(features, batch_size, bucket)
+    for idx in buckets:
+      max_t = max(lengths[i] for i in idx)
+      x = np.zeros((len(idx), max_t, features[0].shape[1]), dtype=np.float32)
+      for row, i in enumerate(idx):
+        x[row, :lengths[i]] = features[i]
+      engine.load_batch(x, [lengths[i] for i in idx])
+      if mask_padding:
+        engine.forward(mask_padding=True)
+      else:
+        engine.forward()
+      res = engine.spot(keywords, trace=trace)
+      for row, i in enumerate(idx):
+        rows = slice(row * K, (row + 1) * K)
+        score[i], spans[i], status[i] = res[0][rows], res[1][rows], res[2][rows]
+        if trace:
+          frames = lengths[i] // 2                               # the utterance's output frames (engine.ctc_lens)
+          trace_score[i], trace_start[i] = res[3][rows, :frames].copy(), res[4][rows, :frames].copy()
+  return (score, spans, status) + ((trace_score, trace_start) if trace else ())
+
+
 _STREAMS = {}      # device -> the stagers' copy stream
 _PINNED = {}       # (device, depth) -> ring of pinned staging buffers, grow-only
 _PIPELINE_LOCK = threading.Lock()
