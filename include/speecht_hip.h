@@ -368,6 +368,39 @@ int st_ctc_align_host(const float* logits, int batch, int frames, int classes, c
                       const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, int32_t* spans,
                       int32_t* states, float* score, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- Forced alignment of one long sequence: the same lattice in tiles (csrc/ctc_align_long.hip) ----
+ * The semantics of st_ctc_align_f32 -- lattice, moves, tie rules, end rule, fit rule -- for ONE sequence whose label may
+ * hold up to 1 048 575 ids: a transcript against the concatenated output frames of a long recording.  On a label that
+ * st_ctc_align_f32 takes, both return the same spans and the same score (there rounded to float).
+ *
+ * logits: dense [frames][row_pitch] floats, columns < classes are read; 2 <= classes <= 32, classes <= row_pitch,
+ * blank = classes - 1; 0 < frames <= 2^31 - 65.  label_ids [label_len], ids in [0, classes - 1): the kernel indexes rows with
+ * them and does not check.  label_len = 0 is valid (label_ids may then be null).  On the device entry logits, label_ids and all
+ * outputs are device pointers; it enqueues only and never allocates.
+ *
+ * Outputs: spans [label_len][2] as st_ctc_align_f32 writes them; score [1] = ln p(best path) as the DOUBLE the lattice is
+ * kept in; status [1] != 0: the label does not fit (frames < label_len + adjacent repeats) -- then score = -inf and the spans
+ * are {-1, -1}.  There is no `states` output.  Every output and workspace write is an ordinary vector store.
+ *
+ * How it runs: a frame block is 64 frames, a state block the 896 states one wave owns (16 per lane in lanes 8-63; lanes 0-7
+ * recompute a halo of 128 states from the neighbouring block's column, which is exact because a state looks at most two
+ * states down per frame).  2 + ceil(frames / 64) + 1 stream-ordered launches: log-softmax rows, init, one launch of
+ * NB = ceil((2 label_len + 1) / 896) workgroups per frame block, one back-trace wave.  The launch boundary is the only
+ * synchronisation between workgroups.
+ *
+ * Workspace (16-byte aligned): st_ctc_align_long_ws = frames * (32 * 8 + 56 * 4 * NB) + 2 * (896 * NB + 128) * 8 + 512 bytes
+ * for frames > 0 and 0 <= label_len <= 1 048 575 (else 0): the ln-softmax rows in double, the back-pointer rows (2 bits per
+ * state, 56 uint32 per state block and frame) and two lattice columns.  The call defines all of it that it reads.
+ *
+ * st_ctc_align_long_host: plain loops over the whole lattice with the same arithmetic (csrc/ctc_align_core.h) and the same
+ * back-pointer layout on HOST pointers: identical spans, score bits and status; needs no device. */
+size_t st_ctc_align_long_ws(long frames, int label_len);
+int st_ctc_align_long_f32(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                          int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int st_ctc_align_long_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                           int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes);
+
 /* ---- Word confidences: exact CTC word posteriors of given labels (csrc/ctc_conf.hip) ----
  * Conventions of st_ctc_align_f32: logits [B, T', C] padded NWC, blank = C-1, labels CSR, labels up to 511 (max_label_len
  * picks the states-per-lane dispatch), seq_lens[b] frames are used, enqueues only, never allocates.  Here C <= 30 (two

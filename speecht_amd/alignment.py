@@ -63,13 +63,50 @@ def frames_to_seconds(frame, sample_rate, hop_length=HOP_LENGTH, duration=None):
   return t if duration is None else min(t, float(duration))
 
 
-def timed_words(ids, spans, sample_rate, duration=None, chars=False, confidence=None):
+def concat_frame_seconds(frame_edges, segments, segment_frames, sample_rate, pad_seconds, duration, end=False):
+  """Frame boundaries of the CONCATENATED output frames of a recording's segments (`align_files(segment=...)`) -> seconds in
+  the file.  ``segments``: [{start, end}] in seconds of the file and time order; ``segment_frames``: the output frames each
+  contributed (0 for one too short for the features); ``pad_seconds``: the zeros in front of each gathered segment.
+
+  A boundary belongs to the segment of the frame it starts -- with ``end=True`` (one past the last frame of a span) to the
+  segment of the frame before it, so the end of a word that closes a segment is not reported at the start of the next one --
+  and is the segment's start, minus its pad, plus `frames_to_seconds` of the frame inside the segment, clipped to the file as
+  `segmentation.stitch` clips.  The result is monotone over the whole file: a segment's times also stay on its own side of the
+  middle of the gap to each neighbour, which only matters where a cut of an over-long utterance leaves no gap for the pads."""
+  counts = [int(n) for n in segment_frames]
+  if len(counts) != len(segments):
+    raise ValueError('concat_frame_seconds: {} segments and {} frame counts'.format(len(segments), len(counts)))
+  first = [0]
+  for n in counts:
+    first.append(first[-1] + n)
+  used = [s for s, n in enumerate(counts) if n > 0]
+  out = []
+  for f in frame_edges:
+    f = int(f)
+    probe = f - 1 if end else f                      # the frame whose segment the boundary is taken in
+    if not used or not 0 <= probe < first[-1]:
+      raise ValueError('concat_frame_seconds: frame boundary {} outside the {} concatenated frames'.format(f, first[-1]))
+    k = max(j for j, s in enumerate(used) if first[s] <= probe)
+    s = used[k]
+    lo = 0.0 if k == 0 else 0.5 * (float(segments[used[k - 1]]['end']) + float(segments[s]['start']))
+    hi = float(duration) if k + 1 == len(used) else 0.5 * (float(segments[s]['end']) + float(segments[used[k + 1]]['start']))
+    t = float(segments[s]['start']) - float(pad_seconds) + frames_to_seconds(f - first[s], sample_rate)
+    out.append(min(max(t, lo, 0.0), hi, float(duration)))
+  return out
+
+
+def timed_words(ids, spans, sample_rate, duration=None, chars=False, confidence=None, concat=None):
   """The JSON form: [{word, start, end}] in seconds (``chars``: of the single characters, as {char, start, end});
-  ``confidence`` (one probability per word): each word also carries `confidence`."""
-  sec = lambda f: round(frames_to_seconds(f, sample_rate, HOP_LENGTH, duration), 4)
+  ``confidence`` (one probability per word): each word also carries `confidence`.  ``concat``: (segments, segment_frames,
+  pad_seconds) of an entry whose spans are in concatenated frames -- the times then come from `concat_frame_seconds`."""
+  if concat is None:
+    sec = end_sec = lambda f: round(frames_to_seconds(f, sample_rate, HOP_LENGTH, duration), 4)
+  else:
+    sec = lambda f: round(concat_frame_seconds([f], concat[0], concat[1], sample_rate, concat[2], duration)[0], 4)
+    end_sec = lambda f: round(concat_frame_seconds([f], concat[0], concat[1], sample_rate, concat[2], duration, end=True)[0], 4)
   if chars:
-    return [dict(char=c, start=sec(a), end=sec(b)) for c, a, b in char_spans(ids, spans)]
-  words = [dict(word=w, start=sec(a), end=sec(b)) for w, a, b in word_spans(ids, spans)]
+    return [dict(char=c, start=sec(a), end=end_sec(b)) for c, a, b in char_spans(ids, spans)]
+  words = [dict(word=w, start=sec(a), end=end_sec(b)) for w, a, b in word_spans(ids, spans)]
   if confidence is not None:
     for w, c in zip(words, confident_words(ids, confidence)):
       w['confidence'] = c['confidence']
@@ -126,7 +163,7 @@ def transcript_ids(text):
 
 
 def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None, mask_padding=False,
-                confidence=False):
+                confidence=False, segment=None):
   """Align audio files with their transcripts -> a list, in ``paths`` order, of dicts
   {path, seconds, sample_rate, text, ids, spans, score, frames, error}.  ``transcripts``: {path: text} (`find_transcripts`) or
   a list parallel to ``paths``; None = no transcript.  ``error`` is the message for a file that is unreadable, too short, has no
@@ -134,7 +171,17 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
   ``spans``: [L, 2] output frames per id; ``frames``: output frames of the utterance; ``sample_rate``: the rate the features
   were computed at (what `frames_to_seconds` needs).  Batch semantics as `transcription.transcribe_files`, ``mask_padding``
   included: with it the spans of a file do not depend on the batch it is in.  ``confidence=True``: every aligned entry gains
-  ``confidence`` = {'log_prob': ln P(transcript), 'words': [probability per word of the transcript]} (`inference.align`)."""
+  ``confidence`` = {'log_prob': ln P(transcript), 'words': [probability per word of the transcript]} (`inference.align`).
+
+  ``segment`` (a segmentation.SegmentOptions): long recordings.  Every file is cut at its silences on the device, the segments
+  go through the network in batches, and the file's WHOLE transcript -- of any length, the limit of MAX_LABELS characters does
+  not apply -- is aligned against the concatenated output frames of its segments (`inference.align_long`).  The entry gains
+  ``segments`` ([{start, end}] in seconds of the file), ``segment_frames`` (the output frames of each; 0 for a segment too short
+  for the features) and ``segment_pad`` (seconds of zeros in front of a gathered segment); ``spans`` are in concatenated frames,
+  ``frames`` is their number, and `concat_frame_seconds` -- through `timed_words`, `result_json`, `print_words` -- maps them to
+  seconds of the file.  Word confidences are not computed on this path."""
+  if segment is not None and confidence:
+    raise ValueError('align_files: word confidences are not available with segment')
   texts = [transcripts.get(p) for p in paths] if isinstance(transcripts, dict) else list(transcripts)
   if len(texts) != len(paths):
     raise ValueError('align_files: {} paths and {} transcripts'.format(len(paths), len(texts)))
@@ -155,7 +202,7 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
       except transcription.TranscriptionError as e:
         raise transcription.TranscriptionError('{}: {}'.format(path, e)) from e
       entry['text'] = text.lower()
-      if len(entry['ids']) > MAX_LABELS:
+      if segment is None and len(entry['ids']) > MAX_LABELS:
         raise transcription.TranscriptionError('{}: transcript of {} characters is too long to align (max {})'.format(
             path, len(entry['ids']), MAX_LABELS))
     except transcription.TranscriptionError as e:
@@ -165,7 +212,27 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
     rates.append(rate)
     ok.append(entry)
   t1 = time.perf_counter()
-  if ok:
+  if ok and segment is not None:
+    from . import segmentation
+    table, gathered, out_offsets = segmentation.segment_audio(signals, rates, segment, engine.device)
+    feats = transcription.device_features_on_device(gathered, out_offsets, [int(rates[i]) for i in table[:, 0]], feature_type,
+                                                    sample_rate) if len(table) else []
+    t2 = time.perf_counter()
+    for i, (entry, rate) in enumerate(zip(ok, rates)):
+      rows = [s for s in range(len(table)) if table[s, 0] == i]
+      entry['segments'] = [dict(start=int(table[s, 1]) / float(rate), end=int(table[s, 2]) / float(rate)) for s in rows]
+      entry['segment_pad'] = segmentation.pad_samples(segment, rate) / float(rate)
+      spans, score, status, frames = inference.align_long(engine, [feats[s] for s in rows if feats[s] is not None], entry['ids'],
+                                                          batch_size=batch_size, mask_padding=mask_padding)
+      frames = iter(frames)
+      entry['segment_frames'] = [next(frames) if feats[s] is not None else 0 for s in rows]
+      entry['frames'] = sum(entry['segment_frames'])
+      if status != 0:
+        entry['error'] = '{}: transcript does not fit: {} characters (repeats need a frame between them) on {} output frames'.format(
+            entry['path'], len(entry['ids']), entry['frames'])
+      else:
+        entry['spans'], entry['score'] = spans, score
+  elif ok:
     feats = transcription.device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
     res = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size, mask_padding=mask_padding,
@@ -198,9 +265,17 @@ def output_frames(feature_frames):
   return int(feature_frames) // 2
 
 
+def concat_of(entry):
+  """The ``concat`` argument of `timed_words` for an entry of `align_files(segment=...)`, None for any other."""
+  if entry.get('segment_frames') is None:
+    return None
+  return entry['segments'], entry['segment_frames'], entry['segment_pad']
+
+
 def result_json(entry, chars=False):
   """The --output line of an aligned (or transcribed with --timestamps) file."""
   rate, dur = entry['sample_rate'], entry['seconds']
+  concat = concat_of(entry)
   out = dict(path=entry['path'], seconds=dur, text=entry['text'])
   if entry.get('score') is not None:
     out['score'] = entry['score']
@@ -211,9 +286,12 @@ def result_json(entry, chars=False):
   if entry.get('spans') is None:                       # transcribed with --confidence alone: words without times
     out['words'] = confident_words(entry['ids'], conf['words'])
     return out
-  out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur, confidence=conf['words'] if conf is not None else None)
+  out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur, confidence=conf['words'] if conf is not None else None,
+                             concat=concat)
   if chars:
-    out['chars'] = timed_words(entry['ids'], entry['spans'], rate, dur, chars=True)
+    out['chars'] = timed_words(entry['ids'], entry['spans'], rate, dur, chars=True, concat=concat)
+  if concat is not None:
+    out['segments'] = [dict(start=round(g['start'], 4), end=round(g['end'], 4)) for g in entry['segments']]
   return out
 
 
@@ -225,11 +303,23 @@ def print_words(entry, file=None):
     words = confident_words(entry['ids'], conf['words'])
   else:
     words = timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds'],
-                        confidence=conf['words'] if conf is not None else None)
+                        confidence=conf['words'] if conf is not None else None, concat=concat_of(entry))
   for w in words:
     times = '{:.3f}\t{:.3f}'.format(w['start'], w['end']) if 'start' in w else '-\t-'
     tail = '\t{:.4f}'.format(w['confidence']) if conf is not None else ''
     print('{}\t{}\t{}{}'.format(entry['path'], times, w['word'], tail), file=file or sys.stdout, flush=True)
+
+
+def segment_options(flags):
+  """The segmentation.SegmentOptions of `speecht-cli align --segment` (None without it).  The four flags are absent from the
+  namespace unless given; their defaults are those of SegmentOptions, which are `transcribe`'s."""
+  if not getattr(flags, 'segment', False):
+    return None
+  from . import segmentation
+  d = segmentation.SegmentOptions()
+  return segmentation.SegmentOptions(threshold=getattr(flags, 'segment_threshold', d.threshold),
+                                     min_silence=getattr(flags, 'min_silence', d.min_silence),
+                                     max_segment=getattr(flags, 'max_segment', d.max_segment))
 
 
 def run_cli(flags):
@@ -249,12 +339,13 @@ def run_cli(flags):
   input_size = transcription.FEATURE_WIDTH[flags.feature_type]
   with contextlib.redirect_stdout(sys.stderr):          # stdout carries the word lines only
     model = create_default_model(flags, input_size, SingleInputLoader(input_size))
+  segment = segment_options(flags)
   with Session(flags.device) as sess:
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)
     results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size,
                           mask_padding=bool(getattr(flags, 'mask_padding', False)),
-                          confidence=bool(getattr(flags, 'confidence', False)))
+                          confidence=bool(getattr(flags, 'confidence', False)), segment=segment)
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:

@@ -6,7 +6,7 @@
 // form shares: device and host choose the same path bit for bit.
 //
 // Structure:
-//  1. align_logsoftmax: one lane per (row, class), ln softmax in double into the workspace [B*T][32].
+//  1. align_logsoftmax (ctc_align_softmax.h): one lane per (row, class), ln softmax in double into the workspace [B*T][32].
 //  2. align_viterbi<KPL>: one WAVE per utterance, states dealt KPL-contiguous per lane as in ctc_alpha_beta_kernel: a frame is
 //     register arithmetic plus two cross-lane shifts (DPP); emission rows come through LDS in 64-frame chunks, prefetched one
 //     chunk ahead.  Every frame leaves one back-pointer row: 2 bits per state, KPL*2 bits = one uint32 per lane, 256 B coalesced.
@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "ctc_align_core.h"
+#include "ctc_align_softmax.h"
 #include "ctc_lattice.h"
 #include "st_common.h"
 
@@ -27,24 +28,6 @@ constexpr int CP = st::AL_CP;  // class pitch of the log-softmax rows
 constexpr int TC = st::LATTICE_TC;   // frames per LDS chunk
 constexpr int BPW = 64;        // back-pointer words per frame (one per lane)
 #define NEG_INF_F (-__builtin_inff())
-
-// ln softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum)
-__global__ __launch_bounds__(256) void align_logsoftmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T,
-                                                               int C, double* __restrict__ ly) {
-  const int lane = threadIdx.x & 63, c = lane & 31;
-  const long i = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-  const bool row_ok = i < (long)B * T;
-  const long ii = row_ok ? i : (long)B * T - 1;
-  const int b = (int)(ii / T), t = (int)(ii - (long)b * T);
-  const float v = c < C ? logits[map.off(b, t) + c] : NEG_INF_F;
-  float m = v;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  double s = c < C ? st::al_exp((double)v - (double)m) : 0.0;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-  if (row_ok) ly[i * CP + c] = st::al_log_softmax(v, m, s);
-}
 
 template <int KPL>
 __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restrict__ ly, int T, int C,
@@ -301,7 +284,7 @@ int st_ctc_align_f32(const st_tensor3* logits, const int32_t* label_ids, const i
   double* ly = reinterpret_cast<double*>(workspace);
   unsigned int* bp = reinterpret_cast<unsigned int*>(ly + rows * CP);
   int* end_state = reinterpret_cast<int*>(bp + rows * BPW);
-  hipLaunchKernelGGL(align_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
+  hipLaunchKernelGGL(st::align_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
                      st::row_map(*logits), B, T, C, ly);
   st::dispatch_kpl(kpl, [&](auto k) {
     hipLaunchKernelGGL(align_viterbi_kernel<k()>, dim3(B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets, seq_lens, bp,

@@ -55,6 +55,12 @@ CANDIDATE_WORKSPACE_BYTES = 1 << 30
 MAX_ALIGN_LABELS = 511          # labels per utterance of st_ctc_align_f32 (the 16-states-per-lane lattice of st_ctc_loss_grad_f32)
 
 
+MAX_ALIGN_LONG_LABELS = 1048575   # labels of the one sequence of st_ctc_align_long_f32
+ALIGN_LONG_FRAME_BLOCK = 64       # frames per launch of its tile kernel (csrc/ctc_align_long.hip)
+ALIGN_LONG_STATE_BLOCK = 896      # lattice states one workgroup of it owns (plus a halo of 2 * ALIGN_LONG_FRAME_BLOCK)
+ALIGN_LONG_WORKSPACE_BYTES = 16 << 30    # the default `max_workspace_bytes` of `align_long`
+
+
 MAX_SPOT_LABELS = 511           # ids per keyword of st_ctc_spot_f32 (the same lattice)
 SPOT_TRACE_BYTES = 256 << 20    # the largest trace (12 bytes per job and frame) one st_ctc_spot_f32 call of `spot` writes
 SPOT_KPLS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16)    # states per lane the lattice kernels are built for (csrc/ctc_lattice.h)
@@ -208,6 +214,49 @@ class DecodeMixin:
     res = ([spans[offs[b]:offs[b + 1]].copy() for b in range(B)],
            host[2 * N + B * T + B:].view(np.float32).reshape(-1, 1).copy(), host[2 * N + B * T:2 * N + B * T + B].copy())
     return res + (host[2 * N:2 * N + B * T].reshape(B, T).copy(),) if return_states else res
+
+  def align_long(self, logits, labels, max_workspace_bytes=ALIGN_LONG_WORKSPACE_BYTES):
+    """Forced alignment of ONE long sequence (st_ctc_align_long_f32; the semantics of `align`, include/speecht_hip.h): the
+    best CTC path of ``labels`` -- up to MAX_ALIGN_LONG_LABELS ids in [0, num_classes - 1) -- against ``logits``, a float32
+    device tensor [T, C] or [T, pitch] (C = num_classes <= pitch) such as the concatenated output frames of a recording's
+    segments -> (spans [L, 2] int32: first frame and one past the last frame of each label, score: ln p(best path) as a Python
+    float, status: != 0 where the label does not fit T frames -- then score = -inf and the spans are -1).
+
+    The lattice runs in tiles of ALIGN_LONG_FRAME_BLOCK frames x ALIGN_LONG_STATE_BLOCK states, one launch per frame block.
+    Its back-pointers take T * ceil((2 L + 1) / 896) * 224 bytes (an hour with 54 000 characters: 6.8 GB) in the engine's
+    storage; a workspace above ``max_workspace_bytes`` is refused with a ValueError that names its size."""
+    lib = _lib.load()
+    C = self.num_classes
+    if not (torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_cuda):
+      raise ValueError('align_long: logits must be a float32 device tensor [T, C]')
+    T, pitch = int(logits.shape[0]), int(logits.shape[1])
+    if T <= 0 or pitch < C:
+      raise ValueError('align_long: logits of shape [{}, {}] for {} classes'.format(T, pitch, C))
+    ids = np.asarray(labels, dtype=np.int32).reshape(-1)
+    L = int(ids.shape[0])
+    if L > MAX_ALIGN_LONG_LABELS:
+      raise ValueError('align_long: label of length {} is too long for the alignment kernel (max {})'.format(L, MAX_ALIGN_LONG_LABELS))
+    # the kernel indexes LDS rows with the id: it must never see one outside the classes
+    if L and (int(ids.min()) < 0 or int(ids.max()) >= C - 1):
+      raise ValueError('align_long: label ids must lie in [0, {}) (blank = {})'.format(C - 1, C - 1))
+    need = int(lib.st_ctc_align_long_ws(T, L))
+    if need > max_workspace_bytes:
+      raise ValueError('align_long: {} frames x {} labels need a workspace of {} bytes ({:.1f} GiB), above max_workspace_bytes = {}'.format(
+          T, L, need, need / 2.0 ** 30, int(max_workspace_bytes)))
+    logits = logits.contiguous()
+    ws = self._storage.view('align_long_ws', need // 4 + 16, torch.int32)[0]
+    # outputs in one buffer, one copy back: score (a double) | status, a spare word | spans [L][2]
+    out = self._storage.view('align_long_out', 4 + 2 * L, torch.int32)[0]
+    at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+    d_ids = self._upload_i32(np.concatenate([ids, np.zeros(1, np.int32)]))
+    self._wait_uploads()
+    self.stream.wait_stream(torch.cuda.current_stream(self.device))    # (the caller made ``logits`` on the current stream)
+    call('st_ctc_align_long_f32', self._ptr(logits), T, C, pitch, self._ptr(d_ids), L, at(4), at(0), at(2), self._ptr(ws),
+         ws.numel() * 4, self.stream_ptr)
+    with torch.cuda.stream(self.stream):
+      host = out[:4 + 2 * L].cpu().numpy()
+    logits.record_stream(self.stream)
+    return host[4:].reshape(L, 2).copy(), float(host[:2].view(np.float64)[0]), int(host[2])
 
   def word_confidence(self, labels, space_id=None):
     """Word confidences (st_ctc_word_conf_f32; semantics: include/speecht_hip.h, tests/conf_oracle.py): for the given id lists,

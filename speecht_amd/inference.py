@@ -229,6 +229,42 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
   return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
 
 
+def align_long(engine, features, labels, batch_size=1, mask_padding=False, return_logits=False):
+  """Forced alignment of ONE recording given as its segments: ``features`` the list of the segments' feature arrays in time
+  order, ``labels`` the id list of the whole transcript, of any length up to ``engine_decode.MAX_ALIGN_LONG_LABELS`` -- which part
+  of the text belongs to which segment is what the alignment finds.  The segments go through the forward pass in the batches
+  `align` forms (``batch_size``, ``mask_padding`` as there), each segment's own output frames are copied, in segment order, into
+  one [sum T, C] device tensor, and ``engine.align_long`` aligns the transcript against it
+  -> (spans [L, 2] int32 in CONCATENATED output frames, score = ln p(best path), status != 0 where the transcript does not fit
+  the frames -- spans is None then --, frames: the output frames of each segment; `alignment.concat_frame_seconds` maps a
+  concatenated frame to seconds).  ``return_logits``: a fifth element, the gathered logits (None without frames)."""
+  import torch
+  lengths, buckets = _plan(features, batch_size, True) if features else ([], [])
+  frames = [l // 2 for l in lengths]                               # the segments' output frames (engine.ctc_lens)
+  first = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+  total = int(first[-1])
+  if total == 0:
+    return (None, float('-inf'), 1, frames) + ((None,) if return_logits else ())
+  logits = torch.empty((total, engine.num_classes), dtype=torch.float32, device=engine.device)
+  for idx in buckets:
+    max_t = max(lengths[i] for i in idx)
+    x = np.zeros((len(idx), max_t, features[0].shape[1]), dtype=np.float32)
+    for row, i in enumerate(idx):
+      x[row, :lengths[i]] = features[i]
+    engine.load_batch(x, [lengths[i] for i in idx])
+    if mask_padding:
+      engine.forward(mask_padding=True)
+    else:
+      engine.forward()
+    with torch.cuda.stream(engine.stream):
+      out = engine.shape.X[-1].interior()
+      for row, i in enumerate(idx):
+        logits[int(first[i]):int(first[i + 1])].copy_(out[row, :frames[i]])
+  logits.record_stream(engine.stream)
+  spans, score, status = engine.align_long(logits, labels)
+  return (spans if status == 0 else None, score, status, frames) + ((logits,) if return_logits else ())
+
+
 def spot(engine, features, keywords, batch_size=1, bucket=True, mask_padding=False, trace=False):
   """Keyword spotting: features as for `transcribe`, ``keywords`` a list of id lists (`spotting.keyword_ids`), every keyword
   searched in every utterance (``engine.spot``; semantics: include/speecht_hip.h)
