@@ -556,6 +556,41 @@ int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int3
                                             int max_out, int32_t* out_lens, float* log_prob, void* workspace,
                                             size_t workspace_bytes, void* stream);
 
+/* ---- N-best lists from both beam searches ------------------------------------------------------------------------------
+ * The same searches (the frame loop is the same code), returning the n_best best final entries instead of the top path;
+ * 1 <= n_best <= beam_width; workspace: st_ctc_beam_ws.  Outputs: ids [B][n_best][max_out], out_lens [B][n_best], log_prob
+ * [B][n_best] float32, n_hyps [B].  Ranking (restated in tests/nbest_oracle.py):
+ *   - LM-free: the hypotheses are entries 0 .. n-1 of the final beam set, which is sorted by (total desc, candidate key asc);
+ *   - LM: every entry first gains its end-of-utterance delta (incomplete word, then </s>), exactly as for the top path; the
+ *     entries are then ranked by (final total desc, rank in the set asc);
+ *   - n_hyps[b] = min(n_best, entries alive): an utterance of length 0 has one entry, the empty prefix;
+ *   - slots at or beyond n_hyps[b] get out_lens = 0 and log_prob = -inf;
+ *   - labels beyond max_out are dropped and out_lens reports the true length;
+ *   - merge_repeated=False: the host's collapsing option is not offered for lists (it could make two hypotheses equal).
+ * n_best = 1 returns the bits of st_ctc_beam_search_decode_ex / st_ctc_beam_search_decode_lm. */
+int st_ctc_beam_search_decode_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int n_best,
+                                    int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int st_ctc_beam_search_decode_lm_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
+                                       float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                       int n_best, int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+/* Sentence scores of n label prefixes (ids [n][pitch], lens [n], ids 0..27 = a-z ' space) under a model: what the LM search adds
+ * to a final entry, without its weights -- a final total splits exactly as
+ *   total = A + lm_weight * (G + word_count_weight * n_words + valid_word_count_weight * n_valid),  A = the acoustic mass;
+ * oov_score never enters.  The ids are cut at every space into words; an empty run (a leading space, two spaces in a row) counts
+ * as a word and scores as <unk>; the trailing run counts only if non-empty.  The context starts as <s> (order > 1) and keeps
+ * the last order - 1 words.  A word spelled in [a-z'] that is a unigram scores as itself and counts in n_valid, any other as
+ * <unk>.  g = sum of log10 p(word | ctx) + log10 p(</s> | ctx): float32 table values summed in double in word order, </s> last.
+ * n = 0 is valid.  _f64: device pointers, `lm` uploaded to the device of `stream`; _host: host pointers, no device.  The two run
+ * the same arithmetic (csrc/lm_score_core.h) and are bit-identical.  An id outside 0..27 or a length outside 0..pitch: the host
+ * form returns ST_EINVAL and writes nothing; the device form, which cannot report without waiting for the stream, marks that
+ * prefix with g = NaN and n_words = n_valid = -1. */
+int st_lm_score_prefixes_f64(void* lm, const int32_t* ids, int pitch, const int32_t* lens, int n, double* g, int32_t* n_words,
+                             int32_t* n_valid, void* stream);
+int st_lm_score_prefixes_host(void* lm, const int32_t* ids, int pitch, const int32_t* lens, int n, double* g, int32_t* n_words,
+                              int32_t* n_valid);
+
 /* ---- exact Levenshtein distances of id sequences (the evaluation's letter and word edit distances, evaluation.py:40-49) ------
  * expected [expected_rows][expected_pitch] with lengths expected_lens, decoded [decoded_rows][decoded_pitch] with decoded_lens, all
  * device int32; pairs: DEVICE [n_pairs][2] = (expected row, decoded row).  distances: DEVICE [n_pairs][2] = {letter distance, word

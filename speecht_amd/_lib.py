@@ -143,6 +143,12 @@ _SIGNATURES = {
     'st_ctc_beam_lm_candidates_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
     'st_ctc_beam_search_decode_lm_candidates': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, POINTER(c_float), c_int, c_float,
                                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_search_decode_nbest': (c_int, [_T3P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_search_decode_lm_nbest': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_int,
+                                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_lm_score_prefixes_f64': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'st_lm_score_prefixes_host': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'st_edit_distance_max_len': (c_int, []),
     'st_edit_distance_pairs': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p]),

@@ -267,12 +267,23 @@ __global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __res
 // arrays; two beam entries per lane in the per-entry phases; the selection bound is the exact W-th largest score (a bitwise binary
 // search over the sortable scores: 32 wave-parallel counts) instead of the lane / pair / quad maxima, which bound only 64.
 // LM: the word n-gram scorer (LmParams) enters through the expansion deltas; LM = false compiles to the LM-free search.
-template <int CPL, int MAXB, bool LM>
+// NBEST: the tail writes the n_best best final entries (NbestArgs) instead of the top path; the frame loop is the same code, and
+// NBEST = false compiles to the top-path kernel (its NbestArgs is empty).
+template <bool NBEST>
+struct NbestArgs {};
+template <>
+struct NbestArgs<true> {
+  int n_best;          // 1 <= n_best <= W; the outputs are [utterance][n_best](...)
+  int* n_hyps;         // [utterance]: min(n_best, entries alive)
+};
+
+template <int CPL, int MAXB, bool LM, bool NBEST = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ lp_all, int T, int C,
                                                       const int* __restrict__ seq_lens, int W,
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
-                                                      int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma) {
+                                                      int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma,
+                                                      NbestArgs<NBEST> nx) {
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -688,6 +699,39 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   }
 
   __syncthreads();
+  // N best: hypothesis h is entry rank_of[h] of the final set with the total final_total[.] (both LDS, the selection's sel_k /
+  // sel_v, free after the last frame); one lane per hypothesis walks its node chain -- dependent global reads, n_best chains side
+  // by side, two rounds above 64 hypotheses.  Slots at or beyond the entries alive get length 0 and -inf.
+  [[maybe_unused]] auto write_nbest = [&](const int* rank_of, const float* final_total) {
+    if constexpr (NBEST) {
+      const BeamSet<MAXB>& S = sets[cur];
+      const int n = min(nx.n_best, nb);
+      if (lane == 0) nx.n_hyps[ob] = n;
+      for (int h = lane; h < nx.n_best; h += 64) {
+        const long o = ob * nx.n_best + h;
+        if (h >= n) {
+          out_lens[o] = 0;
+          out_logp[o] = -INFINITY;
+          continue;
+        }
+        const int e = rank_of ? rank_of[h] : h;
+        const int len = S.len[e], keep = min(len, max_out);
+        out_lens[o] = len;
+        out_logp[o] = (float)((double)final_total[e] + offset);
+        int id = S.node[e];
+        for (int i = len - 1; i >= 0; --i) {
+          const int2 nd = nodes[id];
+          if (i < keep) ids[o * max_out + i] = nd.y;
+          id = nd.x;
+        }
+      }
+    }
+  };
+  if constexpr (NBEST && !LM) {
+    // the final set is sorted by (total desc, candidate key asc): the hypotheses are its entries 0 .. n - 1
+    write_nbest(nullptr, sets[cur].total);
+    return;
+  }
   if constexpr (LM) {
     // end of utterance: every entry scores its incomplete word (if non-empty) and then </s>; the top path is the best total
     // after that (ties: the lower rank)
@@ -707,6 +751,21 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       sel_v[e] = sets[cur].total[e] + lw * d;
     }
     __syncthreads();
+    if constexpr (NBEST) {
+      // rank by (final total desc, rank in the set asc), by counting over LDS: entry e's place is the number of entries ahead of it
+      for (int e = lane; e < nb; e += 64) {
+        const float v = sel_v[e];
+        int r = 0;
+        for (int j = 0; j < nb; ++j) {
+          const float vj = sel_v[j];
+          r += (vj > v || (vj == v && j < e)) ? 1 : 0;
+        }
+        sel_k[r] = e;
+      }
+      __syncthreads();
+      write_nbest(sel_k, sel_v);
+      return;
+    }
     if (lane == 0) {
       int e0 = 0;
       for (int e = 1; e < nb; ++e)
@@ -759,9 +818,10 @@ int st_ctc_beam_search_decode(const st_tensor3* logits, const int32_t* seq_lens,
   return st_ctc_beam_search_decode_ex(logits, seq_lens, beam_width, 0, ids, max_out, out_lens, log_prob, workspace, workspace_bytes, stream);
 }
 
-int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int32_t* ids,
-                                 int max_out, int32_t* out_lens, float* log_prob, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+// the LM-free search: n_best = 0 is the top-path kernel of st_ctc_beam_search_decode_ex, n_best >= 1 the N-best instantiation
+static int beam_search_launch(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int n_best,
+                              int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                              size_t workspace_bytes, void* stream) {
   ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob, "beam search: null argument");
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
              input_transform);
@@ -781,19 +841,44 @@ int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_le
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), logits->batch), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
-  st::trace("ctc_beam<%s> beam=%d transform=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform);
-#define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
-  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, false>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
+  if (n_best > 0)
+    st::trace("ctc_beam<%s> beam=%d transform=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform, n_best);
+  else
+    st::trace("ctc_beam<%s> beam=%d transform=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform);
+#define ST_LAUNCH_BEAM_AS(CPL, MAXB, NBEST, NX)                                                                      \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, false, NBEST>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), lp_rows, \
                      logits->frames, logits->channels, seq_lens, beam_width,                                         \
                      reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
-                     out_lens, log_prob, LmArgs{})
+                     out_lens, log_prob, LmArgs{}, NX)
+#define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
+  do {                                                                                                               \
+    if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                           \
+    else ST_LAUNCH_BEAM_AS(CPL, MAXB, false, NbestArgs<false>{});                                                    \
+  } while (0)
   if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
   else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
   else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
   else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
   else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
+#undef ST_LAUNCH_BEAM_AS
   return st::check_launch("ctc_beam_search");
+}
+
+int st_ctc_beam_search_decode_ex(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int32_t* ids,
+                                 int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return beam_search_launch(logits, seq_lens, beam_width, input_transform, 0, ids, max_out, out_lens, log_prob, nullptr, workspace,
+                            workspace_bytes, stream);
+}
+
+int st_ctc_beam_search_decode_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int n_best,
+                                    int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(n_hyps, "beam search: null argument");
+  ST_REQUIRE(n_best >= 1 && n_best <= beam_width, "beam search: n_best 1..beam width (%d) supported, got %d", beam_width, n_best);
+  return beam_search_launch(logits, seq_lens, beam_width, input_transform, n_best, ids, max_out, out_lens, log_prob, n_hyps, workspace,
+                            workspace_bytes, stream);
 }
 
 // [node pools of min(candidates, kLaunchCandidates) x batch searches | log-softmax rows [batch][frames][32]]: a launch of more
@@ -804,10 +889,12 @@ size_t st_ctc_beam_lm_candidates_ws(int batch, int frames, int beam_width, int c
   return beam_pool_bytes(batch * per_launch, frames, beam_width) + (size_t)batch * frames * kMaxClasses * sizeof(float);
 }
 
-int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
-                                            void* lm, const float* weights, int candidates, float oov_score, int32_t* ids,
-                                            int max_out, int32_t* out_lens, float* log_prob, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
+// the LM-scored search for `candidates` weight triples: n_best = 0 is the top-path kernel, n_best >= 1 (one candidate) the N-best
+// instantiation
+static int beam_search_lm_launch(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                 void* lm, const float* weights, int candidates, float oov_score, int n_best, int32_t* ids,
+                                 int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
   ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob && lm && weights, "LM beam search: null argument");
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "LM beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
              input_transform);
@@ -845,8 +932,12 @@ int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int3
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), B), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
-  st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d candidates=%d", beam_width > 64 ? "wide" : "wave", beam_width,
-            input_transform, copy->view.order, candidates);
+  if (n_best > 0)
+    st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d candidates=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width,
+              input_transform, copy->view.order, candidates, n_best);
+  else
+    st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d candidates=%d", beam_width > 64 ? "wide" : "wave", beam_width,
+              input_transform, copy->view.order, candidates);
   for (int p0 = 0; p0 < candidates; p0 += kLaunchCandidates) {
     const int n = candidates - p0 < kLaunchCandidates ? candidates - p0 : kLaunchCandidates;
     LmArgs lma{};
@@ -855,21 +946,35 @@ int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int3
     for (int p = 0; p < n; ++p)
       for (int k = 0; k < 3; ++k) lma.w[p][k] = weights[3 * (p0 + p) + k];
     int32_t* ids_p = ids + (size_t)p0 * B * max_out;
-#define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
-    hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true>), dim3(B, n), dim3(64), 0, st::as_stream(stream), lp_rows, \
+#define ST_LAUNCH_BEAM_AS(CPL, MAXB, NBEST, NX)                                                                      \
+    hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true, NBEST>), dim3(B, n), dim3(64), 0, st::as_stream(stream), lp_rows, \
                        logits->frames, logits->channels, seq_lens, beam_width,                                       \
                        reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids_p, max_out,    \
-                       out_lens + (size_t)p0 * B, log_prob + (size_t)p0 * B, lma)
+                       out_lens + (size_t)p0 * B, log_prob + (size_t)p0 * B, lma, NX)
+#define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
+    do {                                                                                                             \
+      if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                         \
+      else ST_LAUNCH_BEAM_AS(CPL, MAXB, false, NbestArgs<false>{});                                                  \
+    } while (0)
     if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
     else if (per_lane <= 4) ST_LAUNCH_BEAM(4, 64);
     else if (per_lane <= 8) ST_LAUNCH_BEAM(8, 64);
     else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
     else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
+#undef ST_LAUNCH_BEAM_AS
     const int rc = st::check_launch("ctc_beam_search_lm");
     if (rc != ST_OK) return rc;
   }
   return ST_OK;
+}
+
+int st_ctc_beam_search_decode_lm_candidates(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                            void* lm, const float* weights, int candidates, float oov_score, int32_t* ids,
+                                            int max_out, int32_t* out_lens, float* log_prob, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  return beam_search_lm_launch(logits, seq_lens, beam_width, input_transform, lm, weights, candidates, oov_score, 0, ids, max_out,
+                               out_lens, log_prob, nullptr, workspace, workspace_bytes, stream);
 }
 
 // the single-candidate search is the candidates search with one triple (the same instantiation, the same launch shape)
@@ -880,6 +985,18 @@ int st_ctc_beam_search_decode_lm(const st_tensor3* logits, const int32_t* seq_le
   const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
   return st_ctc_beam_search_decode_lm_candidates(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, ids, max_out,
                                                  out_lens, log_prob, workspace, workspace_bytes, stream);
+}
+
+// ... and its N best final entries (one triple: the outputs are [batch][n_best])
+int st_ctc_beam_search_decode_lm_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, void* lm,
+                                       float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                       int n_best, int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(n_hyps, "LM beam search: null argument");
+  ST_REQUIRE(n_best >= 1 && n_best <= beam_width, "LM beam search: n_best 1..beam width (%d) supported, got %d", beam_width, n_best);
+  const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
+  return beam_search_lm_launch(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, n_best, ids, max_out, out_lens,
+                               log_prob, n_hyps, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -401,6 +401,79 @@ class DecodeMixin:
     ids = sh.dec_ids.view(-1, sh.t_out).cpu().numpy()
     return [ids[b, :lens[b]].tolist() for b in range(len(lens))], sh.dec_score.cpu().numpy().reshape(-1, 1)
 
+  def _nbest_lists(self, n_best, beam_width, launch):
+    """The N-best searches' buffers, one copy back and the lists: `launch(ids, T, lens, score, n_hyps, ws, ws_bytes)` issues the
+    search on the engine's own stream (the serial path, like `align`)."""
+    lib = _lib.load()
+    sh = self.shape
+    B, T, n = sh.dec_lens.numel(), sh.t_out, int(n_best)
+    if not 1 <= n <= int(beam_width):
+      raise ValueError('n_best must lie in 1..beam_width = {}, got {}'.format(int(beam_width), n))
+    need = lib.st_ctc_beam_ws(B, T, int(beam_width))
+    ws = self._storage.view('beam_ws', need // 4 + 16, torch.int32)[0]
+    # outputs in one buffer, one copy back: ids [B][n][T] | lens [B][n] | log_prob [B][n] (float bits) | n_hyps [B]
+    words = B * n * T + 2 * B * n + B
+    out = self._storage.view('nbest_out', words + 2, torch.int32)[0]
+    at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+    self._wait_uploads()
+    launch(at(0), T, at(B * n * T), at(B * n * T + B * n), at(B * n * T + 2 * B * n), self._ptr(ws), ws.numel() * 4)
+    with torch.cuda.stream(self.stream):
+      host = out[:words].cpu().numpy()
+    ids = host[:B * n * T].reshape(B, n, T)
+    lens = host[B * n * T:B * n * T + B * n].reshape(B, n)
+    logp = host[B * n * T + B * n:B * n * T + 2 * B * n].view(np.float32).reshape(B, n)
+    count = host[B * n * T + 2 * B * n:]
+    return [[(ids[b, h, :min(lens[b, h], T)].tolist(), float(logp[b, h])) for h in range(count[b])] for b in range(B)]
+
+  def beam_search_decode_nbest(self, n_best, beam_width=16, input_transform=None):
+    """The N best final prefixes of ``beam_search_decode`` (st_ctc_beam_search_decode_nbest; ranking rules: include/speecht_hip.h,
+    tests/nbest_oracle.py) -> per utterance a list of (ids, log_prob), best first, of min(n_best, entries alive) hypotheses;
+    ``n_best=1`` returns the bits of ``beam_search_decode``.  merge_repeated is not offered: it could make two hypotheses equal."""
+    code = beam_input_transform(input_transform)
+    sh = self.shape
+    return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
+        'st_ctc_beam_search_decode_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, int(n_best), ids, T, lens,
+        score, count, ws, ws_bytes, self.stream_ptr))
+
+  def lm_beam_search_decode_nbest(self, lm, n_best, beam_width=100, input_transform='log10_softmax', lm_weight=0.8,
+                                  word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0):
+    """The N best final prefixes of ``lm_beam_search_decode`` (st_ctc_beam_search_decode_lm_nbest): every final entry gains its
+    end-of-utterance LM terms, then the entries are ranked by (total desc, rank in the beam asc) -> per utterance a list of
+    (ids, log_prob), best first; log_prob includes the LM terms (`nbest.components` splits them off)."""
+    code = beam_input_transform(input_transform)
+    handle = lm.device_handle(self.device)
+    sh = self.shape
+    return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
+        'st_ctc_beam_search_decode_lm_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle, float(lm_weight),
+        float(word_count_weight), float(valid_word_count_weight), float(oov_score), int(n_best), ids, T, lens, score, count, ws,
+        ws_bytes, self.stream_ptr))
+
+  def lm_score_prefixes(self, lm, prefixes):
+    """Sentence scores of id lists (ids 0..27: a-z ' space) under ``lm`` (st_lm_score_prefixes_f64; the definition:
+    include/speecht_hip.h, tests/nbest_oracle.py) -> (G float64 [n]: the sum of the words' log10 n-gram probabilities plus </s>,
+    n_words int32 [n], n_valid int32 [n]).  One lane per prefix, on the engine's own stream."""
+    n = len(prefixes)
+    if n == 0:
+      return np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    lens = np.array([len(p) for p in prefixes], dtype=np.int32)
+    pitch = max(int(lens.max()), 1)
+    ids = np.zeros((n, pitch), dtype=np.int32)
+    for i, p in enumerate(prefixes):
+      ids[i, :lens[i]] = p
+    # (the kernel marks a prefix with an id outside 0..27 instead of failing the call: refuse it here)
+    if int(ids.min()) < 0 or int(ids.max()) > 27:
+      raise ValueError('lm_score_prefixes: ids must lie in 0..27 (a-z, apostrophe, space)')
+    handle = lm.device_handle(self.device)
+    # outputs in one buffer, one copy back: G [n] (doubles) | n_words [n] | n_valid [n]
+    out = self._storage.view('lm_score_out', 4 * n + 2, torch.int32)[0]
+    at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+    d_ids, d_lens = self._upload_i32(ids.reshape(-1)), self._upload_i32(lens)
+    self._wait_uploads()
+    call('st_lm_score_prefixes_f64', handle, self._ptr(d_ids), pitch, self._ptr(d_lens), n, at(0), at(2 * n), at(3 * n), self.stream_ptr)
+    with torch.cuda.stream(self.stream):
+      host = out[:4 * n].cpu().numpy()
+    return host[:2 * n].view(np.float64).copy(), host[2 * n:3 * n].copy(), host[3 * n:].copy()
+
   def lm_beam_search_decode_candidates(self, lm, weights, beam_width=100, input_transform='log10_softmax', oov_score=-1000.0,
                                        max_workspace_bytes=CANDIDATE_WORKSPACE_BYTES):
     """``lm_beam_search_decode`` for several weight triples on the same logits (the LM weight search's generation):

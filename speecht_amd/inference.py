@@ -46,7 +46,7 @@ BEAM_DECODERS = 2
 
 
 def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None,
-               timestamps=False, mask_padding=False, confidence=False):
+               timestamps=False, mask_padding=False, confidence=False, nbest=None, rescore=None):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -78,13 +78,26 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
 
   ``mask_padding=True``: the forward pass masks the padding of every batch (``engine.forward(mask_padding=True)``): an utterance
   gets the logits -- to the rounding of two summation orders -- and hence the ids and spans it gets with ``batch_size=1``,
-  whatever batch it is in.  Off by default: the launch sequence is then exactly the unmasked one."""
+  whatever batch it is in.  Off by default: the launch sequence is then exactly the unmasked one.
+
+  ``nbest=N`` (with ``beam_width`` or ``language_model``; N <= the beam): a last element, per utterance the list of its up to N best
+  hypotheses, best first -- dicts {'ids', 'text', 'log_prob', 'acoustic'} and, when a model was involved, {'lm_log10', 'words',
+  'valid_words'} (`nbest.components`).  The N-best search runs on the engine's own stream (the serial loop, as with timestamps); its
+  first hypothesis is the top path of the search without ``nbest``.  ``rescore``: a dict {'language_model', 'lm_weight' (default: the
+  first pass's), 'word_count_weight', 'valid_word_count_weight' (default: the first pass's)} -- every list is re-ranked under that
+  model (`nbest.rescored`: 'log_prob' becomes the new score, the LM parts those of the second model).  ``ids`` / texts -- and with
+  them ``timestamps`` and ``confidence`` -- are those of the best hypothesis after any rescoring."""
+  if nbest is not None:
+    if not (beam_width or language_model is not None):
+      raise ValueError('transcribe: nbest needs a beam search (beam_width or language_model)')
+  elif rescore is not None:
+    raise ValueError('transcribe: rescore applies to N-best lists (nbest=N)')
   forward = (lambda: engine.forward(mask_padding=True)) if mask_padding else engine.forward
   if not features:
-    return ([], []) + (([],) if timestamps else ()) + (([],) if confidence else ())
+    return ([], []) + (([],) if timestamps else ()) + (([],) if confidence else ()) + (([],) if nbest is not None else ())
   if pipeline is None:
     pipeline = DEFAULT_PIPELINE
-  if timestamps or confidence:
+  if timestamps or confidence or nbest is not None:
     pipeline = False
   lm_opts = dict(lm_options or {})
   if language_model is not None:
@@ -98,6 +111,33 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
       return engine.lm_beam_search_decode(language_model, beam_width, **lm_opts)[0]
     return engine.beam_search_decode(beam_width)[0] if beam_width else engine.greedy_decode()[0]
 
+  first_pass = (float(lm_opts.get('lm_weight', 0.8)), float(lm_opts.get('word_count_weight', 0.0)),
+                float(lm_opts.get('valid_word_count_weight', 2.3)))
+  if rescore is not None:
+    from .language_model import LanguageModel
+    rescore = dict(rescore)
+    lm2 = rescore.get('language_model')
+    if lm2 is None:
+      raise ValueError("transcribe: rescore needs a 'language_model'")
+    rescore['language_model'] = lm2 if isinstance(lm2, LanguageModel) else LanguageModel.load(lm2)
+
+  def decode_nbest():
+    """The lists of the batch the engine holds, split into their parts and re-ranked if asked, each hypothesis with its text."""
+    from . import nbest as nbest_lists
+    if language_model is not None:
+      lists = engine.lm_beam_search_decode_nbest(language_model, nbest, beam_width, **lm_opts)
+    else:
+      lists = engine.beam_search_decode_nbest(nbest, beam_width)
+    lists = nbest_lists.components(engine, language_model, lists, first_pass)
+    if rescore is not None:
+      shared = first_pass if language_model is not None else (0.0, 0.0, 0.0)
+      lists = nbest_lists.rescored(lists, engine, rescore['language_model'], rescore.get('lm_weight', first_pass[0]),
+                                   rescore.get('word_count_weight', shared[1]), rescore.get('valid_word_count_weight', shared[2]))
+    for hyps in lists:
+      for h in hyps:
+        h['text'] = vocabulary.ids_to_sentence(h['ids'])
+    return lists
+
   def decode_async(decode_stream):
     if language_model is not None:
       return engine.lm_beam_search_decode_async(language_model, beam_width, decode_stream, **lm_opts)
@@ -107,6 +147,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   ids_out = [None] * len(features)
   spans_out = [None] * len(features)
   conf_out = [None] * len(features)
+  nbest_out = [None] * len(features)
   if not pipeline:
     for idx in buckets:
       max_t = max(lengths[i] for i in idx)
@@ -115,7 +156,13 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         x[row, :lengths[i]] = features[i]
       engine.load_batch(x, [lengths[i] for i in idx])
       forward()
-      ids = decode_sync()
+      if nbest is not None:
+        lists = decode_nbest()
+        ids = [hyps[0]['ids'] for hyps in lists]
+        for row, i in enumerate(idx):
+          nbest_out[i] = lists[row]
+      else:
+        ids = decode_sync()
       for row, i in enumerate(idx):
         ids_out[i] = ids[row]
       if timestamps:
@@ -127,7 +174,8 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
         for row, i in enumerate(idx):
           conf_out[i] = conf[row]
     texts = [vocabulary.ids_to_sentence(s) for s in ids_out]
-    return (ids_out, texts) + ((spans_out,) if timestamps else ()) + ((conf_out,) if confidence else ())
+    return (ids_out, texts) + ((spans_out,) if timestamps else ()) + ((conf_out,) if confidence else ()) + \
+        ((nbest_out,) if nbest is not None else ())
 
   def collect(handle, idx):
     res = handle.result()

@@ -211,7 +211,7 @@ def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=2
 
 
 def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, batch_size=1, timings=None, timestamps=False,
-                     mask_padding=False, segment=None, confidence=False, **decode):
+                     mask_padding=False, segment=None, confidence=False, nbest=None, rescore=None, **decode):
   """Transcribe audio files (.flac, 16-bit .wav, .npy taken as 16 kHz) -> a list, in ``paths`` order, of dicts
   {path, seconds, text, ids, error}: ``error`` is the message for a file that cannot be read or is too short (its text and
   ids are None); the other files are transcribed as transcribe_audio does (same arguments, same batch semantics).
@@ -227,7 +227,12 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   Segmentation is timed with 'features', the rest with 'transcribe'.
   ``confidence=True`` adds ``confidence``: {'log_prob', 'words': [probability per word of the text]} (inference.transcribe; None
   when the text is too long), which `alignment.timed_words` / `alignment.confident_words` put next to each word; under ``segment``
-  it is per segment and the words of ``segments`` carry `confidence`."""
+  it is per segment and the words of ``segments`` carry `confidence`.
+  ``nbest=N`` (with a beam search; not with ``segment``: per-segment lists do not join into file lists) adds ``nbest``: the file's up
+  to N best hypotheses, best first (inference.transcribe: dicts with 'text', 'log_prob', 'acoustic' and the LM parts); ``rescore``
+  re-ranks them under a second model first, and ``text`` / ``ids`` are the best hypothesis after that."""
+  if nbest is not None and segment is not None:
+    raise ValueError('transcribe_files: nbest is not available with segment (per-segment lists do not join into file lists)')
   results = []
   signals, rates, ok = [], [], []
   t0 = time.perf_counter()
@@ -259,8 +264,13 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   elif ok:
     feats = device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
+    lists = dict(nbest=nbest, rescore=rescore) if nbest is not None else {}
     res = inference.transcribe(engine, feats, batch_size=batch_size, timestamps=timestamps, mask_padding=mask_padding,
-                               **dict(decode, **(dict(confidence=True) if confidence else {})))
+                               **dict(decode, **dict(lists, **(dict(confidence=True) if confidence else {}))))
+    if nbest is not None:
+      for entry, hyps in zip(ok, res[-1]):
+        entry['nbest'] = hyps
+      res = res[:-1]
     for entry, i, t in zip(ok, res[0], res[1]):
       entry['ids'], entry['text'] = i, t
     if timestamps:
@@ -305,9 +315,17 @@ def run_cli(flags):
     if getattr(flags, 'segment', False):
       segment = segmentation.SegmentOptions(threshold=flags.segment_threshold, min_silence=flags.min_silence,
                                             max_segment=flags.max_segment)
+    nbest = getattr(flags, 'nbest', None)
+    rescore = None
+    if nbest and getattr(flags, 'rescore_language_model', None):
+      shared = model.language_model is not None
+      rescore = dict(language_model=flags.rescore_language_model,
+                     lm_weight=getattr(flags, 'rescore_lm_weight', model.lm_weight),
+                     word_count_weight=model.word_count_weight if shared else flags.word_count_weight,
+                     valid_word_count_weight=model.valid_word_count_weight if shared else flags.valid_word_count_weight)
     results = transcribe_files(model.engine, paths, flags.feature_type, flags.sample_rate, flags.batch_size, timestamps=timestamps,
                                mask_padding=bool(getattr(flags, 'mask_padding', False)), segment=segment, confidence=confidence,
-                               **decode)
+                               **dict(decode, **(dict(nbest=nbest, rescore=rescore) if nbest else {})))
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:
@@ -318,6 +336,11 @@ def run_cli(flags):
         continue
       print('{}\t{}'.format(r['path'], r['text']), flush=True)
       line = dict(path=r['path'], seconds=r['seconds'], text=r['text'])
+      if r.get('nbest') is not None:
+        parts = ('text', 'log_prob', 'acoustic', 'lm_log10', 'words', 'valid_words')
+        line['nbest'] = [{k: h[k] for k in parts if k in h} for h in r['nbest']]
+        for rank, h in enumerate(r['nbest'], 1):
+          print('{}\t{}\t{:.4f}\t{}'.format(r['path'], rank, h['log_prob'], h['text']), flush=True)
       if confidence and r.get('confidence') is not None:
         line['log_prob'] = r['confidence']['log_prob']
       if segment is not None:
