@@ -805,6 +805,66 @@ int st_segment_gather_f32(const float* audio, const int64_t* src_start, const fl
  * the SAME padding it would see alone (engine.forward(mask_padding=True)). */
 int st_mask_rows(const st_tensor3* t, const int32_t* valid, int elem_bytes, void* stream);
 
+/* ---- Streaming recognition (csrc/conv_stream.hip, csrc/stream_map.h; no reference counterpart): one step of the forward pass
+ * for many open streams, state carried between steps.  Every layer keeps per stream a linear window of recent input frames,
+ * windows[max_streams][cap][cin_pitch]; position 0 of stream s holds absolute input frame info[s][0].  The per-stream counters are
+ * pure functions of how many frames were fed, so the HOST keeps them (speecht_amd/streaming.py `plan`) and passes tables:
+ *   info  int32 [max_streams][4]  {base: absolute frame at window position 0, n: frames received (valid frames are [0, n)),
+ *                                  base after this step, unused}
+ *   rows  int32 [n_rows][2]       (stream, absolute output frame), a stream's rows adjacent and in frame order
+ * st_stream_conv_f32: one layer, one step, all streams.  Row (s, j) reads the frames j * stride - pad_left ... + width - 1 of stream
+ *   s (pad_left = (width - stride) / 2; frames outside [0, n) and outside the window read as zero), against the engine's packed
+ *   filters [k_pad][n_pad] and bias [n_pad]; bias and optional ReLU applied.  With out_info (the NEXT layer's info table) the result
+ *   goes to out[s][j - out_info[s][0]][out_pitch], channels [cout, out_pitch) as zeros; with out_info NULL row r of the launch goes
+ *   to out[r][out_pitch] (out_cap rows: the logits buffer).  The reduction is cut into `slices` slices of kt_per_slice 32-deep k-tiles
+ *   (st_stream_conv_slices: a function of width, cin_pitch and cout only), partial tiles go to the workspace
+ *   (st_stream_conv_ws bytes for n_rows rows) and a second kernel sums them in slice order: a row's result does not depend on the
+ *   other rows of the launch, their number or its own position.  No float atomics.  n_rows = 0 enqueues nothing.
+ * st_stream_feed_f32: row r of features [n_rows][channels] to position table[r][1] of stream table[r][0]'s first-layer window
+ *   (pad channels as zeros).
+ * st_stream_advance: for every layer l < n_layers and stream, moves frames [info[l][s][2], info[l][s][1]) to the front of the window;
+ *   layer_table is a DEVICE table of n_layers entries {float* windows, int32 cap, int32 c_pitch}, info int32 [n_layers][max_streams][4].
+ * st_ctc_greedy_stream: greedy CTC decoding carried across steps, one wavefront per stream.  table int32 [max_streams][4] =
+ *   {first row, rows, decode limit or -1 while unknown, 1: reset the stream's state first}; rows with frame >= limit are not decoded.
+ *   state int32 [max_streams][4] {last argmax id, frames decoded, -, -} and score double [max_streams] (sum of the chosen logits)
+ *   persist between calls.  First maximum on ties, columns below num_classes only, blank = num_classes - 1, repeats merged across
+ *   calls.  New ids go to ids[s][max_new], their number to new_count[s], the running negative sum to neg_sum_logits[s]. */
+int st_stream_conv_slices(int width, int cin_pitch, int cout, int* kt_per_slice, int* slices);
+size_t st_stream_conv_ws(int n_rows, int width, int cin_pitch, int cout);
+int st_stream_conv_f32(const float* windows, int cap, int cin_pitch, const int32_t* info, const int32_t* rows, int n_rows,
+                       int max_streams, const float* packed, const float* bias, int width, int stride, int cout, int relu,
+                       float* out, int out_cap, int out_pitch, const int32_t* out_info, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int st_stream_feed_f32(const float* features, int channels, const int32_t* table, int n_rows, int max_streams, float* windows,
+                       int cap, int cin_pitch, void* stream);
+int st_stream_advance(const void* layer_table, int n_layers, const int32_t* info, int max_streams, void* stream);
+int st_ctc_greedy_stream(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int max_streams,
+                         int32_t* state, double* score, int32_t* ids, int max_new, int32_t* new_count, float* neg_sum_logits,
+                         void* stream);
+
+/* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
+ * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
+ * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are
+ * transformed in the pairs (2p, 2p + 1) of the whole-utterance kernel, so a frame's log-mel power equals st_melspec_f32's bit for
+ * bit and does not depend on the chunking; an open stream emits whole pairs only.  The host keeps the counters and passes
+ *   table int32: [max_streams][8] {base: absolute sample at window position 0, n: samples received, base after the step, finished,
+ *                                  first row of the stream among this step's frames, new frames, index of the first new frame, reset}
+ *                [max_streams][4] {offset in `samples`, count, window position, -}       (the new samples of each stream)
+ *                [n_pairs][2]     (stream, even frame index)
+ * Causal normalisation (fixed = 0): with h(t) = max(t, warm - 1), or the last frame when the stream ends sooner, ref_t is the largest
+ * mel power over frames 0 ... h(t), x_t = max(dB(S_t) - dB(ref_t), -80), mean_t and std_t the mean and population deviation of all
+ * x_t', t' <= h(t), each as it was computed, and the output (x_t - mean_t) / std_t; sums in double, a frame's values in a fixed
+ * tree, frames one by one.  The first `warm` frames therefore appear together, and an utterance of at most `warm` frames gets the
+ * whole-utterance features.  fixed = 1: x = max(dB(S) - dB(2^ref_log2), -80), output (x - mean) / std, no running update.
+ * A zero deviation is not special-cased (as in st_melspec_f32).  Stream s's frames of this step go to out[s][i][n_mels], i counting
+ * from 0 (out_cap frames per stream; how many is known to the host).  Workspace: st_melspec_stream_ws for max_rows frames per step. */
+size_t st_melspec_stream_state_bytes(int max_streams, int cap_samples, int n_mels, int warm);
+size_t st_melspec_stream_ws(int max_rows, int n_mels);
+int st_melspec_stream_f32(const float* samples, const int32_t* table, int n_pairs, int max_streams, const void* plan, int n_mels,
+                          int hop, int warm, int cap_samples, int fixed, float ref_log2, float mean, float std, void* state,
+                          size_t state_bytes, float* out, int out_cap, int max_rows, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- helpers -------------------------------------------------------------------------- */
 int st_fill_f32(float* dst, float value, size_t n, void* stream);
 /* zero the halo rows of a padded NWC tensor (needed when a buffer is re-described for a new shape) */

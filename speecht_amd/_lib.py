@@ -208,6 +208,18 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p]),
     'st_segment_gather_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     'st_mask_rows': (c_int, [_T3P, c_void_p, c_int, c_void_p]),
+    'st_stream_conv_slices': (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    'st_stream_conv_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'st_stream_conv_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_stream_feed_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'st_stream_advance': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'st_melspec_stream_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'st_melspec_stream_ws': (c_size_t, [c_int, c_int]),
+    'st_melspec_stream_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                      c_float, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_greedy_stream': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_void_p]),
     'st_fill_f32': (c_int, [c_void_p, c_float, c_size_t, c_void_p]),
     'st_zero_halos_f32': (c_int, [_T3P, c_void_p]),
     'st_zero_regions': (c_int, [c_void_p, c_int, c_void_p]),

@@ -124,6 +124,87 @@ __host__ __device__ inline int wave_slots(int max_frames) {
   return ((max_frames + 1) / 2 + 4 * PAIRS_PER_WAVE - 1) / (4 * PAIRS_PER_WAVE) * 4;
 }
 
+// One frame pair of mel_pair_kernel / mel_stream_pair_kernel: window, one 512-point complex FFT of xa + i xb, both power spectra,
+// the sparse mel projection; leaves the piece sums in the wave's FFT buffer (part[slot] = reinterpret_cast<float*>(zb)[slot]).
+// `prefetch` runs once the raw samples are consumed (the caller's loads of the next pair hide behind the FFT).
+template <typename Prefetch>
+__device__ __forceinline__ void mel_pair_transform(const float (&xa)[8], const float (&xb)[8], const float (&win)[8], melfft::cf* zb,
+                                                   float (*pw)[NBINS + PLAN_PIECE - 1], const melfft::cf (*tw1_s)[64],
+                                                   const melfft::cf (*tw2_s)[64], const Plan* __restrict__ plan, int rounds, int lane,
+                                                   Prefetch&& prefetch) {
+  using melfft::cf;
+  float* part = reinterpret_cast<float*>(zb);
+  cf v[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    v[r].x = xa[r] * win[r];
+    v[r].y = xb[r] * win[r];
+  }
+  prefetch();
+  melfft::dft8(v);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) zb[melfft::pad(melfft::out_index(0, lane, r))] = v[r];
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const cf z = zb[melfft::pad(lane + 64 * r)];
+    v[r] = r ? melfft::zmul(z, tw1_s[r][lane]) : z;
+  }
+  wave_lds_sync();
+  melfft::dft8(v);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) zb[melfft::pad(melfft::out_index(1, lane, r))] = v[r];
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const cf z = zb[melfft::pad(lane + 64 * r)];
+    v[r] = r ? melfft::zmul(z, tw2_s[r][lane]) : z;
+  }
+  melfft::dft8(v);                                       // Z[lane + 64 r] = v[r]
+  // Z[512 - k] for k = lane + 64 r: lane (64 - lane) & 63, register 7 - r (lane 0: register 8 - r, own Z[0] for r = 0)
+  const int partner = (64 - lane) & 63;
+  cf q[4];                                               // partner registers 4..7
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    q[r].x = __shfl(v[4 + r].x, partner, 64);
+    q[r].y = __shfl(v[4 + r].y, partner, 64);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    // lanes >= 1 pair register r with partner register 7 - r = q[3 - r]; lane 0 with 8 - r = q[4 - r] (r = 0: itself)
+    cf b = q[3 - r];
+    if (lane == 0) b = r == 0 ? v[0] : q[4 - r];
+    float pa, pb;
+    melfft::pair_power(v[r], b, &pa, &pb);
+    pw[0][lane + 64 * r] = pa;
+    pw[1][lane + 64 * r] = pb;
+  }
+  if (lane == 0) {                                       // k = 256 pairs with itself
+    float pa, pb;
+    melfft::pair_power(v[4], v[4], &pa, &pb);
+    pw[0][256] = pa;
+    pw[1][256] = pb;
+  }
+  wave_lds_sync();
+  for (int round = 0; round < rounds; ++round) {
+    const int slot = round * 64 + lane;
+    const PlanItem it = plan->items[slot];
+    const f32x4* w4 = reinterpret_cast<const f32x4*>(plan->weights[slot]);
+    const f32x4 w0 = w4[0], w1 = w4[1], w2 = w4[2], w3 = w4[3];      // zero beyond the piece (and for idle slots)
+    const float* src = &pw[it.sel][it.k_lo];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      sum = fmaf(w0[i], src[i], sum);
+      sum = fmaf(w1[i], src[4 + i], sum);
+      sum = fmaf(w2[i], src[8 + i], sum);
+      sum = fmaf(w3[i], src[12 + i], sum);
+    }
+    part[slot] = sum;
+  }
+  wave_lds_sync();
+}
+
 __global__ __launch_bounds__(256, 4) void mel_pair_kernel(const float* __restrict__ audio,
                                                           const long* __restrict__ sample_off,
                                                           const Plan* __restrict__ plan, int n_mels, int hop,
@@ -206,75 +287,7 @@ __global__ __launch_bounds__(256, 4) void mel_pair_kernel(const float* __restric
   load_pair(p_begin);
   for (int p = p_begin; p < p_end; ++p) {
     const int ta = 2 * p, tb = ta + 1;
-    cf v[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      v[r].x = xa[r] * win[r];
-      v[r].y = xb[r] * win[r];
-    }
-    if (p + 1 < p_end) load_pair(p + 1);
-    melfft::dft8(v);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) zb[melfft::pad(melfft::out_index(0, lane, r))] = v[r];
-    wave_lds_sync();
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const cf z = zb[melfft::pad(lane + 64 * r)];
-      v[r] = r ? melfft::zmul(z, tw1_s[r][lane]) : z;
-    }
-    wave_lds_sync();
-    melfft::dft8(v);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) zb[melfft::pad(melfft::out_index(1, lane, r))] = v[r];
-    wave_lds_sync();
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const cf z = zb[melfft::pad(lane + 64 * r)];
-      v[r] = r ? melfft::zmul(z, tw2_s[r][lane]) : z;
-    }
-    melfft::dft8(v);                                       // Z[lane + 64 r] = v[r]
-    // Z[512 - k] for k = lane + 64 r: lane (64 - lane) & 63, register 7 - r (lane 0: register 8 - r, own Z[0] for r = 0)
-    const int partner = (64 - lane) & 63;
-    cf q[4];                                               // partner registers 4..7
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      q[r].x = __shfl(v[4 + r].x, partner, 64);
-      q[r].y = __shfl(v[4 + r].y, partner, 64);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      // lanes >= 1 pair register r with partner register 7 - r = q[3 - r]; lane 0 with 8 - r = q[4 - r] (r = 0: itself)
-      cf b = q[3 - r];
-      if (lane == 0) b = r == 0 ? v[0] : q[4 - r];
-      float pa, pb;
-      melfft::pair_power(v[r], b, &pa, &pb);
-      pw[wave][0][lane + 64 * r] = pa;
-      pw[wave][1][lane + 64 * r] = pb;
-    }
-    if (lane == 0) {                                       // k = 256 pairs with itself
-      float pa, pb;
-      melfft::pair_power(v[4], v[4], &pa, &pb);
-      pw[wave][0][256] = pa;
-      pw[wave][1][256] = pb;
-    }
-    wave_lds_sync();
-    for (int round = 0; round < rounds; ++round) {
-      const int slot = round * 64 + lane;
-      const PlanItem it = plan->items[slot];
-      const f32x4* w4 = reinterpret_cast<const f32x4*>(plan->weights[slot]);
-      const f32x4 w0 = w4[0], w1 = w4[1], w2 = w4[2], w3 = w4[3];      // zero beyond the piece (and for idle slots)
-      const float* src = &pw[wave][it.sel][it.k_lo];
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        sum = fmaf(w0[i], src[i], sum);
-        sum = fmaf(w1[i], src[4 + i], sum);
-        sum = fmaf(w2[i], src[8 + i], sum);
-        sum = fmaf(w3[i], src[12 + i], sum);
-      }
-      part[slot] = sum;
-    }
-    wave_lds_sync();
+    mel_pair_transform(xa, xb, win, zb, pw[wave], tw1_s, tw2_s, plan, rounds, lane, [&]() { if (p + 1 < p_end) load_pair(p + 1); });
     // both mel rows are adjacent in memory (frames ta and ta + 1 of the same utterance); a filter's pieces are
     // summed in plan order (deterministic); stored as log2(max(amin, power)): the dB chain downstream is affine in it
     float* dst = logpow + (frame_off[u] + ta) * (long)n_mels;
@@ -592,6 +605,177 @@ __global__ __launch_bounds__(256) void mfcc_finish_kernel(const float* __restric
   }
 }
 
+// ---- streaming front end (st_melspec_stream_f32): one step for all streams ---------------------------------------------------
+// Every stream keeps a linear window of recent samples, win[s][cap]; position 0 holds absolute sample `base`.  As for the
+// convolution windows (conv_stream.hip) the counters are functions of the number of samples fed, so the host keeps them and
+// passes one table per step: minfo[s] = {base, n: samples received, base after the step, finished, first row of the stream in
+// this step's log-power rows, new frames, absolute index of the first new frame, reset}.
+// Frames are ALWAYS transformed in the pairs (2p, 2p + 1) the whole-utterance kernel uses -- a frame's log power then does not
+// depend on the chunking, and equals mel_pair_kernel's bit for bit; an open stream emits whole pairs only, `finish` the odd
+// last frame with an empty partner.
+constexpr int MS_INFO = 8;
+
+__global__ __launch_bounds__(64) void mel_stream_feed_kernel(const float* __restrict__ samples, const int* __restrict__ feed,
+                                                             float* __restrict__ win, int cap) {
+  const int s = blockIdx.x;
+  const int src = feed[4 * s], count = feed[4 * s + 1], at = feed[4 * s + 2];
+  if (count <= 0 || at < 0 || at + count > cap) return;
+  for (int i = threadIdx.x; i < count; i += 64) win[(long)s * cap + at + i] = samples[src + i];
+}
+
+__global__ __launch_bounds__(256, 4) void mel_stream_pair_kernel(const float* __restrict__ win, int cap, const int* __restrict__ minfo,
+                                                                 const int* __restrict__ pairs, int n_pairs, int max_streams,
+                                                                 const Plan* __restrict__ plan, int n_mels, int hop,
+                                                                 float* __restrict__ logpow, int max_rows) {
+  using melfft::cf;
+  __shared__ cf zbuf[4][melfft::LDS_COMPLEX];
+  __shared__ float pw[4][2][NBINS + PLAN_PIECE - 1];
+  __shared__ cf tw1_s[8][64], tw2_s[8][64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int i = tid; i < 8 * 64; i += 256) {
+    (&tw1_s[0][0])[i] = (&plan->tw1[0][0])[i];
+    (&tw2_s[0][0])[i] = (&plan->tw2[0][0])[i];
+  }
+  __syncthreads();                                         // the only workgroup barrier
+  const int p = blockIdx.x * 4 + wave;
+  if (p >= n_pairs) return;
+  const int s = pairs[2 * p], ta = pairs[2 * p + 1];
+  if (s < 0 || s >= max_streams) return;
+  const int* in = minfo + s * MS_INFO;
+  const int base = in[0], n = in[1], finished = in[3], row0 = in[4], new_frames = in[5], first = in[6];
+  const int row = row0 + (ta - first);
+  const bool has_b = ta + 1 < first + new_frames;
+  if (ta < first || row < 0 || row + (has_b ? 2 : 1) > max_rows) return;
+  const float* y = win + (long)s * cap;
+  auto sample = [&](int j) {                               // absolute sample j, reflected at the start and (once known) the end
+    if (j < 0) j = -j;
+    if (finished && j >= n) j = 2 * (n - 1) - j;
+    const int at = j - base;
+    return (j >= 0 && j < n && at >= 0 && at < cap) ? y[at] : 0.f;
+  };
+  if (lane < 2 * (PLAN_PIECE - 1)) pw[wave][lane / (PLAN_PIECE - 1)][NBINS + lane % (PLAN_PIECE - 1)] = 0.f;
+  float win_r[8], xa[8], xb[8];
+  const int j0 = ta * hop - NFFT / 2;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int k = lane + 64 * r;
+    win_r[r] = plan->win[k];
+    xa[r] = sample(j0 + k);
+    xb[r] = has_b ? sample(j0 + hop + k) : 0.f;
+  }
+  cf* zb = zbuf[wave];
+  mel_pair_transform(xa, xb, win_r, zb, pw[wave], tw1_s, tw2_s, plan, plan->rounds, lane, []() {});
+  const float* part = reinterpret_cast<const float*>(zb);
+  float* dst = logpow + (long)row * n_mels;
+  const int valid = (has_b ? 2 : 1) * n_mels;
+  for (int i = lane; i < 2 * n_mels; i += 64) {
+    const int oi = plan->oinfo[i];
+    const int firstp = oi >> 8, count = oi & 255;
+    float a = part[firstp];                                // the pieces of a filter in plan order, as mel_pair_kernel sums them
+    if (count > 1) a += part[firstp + 1];
+    for (int c = 2; c < count; ++c) a += part[firstp + c];
+    if (i < valid) dst[i] = fmaxf(__log2f(a), LOG2_AMIN);
+  }
+}
+
+// Causal normalisation, one wave per stream, the new frames in order.  stats[s] = {log2 of the reference power, number of values,
+// their sum, their sum of squares} (double) persist; the first `warm` frames wait in hold[s] until frame warm - 1 (or the end)
+// has come: they share the reference and the statistics of that moment.  Frame t >= warm: ref_t = max(ref_{t-1}, max S_t),
+// x_t = max(dB(S_t) - dB(ref_t), -80), the running sums take x_t (a frame's values summed in a fixed tree, frames one by one),
+// out = (x_t - mean_t) / std_t.  fixed: x = max(dB(S) - dB(ref), -80), out = (x - mean) / std with the given constants.
+// Afterwards the wave moves the stream's retained samples to the front of its window.
+__global__ __launch_bounds__(64) void mel_stream_norm_kernel(const float* __restrict__ logpow, const int* __restrict__ minfo, int n_mels,
+                                                             int warm, float* __restrict__ hold, double* __restrict__ stats,
+                                                             int fixed, float ref_l2, float mean_f, float std_f,
+                                                             float* __restrict__ out, int out_cap, float* __restrict__ win, int cap, int max_rows) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int* in = minfo + s * MS_INFO;
+  const int base = in[0], n = in[1], new_base = in[2], finished = in[3], row0 = in[4], f0 = in[6], reset = in[7];
+  const int m = (row0 >= 0 && in[5] >= 0 && row0 + in[5] <= max_rows && f0 >= 0) ? in[5] : 0;   // rows outside the step's buffer: none
+  double* stt = stats + 4 * (long)s;
+  float l2ref = reset ? LOG2_AMIN : (float)stt[0];
+  double cnt = reset ? 0.0 : stt[1], s1 = reset ? 0.0 : stt[2], s2 = reset ? 0.0 : stt[3];
+  const float* rows = logpow + (long)row0 * n_mels;
+  float* o = out + (long)s * out_cap * n_mels;
+  float* h = hold + (long)s * warm * n_mels;
+  const int total = f0 + m;
+  auto frame_src = [&](int t) { return t < f0 ? h + (long)t * n_mels : rows + (long)(t - f0) * n_mels; };   // t < f0 only while f0 < warm
+  auto add_frame = [&](const float* src, float ref) {        // the running sums take the frame's x values
+    double a = 0.0, b = 0.0;
+    for (int c = lane; c < n_mels; c += 64) {
+      const double d = (double)to_db(src[c], ref);
+      a += d;
+      b += d * d;
+    }
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) {
+      a += __shfl_xor(a, k, 64);
+      b += __shfl_xor(b, k, 64);
+    }
+    s1 += a;
+    s2 += b;
+    cnt += (double)n_mels;
+  };
+  auto write_frame = [&](const float* src, float ref, float mean, float inv_std, int at) {
+    if (at < 0 || at >= out_cap) return;
+    for (int c = lane; c < n_mels; c += 64) o[(long)at * n_mels + c] = (to_db(src[c], ref) - mean) * inv_std;
+  };
+  auto frame_max = [&](const float* src) {
+    float v = LOG2_AMIN;
+    for (int c = lane; c < n_mels; c += 64) v = fmaxf(v, src[c]);
+    return st::wave_max(v);
+  };
+  auto moments = [&](float* mean, float* inv_std) {          // as mel_finish_kernel: population deviation, a zero one not special-cased
+    const double mu = s1 / cnt;
+    *mean = (float)mu;
+    *inv_std = (float)(1.0 / sqrt(fmax(s2 / cnt - mu * mu, 0.0)));
+  };
+  int written = 0;
+  if (fixed) {
+    const float inv = (float)(1.0 / (double)std_f);
+    for (int t = 0; t < m; ++t) write_frame(rows + (long)t * n_mels, ref_l2, mean_f, inv, written++);
+  } else if (m > 0 || finished) {
+    int t = f0;
+    if (f0 < warm) {
+      if (total < warm && !finished) {                       // still waiting: keep the new frames
+        for (int i = lane; i < m * n_mels; i += 64) h[(long)f0 * n_mels + i] = rows[i];
+        t = total;
+      } else {                                               // frames 0 .. block - 1 share reference and statistics
+        const int block = min(total, warm);
+        for (int u = 0; u < block; ++u) l2ref = fmaxf(l2ref, frame_max(frame_src(u)));
+        for (int u = 0; u < block; ++u) add_frame(frame_src(u), l2ref);
+        float mean = 0.f, inv = 0.f;
+        if (block > 0) moments(&mean, &inv);
+        for (int u = 0; u < block; ++u) write_frame(frame_src(u), l2ref, mean, inv, written++);
+        t = block;
+      }
+    }
+    for (; t < total; ++t) {
+      const float* src = frame_src(t);
+      l2ref = fmaxf(l2ref, frame_max(src));
+      add_frame(src, l2ref);
+      float mean, inv;
+      moments(&mean, &inv);
+      write_frame(src, l2ref, mean, inv, written++);
+    }
+  }
+  if (lane == 0) { stt[0] = (double)l2ref; stt[1] = cnt; stt[2] = s1; stt[3] = s2; }
+  // the sample tail to the front: ascending chunks of 64, each read whole before it is written (the destination lies in front)
+  const int shift = new_base - base, keep = n - new_base;
+  if (shift > 0 && keep > 0 && shift + keep <= cap) {
+    float* w = win + (long)s * cap;
+    for (int q0 = 0; q0 < keep; q0 += 64) {
+      const int q = q0 + lane;
+      const float v = q < keep ? w[q + shift] : 0.f;
+      wave_lds_sync();
+      if (q < keep) w[q] = v;
+    }
+  }
+}
+
+size_t ms_win_bytes(int max_streams, int cap) { return st::round_up((size_t)max_streams * cap * sizeof(float), 256); }
+size_t ms_hold_bytes(int max_streams, int warm, int n_mels) { return st::round_up((size_t)max_streams * std::max(warm, 1) * n_mels * sizeof(float), 256); }
+
 size_t pow_bytes(int64_t total_frames, int n_mels) { return st::round_up((size_t)total_frames * n_mels * sizeof(float), 256); }
 size_t slot_bytes(int n_utts, int64_t max_samples, int hop) {
   return st::round_up((size_t)n_utts * wave_slots((int)(1 + max_samples / hop)) * sizeof(float), 256);
@@ -676,6 +860,48 @@ int st_melspec_f32(const float* audio, const int64_t* sample_offsets, int n_utts
   if (int e = st_melspec_plan_f32(mel_basis, n_mels, n_fft, plan, st_melspec_plan_bytes(), stream)) return e;
   return st_melspec_planned_f32(audio, sample_offsets, n_utts, max_samples, plan, n_mels, n_fft, hop, frame_offsets,
                                 total_frames, out, workspace, front, stream);
+}
+
+size_t st_melspec_stream_state_bytes(int max_streams, int cap_samples, int n_mels, int warm) {
+  if (max_streams <= 0 || cap_samples <= 0 || n_mels <= 0 || warm < 0) return 0;
+  return ms_win_bytes(max_streams, cap_samples) + ms_hold_bytes(max_streams, warm, n_mels) + (size_t)max_streams * 4 * sizeof(double);
+}
+
+size_t st_melspec_stream_ws(int max_rows, int n_mels) {
+  return max_rows > 0 && n_mels > 0 ? pow_bytes(max_rows, n_mels) : 0;
+}
+
+int st_melspec_stream_f32(const float* samples, const int32_t* table, int n_pairs, int max_streams, const void* plan, int n_mels,
+                          int hop, int warm, int cap_samples, int fixed, float ref_log2, float mean, float std, void* state,
+                          size_t state_bytes, float* out, int out_cap, int max_rows, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  ST_REQUIRE(samples && table && plan && state && out && workspace, "melspec stream: null argument");
+  ST_REQUIRE(max_streams > 0 && n_mels > 0 && n_mels <= 256 && hop > 0 && warm >= 0 && cap_samples >= NFFT + hop && out_cap > 0 &&
+                 max_rows > 0 && n_pairs >= 0 && 2 * n_pairs <= max_rows + max_streams,
+             "melspec stream: bad shape");
+  ST_REQUIRE(state_bytes >= st_melspec_stream_state_bytes(max_streams, cap_samples, n_mels, warm), "melspec stream: state buffer too small");
+  if (workspace_bytes < st_melspec_stream_ws(max_rows, n_mels)) {
+    st::set_error("melspec stream: workspace too small (%zu bytes, %zu needed)", workspace_bytes, st_melspec_stream_ws(max_rows, n_mels));
+    return ST_EWORKSPACE;
+  }
+  hipStream_t s = st::as_stream(stream);
+  char* w = reinterpret_cast<char*>(state);
+  float* win = reinterpret_cast<float*>(w);
+  w += ms_win_bytes(max_streams, cap_samples);
+  float* hold = reinterpret_cast<float*>(w);
+  w += ms_hold_bytes(max_streams, warm, n_mels);
+  double* stats = reinterpret_cast<double*>(w);
+  float* logpow = reinterpret_cast<float*>(workspace);
+  const int* minfo = table;
+  const int* feed = table + max_streams * MS_INFO;
+  const int* pairs = feed + max_streams * 4;
+  hipLaunchKernelGGL(mel_stream_feed_kernel, dim3(max_streams), dim3(64), 0, s, samples, feed, win, cap_samples);
+  if (n_pairs > 0)
+    hipLaunchKernelGGL(mel_stream_pair_kernel, dim3(st::ceil_div(n_pairs, 4)), dim3(256), 0, s, win, cap_samples, minfo, pairs, n_pairs,
+                       max_streams, reinterpret_cast<const Plan*>(plan), n_mels, hop, logpow, max_rows);
+  hipLaunchKernelGGL(mel_stream_norm_kernel, dim3(max_streams), dim3(64), 0, s, logpow, minfo, n_mels, warm, hold, stats, fixed, ref_log2,
+                     mean, std, out, out_cap, win, cap_samples, max_rows);
+  return st::check_launch("melspec_stream");
 }
 
 size_t st_mfcc_ws(int n_utts, int64_t total_frames, int n_mels, int n_mfcc) {

@@ -1,0 +1,621 @@
+"""Streaming recognition: a stateful, chunked forward pass with live partial transcripts (csrc/conv_stream.hip).
+
+Every layer's SAME padding has a left part that does not depend on the utterance's length, so an output frame is final as soon
+as its right context has arrived: the first logits row after 99 input frames (0.99 s at the 10 ms hop), a steady lag of 49
+output frames.  Each layer keeps a window of recent input frames per stream; a step runs the eleven products over the frames
+that have become ready in all named streams at once, moves the windows on and decodes greedily across the step boundary.
+
+The index arithmetic below is the Python twin of csrc/stream_map.h: pure functions of the layer list ``(width, stride)`` and a
+stream's counters.  The counters depend only on how many frames were fed, so the host keeps them and sizes every step
+(`plan`) before anything is launched; the device gets them as one small table per step.  Only the decoder's state lives on
+the device.
+
+A stream's logits are bit-identical however its audio was cut into chunks and whatever the other streams were doing: the
+product kernel cuts every layer's reduction into slices that depend on the layer's shape only and sums them in slice order.
+The arithmetic is fp32 (the engine's packed fp32 masters) whatever mode the engine trains in.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call
+
+
+class StreamError(ValueError):
+  """A request the recogniser refuses; nothing was launched and no stream's state has changed."""
+
+
+# ---- index arithmetic (csrc/stream_map.h) ---------------------------------------------------------------------------------
+
+def pad_left(width, stride):
+  return (width - stride) // 2 if width > stride else 0
+
+
+def pad_left_fixed(width, stride):
+  """True when SAME padding's left part is the same for every utterance length."""
+  return stride >= 1 and width >= stride and (width - stride) // 2 == (width - 1) // 2
+
+
+def ready_count(n, width, stride, finished):
+  """Output frames that are final after ``n`` input frames."""
+  if n <= 0:
+    return 0
+  if finished:
+    return -(-n // stride)
+  last = n - width + pad_left(width, stride)
+  return 0 if last < 0 else last // stride + 1
+
+
+def emit_count(n, e, width, stride, finished):
+  return max(ready_count(n, width, stride, finished) - e, 0)
+
+
+def retain_from(e, width, stride):
+  """First absolute input frame still needed once ``e`` outputs are out (negative indices are padding, never stored)."""
+  return max(e * stride - pad_left(width, stride), 0)
+
+
+def decode_limit(total_input_frames):
+  """Logits rows greedy decoding takes: the engine decodes ``seq_len // 2`` rows, so an odd length's last row is not decoded."""
+  return total_input_frames // 2
+
+
+def plan(layers, n, e, new, finished):
+  """One step of one stream.  ``layers``: [(width, stride), ...]; ``n`` / ``e``: input frames received / output frames emitted
+  per layer before the step; ``new`` input frames arrive at the first layer; ``finished``: flush with the right padding.
+  Returns ``(steps, n_after, e_after)``, ``steps[l] = (first, count, base, n, new_base)``: layer l emits output frames
+  ``first ... first + count - 1``, its window starts at absolute input frame ``base`` during the step and holds frames up to
+  ``n``; afterwards it starts at ``new_base``."""
+  steps, n_after, e_after = [], [], []
+  for (width, stride), n_l, e_l in zip(layers, n, e):
+    n_l += new
+    count = emit_count(n_l, e_l, width, stride, finished)
+    steps.append((e_l, count, retain_from(e_l, width, stride), n_l, retain_from(e_l + count, width, stride)))
+    n_after.append(n_l)
+    e_after.append(e_l + count)
+    new = count
+  return steps, n_after, e_after
+
+
+def plan_many(layers, n, e, new, finished):
+  """`plan` for k streams at once: ``n`` / ``e`` int arrays [k, layers], ``new`` [k], ``finished`` bool [k] -> int arrays [k, layers]
+  ``(first, count, base, n_after, new_base)``.  The session sizes a step with this one; the tests hold it to `plan`."""
+  n, e = np.asarray(n, dtype=np.int64), np.asarray(e, dtype=np.int64)
+  add, fin = np.asarray(new, dtype=np.int64), np.asarray(finished, dtype=bool)
+  first, count, base, n_after, new_base = (np.zeros_like(n) for _ in range(5))
+  for l, (width, stride) in enumerate(layers):
+    pl = pad_left(width, stride)
+    n_l = n[:, l] + add
+    last = n_l - width + pl
+    ready = np.where(fin, -(-n_l // stride), np.where(last < 0, 0, last // stride + 1))
+    ready = np.where(n_l <= 0, 0, ready)
+    c = np.maximum(ready - e[:, l], 0)
+    first[:, l], count[:, l], n_after[:, l] = e[:, l], c, n_l
+    base[:, l] = np.maximum(e[:, l] * stride - pl, 0)
+    new_base[:, l] = np.maximum((e[:, l] + c) * stride - pl, 0)
+    add = c
+  return first, count, base, n_after, new_base
+
+
+def max_new_frames(layers, max_chunk):
+  """Upper bound of the frames each layer can receive in one step (``[l]``) and of the rows the last layer can emit (``[-1]``):
+  a layer that receives m frames emits at most ceil((m + width - pad_left + stride - 2) / stride), the flush at `finish` included."""
+  out = [int(max_chunk)]
+  for width, stride in layers:
+    out.append(max(-(-(out[-1] + width - pad_left(width, stride) + stride - 2) // stride), 1))
+  return out
+
+
+def first_row_after(layers):
+  """Input frames after which the first logits row is final, and the steady lag in output frames."""
+  n = 0
+  while True:
+    n += 1
+    r = n
+    for width, stride in layers:
+      r = ready_count(r, width, stride, False)
+    if r > 0:
+      break
+  total = 1
+  for _, stride in layers:
+    total *= stride
+  return n, -(-n // total) - 1
+
+
+# ---- the session ----------------------------------------------------------------------------------------------------------
+
+class StepResult:
+  """What one `step` / `finish` produced: ``ids[slot]`` new label ids, ``logits[slot]`` new rows [r, C] (on request),
+  ``score[slot]`` the running negative sum of the chosen logits."""
+
+  def __init__(self):
+    self.ids, self.logits, self.score = {}, {}, {}
+
+
+class StreamingRecognizer:
+  """Owns the per-layer windows, the workspace and the decoder state of up to ``max_streams`` streams on the engine's device.
+
+  ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
+  ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
+
+  def __init__(self, engine, max_streams, max_chunk_frames=64):
+    if max_streams < 1 or max_chunk_frames < 1:
+      raise StreamError('max_streams and max_chunk_frames must be positive')
+    self.engine, self.device = engine, engine.device
+    self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
+    self.layers = engine.layers
+    self.geo = [(l.width, l.stride) for l in self.layers]
+    for w, s in self.geo:
+      if not pad_left_fixed(w, s):
+        raise StreamError('a layer of width {} and stride {} has no length-independent left padding'.format(w, s))
+    self.num_classes = engine.num_classes
+    L, S = len(self.layers), self.max_streams
+    self.in_max = max_new_frames(self.geo, self.max_chunk)
+    self.cap = [l.width + self.in_max[i] for i, l in enumerate(self.layers)]            # retained (< width) + new
+    self.max_rows = [S * self.in_max[i + 1] for i in range(L)]
+    self.max_new = self.in_max[L]
+    dev = self.device
+    with torch.cuda.stream(engine.stream):
+      self.windows = [torch.zeros(S * self.cap[i] * l.cin_pitch, dtype=torch.float32, device=dev) for i, l in enumerate(self.layers)]
+      self.logits_pitch = self.layers[-1].cout_pitch
+      self.logits = torch.zeros(self.max_rows[-1] * self.logits_pitch, dtype=torch.float32, device=dev)
+      lib = _lib.load()
+      self.ws_bytes = max(int(lib.st_stream_conv_ws(self.max_rows[i], l.width, l.cin_pitch, l.cout)) for i, l in enumerate(self.layers))
+      self.workspace = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
+      self.dec_state = torch.zeros(S * 4, dtype=torch.int32, device=dev)
+      self.dec_score = torch.zeros(S, dtype=torch.float64, device=dev)
+      # the decoder's outputs in one buffer, so that a step's results come back with one copy: [ids | counts | scores]
+      self.dec_out = torch.zeros(S * self.max_new + 2 * S, dtype=torch.int32, device=dev)
+      self.ids = self.dec_out[:S * self.max_new]
+      self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
+      self.neg_sum = self.dec_out[S * self.max_new + S:].view(torch.float32)
+      table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
+      for i, l in enumerate(self.layers):
+        table[2 * i] = self.windows[i].data_ptr()
+        table[2 * i + 1] = self.cap[i] | (l.cin_pitch << 32)
+      self.layer_table = torch.from_numpy(table).to(dev)
+    # the host's counters: per stream and layer the frames received and emitted, per stream the input frames in all
+    self._open, self._fresh, self._finished = (np.zeros(S, dtype=bool) for _ in range(3))
+    self._n, self._e = np.zeros((S, L), dtype=np.int64), np.zeros((S, L), dtype=np.int64)
+    self._total = np.zeros(S, dtype=np.int64)
+    self._info = np.zeros((L, S, 4), dtype=np.int32)             # {base, n, base, 0} of every stream between steps
+    self.launches = 0            # kernels enqueued by the last pass (products count two: slices + epilogue)
+
+  # -- slots --
+
+  def open(self):
+    free = np.flatnonzero(~self._open)
+    if not len(free):
+      raise StreamError('all {} streams are open'.format(self.max_streams))
+    i = int(free[0])
+    self._open[i], self._fresh[i], self._finished[i] = True, True, False     # the first step resets the slot's decoder state;
+    self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
+    self._info[:, i] = 0                                                       # [0, n) are never read
+    return i
+
+  def close(self, slot):
+    self._slot(slot, allow_finished=True)
+    self._open[slot] = False
+    self._info[:, slot] = 0
+
+  def _slot(self, slot, allow_finished=False):
+    if not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.max_streams or not self._open[slot]:
+      raise StreamError('stream {} is not open'.format(slot))
+    if self._finished[slot] and not allow_finished:
+      raise StreamError('stream {} has been finished: close it and open a new one'.format(slot))
+
+  # -- steps --
+
+  def step(self, feeds, return_logits=False, fetch=True):
+    """``feeds``: {slot: float array [t, C]} (t may be 0).  A feed longer than ``max_chunk_frames`` is split into several passes.
+    ``fetch=False`` only enqueues (no host wait at all) and returns None: the new ids of such a step are dropped."""
+    return self._run(feeds, (), return_logits, fetch)
+
+  def finish(self, slot, return_logits=False):
+    """Flush ``slot`` with the right padding; returns the rest.  The slot stays allocated until `close`."""
+    return self._run({}, (slot,), return_logits, True)
+
+  def finish_many(self, slots, return_logits=False):
+    return self._run({}, tuple(slots), return_logits, True)
+
+  def _run(self, feeds, finishing, return_logits, fetch):
+    c_in = self.layers[0].cin
+    arrays = {}
+    for slot, x in feeds.items():
+      self._slot(slot)
+      x = np.asarray(x, dtype=np.float32) if not isinstance(x, torch.Tensor) else x.detach().to('cpu', torch.float32).numpy()
+      if x.ndim != 2 or x.shape[1] != c_in:
+        raise StreamError('stream {}: features must be [frames, {}], got {}'.format(slot, c_in, tuple(x.shape)))
+      arrays[int(slot)] = np.ascontiguousarray(x)
+    for slot in finishing:
+      self._slot(slot)
+    result = StepResult()
+    for slot in list(arrays) + [int(s) for s in finishing]:
+      result.ids[slot], result.score[slot] = [], 0.0
+      if return_logits:
+        result.logits[slot] = []
+    longest = max([a.shape[0] for a in arrays.values()] + [0])
+    passes = max(-(-longest // self.max_chunk), 1)
+    for p in range(passes):
+      part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
+      self._pass(part, finishing if p == passes - 1 else (), result, return_logits, fetch)
+    if return_logits:
+      for slot, parts in result.logits.items():
+        rows = [t.cpu().numpy() for t in parts]
+        result.logits[slot] = np.concatenate(rows) if rows else np.zeros((0, self.num_classes), np.float32)
+    return result if fetch else None
+
+  def _pass(self, part, finishing, result, return_logits, fetch):
+    eng, L, S = self.engine, len(self.layers), self.max_streams
+    named = np.asarray(sorted(set(part) | set(int(s) for s in finishing)), dtype=np.int64)
+    # 1. size the step on the host (all named streams at once)
+    new = np.asarray([part[s].shape[0] if s in part else 0 for s in named], dtype=np.int64)
+    fin = np.isin(named, [int(s) for s in finishing])
+    first, count, base, n_after, new_base = plan_many(self.geo, self._n[named], self._e[named], new, fin)
+    over = (n_after - base > np.asarray(self.cap)) | (count > np.asarray(self.in_max[1:]))
+    if over.any():
+      k, l = np.argwhere(over)[0]
+      raise StreamError('stream {}: layer {} would overrun its window ({} frames, capacity {})'.format(
+          int(named[k]), int(l), int(n_after[k, l] - base[k, l]), self.cap[l]))
+    info = self._info.copy()                                     # streams that sit this step out keep their windows
+    info[:, named, 0], info[:, named, 1], info[:, named, 2] = base.T, n_after.T, new_base.T
+
+    def table_rows(counts, firsts):                              # (stream, first + j) for j < count, stream by stream
+      total = int(counts.sum())
+      starts = np.cumsum(counts) - counts
+      return np.stack([np.repeat(named, counts), np.repeat(firsts - starts, counts) + np.arange(total)], axis=1).astype(np.int32), starts
+
+    rows = [table_rows(count[:, l], first[:, l])[0] for l in range(L)]
+    row0 = np.cumsum(count[:, -1]) - count[:, -1]
+    dec = np.zeros((S, 4), dtype=np.int32)
+    dec[:, 2] = -1
+    dec[named, 0], dec[named, 1], dec[named, 3] = row0, count[:, -1], self._fresh[named]
+    dec[named, 2] = np.where(fin, (self._total[named] + new) // 2, -1)
+    feed_rows, _ = table_rows(new, self._n[named, 0] - base[:, 0])
+    # 2. one table, one upload
+    parts = [info.reshape(-1)] + [r.reshape(-1) for r in rows] + [dec.reshape(-1), feed_rows.reshape(-1)]
+    offs = np.cumsum([0] + [p.size for p in parts])
+    table = self._upload(np.concatenate(parts), torch.int32)
+    tptr = lambda i: ctypes.c_void_p(table.data_ptr() + 4 * int(offs[i]))
+    info_ptr = lambda l: ctypes.c_void_p(table.data_ptr() + 4 * l * S * 4)
+    ptr, sp = eng._ptr, eng.stream_ptr
+    self.launches = 0
+    if len(feed_rows):
+      feat = self._upload(np.concatenate([part[s] for s in named.tolist() if s in part and part[s].shape[0]]), torch.float32)
+      call('st_stream_feed_f32', ptr(feat), self.layers[0].cin, tptr(L + 2), len(feed_rows), S, ptr(self.windows[0]), self.cap[0],
+           self.layers[0].cin_pitch, sp)
+      self.launches += 1
+    # 3. eleven products with their epilogues, one advance, one decode
+    for l, spec in enumerate(self.layers):
+      if not len(rows[l]):
+        continue
+      pf, pb = eng._slice(eng.params, l)
+      lastl = l == L - 1
+      out = self.logits if lastl else self.windows[l + 1]
+      call('st_stream_conv_f32', ptr(self.windows[l]), self.cap[l], spec.cin_pitch, info_ptr(l), tptr(1 + l), len(rows[l]), S, ptr(pf),
+           ptr(pb), spec.width, spec.stride, spec.cout, int(spec.relu), ptr(out), self.max_rows[-1] if lastl else self.cap[l + 1],
+           spec.cout_pitch, None if lastl else info_ptr(l + 1), ptr(self.workspace), self.ws_bytes, sp)
+      self.launches += 2
+    call('st_stream_advance', ptr(self.layer_table), L, info_ptr(0), S, sp)
+    call('st_ctc_greedy_stream', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), S, ptr(self.dec_state),
+         ptr(self.dec_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum), sp)
+    self.launches += 2
+    # 4. the host's counters follow; nothing above waited
+    self._n[named], self._e[named] = n_after, first + count
+    self._total[named] += new
+    self._fresh[named], self._finished[named] = False, fin
+    self._info[:, named, 0], self._info[:, named, 1], self._info[:, named, 2] = new_base.T, n_after.T, new_base.T
+    if not fetch:
+      return
+    with torch.cuda.stream(eng.stream):
+      if return_logits:
+        view = self.logits.view(-1, self.logits_pitch)
+        for k, s in enumerate(named.tolist()):
+          if count[k, -1]:
+            result.logits[s].append(view[int(row0[k]):int(row0[k] + count[k, -1]), :self.num_classes].clone())
+      words = self.dec_out.cpu().numpy()                         # the step's one wait
+    ids, counts = words[:S * self.max_new].reshape(S, self.max_new), words[S * self.max_new:S * self.max_new + S]
+    score = words[S * self.max_new + S:].view(np.float32)
+    for s in named.tolist():
+      result.ids[s] += ids[s, :counts[s]].tolist()
+      result.score[s] = float(score[s])
+
+  def _upload(self, array, dtype):
+    """Host array -> device as a stream operation (pinned staging from torch's caching host allocator: no wait for the stream's
+    earlier kernels, and the block is not reused before the copy has run)."""
+    host = torch.from_numpy(array).pin_memory()
+    with torch.cuda.stream(self.engine.stream):
+      return host.to(self.device, non_blocking=True)
+
+
+# ---- the mel front end -------------------------------------------------------------------------------------------------------
+
+N_FFT = 512
+
+
+def frames_ready(n, hop, finished):
+  """Frames whose log-mel power can be computed after ``n`` samples.  Frame t needs samples t * hop - 256 ... t * hop + 255 (and
+  frame 0, reflected at the start, sample 256).  An open stream counts whole pairs (2p, 2p + 1) only: the kernels transform two
+  frames with one FFT, and a fixed pairing keeps a frame's value independent of the chunking (at most one hop of delay)."""
+  if finished:
+    return 1 + n // hop
+  if n <= N_FFT // 2:
+    return 0
+  ready = (n - N_FFT // 2) // hop + 1
+  return ready - ready % 2
+
+
+def sample_base(f, hop):
+  """First absolute sample still needed once ``f`` frames are out."""
+  return max(f * hop - N_FFT // 2, 0)
+
+
+class _FeatSlot:
+  __slots__ = ('n', 'f', 'fresh', 'finished')
+
+  def __init__(self):
+    self.n, self.f, self.fresh, self.finished = 0, 0, True, False
+
+
+class StreamingFeatures:
+  """Log-mel features of up to ``max_streams`` sample streams, computed as the samples arrive (st_melspec_stream_f32).
+
+  ``stats=None``: causal normalisation -- the first ``warm`` frames appear together with the reference and the statistics of frame
+  ``warm - 1`` (the network waits 99 frames for its first output anyway), every later frame with the running ones; an utterance of at
+  most ``warm`` frames gets the whole-utterance features.  ``stats=(ref, mean, std)`` (largest mel power, mean and deviation of the dB
+  values): fixed statistics, every utterance gets the features those constants give.  Mel features only."""
+
+  def __init__(self, samplerate, n_mels, max_streams=1, max_chunk_samples=16000, warm=100, stats=None, hop_length=160, device='cuda:0'):
+    from .preprocessing import mel_filterbank
+    if max_streams < 1 or max_chunk_samples < 1 or warm < 1 or not 0 < n_mels <= 256:
+      raise StreamError('bad StreamingFeatures sizes')
+    self.device = torch.device(device)
+    self.n_mels, self.hop, self.warm, self.max_streams = int(n_mels), int(hop_length), int(warm), int(max_streams)
+    self.max_chunk = int(max_chunk_samples)
+    self.cap = N_FFT + 2 * self.hop + self.max_chunk + 16
+    self.max_new = self.max_chunk // self.hop + 4
+    self.max_rows = self.max_streams * self.max_new
+    self.out_cap = self.warm + self.max_new
+    self.stats = None if stats is None else (float(np.log2(max(stats[0], 1e-10))), float(stats[1]), float(stats[2]))
+    lib = _lib.load()
+    dev = self.device
+    basis = torch.as_tensor(mel_filterbank(float(samplerate), N_FFT, self.n_mels).astype(np.float32)).contiguous().to(dev)
+    self.plan = torch.zeros(int(lib.st_melspec_plan_bytes()) // 4, dtype=torch.float32, device=dev)
+    self._stream = torch.cuda.current_stream(dev)
+    call('st_melspec_plan_f32', self._p(basis), self.n_mels, N_FFT, self._p(self.plan), self.plan.numel() * 4, self._sp)
+    self.state_bytes = int(lib.st_melspec_stream_state_bytes(self.max_streams, self.cap, self.n_mels, self.warm))
+    self.state = torch.zeros(self.state_bytes // 4 + 2, dtype=torch.float32, device=dev)
+    self.ws_bytes = int(lib.st_melspec_stream_ws(self.max_rows, self.n_mels))
+    self.workspace = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
+    self.out = torch.zeros(self.max_streams * self.out_cap * self.n_mels, dtype=torch.float32, device=dev)
+    self.slots = [None] * self.max_streams
+    torch.cuda.current_stream(dev).synchronize()                 # (the basis may be freed once the plan is made)
+
+  @staticmethod
+  def _p(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+  @property
+  def _sp(self):
+    return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+  def open(self):
+    for i, s in enumerate(self.slots):
+      if s is None:
+        self.slots[i] = _FeatSlot()
+        return i
+    raise StreamError('all {} streams are open'.format(self.max_streams))
+
+  def close(self, slot):
+    self._slot(slot, True)
+    self.slots[slot] = None
+
+  def _slot(self, slot, allow_finished=False):
+    if not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.max_streams or self.slots[slot] is None:
+      raise StreamError('stream {} is not open'.format(slot))
+    if self.slots[slot].finished and not allow_finished:
+      raise StreamError('stream {} has been finished: close it and open a new one'.format(slot))
+    return self.slots[slot]
+
+  def step(self, feeds):
+    """``feeds``: {slot: float samples [n]} -> {slot: new features [t, n_mels]} (float32 numpy; t may be 0)."""
+    return self._run(feeds, ())
+
+  def finish(self, slot):
+    """Flush: the frames up to 1 + n // hop, reflected at the end.  Returns the rest of the slot's features."""
+    st = self._slot(slot)
+    if st.n <= N_FFT // 2:
+      raise StreamError('stream {}: {} samples, the reflection at the ends needs more than {}'.format(slot, st.n, N_FFT // 2))
+    return self._run({}, (slot,))[slot]
+
+  def _run(self, feeds, finishing):
+    arrays = {}
+    for slot, y in feeds.items():
+      self._slot(slot)
+      y = np.ascontiguousarray(np.asarray(y, dtype=np.float32))
+      if y.ndim != 1:
+        raise StreamError('stream {}: samples must be a one-dimensional array, got shape {}'.format(slot, tuple(y.shape)))
+      arrays[int(slot)] = y
+    for slot in finishing:
+      self._slot(slot)
+    result = {s: [] for s in list(arrays) + [int(s) for s in finishing]}
+    longest = max([len(a) for a in arrays.values()] + [0])
+    passes = max(-(-longest // self.max_chunk), 1)
+    for p in range(passes):
+      part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
+      self._pass(part, finishing if p == passes - 1 else (), result)
+    return {s: (np.concatenate(r) if r else np.zeros((0, self.n_mels), np.float32)) for s, r in result.items()}
+
+  def _pass(self, part, finishing, result):
+    S = self.max_streams
+    minfo = np.zeros((S, 8), dtype=np.int32)
+    feed = np.zeros((S, 4), dtype=np.int32)
+    for s, st in enumerate(self.slots):
+      if st is not None:
+        b = sample_base(st.f, self.hop)
+        minfo[s] = (b, st.n, b, 0, 0, 0, st.f, 0)
+    pairs, after, rows, src, chunks = [], {}, 0, 0, []
+    for s in sorted(set(part) | set(int(x) for x in finishing)):
+      st = self.slots[s]
+      new = len(part[s]) if s in part else 0
+      fin = s in finishing
+      n = st.n + new
+      f_new = max(frames_ready(n, self.hop, fin), st.f)
+      m = f_new - st.f
+      base = sample_base(st.f, self.hop)
+      if n - base > self.cap or m > self.max_new:
+        raise StreamError('stream {}: {} samples would overrun the window'.format(s, n - base))
+      minfo[s] = (base, n, sample_base(f_new, self.hop), int(fin), rows, m, st.f, int(st.fresh))
+      feed[s] = (src, new, st.n - base, 0)
+      pairs += [(s, t) for t in range(st.f, f_new, 2)]
+      if new:
+        chunks.append(part[s])
+      if self.stats is not None:
+        count = m
+      elif st.f < self.warm:
+        count = f_new if (f_new >= self.warm or fin) else 0
+      else:
+        count = m
+      after[s] = (n, f_new, fin, count)
+      rows += m
+      src += new
+    table = np.concatenate([minfo.reshape(-1), feed.reshape(-1), np.asarray(pairs, dtype=np.int32).reshape(-1)]).astype(np.int32)
+    d_table = torch.from_numpy(table).pin_memory().to(self.device, non_blocking=True)
+    samples = np.concatenate(chunks) if chunks else np.zeros(1, np.float32)
+    d_samples = torch.from_numpy(samples).pin_memory().to(self.device, non_blocking=True)
+    fixed = self.stats is not None
+    ref, mean, std = self.stats if fixed else (0.0, 0.0, 1.0)
+    call('st_melspec_stream_f32', self._p(d_samples), self._p(d_table), len(pairs), S, self._p(self.plan), self.n_mels, self.hop, self.warm,
+         self.cap, int(fixed), ref, mean, std, self._p(self.state), self.state_bytes, self._p(self.out), self.out_cap, self.max_rows,
+         self._p(self.workspace), self.ws_bytes, self._sp)
+    view = self.out.view(S, self.out_cap, self.n_mels)
+    for s, (n, f_new, fin, count) in after.items():
+      st = self.slots[s]
+      st.n, st.f, st.fresh, st.finished = n, f_new, False, fin
+      if count:
+        result[s].append(view[s, :count].cpu().numpy())
+
+
+def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False):
+  """One stream: feed the feature chunks ([t, C] each) in order, finish, and return ``(ids, partials)`` -- all label ids and the
+  list of (input frames so far, ids so far) after every chunk that produced any -- plus the logits [T', C] on request."""
+  rec = StreamingRecognizer(engine, 1, max_chunk_frames)
+  slot = rec.open()
+  ids, partials, rows, frames = [], [], [], 0
+  for chunk in chunks:
+    r = rec.step({slot: chunk}, return_logits=return_logits)
+    frames += len(chunk)
+    if r.ids[slot]:
+      ids += r.ids[slot]
+      partials.append((frames, list(ids)))
+    if return_logits:
+      rows.append(r.logits[slot])
+  r = rec.finish(slot, return_logits=return_logits)
+  ids += r.ids[slot]
+  partials.append((frames, list(ids)))
+  rec.close(slot)
+  if return_logits:
+    rows.append(r.logits[slot])
+    return ids, partials, np.concatenate(rows)
+  return ids, partials
+
+
+# ---- `speecht-cli stream` -----------------------------------------------------------------------------------------------------
+
+def _pcm_chunks(stream, samples_per_chunk):
+  """Raw 16-bit little-endian mono PCM from a binary stream -> float32 pieces in [-1, 1) as they arrive."""
+  want = 2 * samples_per_chunk
+  while True:
+    data = stream.read(want)
+    if not data:
+      return
+    data = data[:len(data) // 2 * 2]
+    if data:
+      yield np.frombuffer(data, dtype='<i2').astype(np.float32) / 32768.0
+
+
+def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None):
+  """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
+  ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
+  ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
+  which are then fed piece by piece -- not live; it yields what `transcribe --batch-size 1` yields and exists for comparison."""
+  hop = 160
+  if normalize not in ('running', 'file'):
+    raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
+  ids, fed = [], 0
+
+  def feed(rec, slot, feats, seconds):
+    r = rec.step({slot: feats})
+    if r.ids[slot]:
+      ids.extend(r.ids[slot])
+      if on_partial:
+        on_partial(seconds, list(ids))
+
+  if normalize == 'file':
+    pieces = [np.asarray(p, np.float32) for p in pieces]
+    y = np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
+    if len(y) <= N_FFT // 2:
+      raise StreamError('too short: {} samples (the features need more than {})'.format(len(y), N_FFT // 2))
+    front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=16000, warm=1 + len(y) // hop, device=engine.device)
+    slot = front.open()
+    front.step({slot: y})
+    feats = front.finish(slot)
+    per = max(max(len(p) for p in pieces) // hop, 1)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8))
+    rslot = rec.open()
+    for at in range(0, len(feats), per):
+      feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
+    fed = len(y)
+  else:
+    max_piece = int(max_piece or 16000)
+    front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
+    slot = front.open()
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8))
+    rslot = rec.open()
+    for p in pieces:
+      p = np.asarray(p, np.float32)
+      fed += len(p)
+      feed(rec, rslot, front.step({slot: p})[slot], fed / float(samplerate))
+    if fed <= N_FFT // 2:
+      raise StreamError('too short: {} samples (the features need more than {})'.format(fed, N_FFT // 2))
+    feed(rec, rslot, front.finish(slot), fed / float(samplerate))
+  r = rec.finish(rslot)
+  ids.extend(r.ids[rslot])
+  return ids, fed / float(samplerate)
+
+
+def run_cli(flags):
+  """`speecht-cli stream PATH|-`: one line "seconds<TAB>transcript so far" per step that produced text, then the final transcript
+  as `transcribe` prints it ("path<TAB>transcript").  Creates no train / data / log directory."""
+  import contextlib
+  import sys
+  from . import transcription, vocabulary
+  from .speech_input import SingleInputLoader
+  from .speech_model import Session, create_default_model
+  if flags.feature_type != 'power':
+    print('stream: mel features only (MFCC deltas need a look-ahead of their own)', file=sys.stderr)
+    return 2
+  input_size = transcription.FEATURE_WIDTH['power']
+  with contextlib.redirect_stdout(sys.stderr):          # stdout carries the transcripts only
+    model = create_default_model(flags, input_size, SingleInputLoader(input_size))
+  try:
+    if flags.path == '-':
+      rate = int(flags.sample_rate)
+      per = max(int(rate * flags.chunk_ms / 1000.0), 1)
+      pieces = _pcm_chunks(sys.stdin.buffer, per)
+    else:
+      samples, rate = transcription.load_native(flags.path)
+      per = max(int(rate * flags.chunk_ms / 1000.0), 1)
+      pieces = [samples[at:at + per] for at in range(0, len(samples), per)]
+    with Session(flags.device) as sess:
+      with contextlib.redirect_stdout(sys.stderr):
+        model.restore(sess, flags.run_train_dir)
+      partial = lambda seconds, ids: print('{:.2f}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids)), flush=True)
+      ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per)
+  except (StreamError, transcription.TranscriptionError) as e:
+    print('stream: {}'.format(e), file=sys.stderr)
+    return 1
+  print('{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids)), flush=True)
+  return 0
