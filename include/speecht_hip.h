@@ -173,6 +173,11 @@ int st_gemm_tn_batched_f32(const float* a, int64_t lda, int64_t a_batch, const f
  * rows read at half length -- both against that bin's gradient spectra */
 int st_gemm_tn_batched_shared_f32(const float* a, int64_t lda, int64_t a_batch, const float* z, int64_t ldz, int64_t z_batch,
                                   float* out, int64_t out_batch, int m, int k, int n, int batches, int z_batch_shift, void* stream);
+/* ... on output tiles of 128 x tile_n, tile_n 128 or 64 (the entry points above choose by shape: 64 for a short reduction
+ * whose 128-wide tiles are little more than one per CU -- the 7-tap layers; the same bits either way) */
+int st_gemm_tn_batched_tile_f32(const float* a, int64_t lda, int64_t a_batch, const float* z, int64_t ldz, int64_t z_batch,
+                                float* out, int64_t out_batch, int m, int k, int n, int batches, int z_batch_shift, int tile_n,
+                                void* stream);
 /* A bin's COMPLEX product in three real products instead of four (Gauss: (a + ib)(c + id) = (k1 - k3) + i (k1 + k2), k1 = c (a + b),
  * k2 = a (d - c), k3 = b (c + d)), the shared product computed once per output tile (round 6; the 32-tap layer's per-bin products,
  * 25 % fewer multiplications).  Operand planes A_p = a + a_off[p], B_p = b + b_off[p] (p = 0, 1, 2; offsets in floats; b rows ldb

@@ -54,6 +54,8 @@ _SIGNATURES = {
                                        c_int, c_int, c_void_p]),
     'st_gemm_tn_batched_shared_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int,
                                               c_int, c_int, c_int, c_void_p]),
+    'st_gemm_tn_batched_tile_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int,
+                                            c_int, c_int, c_int, c_int, c_void_p]),
     'st_gemm_nn_g3_batched_f32': (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int64), c_void_p, c_int64, c_int64, POINTER(c_int64), c_int,
                                           c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     'st_gemm_tn_g3_batched_f32': (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int64), c_void_p, c_int64, c_int64, POINTER(c_int64),

@@ -605,7 +605,16 @@ __global__ __launch_bounds__(64 * FUSE_BLOCKS, 1) void idft_ola_dft_rows_kernel(
   static_assert(2 * HP % CH == 0 && HP <= HB / 2, "pairs per term must fill whole stages");
   __shared__ __attribute__((aligned(16))) float wl[KP * KP];
   __shared__ __attribute__((aligned(16))) float wf[32 * KP * 2];
-  __shared__ float spill[FUSE_BLOCKS][2][FUSE_HALO][32];                      // [block][into the block before | after][frame][channel]
+  // The spills, [into the block before | after][block][frame][channel], 4 KB each way.  The inverse reads k-pairs [0, HP) and
+  // [HB / 2, HB / 2 + HP) of wl only; up to HP = 18 the six or more pairs behind each range (768 bytes a pair) hold a spill
+  // array, and the workgroup takes 60 KB instead of 68: it then fits beside two 48 KB workgroups of the lag products of the layer
+  // above (gemm_tn_kernel<64>), which otherwise hold it off until they retire.  Nobody reads those pairs,
+  // and the matrix is staged before the first barrier, the spills written after it.
+  constexpr int SPILL = FUSE_BLOCKS * FUSE_HALO * 32;
+  constexpr bool SPILL_IN_WL = (HB / 2 - HP) * KP * 2 >= SPILL;
+  __shared__ float spill_own[SPILL_IN_WL ? 32 : 2 * SPILL];
+  float* const spill_before = SPILL_IN_WL ? wl + HP * KP * 2 : spill_own;
+  float* const spill_after = SPILL_IN_WL ? wl + (HB / 2 + HP) * KP * 2 : spill_own + SPILL;
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / nchunks, chunk = blockIdx.x - b * nchunks;
@@ -666,15 +675,15 @@ __global__ __launch_bounds__(64 * FUSE_BLOCKS, 1) void idft_ola_dft_rows_kernel(
     }
     // rows 64 .. 67 of the window (h = 0 lanes, registers 0 .. 3 of the third tile) belong to the block before, 68 .. 71 (h = 1) to the one after
 #pragma unroll
-    for (int e = 0; e < FUSE_HALO; ++e) spill[j][h][e][l31] = acc[2][e];
+    for (int e = 0; e < FUSE_HALO; ++e) (h ? spill_after : spill_before)[(j * FUSE_HALO + e) * 32 + l31] = acc[2][e];
   }
   __syncthreads();
   if (!active) return;
   // overlap-add: frames 0 .. right - 1 get what the block before spilled forward, frames V - pl .. V - 1 what the block after spilled back
 #pragma unroll
   for (int e = 0; e < FUSE_HALO; ++e) {
-    if (h == 0) { if (j > 0 && e < right) acc[0][e] += spill[j - 1][1][e][l31]; }
-    else { if (j + 1 < blocks && e >= FUSE_HALO - pad_left) acc[1][12 + e] += spill[j + 1][0][e - (FUSE_HALO - pad_left)][l31]; }
+    if (h == 0) { if (j > 0 && e < right) acc[0][e] += spill_after[((j - 1) * FUSE_HALO + e) * 32 + l31]; }
+    else { if (j + 1 < blocks && e >= FUSE_HALO - pad_left) acc[1][12 + e] += spill_before[((j + 1) * FUSE_HALO + e - (FUSE_HALO - pad_left)) * 32 + l31]; }
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -1131,6 +1140,13 @@ int st_gemm_tn_batched_shared_f32(const float* a, int64_t lda, int64_t a_batch, 
                                   int64_t out_batch, int m, int k, int n, int batches, int z_batch_shift, void* stream) {
   ST_REQUIRE(z_batch_shift >= 0 && z_batch_shift < 8, "gemm_tn_batched_shared: bad shift");
   return st::gemm_tn_batched(a, lda, a_batch, z, ldz, z_batch, out, out_batch, m, k, n, batches, st::as_stream(stream), z_batch_shift);
+}
+
+int st_gemm_tn_batched_tile_f32(const float* a, int64_t lda, int64_t a_batch, const float* z, int64_t ldz, int64_t z_batch, float* out,
+                                int64_t out_batch, int m, int k, int n, int batches, int z_batch_shift, int tile_n, void* stream) {
+  ST_REQUIRE(z_batch_shift >= 0 && z_batch_shift < 8, "gemm_tn_batched_tile: bad shift");
+  ST_REQUIRE(tile_n == 64 || tile_n == 128, "gemm_tn_batched_tile: tile_n is 64 or 128");
+  return st::gemm_tn_batched(a, lda, a_batch, z, ldz, z_batch, out, out_batch, m, k, n, batches, st::as_stream(stream), z_batch_shift, tile_n);
 }
 
 int st_gemm_nn_g3_batched_f32(const float* a, int64_t lda, int64_t a_batch, const int64_t* a_off, const float* b, int64_t ldb, int64_t b_batch,

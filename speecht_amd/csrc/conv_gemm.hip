@@ -86,6 +86,14 @@ __device__ __forceinline__ void dma16_sv(unsigned lds_byte_addr, const void* sba
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff_bytes), "s"(sbase) : "memory");
 }
+// Uniform base + 32-bit per-lane byte offset for plain loads and stores: the rows a lane addresses differ in the UNIFORM part
+// only, so a lane keeps one address register however many rows it touches (16 row pointers of 64 bits are 32 registers).
+__device__ __forceinline__ float* at_bytes(float* ubase, unsigned voff_bytes) {
+  return reinterpret_cast<float*>(reinterpret_cast<char*>(ubase) + voff_bytes);
+}
+__device__ __forceinline__ const float* at_bytes(const float* ubase, unsigned voff_bytes) {
+  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(ubase) + voff_bytes);
+}
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ unsigned lds_addr(const float* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const float*)p;
@@ -568,8 +576,13 @@ struct BinsParams {
 
 // BT: B given transposed ([N][ldb], the reduction index contiguous) -- back-prop to the input reads the FORWARD filter spectra
 // (gbwd = gfwd^T); staged and read like the A operand, a lane's two columns 32 apart (see gemm_nn_kernel).
-template <int BM, int BN, int WMW, int WNW, int MINW, bool BT>
-__global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams p) {
+// Footprint: 48 KB of LDS lets three workgroups share a CU, so the register bound is three waves per SIMD (168 registers; the
+// kernel takes 167 with BT, 155 without, no scratch).  The persistent grids keep two (8 x 64) or three (8 x 96) resident per CU;
+// with two, a third of the register file and 60 KB of LDS stay free for another stream's kernels -- back-prop's products run
+// beside the filter-gradient chain of the layer above.  What keeps it there: no per-row 64-bit addresses
+// (at_bytes), which hipcc otherwise hoists out of the piece loop, 64 registers of them.
+template <int BM, int BN, int WMW, int WNW, bool BT>
+__global__ __launch_bounds__(NTHREADS, 3) void gemm_nn_bins_kernel(BinsParams p) {
   typedef NNStage<BM, BN, WMW, WNW, BT> S;
   constexpr int WTM = S::WTM, WTN = S::WTN, MT = S::MT, NT = S::NT;
   constexpr int A_DMA = S::A_DMA, B_DMA = S::B_DMA, N_DMA = S::N_DMA, A_SZ = S::A_SZ, B_SZ = S::B_SZ;
@@ -601,20 +614,20 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
 
   // lane-constant parts of the DMA sources (see gemm_nn_kernel): A instruction i of this wave covers rows
   // (wave * A_DMA + i) * 8 .. +8, lane -> (row, swizzled 16-byte slot); B instruction i covers 64 / B_LPR rows of k
-  int a_lane[A_DMA];
+  unsigned a_lane[A_DMA];                                                                // (byte offsets)
 #pragma unroll
   for (int i = 0; i < A_DMA; ++i) {
     const int row = (wave * A_DMA + i) * 8 + (lane >> 3);
-    a_lane[i] = row * (int)p.lda + swz_slot4(lane, row);                                // (BM rows of a bin: fits an int)
+    a_lane[i] = (unsigned)(row * (int)p.lda + swz_slot4(lane, row)) * 4u;               // (BM rows of a bin: fits, checked by the host)
   }
-  int b_lane[B_DMA];
+  unsigned b_lane[B_DMA];
 #pragma unroll
   for (int i = 0; i < B_DMA; ++i) {
     if (BT) {
       const int row = (wave * B_DMA + i) * 8 + (lane >> 3);
-      b_lane[i] = row * (int)p.ldb + swz_slot4(lane, row);                                                  // (BN rows of Bt)
+      b_lane[i] = (unsigned)(row * (int)p.ldb + swz_slot4(lane, row)) * 4u;                                                  // (BN rows of Bt)
     } else {
-      b_lane[i] = ((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * (int)p.ldb + (lane % B_LPR) * 4;   // (32 rows of B)
+      b_lane[i] = (unsigned)(((wave * B_DMA + i) * (64 / B_LPR) + lane / B_LPR) * (int)p.ldb + (lane % B_LPR) * 4) * 4u;   // (32 rows of B)
     }
   }
   int bt_frag[4];
@@ -632,6 +645,12 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
   const int b_frag = (4 * h) * BN + wn * WTN + NT * l31;
   const int tcol = wn * WTN + NT * l31;                      // this lane's first column inside the tile (the partial tiles'
                                                              // 8-byte slots keep this address also when the columns are 32 apart)
+  // Row r of MFMA tile i is tile row lrow + trow(i, r): lrow per lane, trow a constant.  Partial tiles and the output are
+  // addressed as (uniform row pointer)[lane offset] (at_bytes) -- 2 address registers instead of 64.
+  const int lrow = wm * WTM + 4 * h;
+  const unsigned part_lane = (unsigned)(lrow * BN + tcol) * 4u;
+  const unsigned c_lane = (unsigned)(lrow * (int)p.ldc + (BT ? wn * WTN + l31 : tcol)) * 4u;          // (64 rows of C: fits, checked by the host)
+  auto trow = [](int i, int r) { return i * 32 + (r & 3) + 8 * (r >> 2); };
 
   while (cur.u < cur.u_end) {
     const st::SkPiece pc = st::sk_piece(p.plan, cur);
@@ -641,19 +660,14 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const float* __restrict__ Ab = p.A + (long)bin * p.a_batch + (long)m0 * p.lda;
     const float* __restrict__ Bb = p.B + (long)bin * p.b_batch + (BT ? (long)n0 * p.ldb : (long)n0);
-    const float* aptr[A_DMA];
-    const float* bptr[B_DMA];
-#pragma unroll
-    for (int i = 0; i < A_DMA; ++i) aptr[i] = Ab + a_lane[i];
-#pragma unroll
-    for (int i = 0; i < B_DMA; ++i) bptr[i] = Bb + b_lane[i];
+    // (DMA sources as uniform pointer + the lane's 32-bit offset, like the epilogue's rows: the k-tile advances the uniform part)
     auto dma_piece = [&](int pcx, int k0, int buf) {
       if (pcx < A_DMA) {
         const int i = pcx < A_DMA ? pcx : 0;
-        __builtin_amdgcn_global_load_lds((st::gptr_t)(aptr[i] + k0), (st::lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((st::gptr_t)at_bytes(Ab + k0, a_lane[i]), (st::lptr_t)(As + buf * A_SZ + (wave * A_DMA + i) * 256), 16, 0, 0);
       } else {
         const int i = pcx - A_DMA < B_DMA ? pcx - A_DMA : 0;
-        __builtin_amdgcn_global_load_lds((st::gptr_t)(BT ? bptr[i] + k0 : bptr[i] + (long)k0 * p.ldb), (st::lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((st::gptr_t)at_bytes(BT ? Bb + k0 : Bb + (long)k0 * p.ldb, b_lane[i]), (st::lptr_t)(Bs + buf * B_SZ + (wave * B_DMA + i) * 256), 16, 0, 0);
       }
     };
 
@@ -680,9 +694,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
           const u64 bits = (u64)__float_as_uint(acc[i][0][r]) | ((u64)__float_as_uint(acc[i][1][r]) << 32);
-          __hip_atomic_store(reinterpret_cast<u64*>(mine + row * BN + tcol), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(reinterpret_cast<u64*>(at_bytes(mine + trow(i, r) * BN, part_lane)), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -716,10 +729,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
       for (int i = 0; i < MT; ++i) {
         u64 part[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          part[r] = __hip_atomic_load(reinterpret_cast<const u64*>(theirs + row * BN + tcol), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (int r = 0; r < 16; ++r)
+          part[r] = __hip_atomic_load(reinterpret_cast<const u64*>(at_bytes(theirs + trow(i, r) * BN, part_lane)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           acc[i][0][r] += __uint_as_float((unsigned)part[r]) + poison;
@@ -728,20 +739,20 @@ __global__ __launch_bounds__(NTHREADS, MINW) void gemm_nn_bins_kernel(BinsParams
       }
       covered += min(p.plan.upw, p.plan.nk - covered);
     }
-    float* __restrict__ Cb = p.C + (long)bin * p.c_batch + (long)m0 * p.ldc + n0 + (BT ? wn * WTN + l31 : tcol);
+    float* __restrict__ Cb = p.C + (long)bin * p.c_batch + (long)m0 * p.ldc + n0;     // the tile's corner: uniform
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        float* const crow = Cb + (long)trow(i, r) * p.ldc;
         if (BT) {                            // this lane's columns are 32 apart
 #pragma unroll
-          for (int n = 0; n < NT; ++n) Cb[(long)row * p.ldc + n * 32] = acc[i][n][r];
+          for (int n = 0; n < NT; ++n) *at_bytes(crow + n * 32, c_lane) = acc[i][n][r];
         } else {
           bvec out;
 #pragma unroll
           for (int n = 0; n < NT; ++n) vset<NT>(out, n, acc[i][n][r]);
-          *reinterpret_cast<bvec*>(Cb + (long)row * p.ldc) = out;
+          *reinterpret_cast<bvec*>(at_bytes(crow, c_lane)) = out;
         }
       }
   }
@@ -1572,7 +1583,8 @@ int st::gemm_nn_batched(const float* A, long lda, long a_batch, const float* B, 
   // st_set_tuning("streamk", 1) forces it wherever the shape allows, 2 turns it off; "streamk_slots" = workgroups per XCD
   // (64 or 96; 0 = the policy's).
   const int knob = st::tuning(st::TUNE_STREAMK);
-  if (sk_ws && knob != 2 && M % 64 == 0 && a_batch % 4 == 0 && b_batch % 4 == 0 && (long)64 * lda < (1L << 30) && (long)32 * N < (1L << 30)) {
+  if (sk_ws && knob != 2 && M % 64 == 0 && a_batch % 4 == 0 && b_batch % 4 == 0 && (long)64 * lda < (1L << 30) && (long)32 * N < (1L << 30) &&
+      (long)64 * ldc < (1L << 29) && (!b_transposed || (long)128 * K < (1L << 29))) {   // (the kernel's 32-bit lane offsets, in bytes)
     const long tiles = (long)batches * (M / 64) * (N / 128);
     const double per_cu = (double)tiles / 256.0;
     const bool uneven = tiles > 256 && tiles <= 768 && std::ceil(per_cu) / per_cu > 1.2;
@@ -1598,13 +1610,8 @@ int st::gemm_nn_batched(const float* A, long lda, long a_batch, const float* B, 
       {
         st::LaunchTimer timer(s);
         const dim3 grid(8 * plan.wgs_per_xcd), block(NTHREADS);
-        if (b_transposed) {
-          if (plan.wgs_per_xcd > 64) st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, 3, true>, grid, block, s, q);
-          else st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, 2, true>, grid, block, s, q);
-        } else {
-          if (plan.wgs_per_xcd > 64) st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, 3, false>, grid, block, s, q);
-          else st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, 2, false>, grid, block, s, q);
-        }
+        if (b_transposed) st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, true>, grid, block, s, q);
+        else st::launch_timed(timer, gemm_nn_bins_kernel<64, 128, 2, 2, false>, grid, block, s, q);
       }
       return st::check_launch("gemm_nn_bins");
     }
@@ -1642,11 +1649,20 @@ int st::gemm_nn_batched(const float* A, long lda, long a_batch, const float* B, 
 
 // Plain batched out[b] = A[b]^T * Z[b] on the filter-gradient kernel: A [M][lda] (K <= lda columns used), Z [M][ldz]
 // (N columns), out [K][N]; the reduction runs over the M rows.  K a multiple of 128, N of 128, M of 32.
+// tile_n: output tiles of 128 x 128 or 128 x 64; 0 = by shape (below).
 int st::gemm_tn_batched(const float* A, long lda, long a_batch, const float* Z, long ldz, long z_batch, float* out,
-                        long o_batch, int M, int K, int N, int batches, hipStream_t s, int z_batch_shift) {
-  if (!(A && Z && out && M > 0 && M % 32 == 0 && K % 128 == 0 && N % 128 == 0 && batches > 0)) {
-    st::set_error("gemm_tn_batched: bad shape M=%d K=%d N=%d", M, K, N);
+                        long o_batch, int M, int K, int N, int batches, hipStream_t s, int z_batch_shift, int tile_n) {
+  if (!(A && Z && out && M > 0 && M % 32 == 0 && K % 128 == 0 && N % 128 == 0 && batches > 0 && (tile_n == 0 || tile_n == 64 || tile_n == 128))) {
+    st::set_error("gemm_tn_batched: bad shape M=%d K=%d N=%d tile_n=%d", M, K, N, tile_n);
     return ST_EINVAL;
+  }
+  // Tile policy.  The 128 x 128 tile holds 64 KB of LDS: two workgroups per CU, none beside two per-bin product workgroups of
+  // another stream.  A launch of a little more than one such tile per CU (the 7-tap layers: 72 products x 4 = 288 on 256 CUs, the
+  // second round an eighth full) over a short reduction runs on 128 x 64 tiles instead: twice the workgroups (2.25 per CU) of
+  // 48 KB and about half the registers each.  Every output element sums its rows in the same order: the same bits.
+  if (tile_n == 0) {
+    const long tiles128 = (long)batches * (K / 128) * (N / 128);
+    tile_n = (tiles128 > 256 && tiles128 <= 320 && M <= 512) ? 64 : 128;
   }
   TNParams p{};
   p.A = A;
@@ -1661,16 +1677,18 @@ int st::gemm_tn_batched(const float* A, long lda, long a_batch, const float* Z, 
   p.rows_per_split = M;
   p.out = out;
   p.tiles_k = K / 128;
-  p.tiles_n = N / 128;
+  p.tiles_n = N / tile_n;
   p.amap_batches = 1;
   p.adv_b = 32 / M;
   p.adv_t = 32 % M;
   p.a_batch = a_batch; p.z_batch = z_batch; p.o_batch = o_batch;
   p.z_shift = z_batch_shift;
-  st::trace("gemm_tn<128> batched bins=%d M=%d Kp=%d Np=%d gflop=%.3f", batches, M, K, N, 2e-9 * M * (double)K * N * batches);
+  st::trace("gemm_tn<%d> batched bins=%d M=%d Kp=%d Np=%d gflop=%.3f", tile_n, batches, M, K, N, 2e-9 * M * (double)K * N * batches);
   {
     st::LaunchTimer timer(s);
-    st::launch_timed(timer, gemm_tn_kernel<128, 2, 2>, dim3(p.tiles_k * p.tiles_n, 1, batches), dim3(TN_THREADS), s, p);
+    const dim3 grid(p.tiles_k * p.tiles_n, 1, batches);
+    if (tile_n == 64) st::launch_timed(timer, gemm_tn_kernel<64, 2, 2>, grid, dim3(TN_THREADS), s, p);
+    else st::launch_timed(timer, gemm_tn_kernel<128, 2, 2>, grid, dim3(TN_THREADS), s, p);
   }
   return st::check_launch("gemm_tn_batched");
 }

@@ -46,12 +46,13 @@ int tuning(int key);
 // sk_ws: optional SK_WS_FLOATS floats of scratch for the persistent stream-K form of an uneven launch (conv_gemm.hip,
 // gemm_nn_bins_kernel): [control words: 768 flags | timeout count] then 768 partial tiles of 64 x 128.  Any content before the
 // first call (flags carry the launch's epoch and are put back to zero by their reader); one scratch per stream.
+// gemm_tn_batched's tile_n: 128 or 64 columns per output tile, 0 = by shape (64 for short reductions with few 128 tiles).
 constexpr int SK_FLAGS = 0, SK_TIMEOUTS = 768, SK_CTRL_WORDS = 1024;
 constexpr long SK_WS_FLOATS = SK_CTRL_WORDS + 768L * 64 * 128;
 int gemm_nn_batched(const float* A, long lda, long a_batch, const float* B, long b_batch, float* C, long ldc, long c_batch,
                     int M, int K, int N, int batches, hipStream_t s, float* sk_ws = nullptr, bool b_transposed = false);
 int gemm_tn_batched(const float* A, long lda, long a_batch, const float* Z, long ldz, long z_batch, float* out, long o_batch,
-                    int M, int K, int N, int batches, hipStream_t s, int z_batch_shift = 0);
+                    int M, int K, int N, int batches, hipStream_t s, int z_batch_shift = 0, int tile_n = 0);
 // the same products of COMPLEX operands as three real products per bin instead of four (Gauss; conv_gemm.hip gemm_nn_g3_kernel /
 // gemm_tn_g3_kernel): operand planes A_p = A + a_off[p] etc., the real and the imaginary result c_off2 columns / o_part floats apart
 int gemm_nn_g3_batched(const float* A, long lda, long a_batch, const long a_off[3], const float* B, long ldb, long b_batch,
