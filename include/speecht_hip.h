@@ -847,6 +847,42 @@ int st_ctc_greedy_stream(const float* logits, int pitch, int num_classes, const 
                          int32_t* state, double* score, int32_t* ids, int max_new, int32_t* new_count, float* neg_sum_logits,
                          void* stream);
 
+/* ---- Beam search carried across steps (csrc/ctc_beam.hip: ctc_beam_kernel<.., STREAM>, ctc_beam_read_kernel).  The prefix beam
+ * searches of st_ctc_beam_search_decode_ex / _lm, one wavefront per stream, with everything that lives across frames kept in a
+ * per-stream state record between calls, so that a stream decoded in steps IS the whole-utterance search on the concatenated rows:
+ * ids, length and log_prob are bit-identical however the rows were cut.  lm NULL: the LM-free search (2..32 classes); with a model
+ * (uploaded to the stream's device) the classes are a-z ' space blank (29) and one weight triple applies.  Beams 1..128.
+ *   state  max_streams records of st_ctc_beam_stream_state_bytes(beam_width, lm != NULL) bytes, 8-byte aligned: a 32-byte header
+ *          {magic, live entries, frames decoded, status, stable_len, -, double offset}, the live beam set (40 B per entry of 64 or,
+ *          above beam 64, 128) and with a model each entry's LM state (44 B) and 28 expansion deltas (128 B).  Any content before a
+ *          stream's first step, which carries reset = 1; a record never reset for this beam width and kind is left alone.
+ *   pool   max_streams node pools of st_ctc_beam_stream_pool_bytes(max_frames, beam_width) bytes: (parent, label) pairs, the pair
+ *          of frame t and rank r at 1 + t * beam_width + r with t the stream's ABSOLUTE frame index.  A frame at or beyond
+ *          max_frames is NOT decoded: status bit 0 is set in the record instead and nothing is written outside the pool.
+ *   rows, table  the tables of st_ctc_greedy_stream: rows int32 [n_rows][2] (stream, absolute frame), table int32 [max_streams][4]
+ *          {first row, rows, decode limit or -1, reset}; row r of the launch is logits[r * pitch].  Rows at or past the limit are
+ *          not decoded.
+ * st_ctc_beam_stream_step: the log-softmax of the step's rows (the arithmetic of the whole-utterance searches, input_transform as
+ *   there) into the workspace (st_ctc_beam_stream_ws(n_rows) bytes), then the frames of every stream; no tail, no output.
+ * st_ctc_beam_stream_read: for every stream with rows in the step, a reset or a limit >= 0 (the others' outputs stay untouched):
+ *   stable_len, the length of the longest common prefix -- compared by labels -- of all live entries: every later entry extends a
+ *   live one, so these labels are final.  The kernel walks the chains down to the stored stable_len only and stores the new one.
+ *   The reported hypothesis is entry 0 of the set (running total, no end-of-utterance terms) while the stream is open and, once
+ *   limit >= 0, exactly the whole-utterance result: with a model every entry gains lm_weight * (incomplete word, then </s>) and the
+ *   best total wins, ties to the lower rank.  result int32 [max_streams][4] = {length of the hypothesis, new stable_len, log_prob
+ *   (float bits), status: bit 0 pool full, bit 1 no state}; tail[s][i] = label (old stable_len + i) of the hypothesis, i < max_tail.
+ *   The caller keeps the labels below stable_len from earlier reads. */
+size_t st_ctc_beam_stream_state_bytes(int beam_width, int lm);
+size_t st_ctc_beam_stream_pool_bytes(int max_frames, int beam_width);
+size_t st_ctc_beam_stream_ws(int max_rows);
+int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                            int32_t* tail, int max_tail, int32_t* result, void* stream);
+
 /* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
  * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
  * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are

@@ -222,6 +222,13 @@ _SIGNATURES = {
                                       c_float, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'st_ctc_greedy_stream': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                      c_void_p, c_void_p]),
+    'st_ctc_beam_stream_state_bytes': (c_size_t, [c_int, c_int]),
+    'st_ctc_beam_stream_pool_bytes': (c_size_t, [c_int, c_int]),
+    'st_ctc_beam_stream_ws': (c_size_t, [c_int]),
+    'st_ctc_beam_stream_step': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float,
+                                        c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_stream_read': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_int, c_void_p, c_void_p]),
     'st_fill_f32': (c_int, [c_void_p, c_float, c_size_t, c_void_p]),
     'st_zero_halos_f32': (c_int, [_T3P, c_void_p]),
     'st_zero_regions': (c_int, [c_void_p, c_int, c_void_p]),

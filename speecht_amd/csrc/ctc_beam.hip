@@ -1,6 +1,8 @@
 // CTC prefix beam search (top path) on gfx950 -- SURVEY 8(f) item 3, BASELINE config 5 -- without a scorer, and with the word
 // n-gram scorer of the reference's decoder (ctc_beam_kernel<.., LM = true>, st_ctc_beam_search_decode_lm), also for several
 // weight triples in one launch (a grid of utterances x candidates, st_ctc_beam_search_decode_lm_candidates: the LM weight search).
+// Both searches also run carried across the steps of a live stream (ctc_beam_kernel<.., STREAM = true>, ctc_beam_read_kernel;
+// st_ctc_beam_stream_step / _read): the same frame loop between a load and a save of the beam's state.
 //
 // The reference reaches a beam search only through its KenLM TensorFlow fork (speech_model.py:101-111);
 // this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion, with the candidate order of
@@ -157,6 +159,24 @@ __device__ __forceinline__ void lm_enter(const LmParams& P, const LmSet<MAXB>& S
   NL.n_ctx[e] = nc;
 }
 
+// end of utterance: entry e scores its incomplete word (if non-empty) and then </s>; returns its total after that.  ONE function
+// for the whole-utterance tail and the stream's read-out (L and row in LDS there, in the state record here), so that both compile
+// the same operations: the two results are compared bit for bit.
+template <int MAXB>
+__device__ __forceinline__ float lm_final_total(const LmParams& P, const LmSet<MAXB>& L, const float* row, float total, int e) {
+  int ctx[kCtx];
+#pragma unroll
+  for (int i = 0; i < kCtx; ++i) ctx[i] = L.ctx[i][e];
+  int nc = L.n_ctx[e];
+  float d = -L.wpart[e];
+  if (L.node[e] != 0) {
+    d = row[kSpace];
+    push_ctx(ctx, nc, P.v.order - 1, L.word[e] >= 0 ? L.word[e] : stlm::kUnk);
+  }
+  d += stlm::score(P.v, ctx, nc, stlm::kEos);
+  return total + P.lm_weight * d;
+}
+
 __device__ __forceinline__ unsigned long long child_hash(unsigned long long h, int c) {
   unsigned long long x = h + 0x9E3779B97F4A7C15ull * (unsigned long long)(c + 1);
   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
@@ -228,12 +248,8 @@ __device__ __forceinline__ float order_value(unsigned ord) {
 // frames at or beyond an utterance's length are skipped.
 // transform 1: the decoder's input is tf.log(tf.nn.softmax(logits) + 1e-8) / log(10) -- what the reference hands its beam search
 // (speech_model.py:102) -- and the decoder then normalises THAT per frame like any other input (ctc_beam_search.h Step).
-__global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __restrict__ logits, RowMap map, int T, int C,
-                                                              const int* __restrict__ seq_lens, int transform, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63, b = blockIdx.y;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= min(seq_lens[b], T)) return;
-  const float x = lane < C ? logits[map.off(b, t) + lane] : -INFINITY;
+// one row by one wave: x is lane's logit (-inf for lane >= C), the row goes to out[0 .. 32)
+__device__ __forceinline__ void logsoftmax_row(float x, int lane, int C, int transform, float* __restrict__ out) {
   const float m = wave_max_f32(x);
   const float z = wave_sum_f32(lane < C ? expf(x - m) : 0.f);
   if (transform == 1) {
@@ -249,10 +265,29 @@ __global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __res
     const double xt = lane < C ? log10(e / zz + 1e-8) : -INFINITY;
     const float mt = wave_max_f32((float)xt);                       // any value near the maximum centres the sum
     const double z2 = wsum(lane < C ? exp(xt - (double)mt) : 0.0);
-    if (lane < kMaxClasses) out[((long)b * T + t) * kMaxClasses + lane] = lane < C ? (float)(xt - (double)mt - log(z2)) : 0.f;
+    if (lane < kMaxClasses) out[lane] = lane < C ? (float)(xt - (double)mt - log(z2)) : 0.f;
     return;
   }
-  if (lane < kMaxClasses) out[((long)b * T + t) * kMaxClasses + lane] = lane < C ? x - m - logf(z) : 0.f;
+  if (lane < kMaxClasses) out[lane] = lane < C ? x - m - logf(z) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __restrict__ logits, RowMap map, int T, int C,
+                                                              const int* __restrict__ seq_lens, int transform, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, b = blockIdx.y;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= min(seq_lens[b], T)) return;
+  const float x = lane < C ? logits[map.off(b, t) + lane] : -INFINITY;
+  logsoftmax_row(x, lane, C, transform, out + ((long)b * T + t) * kMaxClasses);
+}
+
+// ... and of the rows of one streaming step, row r of the launch at logits[r * pitch]: out[r * 32 + c]
+__global__ __launch_bounds__(256) void logsoftmax_step_rows_kernel(const float* __restrict__ logits, int pitch, int n_rows, int C,
+                                                                   int transform, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_rows) return;
+  const float x = lane < C ? logits[(long)r * pitch + lane] : -INFINITY;
+  logsoftmax_row(x, lane, C, transform, out + (long)r * kMaxClasses);
 }
 
 // The search kernel runs ONE wavefront per workgroup, and a wave's LDS operations execute in order: between its phases it
@@ -277,13 +312,57 @@ struct NbestArgs<true> {
   int* n_hyps;         // [utterance]: min(n_best, entries alive)
 };
 
-template <int CPL, int MAXB, bool LM, bool NBEST = false>
+// STREAM: the search carried across steps (st_ctc_beam_stream_step).  Block b is stream b; it starts from the stream's state
+// record instead of the root (from the root when the table row says reset), decodes the stream's rows of this step -- lp_all holds
+// the log-softmax rows of the STEP, row r of the launch at lp_all[r * 32] -- numbers its nodes with the absolute frame index, so
+// that the chains are those of the whole-utterance search, saves the state again and has no tail (ctc_beam_read_kernel reads the
+// hypothesis out).  A frame whose nodes would lie beyond the stream's pool is not decoded: the record's status word says so.
+// STREAM = false compiles to the kernels above (its StreamArgs is empty).
+struct StreamHeader {     // the first kStateHeader bytes of a state record
+  int magic;              // stream_magic(W, LM) once the record has been reset by a launch of this beam width and kind
+  int nb;                 // live entries
+  int frames;             // frames decoded so far
+  int status;             // kPoolFull: a frame was refused
+  int stable_len;         // labels every live entry shares (kept by the read-out)
+  int pad;
+  double offset;
+};
+constexpr int kStateHeader = 32;
+constexpr int kPoolFull = 1;
+static_assert(sizeof(StreamHeader) == kStateHeader, "state record header");
+__host__ __device__ constexpr int stream_magic(int W, bool lm) { return 0x53420000 | (W << 1) | (lm ? 1 : 0); }
+// record: [header | BeamSet<MAXB> | LM: LmSet<MAXB>, deltas [MAXB][kDeltaPitch]]
+template <int MAXB>
+constexpr size_t stream_state_bytes(bool lm) {
+  return kStateHeader + sizeof(BeamSet<MAXB>) + (lm ? sizeof(LmSet<MAXB>) + sizeof(float) * MAXB * kDeltaPitch : 0);
+}
+
+template <bool STREAM>
+struct StreamArgs {};
+template <>
+struct StreamArgs<true> {
+  const int* rows;        // [n_rows][2] (stream, absolute frame) of the step
+  const int* table;       // [streams][4] {first row, rows, decode limit or -1, reset}
+  char* state;            // [streams] records of state_stride bytes
+  long state_stride;
+  int max_frames;         // the pool holds max_frames * W + 1 nodes per stream
+};
+
+// words of 4 bytes between LDS and a state record, lane-strided
+__device__ __forceinline__ void copy_words(void* dst, const void* src, int bytes, int lane) {
+  int* d = static_cast<int*>(dst);
+  const int* s = static_cast<const int*>(src);
+  for (int i = lane; i < bytes / 4; i += 64) d[i] = s[i];
+}
+
+template <int CPL, int MAXB, bool LM, bool NBEST = false, bool STREAM = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ lp_all, int T, int C,
                                                       const int* __restrict__ seq_lens, int W,
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
                                                       int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma,
-                                                      NbestArgs<NBEST> nx) {
+                                                      NbestArgs<NBEST> nx, StreamArgs<STREAM> sx = {}) {
+  static_assert(!(NBEST && STREAM), "a stream has no N-best lists");
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -308,7 +387,30 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   const LmParams lmp{lma.v, lma.w[p][0], lma.w[p][1], lma.w[p][2], lma.oov_score};
   const long ob = LM ? (long)p * gridDim.x + b : b;
   const float lw = lmp.lm_weight;
-  const int Tb = min(seq_lens[b], T);
+  // STREAM: the frames of this step (Tb of them, the first at row `first` of the launch) continue the t0 frames decoded before
+  int Tb, t0 = 0, first = 0, status = 0;
+  bool fresh = true;
+  [[maybe_unused]] StreamHeader* hdr = nullptr;
+  if constexpr (STREAM) {
+    hdr = reinterpret_cast<StreamHeader*>(sx.state + b * sx.state_stride);
+    first = sx.table[4 * b];
+    const int count = sx.table[4 * b + 1], limit = sx.table[4 * b + 2];
+    fresh = sx.table[4 * b + 3] != 0;
+    if (!fresh && hdr->magic != stream_magic(W, LM)) return;     // never reset for this search: nothing to continue
+    if (!fresh) { t0 = hdr->frames; status = hdr->status; }
+    Tb = count;
+    if (limit >= 0 && count > 0) Tb = max(min(count, limit - sx.rows[2 * first + 1]), 0);   // rows at or past the limit
+    if (Tb > sx.max_frames - t0) {                                                        // ... or past the pool
+      Tb = max(sx.max_frames - t0, 0);
+      status |= kPoolFull;
+    }
+    if (!fresh && Tb == 0) {                                     // nothing to decode: the record stays as it is
+      if (lane == 0 && status != hdr->status) hdr->status = status;
+      return;
+    }
+  } else {
+    Tb = min(seq_lens[b], T);
+  }
   const int blank = C - 1;
   int2* nodes = node_pool + ob * pool_stride;
 
@@ -325,7 +427,20 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
 
   int cur = 0, nb = 1;
   double offset = 0.0;                   // log-probability of the current best entry (wave-uniform)
-  if (lane == 0) {
+  if constexpr (STREAM) {
+    if (!fresh) {
+      const char* rec = sx.state + b * sx.state_stride;
+      nb = min(max(hdr->nb, 0), W);
+      offset = hdr->offset;
+      copy_words(&sets[0], rec + kStateHeader, sizeof(BeamSet<MAXB>), lane);
+      if constexpr (LM) {
+        copy_words(&lms[0], rec + kStateHeader + sizeof(BeamSet<MAXB>), sizeof(LmSet<MAXB>), lane);
+        copy_words(&delta_s[0][0][0], rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>),
+                   sizeof(float) * MAXB * kDeltaPitch, lane);
+      }
+    }
+  }
+  if (lane == 0 && fresh) {
     BeamSet<MAXB>& s = sets[0];
     s.hash[0] = kRootHash; s.parent_hash[0] = 0; s.len[0] = 0; s.last[0] = -1; s.node[0] = 0;
     s.pb[0] = 0.f; s.pl[0] = -INFINITY; s.total[0] = 0.f;
@@ -345,7 +460,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   __syncthreads();
 
   // log-softmax rows of this utterance, written by logsoftmax_rows_kernel: [t][32]
-  const float* __restrict__ lp_rows = lp_all + (long)b * T * kMaxClasses;
+  const float* __restrict__ lp_rows = lp_all + (STREAM ? (long)first : (long)b * T) * kMaxClasses;
   float lp_next = (lane < kMaxClasses && Tb > 0) ? lp_rows[lane] : 0.f;
   for (int t = 0; t < Tb; ++t) {
     const BeamSet<MAXB>& S = sets[cur];
@@ -672,7 +787,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       const int len0 = S.len[slot], last0 = S.last[slot], node0 = S.node[slot];
       const float spb = stay_pb[slot], spl = stay_pl[slot];
       const bool stay = c == blank;
-      const int id = 1 + t * W + e;
+      const int id = 1 + (t0 + t) * W + e;
       if (!stay) nodes[id] = make_int2(node0, c);
       N.hash[e] = stay ? h0 : child_hash(h0, c);
       N.parent_hash[e] = stay ? ph0 : h0;
@@ -699,6 +814,26 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   }
 
   __syncthreads();
+  if constexpr (STREAM) {
+    // the state back into the stream's record (the live set in its first buffer again); the read-out kernel does the rest
+    char* rec = sx.state + b * sx.state_stride;
+    copy_words(rec + kStateHeader, &sets[cur], sizeof(BeamSet<MAXB>), lane);
+    if constexpr (LM) {
+      copy_words(rec + kStateHeader + sizeof(BeamSet<MAXB>), &lms[cur], sizeof(LmSet<MAXB>), lane);
+      copy_words(rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>), &delta_s[cur][0][0],
+                 sizeof(float) * MAXB * kDeltaPitch, lane);
+    }
+    if (lane == 0) {
+      hdr->magic = stream_magic(W, LM);
+      hdr->nb = nb;
+      hdr->frames = t0 + Tb;
+      hdr->status = status;
+      if (fresh) hdr->stable_len = 0;
+      hdr->pad = 0;
+      hdr->offset = offset;
+    }
+    return;
+  }
   // N best: hypothesis h is entry rank_of[h] of the final set with the total final_total[.] (both LDS, the selection's sel_k /
   // sel_v, free after the last frame); one lane per hypothesis walks its node chain -- dependent global reads, n_best chains side
   // by side, two rounds above 64 hypotheses.  Slots at or beyond the entries alive get length 0 and -inf.
@@ -736,20 +871,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     // end of utterance: every entry scores its incomplete word (if non-empty) and then </s>; the top path is the best total
     // after that (ties: the lower rank)
     const LmSet<LMB>& L = lms[cur];
-    for (int e = lane; e < nb; e += 64) {
-      const float* row = delta_s[cur][e];
-      int ctx[kCtx];
-#pragma unroll
-      for (int i = 0; i < kCtx; ++i) ctx[i] = L.ctx[i][e];
-      int nc = L.n_ctx[e];
-      float d = -L.wpart[e];
-      if (L.node[e] != 0) {
-        d = row[kSpace];
-        push_ctx(ctx, nc, lmp.v.order - 1, L.word[e] >= 0 ? L.word[e] : stlm::kUnk);
-      }
-      d += stlm::score(lmp.v, ctx, nc, stlm::kEos);
-      sel_v[e] = sets[cur].total[e] + lw * d;
-    }
+    for (int e = lane; e < nb; e += 64) sel_v[e] = lm_final_total(lmp, L, delta_s[cur][e], sets[cur].total[e], e);
     __syncthreads();
     if constexpr (NBEST) {
       // rank by (final total desc, rank in the set asc), by counting over LDS: entry e's place is the number of entries ahead of it
@@ -795,6 +917,92 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       if (i < n) ids[(long)b * max_out + i] = nd.y;
       id = nd.x;
     }
+  }
+}
+
+// ---- the stream's read-out (st_ctc_beam_stream_read) --------
+// One wave per stream, on the record ctc_beam_kernel<.., STREAM> saved.  Streams without rows in this step that are neither
+// finishing nor reset are skipped (their outputs stay as they are).
+//  - Committed text: stable_len = the length of the longest common prefix, by LABELS, of all live entries (a prefix that left the
+//    beam and came back has a second chain, so node ids say nothing).  Every future entry extends a live one, so this prefix can
+//    never change.  One lane per entry (two when wide) walks its chain against entry 0's from the shortest entry's length down to
+//    the stored stable_len -- never to the root -- and stops early where the two chains join.
+//  - Hypothesis: open stream: entry 0 (running total).  Finishing (limit >= 0): the whole-utterance tail -- with the LM every entry
+//    gains its end-of-utterance terms (lm_final_total) and the best total wins, ties to the lower rank; LM-free entry 0.
+// result[s] = {length of the hypothesis, new stable_len, log-probability (float bits), status}; tail[s][i] = label stable_len_old + i
+// of the hypothesis for i < max_tail.
+constexpr int kNoState = 2;
+template <int MAXB, bool LM>
+__global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict__ table, int W, char* __restrict__ state, long state_stride,
+                                                           const int2* __restrict__ node_pool, long pool_stride,
+                                                           int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma) {
+  __shared__ float fin[MAXB];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int count = table[4 * s + 1], limit = table[4 * s + 2], reset = table[4 * s + 3];
+  if (count == 0 && limit < 0 && !reset) return;
+  char* rec = state + s * state_stride;
+  StreamHeader* hdr = reinterpret_cast<StreamHeader*>(rec);
+  int* res = result + 4 * s;
+  const int nb = min(max(hdr->nb, 0), W);
+  if (hdr->magic != stream_magic(W, LM) || nb == 0) {
+    if (lane == 0) {
+      res[0] = 0; res[1] = 0; res[2] = __float_as_int(-INFINITY); res[3] = kNoState;
+    }
+    return;
+  }
+  const BeamSet<MAXB>& S = *reinterpret_cast<const BeamSet<MAXB>*>(rec + kStateHeader);
+  const int2* __restrict__ nodes = node_pool + s * pool_stride;
+  const int stable0 = hdr->stable_len;
+  // the reported entry and its total
+  int e0 = 0;
+  float v0 = S.total[0];
+  if constexpr (LM) {
+    if (limit >= 0) {
+      const LmSet<MAXB>& L = *reinterpret_cast<const LmSet<MAXB>*>(rec + kStateHeader + sizeof(BeamSet<MAXB>));
+      const float* deltas = reinterpret_cast<const float*>(rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>));
+      const LmParams lmp{lma.v, lma.w[0][0], lma.w[0][1], lma.w[0][2], lma.oov_score};
+      for (int e = lane; e < nb; e += 64) fin[e] = lm_final_total(lmp, L, deltas + (long)e * kDeltaPitch, S.total[e], e);
+      __syncthreads();
+      for (int e = 1; e < nb; ++e)
+        if (fin[e] > fin[e0]) e0 = e;
+      v0 = fin[e0];
+    }
+  }
+  // the common prefix: no longer than the shortest live entry
+  unsigned shortest = 0x7fffffffu;
+#pragma unroll
+  for (int e = lane; e < MAXB; e += 64)
+    if (e < nb) shortest = min(shortest, (unsigned)S.len[e]);
+  const int minlen = (int)wave_min_u32(shortest);
+  const int len_r = S.len[0];
+  int lcp = minlen;
+#pragma unroll
+  for (int e = lane; e < MAXB; e += 64) {
+    if (e == 0 || e >= nb) continue;
+    int a = S.node[e], r = S.node[0];
+    for (int p = S.len[e] - 1; p >= minlen; --p) a = nodes[a].x;
+    for (int p = len_r - 1; p >= minlen; --p) r = nodes[r].x;
+    for (int p = minlen - 1; p >= stable0 && a != r; --p) {
+      const int2 na = nodes[a], nr = nodes[r];
+      if (na.y != nr.y) lcp = min(lcp, p);                       // (a lane's second entry must not raise the first one's)
+      a = na.x;
+      r = nr.x;
+    }
+  }
+  const int stable = max((int)wave_min_u32((unsigned)lcp), stable0);
+  if (lane == 0) {
+    const int len0 = S.len[e0];
+    int id = S.node[e0];
+    for (int p = len0 - 1; p >= stable0; --p) {
+      const int2 nd = nodes[id];
+      if (p - stable0 < max_tail) tail[(long)s * max_tail + (p - stable0)] = nd.y;
+      id = nd.x;
+    }
+    res[0] = len0;
+    res[1] = stable;
+    res[2] = __float_as_int((float)((double)v0 + hdr->offset));
+    res[3] = hdr->status;
+    hdr->stable_len = stable;
   }
 }
 
@@ -997,6 +1205,132 @@ int st_ctc_beam_search_decode_lm_nbest(const st_tensor3* logits, const int32_t* 
   const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
   return beam_search_lm_launch(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, n_best, ids, max_out, out_lens,
                                log_prob, n_hyps, workspace, workspace_bytes, stream);
+}
+
+// ---- the search carried across steps --------
+
+size_t st_ctc_beam_stream_state_bytes(int beam_width, int lm) {
+  if (beam_width < 1 || beam_width > kMaxBeam) return 0;
+  return st::round_up(beam_width > 64 ? stream_state_bytes<128>(lm != 0) : stream_state_bytes<64>(lm != 0), 64);
+}
+
+size_t st_ctc_beam_stream_pool_bytes(int max_frames, int beam_width) {
+  if (max_frames < 1 || beam_width < 1 || beam_width > kMaxBeam) return 0;
+  return st::round_up(((size_t)max_frames * beam_width + 1) * sizeof(int2), 64);
+}
+
+size_t st_ctc_beam_stream_ws(int max_rows) {
+  return max_rows <= 0 ? 0 : (size_t)max_rows * kMaxClasses * sizeof(float);
+}
+
+// what the two entry points share: the arguments' checks and the scorer's kernel argument (lm NULL: the LM-free search)
+static int beam_stream_common(const char* who, const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight,
+                              float word_count_weight, float valid_word_count_weight, float oov_score, void* state, const void* pool,
+                              int max_frames, void* stream, LmArgs* lma) {
+  ST_REQUIRE(table && state && pool, "%s: null argument", who);
+  ST_REQUIRE(max_streams >= 1, "%s: max_streams must be positive, got %d", who, max_streams);
+  ST_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, "%s: beam width 1..%d supported, got %d", who, kMaxBeam, beam_width);
+  ST_REQUIRE(max_frames >= 1 && (long)max_frames * beam_width + 1 <= 0x7fffffffL, "%s: max_frames %d with beam %d: the node ids are 31 bits",
+             who, max_frames, beam_width);
+  ST_REQUIRE(reinterpret_cast<uintptr_t>(state) % 8 == 0 && reinterpret_cast<uintptr_t>(pool) % 8 == 0,
+             "%s: state and pool must be 8-byte aligned", who);
+  *lma = LmArgs{};
+  if (!lm) return ST_OK;
+  ST_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_count_weight) && std::isfinite(valid_word_count_weight) &&
+                 std::isfinite(oov_score), "%s: weights and oov_score must be finite", who);
+  int device = -1;
+  if (hipStreamGetDevice(st::as_stream(stream), &device) != hipSuccess) {
+    st::set_error("%s: hipStreamGetDevice failed", who);
+    return ST_ELAUNCH;
+  }
+  const stlm::DeviceCopy* copy = static_cast<const stlm::Model*>(lm)->on(device);
+  ST_REQUIRE(copy, "%s: the language model is not on device %d (st_lm_upload with a stream of that device)", who, device);
+  lma->v = copy->view;
+  lma->oov_score = oov_score;
+  lma->w[0][0] = lm_weight; lma->w[0][1] = word_count_weight; lma->w[0][2] = valid_word_count_weight;
+  return ST_OK;
+}
+
+int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  const char* who = "beam stream step";
+  ST_REQUIRE(logits && rows, "%s: null argument", who);
+  ST_REQUIRE(input_transform == 0 || input_transform == 1, "%s: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d", who,
+             input_transform);
+  if (lm)
+    ST_REQUIRE(num_classes == kSpace + 2, "%s: with a language model the classes must be a-z ' space blank (%d), got %d", who, kSpace + 2,
+               num_classes);
+  ST_REQUIRE(num_classes >= 2 && num_classes <= kMaxClasses && pitch >= num_classes, "%s: 2..%d classes at a pitch >= classes, got %d at %d",
+             who, kMaxClasses, num_classes, pitch);
+  ST_REQUIRE(n_rows >= 0, "%s: negative row count %d", who, n_rows);
+  LmArgs lma;
+  if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
+                                 state, pool, max_frames, stream, &lma))
+    return e;
+  const size_t need = st_ctc_beam_stream_ws(n_rows);
+  if (need && (!workspace || workspace_bytes < need)) {
+    st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    return ST_EWORKSPACE;
+  }
+  hipStream_t s = st::as_stream(stream);
+  float* lp_rows = reinterpret_cast<float*>(workspace);
+  if (n_rows > 0)
+    hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
+                       input_transform, lp_rows);
+  const bool wide = beam_width > 64;
+  if (lm)
+    st::trace("ctc_beam_stream_lm<%s> beam=%d transform=%d order=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width,
+              input_transform, lma.v.order, max_streams, n_rows);
+  else
+    st::trace("ctc_beam_stream<%s> beam=%d transform=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width, input_transform,
+              max_streams, n_rows);
+  const StreamArgs<true> sx{rows, table, static_cast<char*>(state), (long)st_ctc_beam_stream_state_bytes(beam_width, lm != nullptr),
+                            max_frames};
+  const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));   // pairs per stream
+  const int per_lane = st::ceil_div(beam_width * num_classes, 64);
+#define ST_LAUNCH_STREAM_AS(CPL, MAXB, LM)                                                                            \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, LM, false, true>), dim3(max_streams), dim3(64), 0, s, lp_rows, 0, num_classes, \
+                     (const int*)nullptr, beam_width, reinterpret_cast<int2*>(pool), pool_stride, \
+                     (int*)nullptr, 0, (int*)nullptr, (float*)nullptr, lma, NbestArgs<false>{}, sx)
+#define ST_LAUNCH_STREAM(CPL, MAXB)                                                                                   \
+  do {                                                                                                                \
+    if (lm) ST_LAUNCH_STREAM_AS(CPL, MAXB, true);                                                                      \
+    else ST_LAUNCH_STREAM_AS(CPL, MAXB, false);                                                                        \
+  } while (0)
+  if (wide) ST_LAUNCH_STREAM(64, 128);
+  else if (per_lane <= 4) ST_LAUNCH_STREAM(4, 64);
+  else if (per_lane <= 8) ST_LAUNCH_STREAM(8, 64);
+  else if (per_lane <= 16) ST_LAUNCH_STREAM(16, 64);
+  else ST_LAUNCH_STREAM(32, 64);
+#undef ST_LAUNCH_STREAM
+#undef ST_LAUNCH_STREAM_AS
+  return st::check_launch("ctc_beam_stream_step");
+}
+
+int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                            int32_t* tail, int max_tail, int32_t* result, void* stream) {
+  const char* who = "beam stream read";
+  ST_REQUIRE(tail && result, "%s: null argument", who);
+  ST_REQUIRE(max_tail >= 1, "%s: max_tail must be positive, got %d", who, max_tail);
+  LmArgs lma;
+  if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
+                                 state, pool, max_frames, stream, &lma))
+    return e;
+  const bool wide = beam_width > 64;
+  st::trace("ctc_beam_stream_read<%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", beam_width, max_streams);
+  const long stride = (long)st_ctc_beam_stream_state_bytes(beam_width, lm != nullptr);
+  const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));
+#define ST_LAUNCH_READ(MAXB, LM)                                                                                      \
+  hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM>), dim3(max_streams), dim3(64), 0, st::as_stream(stream), table, beam_width, \
+                     static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
+                     tail, max_tail, result, lma)
+  if (wide) { if (lm) ST_LAUNCH_READ(128, true); else ST_LAUNCH_READ(128, false); }
+  else { if (lm) ST_LAUNCH_READ(64, true); else ST_LAUNCH_READ(64, false); }
+#undef ST_LAUNCH_READ
+  return st::check_launch("ctc_beam_stream_read");
 }
 
 }  // extern "C"

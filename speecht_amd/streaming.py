@@ -13,6 +13,13 @@ the device.
 A stream's logits are bit-identical however its audio was cut into chunks and whatever the other streams were doing: the
 product kernel cuts every layer's reduction into slices that depend on the layer's shape only and sums them in slice order.
 The arithmetic is fp32 (the engine's packed fp32 masters) whatever mode the engine trains in.
+
+With ``beam=StreamBeam(...)`` a step also advances a CTC prefix beam search per stream -- LM-free or scored by a word n-gram
+model, the searches of `transcribe` -- whose state (the live beam set, its LM states, the node pool) stays on the device between
+steps.  A chunked search is the whole-utterance search: after `finish` the hypothesis and its log-probability are what
+``engine.beam_search_decode`` / ``lm_beam_search_decode`` return on the stream's logits, bit for bit and however the audio was cut.
+Before that a step reports the best hypothesis so far and how many of its leading ids are final (the common prefix of all live
+entries).  Such a stream can decode ``StreamBeam.max_seconds`` of audio: its node pool is sized when the recogniser is built.
 """
 import ctypes
 
@@ -24,7 +31,9 @@ from ._lib import call
 
 
 class StreamError(ValueError):
-  """A request the recogniser refuses; nothing was launched and no stream's state has changed."""
+  """A request the recogniser refuses; nothing was launched and no stream's state has changed.  (One exception: a beam search
+  whose read-out gave up -- more labels still open than ``max_tail`` -- is reported after its step; that stream can only be
+  closed, the others go on, and their results of the step are in the exception's ``result``.)"""
 
 
 # ---- index arithmetic (csrc/stream_map.h) ---------------------------------------------------------------------------------
@@ -126,12 +135,41 @@ def first_row_after(layers):
 
 # ---- the session ----------------------------------------------------------------------------------------------------------
 
+class StreamBeam:
+  """The beam search of a `StreamingRecognizer` (st_ctc_beam_stream_step / _read): the prefix beam search of
+  ``engine.beam_search_decode`` -- with ``lm`` (a `language_model.LanguageModel` or the path of an ARPA file) that of
+  ``engine.lm_beam_search_decode`` -- carried across steps, with those methods' defaults: beam 16 on the logits without a model,
+  beam 100 on log10(softmax + 1e-8) with one.  ``max_seconds`` sizes every stream's node pool (8 B x beam x 50 output frames per
+  second of audio); ``max_tail`` is the longest run of not yet final labels a step can report."""
+
+  def __init__(self, beam_width=None, lm=None, lm_weight=0.8, word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0,
+               input_transform='default', max_seconds=120.0, max_tail=256):
+    if isinstance(lm, str):
+      from .language_model import LanguageModel
+      lm = LanguageModel.load(lm)
+    self.lm = lm
+    self.beam_width = int(beam_width) if beam_width else (100 if lm is not None else 16)
+    if input_transform == 'default':
+      input_transform = 'log10_softmax' if lm is not None else None
+    self.input_transform = input_transform
+    self.lm_weight, self.word_count_weight = float(lm_weight), float(word_count_weight)
+    self.valid_word_count_weight, self.oov_score = float(valid_word_count_weight), float(oov_score)
+    self.max_seconds, self.max_tail = float(max_seconds), int(max_tail)
+    if not 1 <= self.beam_width <= 128:
+      raise StreamError('beam width 1..128 supported, got {}'.format(self.beam_width))
+    if self.max_seconds <= 0 or self.max_tail < 1:
+      raise StreamError('max_seconds and max_tail must be positive')
+
+
 class StepResult:
   """What one `step` / `finish` produced: ``ids[slot]`` new label ids, ``logits[slot]`` new rows [r, C] (on request),
-  ``score[slot]`` the running negative sum of the chosen logits."""
+  ``score[slot]`` the running negative sum of the chosen logits.  With a beam search also ``hyp[slot]``, all ids of the best
+  hypothesis so far, ``stable[slot]``, how many of its leading ids are final, and ``logp[slot]``, its log-probability (after
+  `finish`: what the whole-utterance search returns); ``ids`` and ``score`` stay the greedy ones."""
 
   def __init__(self):
     self.ids, self.logits, self.score = {}, {}, {}
+    self.hyp, self.stable, self.logp = {}, {}, {}
 
 
 class StreamingRecognizer:
@@ -140,9 +178,12 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64):
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None):
+    """``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
+    ``logp``); None: greedy decoding only."""
     if max_streams < 1 or max_chunk_frames < 1:
       raise StreamError('max_streams and max_chunk_frames must be positive')
+    self.beam = beam
     self.engine, self.device = engine, engine.device
     self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
     self.layers = engine.layers
@@ -167,10 +208,30 @@ class StreamingRecognizer:
       self.dec_state = torch.zeros(S * 4, dtype=torch.int32, device=dev)
       self.dec_score = torch.zeros(S, dtype=torch.float64, device=dev)
       # the decoder's outputs in one buffer, so that a step's results come back with one copy: [ids | counts | scores]
-      self.dec_out = torch.zeros(S * self.max_new + 2 * S, dtype=torch.int32, device=dev)
+      # (with a beam search: ... | result [S][4] | tail [S][max_tail])
+      greedy_words = S * self.max_new + 2 * S
+      self.dec_out = torch.zeros(greedy_words + (S * (4 + beam.max_tail) if beam else 0), dtype=torch.int32, device=dev)
       self.ids = self.dec_out[:S * self.max_new]
       self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
-      self.neg_sum = self.dec_out[S * self.max_new + S:].view(torch.float32)
+      self.neg_sum = self.dec_out[S * self.max_new + S:greedy_words].view(torch.float32)
+      if beam:
+        if beam.lm is not None and self.num_classes != 29:
+          raise StreamError('a language model needs the 29 classes a-z \' space blank, the engine has {}'.format(self.num_classes))
+        if not 2 <= self.num_classes <= 32:
+          raise StreamError('the beam search supports 2..32 classes, the engine has {}'.format(self.num_classes))
+        total_stride = int(np.prod([s for _, s in self.geo]))
+        self.max_frames = int(np.ceil(beam.max_seconds * 100.0 / total_stride - 1e-9))   # output frames (10 ms hop)
+        self._lm_handle = beam.lm.device_handle(dev) if beam.lm is not None else None
+        from .engine_decode import beam_input_transform
+        self._transform = beam_input_transform(beam.input_transform)
+        state_bytes = int(lib.st_ctc_beam_stream_state_bytes(beam.beam_width, int(beam.lm is not None)))
+        pool_bytes = int(lib.st_ctc_beam_stream_pool_bytes(self.max_frames, beam.beam_width))
+        self.beam_ws_bytes = int(lib.st_ctc_beam_stream_ws(self.max_rows[-1]))
+        self.beam_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
+        self.beam_pool = torch.empty(S * pool_bytes // 8, dtype=torch.int64, device=dev)     # (a chain only holds written nodes)
+        self.beam_ws = torch.empty(self.beam_ws_bytes // 4, dtype=torch.float32, device=dev)
+        self.beam_result = self.dec_out[greedy_words:greedy_words + 4 * S]
+        self.beam_tail = self.dec_out[greedy_words + 4 * S:]
       table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
       for i, l in enumerate(self.layers):
         table[2 * i] = self.windows[i].data_ptr()
@@ -180,6 +241,10 @@ class StreamingRecognizer:
     self._open, self._fresh, self._finished = (np.zeros(S, dtype=bool) for _ in range(3))
     self._n, self._e = np.zeros((S, L), dtype=np.int64), np.zeros((S, L), dtype=np.int64)
     self._total = np.zeros(S, dtype=np.int64)
+    # beam search: output frames decoded per stream (the pool's capacity is checked before a launch), the last hypothesis read
+    # (its first `_stable` ids are final: the device reports only what follows them), and the streams a read-out gave up on
+    self._frames, self._stable, self._failed = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64), np.zeros(S, dtype=bool)
+    self._hyp, self._logp = [[] for _ in range(S)], np.zeros(S, dtype=np.float32)
     self._info = np.zeros((L, S, 4), dtype=np.int32)             # {base, n, base, 0} of every stream between steps
     self.launches = 0            # kernels enqueued by the last pass (products count two: slices + epilogue)
 
@@ -193,6 +258,7 @@ class StreamingRecognizer:
     self._open[i], self._fresh[i], self._finished[i] = True, True, False     # the first step resets the slot's decoder state;
     self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
     self._info[:, i] = 0                                                       # [0, n) are never read
+    self._frames[i], self._stable[i], self._failed[i], self._hyp[i], self._logp[i] = 0, 0, False, [], 0.0
     return i
 
   def close(self, slot):
@@ -205,6 +271,8 @@ class StreamingRecognizer:
       raise StreamError('stream {} is not open'.format(slot))
     if self._finished[slot] and not allow_finished:
       raise StreamError('stream {} has been finished: close it and open a new one'.format(slot))
+    if self._failed[slot] and not allow_finished:
+      raise StreamError('stream {}: its beam search has failed: close it and open a new one'.format(slot))
 
   # -- steps --
 
@@ -234,6 +302,8 @@ class StreamingRecognizer:
     result = StepResult()
     for slot in list(arrays) + [int(s) for s in finishing]:
       result.ids[slot], result.score[slot] = [], 0.0
+      if self.beam:
+        result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(self._logp[slot])
       if return_logits:
         result.logits[slot] = []
     longest = max([a.shape[0] for a in arrays.values()] + [0])
@@ -259,6 +329,15 @@ class StreamingRecognizer:
       k, l = np.argwhere(over)[0]
       raise StreamError('stream {}: layer {} would overrun its window ({} frames, capacity {})'.format(
           int(named[k]), int(l), int(n_after[k, l] - base[k, l]), self.cap[l]))
+    limit = np.where(fin, (self._total[named] + new) // 2, -1)
+    if self.beam:
+      # rows the searches will take (those at or past a finishing stream's limit are not decoded) against the pools' capacity
+      taken = np.where(fin, np.clip(limit - first[:, -1], 0, count[:, -1]), count[:, -1])
+      full = self._frames[named] + taken > self.max_frames
+      if full.any():
+        k = int(np.flatnonzero(full)[0])
+        raise StreamError('stream {}: {} output frames would pass the beam search\'s node pool ({} frames, max_seconds = {})'.format(
+            int(named[k]), int(self._frames[named[k]] + taken[k]), self.max_frames, self.beam.max_seconds))
     info = self._info.copy()                                     # streams that sit this step out keep their windows
     info[:, named, 0], info[:, named, 1], info[:, named, 2] = base.T, n_after.T, new_base.T
 
@@ -302,6 +381,21 @@ class StreamingRecognizer:
     call('st_ctc_greedy_stream', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), S, ptr(self.dec_state),
          ptr(self.dec_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum), sp)
     self.launches += 2
+    if self.beam:
+      # the beam searches take the same rows through the same table; the read-out only when its result is fetched (so that
+      # the labels the device has declared final are exactly those the host holds)
+      bm = self.beam
+      lm_args = (self._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score)
+      call('st_ctc_beam_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]), S,
+           bm.beam_width, self._transform, *lm_args, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
+           self.beam_ws_bytes, sp)
+      self.launches += 2 if len(rows[-1]) else 1
+      if fetch:
+        call('st_ctc_beam_stream_read', tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
+             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp)
+        self.launches += 1
+      read = (count[:, -1] > 0) | fin | self._fresh[named]       # the streams the read-out reports on
+      self._frames[named] = np.where(self._fresh[named], 0, self._frames[named]) + taken
     # 4. the host's counters follow; nothing above waited
     self._n[named], self._e[named] = n_after, first + count
     self._total[named] += new
@@ -321,6 +415,26 @@ class StreamingRecognizer:
     for s in named.tolist():
       result.ids[s] += ids[s, :counts[s]].tolist()
       result.score[s] = float(score[s])
+    if self.beam:
+      g = S * self.max_new + 2 * S
+      res, tail = words[g:g + 4 * S].reshape(S, 4), words[g + 4 * S:].reshape(S, self.beam.max_tail)
+      failed = None
+      for k, s in enumerate(named.tolist()):
+        if read[k]:
+          length, stable, old = int(res[s, 0]), int(res[s, 1]), int(self._stable[s])
+          if res[s, 3] != 0 or length - old > self.beam.max_tail or length < old:
+            self._failed[s] = True
+            why = ('status {}'.format(int(res[s, 3])) if res[s, 3] != 0 else
+                   '{} labels are not final yet, max_tail = {}'.format(length - old, self.beam.max_tail))
+            failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
+            continue
+          self._hyp[s] = self._hyp[s][:old] + tail[s, :length - old].tolist()
+          self._stable[s] = length if fin[k] else stable           # a finished stream's hypothesis is final as a whole
+          self._logp[s] = res[s, 2:3].view(np.float32)[0]
+        result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
+      if failed is not None:
+        failed.result = result                                    # the other streams' results of this step
+        raise failed
 
   def _upload(self, array, dtype):
     """Host array -> device as a stream operation (pinned staging from torch's caching host allocator: no wait for the stream's
@@ -498,23 +612,32 @@ class StreamingFeatures:
         result[s].append(view[s, :count].cpu().numpy())
 
 
-def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False):
+def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False, beam=None):
   """One stream: feed the feature chunks ([t, C] each) in order, finish, and return ``(ids, partials)`` -- all label ids and the
-  list of (input frames so far, ids so far) after every chunk that produced any -- plus the logits [T', C] on request."""
-  rec = StreamingRecognizer(engine, 1, max_chunk_frames)
+  list of (input frames so far, ids so far) after every chunk that produced any -- plus the logits [T', C] on request.
+  ``beam`` (a `StreamBeam`): the ids are the beam search's hypothesis -- at the end the whole-utterance search's result -- and a
+  partial is (input frames so far, hypothesis so far, how many of its leading ids are final) after every chunk that changed either."""
+  rec = StreamingRecognizer(engine, 1, max_chunk_frames, beam=beam)
   slot = rec.open()
   ids, partials, rows, frames = [], [], [], 0
   for chunk in chunks:
     r = rec.step({slot: chunk}, return_logits=return_logits)
     frames += len(chunk)
-    if r.ids[slot]:
+    if beam:
+      if not partials or (r.hyp[slot], r.stable[slot]) != partials[-1][1:]:
+        partials.append((frames, r.hyp[slot], r.stable[slot]))
+    elif r.ids[slot]:
       ids += r.ids[slot]
       partials.append((frames, list(ids)))
     if return_logits:
       rows.append(r.logits[slot])
   r = rec.finish(slot, return_logits=return_logits)
-  ids += r.ids[slot]
-  partials.append((frames, list(ids)))
+  if beam:
+    ids = r.hyp[slot]
+    partials.append((frames, ids, r.stable[slot]))
+  else:
+    ids += r.ids[slot]
+    partials.append((frames, list(ids)))
   rec.close(slot)
   if return_logits:
     rows.append(r.logits[slot])
@@ -536,19 +659,26 @@ def _pcm_chunks(stream, samples_per_chunk):
       yield np.frombuffer(data, dtype='<i2').astype(np.float32) / 32768.0
 
 
-def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None):
+def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
   ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
-  which are then fed piece by piece -- not live; it yields what `transcribe --batch-size 1` yields and exists for comparison."""
+  which are then fed piece by piece -- not live; it yields what `transcribe --batch-size 1` yields and exists for comparison.
+  ``beam`` (a `StreamBeam`): the ids are the beam search's -- at the end the whole-utterance search's result -- and
+  ``on_partial(seconds, hypothesis so far, how many of its leading ids are final)`` is called whenever either has changed."""
   hop = 160
   if normalize not in ('running', 'file'):
     raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
-  ids, fed = [], 0
+  ids, fed, last = [], 0, [([], 0)]
 
   def feed(rec, slot, feats, seconds):
     r = rec.step({slot: feats})
-    if r.ids[slot]:
+    if beam:
+      if (r.hyp[slot], r.stable[slot]) != last[0]:
+        last[0] = (r.hyp[slot], r.stable[slot])
+        if on_partial:
+          on_partial(seconds, list(r.hyp[slot]), r.stable[slot])
+    elif r.ids[slot]:
       ids.extend(r.ids[slot])
       if on_partial:
         on_partial(seconds, list(ids))
@@ -563,7 +693,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     front.step({slot: y})
     feats = front.finish(slot)
     per = max(max(len(p) for p in pieces) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8))
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam)
     rslot = rec.open()
     for at in range(0, len(feats), per):
       feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
@@ -572,7 +702,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     max_piece = int(max_piece or 16000)
     front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
     slot = front.open()
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8))
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam)
     rslot = rec.open()
     for p in pieces:
       p = np.asarray(p, np.float32)
@@ -582,13 +712,17 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
       raise StreamError('too short: {} samples (the features need more than {})'.format(fed, N_FFT // 2))
     feed(rec, rslot, front.finish(slot), fed / float(samplerate))
   r = rec.finish(rslot)
+  if beam:
+    return r.hyp[rslot], fed / float(samplerate)
   ids.extend(r.ids[rslot])
   return ids, fed / float(samplerate)
 
 
 def run_cli(flags):
   """`speecht-cli stream PATH|-`: one line "seconds<TAB>transcript so far" per step that produced text, then the final transcript
-  as `transcribe` prints it ("path<TAB>transcript").  Creates no train / data / log directory."""
+  as `transcribe` prints it ("path<TAB>transcript").  With --language-model or --beam-width (the flags of `transcribe`, with their
+  meaning there) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
+  leading characters that are final".  Creates no train / data / log directory."""
   import contextlib
   import sys
   from . import transcription, vocabulary
@@ -601,6 +735,13 @@ def run_cli(flags):
   with contextlib.redirect_stdout(sys.stderr):          # stdout carries the transcripts only
     model = create_default_model(flags, input_size, SingleInputLoader(input_size))
   try:
+    beam = None
+    if getattr(flags, 'language_model', None) or getattr(flags, 'beam_width', 0):
+      from .language_model import LanguageModel
+      lm = LanguageModel.load(flags.language_model) if flags.language_model else None
+      # a stream's length is not known when it starts: an hour of node pool unless the file says less
+      beam = dict(beam_width=flags.beam_width or None, lm=lm, lm_weight=flags.lm_weight, word_count_weight=flags.word_count_weight,
+                  valid_word_count_weight=flags.valid_word_count_weight, input_transform=flags.beam_input or 'default', max_seconds=3600.0)
     if flags.path == '-':
       rate = int(flags.sample_rate)
       per = max(int(rate * flags.chunk_ms / 1000.0), 1)
@@ -612,9 +753,15 @@ def run_cli(flags):
     with Session(flags.device) as sess:
       with contextlib.redirect_stdout(sys.stderr):
         model.restore(sess, flags.run_train_dir)
-      partial = lambda seconds, ids: print('{:.2f}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids)), flush=True)
-      ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per)
-  except (StreamError, transcription.TranscriptionError) as e:
+      if beam:
+        if flags.path != '-':
+          beam['max_seconds'] = len(samples) / float(rate) + 1.0
+        partial = lambda seconds, ids, stable: print('{:.2f}\t{}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids), stable), flush=True)
+        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per, beam=StreamBeam(**beam))
+      else:
+        partial = lambda seconds, ids: print('{:.2f}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids)), flush=True)
+        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per)
+  except (StreamError, transcription.TranscriptionError, ValueError) as e:
     print('stream: {}'.format(e), file=sys.stderr)
     return 1
   print('{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids)), flush=True)
