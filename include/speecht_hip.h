@@ -906,6 +906,32 @@ int st_melspec_stream_f32(const float* samples, const int32_t* table, int n_pair
                           size_t state_bytes, float* out, int out_cap, int max_rows, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- SpecAugment while the batch is loaded (csrc/spec_augment.hip, csrc/spec_augment_core.h; no reference counterpart: the
+ * reference trains without augmentation).  The copy of a staged feature batch src [batch][frames][channels] (fp32, contiguous) into
+ * the padded input tensor `dst`, with every utterance's time warp, frequency masks and time masks (Park et al. 2019) applied on the
+ * way: one launch, the bytes of the plain copy.  Only interior rows and the valid channels of dst are written; rows at or past an
+ * utterance's seq_len get the source's rows unchanged.  Masked elements become 0 (the features are zero-mean per utterance).
+ *   policy    time_warp W (largest displacement, frames; the warp applies to utterances of at least 2W + 2 frames), freq_masks
+ *             masks of width 0 .. min(freq_width, channels), time_masks masks of width 0 .. min(time_width, floor(p seq_len)) with
+ *             p = time_ratio_q16 / 65536 (0 .. 65536); 0 .. 8 masks of each kind.  All zero: the plain copy, bit for bit.
+ *   seq_lens  int32 [batch], the utterances' own lengths (0 .. frames; the kernel clamps, the host forms refuse others)
+ *   draw_ids  int64 [batch]: with `seed` the whole source of an utterance's randomness (Philox4x32-10, key = seed, counter =
+ *             {draw id, block, 0}; which block and word feeds which draw: csrc/spec_augment_core.h).  Nothing depends on the
+ *             utterance's row, the batch size, the padded length or the rest of the batch.
+ *   plan_out  optional int32 [batch][2 + 2 (freq_masks + time_masks)]: per utterance {c, w, (f0, f) per frequency mask, (t0, t)
+ *             per time mask}; the warp maps output row c + w to source row c, c = w = 0 when the utterance is not warped.
+ * st_spec_augment_host: the same on HOST pointers (dst->base a host buffer of the same geometry), bit-identical to the kernel: the
+ *   two share their arithmetic.  st_spec_augment_plan_host: the plans only (any length >= 0).  Neither needs a GPU. */
+int st_spec_augment_f32(const float* src, int batch, int frames, int channels, const int32_t* seq_lens, const int64_t* draw_ids,
+                        uint64_t seed, int time_warp, int freq_width, int freq_masks, int time_width, int time_masks,
+                        int time_ratio_q16, const st_tensor3* dst, int32_t* plan_out, void* stream);
+int st_spec_augment_host(const float* host_src, int batch, int frames, int channels, const int32_t* host_seq_lens,
+                         const int64_t* host_draw_ids, uint64_t seed, int time_warp, int freq_width, int freq_masks, int time_width,
+                         int time_masks, int time_ratio_q16, const st_tensor3* host_dst, int32_t* host_plan_out);
+int st_spec_augment_plan_host(const int32_t* host_seq_lens, const int64_t* host_draw_ids, int batch, int channels, uint64_t seed,
+                              int time_warp, int freq_width, int freq_masks, int time_width, int time_masks, int time_ratio_q16,
+                              int32_t* host_plan_out);
+
 /* ---- helpers -------------------------------------------------------------------------- */
 int st_fill_f32(float* dst, float value, size_t n, void* stream);
 /* zero the halo rows of a padded NWC tensor (needed when a buffer is re-described for a new shape) */

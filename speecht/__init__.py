@@ -8,7 +8,7 @@ import importlib
 import sys
 
 _MODULES = ('vocabulary', 'preprocessing', 'speech_input', 'speech_model', 'evaluation', 'training', 'execution', 'exporting',
-            'parameter_search')
+            'parameter_search', 'augmentation')
 _OUT_OF_SCOPE = ('corpus', 'recording', 'record_utils')
 
 

@@ -229,6 +229,12 @@ _SIGNATURES = {
                                         c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'st_ctc_beam_stream_read': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
                                         c_void_p, c_int, c_void_p, c_void_p]),
+    'st_spec_augment_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, _T3P, c_void_p, c_void_p]),
+    'st_spec_augment_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, _T3P, c_void_p]),
+    'st_spec_augment_plan_host': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p]),
     'st_fill_f32': (c_int, [c_void_p, c_float, c_size_t, c_void_p]),
     'st_zero_halos_f32': (c_int, [_T3P, c_void_p]),
     'st_zero_regions': (c_int, [c_void_p, c_int, c_void_p]),

@@ -104,6 +104,7 @@ class Wav2LetterEngine(DecodeMixin):
     self._h2d, self._pin_ring, self._pin_turn = None, [[None, None] for _ in range(8)], 0
     self._up_stream, self._uploads = None, []
     self.max_label_len, self._rejected_labels, self.defer_label_errors = 0, [], False
+    self.augment_plan = None                       # int32 [B, 2 + 2 (mF + mT)] on the device: what the last augmented load_batch drew
     # the side streams of `_on_side_stream` and the event each one's last chain ended with; forward graphs by (shape, generation)
     self._side = self._side2 = self._side_done = self._side2_done = None
     self._graphs, self._graph_seen = {}, set()
@@ -404,9 +405,11 @@ class Wav2LetterEngine(DecodeMixin):
 
   # ---- the path ----------------------------------------------------------------------------
 
-  def load_batch(self, inputs, seq_lens):
+  def load_batch(self, inputs, seq_lens, augment=None):
     """inputs: [B, T, input_size] (numpy or torch, any float dtype, or a ``speech_input.StagedBatch`` that the
-    input pipeline already copied to the device); seq_lens: [B] unpadded frames."""
+    input pipeline already copied to the device); seq_lens: [B] unpadded frames.  ``augment``: an
+    ``augmentation.SpecAugment`` with one draw id per row -- the copy into the input tensor becomes the SpecAugment
+    kernel (st_spec_augment_f32) and ``self.augment_plan`` the device table of what was drawn."""
     if hasattr(inputs, 'event') and hasattr(inputs, 'tensor'):
       stream = self.stream
       stream.wait_event(inputs.event)              # H2D ran on the pipeline's copy stream
@@ -418,6 +421,8 @@ class Wav2LetterEngine(DecodeMixin):
     B, T, C = x.shape
     assert C == self.layers[0].cin, 'input_size mismatch'
     self._ensure_shape(B, T)
+    if augment is not None:
+      return self._load_augmented(x, seq_lens, augment, staged)
     self.shape.X[0].interior().copy_(x.to(torch.float32), non_blocking=True)
     if staged is not None and hasattr(staged, 'consumed'):
       staged.taken = True
@@ -425,6 +430,40 @@ class Wav2LetterEngine(DecodeMixin):
     self.seq_lens_host = np.asarray(seq_lens, dtype=np.int64)
     # the reference feeds sequence_lengths // 2 to CTC and the decoder (speech_model.py:74,114)
     self.ctc_lens = self._upload_i32((self.seq_lens_host // 2).astype(np.int32))
+
+  def _load_augmented(self, x, seq_lens, augment, staged):
+    """The rest of `load_batch` with SpecAugment: the batch goes into X[0] through st_spec_augment_f32 instead of the copy -- same
+    bytes read and written, each utterance's time warp and masks applied on the way.  The draw ids, the real lengths (not the // 2
+    CTC gets) and CTC's lengths go up in ONE pinned upload; the compute stream waits for it before the launch."""
+    B, T, C = x.shape
+    lens = np.asarray(seq_lens, dtype=np.int64).reshape(-1)
+    ids = None if augment.draw_ids is None else np.ascontiguousarray(augment.draw_ids, dtype=np.int64).reshape(-1)
+    if ids is None or len(ids) != B or len(lens) != B:
+      raise ValueError('load_batch: augmentation needs one draw id and one length per row of the batch of {}'.format(B))
+    if lens.min() < 0 or lens.max() > T:
+      raise ValueError('load_batch: sequence lengths outside 0 .. {} frames'.format(T))
+    policy = augment.policy
+    # {ids as 8-byte words | lengths | (to a 256-byte boundary) lengths // 2}
+    ctc_at = _round_up(3 * B, 64)
+    words = np.zeros(ctc_at + B, dtype=np.int32)
+    words[:2 * B] = ids.view(np.int32)
+    words[2 * B:3 * B] = lens
+    words[ctc_at:] = lens // 2
+    table = self._upload_i32(words)
+    if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+      with torch.cuda.stream(self.stream):           # (a host batch: the H2D copy runs on the compute stream, as the plain path's does)
+        x = x.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+    with torch.cuda.stream(self.stream):
+      plan = torch.empty((B, policy.plan_words), dtype=torch.int32, device=self.device)
+    self._wait_uploads()
+    call('st_spec_augment_f32', self._ptr(x), B, T, C, self._ptr(table[2 * B:]), self._ptr(table), augment.seed, *policy.c_args(),
+         self.shape.X[0].ref, self._ptr(plan), self.stream_ptr)
+    self.augment_plan = plan
+    if staged is not None and hasattr(staged, 'consumed'):
+      staged.taken = True
+      staged.consumed.record(self.stream)
+    self.seq_lens_host = lens
+    self.ctc_lens = table[ctc_at:]
 
   def stage_host_batch(self, x_host):
     """Asynchronous H2D copy of a padded feature batch [B, T, C] (float32; a pinned torch tensor copies without

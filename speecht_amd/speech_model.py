@@ -13,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from . import vocabulary
+from . import augmentation, vocabulary
 from .speech_input import BaseInputLoader, SparseTensorValue, sparse_to_label_lists
 
 
@@ -265,6 +265,7 @@ class SpeechModel:
     self._world = 1
     self._rank = 0
     self._skips_seen = 0
+    self.spec_augment = None
 
   # ---- graph-building protocol ---------------------------------------------------------------
   def _convolution(self, value, filter_width, stride, input_channels, out_channels, apply_non_linearity=True):
@@ -278,9 +279,11 @@ class SpeechModel:
   def _create_network(self, num_classes):
     raise NotImplementedError()
 
-  def add_training_ops(self, learning_rate=1e-3, learning_rate_decay_factor=0, max_gradient_norm=5.0, momentum=0.9):
+  def add_training_ops(self, learning_rate=1e-3, learning_rate_decay_factor=0, max_gradient_norm=5.0, momentum=0.9, spec_augment=None):
     """CTC loss -> mean -> clip_by_global_norm -> Adam(epsilon=1e-3) (speech_model.py:53-82).
-    ``momentum`` is accepted and unused, exactly as in the reference."""
+    ``momentum`` is accepted and unused, exactly as in the reference.  ``spec_augment`` (extension): an
+    ``augmentation.SpecAugment`` (policy + seed) applied to the batches of updating steps, see ``step``."""
+    self.spec_augment = spec_augment
     self.learning_rate = _Scalar(learning_rate, float)
     self.learning_rate_decay_op = self.learning_rate.assign(
         lambda: self.learning_rate.value * learning_rate_decay_factor)
@@ -398,7 +401,13 @@ class SpeechModel:
       labels = feed_dict.get(self.labels, labels) if self.labels is not None else labels
     if (loss or update) and labels is None:
       raise ValueError('loss/update requested but the input loader provides no labels')
-    eng.load_batch(inputs, seq_lens)
+    if update and self.spec_augment is not None:
+      # SpecAugment on updating steps only (evaluation, decoding and update=False steps see the features as they are).  Draw ids:
+      # global_step * global batch + the row in the global batch -- what one process that sees the whole global batch would give
+      # the utterance; global_step is check-pointed, so a resumed run continues the same sequence of draws
+      eng.load_batch(inputs, seq_lens, augment=self.spec_augment.for_step(self.global_step.value, len(seq_lens), self._world, self._rank))
+    else:
+      eng.load_batch(inputs, seq_lens)
     eng.forward()
     out = []
     avg_loss = None
@@ -523,7 +532,8 @@ def create_default_model(flags, input_size: int, speech_input: BaseInputLoader) 
   if flags.command == 'train':
     model.add_training_ops(learning_rate=flags.learning_rate,
                            learning_rate_decay_factor=flags.learning_rate_decay_factor,
-                           max_gradient_norm=flags.max_gradient_norm, momentum=flags.momentum)
+                           max_gradient_norm=flags.max_gradient_norm, momentum=flags.momentum,
+                           spec_augment=augmentation.from_flags(flags))
     model.add_decoding_ops()
   elif flags.command == 'export':
     model.add_training_ops()

@@ -79,6 +79,8 @@ class Training(execution.DatasetExecutor):
       history = []
       steps_done = 0
       print('Begin training')
+      if getattr(model, 'spec_augment', None) is not None:
+        print('SpecAugment: {}; seed {}'.format(model.spec_augment.policy.describe(), model.spec_augment.seed))
       try:
         while not coordinator.should_stop():
           steps_done += 1
