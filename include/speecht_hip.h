@@ -580,6 +580,46 @@ int st_ctc_beam_search_decode_lm_nbest(const st_tensor3* logits, const int32_t* 
                                        float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
                                        int n_best, int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps,
                                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- hotword biasing of both beam searches -----------------------------------------------------------------------------
+ * K phrases of 1..64 ids in 0..27 and one weight w >= 0 per matched character: a hypothesis with prefix x scores, during the search,
+ *   total(x) = CTC mass + lm_weight * LM terms (with a model) + w * (M(x) + r(x)),
+ * M = the characters of completed phrase occurrences banked so far, r = the length of the partial match still open (a partial match
+ * earns credit while it grows and gives it back when it fails); at the end of the utterance w * r(x) is replaced by what the flush
+ * banks.  x is scanned left to right with a state n, a node of the phrases' trie whose path is the open match (the specification,
+ * on strings: tests/hotword_oracle.py):
+ *   - label c, (a): n has a child c: move to it; if that child ends a phrase and has no children, bank its depth, return to the root;
+ *   - label c, (b) otherwise: at the root, stay.  Else let t be the deepest phrase-ending node on n's path (n included): bank
+ *     depth(t) (0 without one), take u = the path without its first depth(t) characters (without its first character if there is
+ *     no t), restart at the root and feed u, then c, by these same rules;
+ *   - end of utterance (flush): repeat the resolution of (b) without a label until the state is the root; what is banked on the
+ *     way counts, the rest is forfeited.
+ * The rules are functions of (n, c) and of n, so the caller tabulates them (speecht_amd/hotwords.py) and the kernels read tables:
+ *   next [n_states][32] int32, gain [n_states][32] float32 = w * (banked + depth(next) - depth(n)), fin [n_states] float32 =
+ *   w * (flush bank - depth(n)); state 0 is the root; columns >= 28 hold the state itself and 0 (a label outside 0..27, which an
+ *   LM-free search of more classes may have, neither advances nor breaks a match).  All three are DEVICE pointers on the device of
+ *   `stream`, read while the search runs; 1 <= n_states <= 2^20.
+ * The state is a function of the prefix alone, so merging prefixes by hash stays correct.  The gain enters wherever the LM's delta
+ * does (child candidates, the stay candidate's parent inflow) and fin with the LM's end-of-utterance delta; BOTH searches then rank
+ * the final set by (final total desc, rank in the set asc).  Everything else -- arguments, checks, workspace (st_ctc_beam_ws),
+ * outputs -- is that of st_ctc_beam_search_decode_nbest / _lm_nbest; the top path of a biased search is its n_best = 1 list.  Tables
+ * of one state, or whose gain and fin are all zero, return the bits of the unbiased entry points.  Every state read from `next` is
+ * clamped to [0, n_states): a malformed table gives wrong text, never a read outside the tables. */
+typedef struct st_bias_tables {
+  const int32_t* next;
+  const float* gain;
+  const float* fin;
+  int32_t n_states;
+} st_bias_tables;
+int st_ctc_beam_search_decode_bias_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                         const st_bias_tables* bias, int n_best, int32_t* ids, int max_out, int32_t* out_lens,
+                                         float* log_prob, int32_t* n_hyps, void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_beam_search_decode_lm_bias_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                            void* lm, float lm_weight, float word_count_weight, float valid_word_count_weight,
+                                            float oov_score, const st_bias_tables* bias, int n_best, int32_t* ids, int max_out,
+                                            int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+
 /* Sentence scores of n label prefixes (ids [n][pitch], lens [n], ids 0..27 = a-z ' space) under a model: what the LM search adds
  * to a final entry, without its weights -- a final total splits exactly as
  *   total = A + lm_weight * (G + word_count_weight * n_words + valid_word_count_weight * n_valid),  A = the acoustic mass;

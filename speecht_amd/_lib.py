@@ -15,6 +15,11 @@ class Tensor3(ctypes.Structure):
               ('halo', c_int32), ('t_pitch', c_int32), ('c_pitch', c_int32)]
 
 
+class BiasTables(ctypes.Structure):
+  """st_bias_tables: the hotword automaton's device tables."""
+  _fields_ = [('next', c_void_p), ('gain', c_void_p), ('fin', c_void_p), ('n_states', c_int32)]
+
+
 class SpeechtHipError(RuntimeError):
   pass
 
@@ -149,6 +154,11 @@ _SIGNATURES = {
                                                 c_void_p, c_size_t, c_void_p]),
     'st_ctc_beam_search_decode_lm_nbest': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_search_decode_bias_nbest': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_beam_search_decode_lm_bias_nbest': (c_int, [_T3P, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float,
+                                                        c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_size_t, c_void_p]),
     'st_lm_score_prefixes_f64': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'st_lm_score_prefixes_host': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'st_edit_distance_max_len': (c_int, []),

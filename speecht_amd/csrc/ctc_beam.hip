@@ -3,6 +3,8 @@
 // weight triples in one launch (a grid of utterances x candidates, st_ctc_beam_search_decode_lm_candidates: the LM weight search).
 // Both searches also run carried across the steps of a live stream (ctc_beam_kernel<.., STREAM = true>, ctc_beam_read_kernel;
 // st_ctc_beam_stream_step / _read): the same frame loop between a load and a save of the beam's state.
+// Hotword biasing (ctc_beam_kernel<.., BIAS = true>, st_ctc_beam_search_decode_bias_nbest / _lm_bias_nbest) is a second scorer of the
+// LM's shape: a table-driven automaton over the labels whose state is a function of the prefix alone (BiasArgs below).
 //
 // The reference reaches a beam search only through its KenLM TensorFlow fork (speech_model.py:101-111);
 // this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion, with the candidate order of
@@ -348,6 +350,26 @@ struct StreamArgs<true> {
   int max_frames;         // the pool holds max_frames * W + 1 nodes per stream
 };
 
+// BIAS: hotword biasing.  The phrases' trie is an automaton over the labels (semantics: include/speecht_hip.h,
+// tests/hotword_oracle.py), tabulated by the host: next[n][32] / gain[n][32] / fin[n] in global memory.  An entry carries its state and
+// `bself`, the gain it was entered with (double buffered beside the sets); the scorer enters the frame loop where the LM does: a child
+// candidate adds gain[state(slot)][c], the stay candidate's parent inflow adds bself[e], the tail adds fin[state(e)] before ranking.
+// The gain rows are read from the GLOBAL table in the scoring pass (one LDS read of the slot's state, then one load per candidate,
+// all issued with the pass's LDS reads; the table of a phrase list is a few hundred KB and stays in L2): copies of the rows in LDS,
+// as the LM deltas have, would cost 32 KB more at MAXB = 128 and a 128-byte copy per entry and frame for a row that, unlike the LM's,
+// costs nothing to look up again.  Every state written to LDS is clamped to [0, n_states): a malformed table gives wrong text, never
+// a read outside the tables.  BIAS = false compiles to the kernels above (its BiasArgs is empty).
+template <bool BIAS>
+struct BiasArgs {};
+template <>
+struct BiasArgs<true> {
+  const int* next;        // [n_states][kBiasPitch]
+  const float* gain;      // [n_states][kBiasPitch]
+  const float* fin;       // [n_states]
+  int n_states;
+};
+constexpr int kBiasPitch = 32;
+
 // words of 4 bytes between LDS and a state record, lane-strided
 __device__ __forceinline__ void copy_words(void* dst, const void* src, int bytes, int lane) {
   int* d = static_cast<int*>(dst);
@@ -355,14 +377,15 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, int bytes
   for (int i = lane; i < bytes / 4; i += 64) d[i] = s[i];
 }
 
-template <int CPL, int MAXB, bool LM, bool NBEST = false, bool STREAM = false>
+template <int CPL, int MAXB, bool LM, bool NBEST = false, bool STREAM = false, bool BIAS = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ lp_all, int T, int C,
                                                       const int* __restrict__ seq_lens, int W,
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
                                                       int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma,
-                                                      NbestArgs<NBEST> nx, StreamArgs<STREAM> sx = {}) {
+                                                      NbestArgs<NBEST> nx, StreamArgs<STREAM> sx = {}, BiasArgs<BIAS> bx = {}) {
   static_assert(!(NBEST && STREAM), "a stream has no N-best lists");
+  static_assert(!BIAS || (NBEST && !STREAM), "hotwords: the N-best instantiations only (the top path is the n_best = 1 list)");
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -380,6 +403,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   constexpr int LMB = LM ? MAXB : 1;
   __shared__ LmSet<LMB> lms[2];
   __shared__ __attribute__((aligned(16))) float delta_s[2][LMB][kDeltaPitch];
+  // hotword state and entry gain of the entries (double buffered with the sets; a single element when BIAS is off)
+  constexpr int BB = BIAS ? MAXB : 1;
+  __shared__ int bstate_s[2][BB];
+  __shared__ float bself_s[2][BB];
 
   const int b = blockIdx.x, lane = threadIdx.x;
   // LM: the candidate axis -- blockIdx.y picks the weight triple, its own node pool and its own output rows
@@ -444,6 +471,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     BeamSet<MAXB>& s = sets[0];
     s.hash[0] = kRootHash; s.parent_hash[0] = 0; s.len[0] = 0; s.last[0] = -1; s.node[0] = 0;
     s.pb[0] = 0.f; s.pl[0] = -INFINITY; s.total[0] = 0.f;
+    if constexpr (BIAS) { bstate_s[0][0] = 0; bself_s[0][0] = 0.f; }
     if constexpr (LM) {
       // root: context <s>, the trie root, lm_score = score = 0
       LmSet<LMB>& L = lms[0];
@@ -556,7 +584,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       float npl = -INFINITY;
       if (len0 > 0) {
         float mass = pl0;
-        if constexpr (LM) {
+        if constexpr (BIAS) {
+          float inflow = (plen > 0 && plast == last0) ? ppb : ptot;
+          if constexpr (LM) inflow += lw * lms[cur].dself[e];
+          if (p >= 0) mass = lse(mass, inflow + bself_s[cur][e]);
+        } else if constexpr (LM) {
           if (p >= 0) mass = lse(mass, ((plen > 0 && plast == last0) ? ppb : ptot) + lw * lms[cur].dself[e]);
         } else {
           if (p >= 0) mass = lse(mass, (plen > 0 && plast == last0) ? ppb : ptot);
@@ -578,6 +610,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       unsigned dd[CPL];
       float lpc[CPL];
       float dl[LM ? CPL : 1];
+      [[maybe_unused]] float bg[BIAS ? CPL : 1];
+      if constexpr (BIAS) {
+        // the gains first: a global load behind an LDS read, in flight under the LDS reads below
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) bg[j] = bx.gain[bstate_s[cur][cslot[j] < nb ? cslot[j] : 0] * kBiasPitch + ccls[j]];
+      }
 #pragma unroll
       for (int j = 0; j < CPL; ++j) {
         const int sl = cslot[j] < nb ? cslot[j] : 0;
@@ -590,7 +628,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       for (int j = CPL - 1; j >= 0; --j) {                // descending j + ">=": the lowest j wins a tie
         const int c = ccls[j];
         float child;
-        if constexpr (LM)                                    // TF GetStateExpansionScore(child state, previous)
+        if constexpr (BIAS) {
+          float base = (__float_as_int(info[j].w) == c) ? info[j].y : info[j].x;
+          if constexpr (LM) base += lw * dl[j];
+          child = ((dd[j] >> c) & 1u) ? -INFINITY : (base + bg[j]) + lpc[j];
+        } else if constexpr (LM)                             // TF GetStateExpansionScore(child state, previous)
           child = ((dd[j] >> c) & 1u) ? -INFINITY : (((__float_as_int(info[j].w) == c) ? info[j].y : info[j].x) + lw * dl[j]) + lpc[j];
         else
           child = ((dd[j] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[j].w) == c) ? info[j].y : info[j].x) + lpc[j];
@@ -609,6 +651,14 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         float4 info[8];
         unsigned dd[8];
         float dl[LM ? 8 : 1];
+        [[maybe_unused]] float bg[BIAS ? 8 : 1];
+        if constexpr (BIAS) {
+#pragma unroll
+          for (int jj = 0; jj < 8; ++jj) {
+            const int sl = wslot0 + 2 * (j0 + jj);
+            bg[jj] = bx.gain[bstate_s[cur][sl < nb ? sl : 0] * kBiasPitch + c];
+          }
+        }
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           const int sl = wslot0 + 2 * (j0 + jj);
@@ -620,7 +670,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         for (int jj = 0; jj < 8; ++jj) {
           const int sl = wslot0 + 2 * (j0 + jj);
           float child;
-          if constexpr (LM)
+          if constexpr (BIAS) {
+            float base = (__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x;
+            if constexpr (LM) base += lw * dl[jj];
+            child = ((dd[jj] >> c) & 1u) ? -INFINITY : (base + bg[jj]) + lpc;
+          } else if constexpr (LM)
             child = ((dd[jj] >> c) & 1u) ? -INFINITY : (((__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x) + lw * dl[jj]) + lpc;
           else
             child = ((dd[jj] >> c) & 1u) ? -INFINITY : ((__float_as_int(info[jj].w) == c) ? info[jj].y : info[jj].x) + lpc;
@@ -797,6 +851,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       N.pb[e] = stay ? spb - top : -INFINITY;
       N.pl[e] = stay ? spl - top : v - top;
       N.total[e] = v - top;
+      if constexpr (BIAS) {
+        // a child reads its state and the gain it enters with once, here; a stay keeps its parent's
+        const int ps = bstate_s[cur][slot];
+        const int at = ps * kBiasPitch + c;
+        bstate_s[cur ^ 1][e] = stay ? ps : min(max(bx.next[at], 0), bx.n_states - 1);
+        bself_s[cur ^ 1][e] = stay ? bself_s[cur][slot] : bx.gain[at];
+      }
     }
     if constexpr (LM) {
       // the new entries' LM state from their parents' (all in LDS), then -- for a child -- its expansion deltas: one entry at a
@@ -862,16 +923,22 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       }
     }
   };
-  if constexpr (NBEST && !LM) {
+  if constexpr (NBEST && !LM && !BIAS) {
     // the final set is sorted by (total desc, candidate key asc): the hypotheses are its entries 0 .. n - 1
     write_nbest(nullptr, sets[cur].total);
     return;
   }
-  if constexpr (LM) {
+  if constexpr (LM || BIAS) {
     // end of utterance: every entry scores its incomplete word (if non-empty) and then </s>; the top path is the best total
-    // after that (ties: the lower rank)
-    const LmSet<LMB>& L = lms[cur];
-    for (int e = lane; e < nb; e += 64) sel_v[e] = lm_final_total(lmp, L, delta_s[cur][e], sets[cur].total[e], e);
+    // after that (ties: the lower rank).  BIAS: the open hotword match is resolved (fin: what it banks minus what it was lent).
+    [[maybe_unused]] const LmSet<LMB>& L = lms[cur];
+    for (int e = lane; e < nb; e += 64) {
+      float v;
+      if constexpr (LM) v = lm_final_total(lmp, L, delta_s[cur][e], sets[cur].total[e], e);
+      else v = sets[cur].total[e];
+      if constexpr (BIAS) v += bx.fin[bstate_s[cur][e]];
+      sel_v[e] = v;
+    }
     __syncthreads();
     if constexpr (NBEST) {
       // rank by (final total desc, rank in the set asc), by counting over LDS: entry e's place is the number of entries ahead of it
@@ -1026,10 +1093,23 @@ int st_ctc_beam_search_decode(const st_tensor3* logits, const int32_t* seq_lens,
   return st_ctc_beam_search_decode_ex(logits, seq_lens, beam_width, 0, ids, max_out, out_lens, log_prob, workspace, workspace_bytes, stream);
 }
 
-// the LM-free search: n_best = 0 is the top-path kernel of st_ctc_beam_search_decode_ex, n_best >= 1 the N-best instantiation
+// the hotword tables of a biased search: the struct's checks (the pointers are the device's; nothing is read here)
+static int bias_args(const char* who, const st_bias_tables* bias, BiasArgs<true>* bx) {
+  ST_REQUIRE(bias && bias->next && bias->gain && bias->fin, "%s: null hotword tables", who);
+  ST_REQUIRE(bias->n_states >= 1 && bias->n_states <= (1 << 20), "%s: hotword tables of 1..%d states supported, got %d", who, 1 << 20,
+             bias->n_states);
+  *bx = BiasArgs<true>{bias->next, bias->gain, bias->fin, bias->n_states};
+  return ST_OK;
+}
+
+// the LM-free search: n_best = 0 is the top-path kernel of st_ctc_beam_search_decode_ex, n_best >= 1 the N-best instantiation, with
+// `bias` its hotword-biased form
 static int beam_search_launch(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform, int n_best,
                               int32_t* ids, int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
-                              size_t workspace_bytes, void* stream) {
+                              size_t workspace_bytes, void* stream, const st_bias_tables* bias = nullptr) {
+  BiasArgs<true> bx{};
+  if (bias)
+    if (int e = bias_args("beam search", bias, &bx)) return e;
   ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob, "beam search: null argument");
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
              input_transform);
@@ -1049,7 +1129,10 @@ static int beam_search_launch(const st_tensor3* logits, const int32_t* seq_lens,
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), logits->batch), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
-  if (n_best > 0)
+  if (bias)
+    st::trace("ctc_beam_bias<%s> beam=%d transform=%d states=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform,
+              bx.n_states, n_best);
+  else if (n_best > 0)
     st::trace("ctc_beam<%s> beam=%d transform=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform, n_best);
   else
     st::trace("ctc_beam<%s> beam=%d transform=%d", beam_width > 64 ? "wide" : "wave", beam_width, input_transform);
@@ -1058,9 +1141,15 @@ static int beam_search_launch(const st_tensor3* logits, const int32_t* seq_lens,
                      logits->frames, logits->channels, seq_lens, beam_width,                                         \
                      reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
                      out_lens, log_prob, LmArgs{}, NX)
+#define ST_LAUNCH_BEAM_BIAS(CPL, MAXB)                                                                               \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, false, true, false, true>), dim3(logits->batch), dim3(64), 0, st::as_stream(stream), \
+                     lp_rows, logits->frames, logits->channels, seq_lens, beam_width,                                \
+                     reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids, max_out,        \
+                     out_lens, log_prob, LmArgs{}, (NbestArgs<true>{n_best, n_hyps}), StreamArgs<false>{}, bx)
 #define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
   do {                                                                                                               \
-    if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                           \
+    if (bias) ST_LAUNCH_BEAM_BIAS(CPL, MAXB);                                                                        \
+    else if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                      \
     else ST_LAUNCH_BEAM_AS(CPL, MAXB, false, NbestArgs<false>{});                                                    \
   } while (0)
   if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
@@ -1069,6 +1158,7 @@ static int beam_search_launch(const st_tensor3* logits, const int32_t* seq_lens,
   else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
   else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
+#undef ST_LAUNCH_BEAM_BIAS
 #undef ST_LAUNCH_BEAM_AS
   return st::check_launch("ctc_beam_search");
 }
@@ -1089,6 +1179,16 @@ int st_ctc_beam_search_decode_nbest(const st_tensor3* logits, const int32_t* seq
                             workspace_bytes, stream);
 }
 
+// ... biased by hotwords (the same launch function and workspace; the top path of a biased search is its n_best = 1 list)
+int st_ctc_beam_search_decode_bias_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                         const st_bias_tables* bias, int n_best, int32_t* ids, int max_out, int32_t* out_lens,
+                                         float* log_prob, int32_t* n_hyps, void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(n_hyps && bias, "beam search: null argument");
+  ST_REQUIRE(n_best >= 1 && n_best <= beam_width, "beam search: n_best 1..beam width (%d) supported, got %d", beam_width, n_best);
+  return beam_search_launch(logits, seq_lens, beam_width, input_transform, n_best, ids, max_out, out_lens, log_prob, n_hyps, workspace,
+                            workspace_bytes, stream, bias);
+}
+
 // [node pools of min(candidates, kLaunchCandidates) x batch searches | log-softmax rows [batch][frames][32]]: a launch of more
 // candidates than kLaunchCandidates is split, and the launches of one call run in stream order on the same pools
 size_t st_ctc_beam_lm_candidates_ws(int batch, int frames, int beam_width, int candidates) {
@@ -1102,8 +1202,11 @@ size_t st_ctc_beam_lm_candidates_ws(int batch, int frames, int beam_width, int c
 static int beam_search_lm_launch(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
                                  void* lm, const float* weights, int candidates, float oov_score, int n_best, int32_t* ids,
                                  int max_out, int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+                                 size_t workspace_bytes, void* stream, const st_bias_tables* bias = nullptr) {
   ST_REQUIRE(logits && logits->base && seq_lens && ids && out_lens && log_prob && lm && weights, "LM beam search: null argument");
+  BiasArgs<true> bx{};
+  if (bias)
+    if (int e = bias_args("LM beam search", bias, &bx)) return e;
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "LM beam search: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d",
              input_transform);
   ST_REQUIRE(logits->channels == kSpace + 2, "LM beam search: the classes must be a-z ' space blank (%d), got %d", kSpace + 2,
@@ -1140,7 +1243,10 @@ static int beam_search_lm_launch(const st_tensor3* logits, const int32_t* seq_le
   hipLaunchKernelGGL(logsoftmax_rows_kernel, dim3(st::ceil_div(logits->frames, 4), B), dim3(256), 0, st::as_stream(stream),
                      logits->base, map, logits->frames, logits->channels, seq_lens, input_transform, lp_rows);
   const int per_lane = st::ceil_div(beam_width * logits->channels, 64);
-  if (n_best > 0)
+  if (bias)
+    st::trace("ctc_beam_lm_bias<%s> beam=%d transform=%d order=%d states=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width,
+              input_transform, copy->view.order, bx.n_states, n_best);
+  else if (n_best > 0)
     st::trace("ctc_beam_lm<%s> beam=%d transform=%d order=%d candidates=%d nbest=%d", beam_width > 64 ? "wide" : "wave", beam_width,
               input_transform, copy->view.order, candidates, n_best);
   else
@@ -1159,9 +1265,16 @@ static int beam_search_lm_launch(const st_tensor3* logits, const int32_t* seq_le
                        logits->frames, logits->channels, seq_lens, beam_width,                                       \
                        reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids_p, max_out,    \
                        out_lens + (size_t)p0 * B, log_prob + (size_t)p0 * B, lma, NX)
+#define ST_LAUNCH_BEAM_BIAS(CPL, MAXB)                                                                               \
+    hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, true, true, false, true>), dim3(B, n), dim3(64), 0, st::as_stream(stream), lp_rows, \
+                       logits->frames, logits->channels, seq_lens, beam_width,                                       \
+                       reinterpret_cast<int2*>(workspace), (long)logits->frames * beam_width + 1, ids_p, max_out,    \
+                       out_lens + (size_t)p0 * B, log_prob + (size_t)p0 * B, lma, (NbestArgs<true>{n_best, n_hyps}), \
+                       StreamArgs<false>{}, bx)
 #define ST_LAUNCH_BEAM(CPL, MAXB)                                                                                    \
     do {                                                                                                             \
-      if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                         \
+      if (bias) ST_LAUNCH_BEAM_BIAS(CPL, MAXB);                                                                      \
+      else if (n_best > 0) ST_LAUNCH_BEAM_AS(CPL, MAXB, true, (NbestArgs<true>{n_best, n_hyps}));                    \
       else ST_LAUNCH_BEAM_AS(CPL, MAXB, false, NbestArgs<false>{});                                                  \
     } while (0)
     if (beam_width > 64) ST_LAUNCH_BEAM(64, 128);
@@ -1170,6 +1283,7 @@ static int beam_search_lm_launch(const st_tensor3* logits, const int32_t* seq_le
     else if (per_lane <= 16) ST_LAUNCH_BEAM(16, 64);
     else ST_LAUNCH_BEAM(32, 64);
 #undef ST_LAUNCH_BEAM
+#undef ST_LAUNCH_BEAM_BIAS
 #undef ST_LAUNCH_BEAM_AS
     const int rc = st::check_launch("ctc_beam_search_lm");
     if (rc != ST_OK) return rc;
@@ -1205,6 +1319,19 @@ int st_ctc_beam_search_decode_lm_nbest(const st_tensor3* logits, const int32_t* 
   const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
   return beam_search_lm_launch(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, n_best, ids, max_out, out_lens,
                                log_prob, n_hyps, workspace, workspace_bytes, stream);
+}
+
+// ... biased by hotwords
+int st_ctc_beam_search_decode_lm_bias_nbest(const st_tensor3* logits, const int32_t* seq_lens, int beam_width, int input_transform,
+                                            void* lm, float lm_weight, float word_count_weight, float valid_word_count_weight,
+                                            float oov_score, const st_bias_tables* bias, int n_best, int32_t* ids, int max_out,
+                                            int32_t* out_lens, float* log_prob, int32_t* n_hyps, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(n_hyps && bias, "LM beam search: null argument");
+  ST_REQUIRE(n_best >= 1 && n_best <= beam_width, "LM beam search: n_best 1..beam width (%d) supported, got %d", beam_width, n_best);
+  const float w[3] = {lm_weight, word_count_weight, valid_word_count_weight};
+  return beam_search_lm_launch(logits, seq_lens, beam_width, input_transform, lm, w, 1, oov_score, n_best, ids, max_out, out_lens,
+                               log_prob, n_hyps, workspace, workspace_bytes, stream, bias);
 }
 
 // ---- the search carried across steps --------

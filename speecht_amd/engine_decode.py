@@ -425,24 +425,44 @@ class DecodeMixin:
     count = host[B * n * T + 2 * B * n:]
     return [[(ids[b, h, :min(lens[b, h], T)].tolist(), float(logp[b, h])) for h in range(count[b])] for b in range(B)]
 
-  def beam_search_decode_nbest(self, n_best, beam_width=16, input_transform=None):
+  def _bias_tables(self, hotwords):
+    """st_bias_tables of a `hotwords.Hotwords` on the engine's device -> (the struct by reference, what must stay alive)."""
+    nxt, gain, fin = hotwords.device_tables(self.device)
+    tables = _lib.BiasTables(nxt.data_ptr(), gain.data_ptr(), fin.data_ptr(), int(hotwords.n_states))
+    return ctypes.byref(tables), (tables, nxt, gain, fin)
+
+  def beam_search_decode_nbest(self, n_best, beam_width=16, input_transform=None, hotwords=None):
     """The N best final prefixes of ``beam_search_decode`` (st_ctc_beam_search_decode_nbest; ranking rules: include/speecht_hip.h,
     tests/nbest_oracle.py) -> per utterance a list of (ids, log_prob), best first, of min(n_best, entries alive) hypotheses;
-    ``n_best=1`` returns the bits of ``beam_search_decode``.  merge_repeated is not offered: it could make two hypotheses equal."""
+    ``n_best=1`` returns the bits of ``beam_search_decode``.  merge_repeated is not offered: it could make two hypotheses equal.
+    ``hotwords`` (a `hotwords.Hotwords`): the search biased towards its phrases (st_ctc_beam_search_decode_bias_nbest; log_prob then
+    includes the bias, which `nbest.components` splits off); None is the unbiased code path."""
     code = beam_input_transform(input_transform)
     sh = self.shape
+    if hotwords is not None:
+      bias, keep = self._bias_tables(hotwords)
+      return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
+          'st_ctc_beam_search_decode_bias_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, bias, int(n_best), ids,
+          T, lens, score, count, ws, ws_bytes, self.stream_ptr))
     return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
         'st_ctc_beam_search_decode_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, int(n_best), ids, T, lens,
         score, count, ws, ws_bytes, self.stream_ptr))
 
   def lm_beam_search_decode_nbest(self, lm, n_best, beam_width=100, input_transform='log10_softmax', lm_weight=0.8,
-                                  word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0):
+                                  word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0, hotwords=None):
     """The N best final prefixes of ``lm_beam_search_decode`` (st_ctc_beam_search_decode_lm_nbest): every final entry gains its
     end-of-utterance LM terms, then the entries are ranked by (total desc, rank in the beam asc) -> per utterance a list of
-    (ids, log_prob), best first; log_prob includes the LM terms (`nbest.components` splits them off)."""
+    (ids, log_prob), best first; log_prob includes the LM terms (`nbest.components` splits them off).  ``hotwords``: as
+    ``beam_search_decode_nbest`` (st_ctc_beam_search_decode_lm_bias_nbest)."""
     code = beam_input_transform(input_transform)
     handle = lm.device_handle(self.device)
     sh = self.shape
+    if hotwords is not None:
+      bias, keep = self._bias_tables(hotwords)
+      return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
+          'st_ctc_beam_search_decode_lm_bias_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle,
+          float(lm_weight), float(word_count_weight), float(valid_word_count_weight), float(oov_score), bias, int(n_best), ids, T, lens,
+          score, count, ws, ws_bytes, self.stream_ptr))
     return self._nbest_lists(n_best, beam_width, lambda ids, T, lens, score, count, ws, ws_bytes: call(
         'st_ctc_beam_search_decode_lm_nbest', sh.X[-1].ref, self._ptr(self.ctc_lens), int(beam_width), code, handle, float(lm_weight),
         float(word_count_weight), float(valid_word_count_weight), float(oov_score), int(n_best), ids, T, lens, score, count, ws,

@@ -46,7 +46,7 @@ BEAM_DECODERS = 2
 
 
 def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam_width=None, language_model=None, lm_options=None,
-               timestamps=False, mask_padding=False, confidence=False, nbest=None, rescore=None):
+               timestamps=False, mask_padding=False, confidence=False, nbest=None, rescore=None, hotwords=None):
   """features: list of [T_i, input_size] arrays.  Returns (list of id lists, list of strings) in the
   input order, decoded greedily (speech_model.py:113-115) batch by batch -- or, with ``beam_width``, by the LM-free prefix
   beam search (the reference's beam search needs its KenLM fork, speech_model.py:101-111; configs[4] asks for beam 16).
@@ -86,7 +86,20 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   first hypothesis is the top path of the search without ``nbest``.  ``rescore``: a dict {'language_model', 'lm_weight' (default: the
   first pass's), 'word_count_weight', 'valid_word_count_weight' (default: the first pass's)} -- every list is re-ranked under that
   model (`nbest.rescored`: 'log_prob' becomes the new score, the LM parts those of the second model).  ``ids`` / texts -- and with
-  them ``timestamps`` and ``confidence`` -- are those of the best hypothesis after any rescoring."""
+  them ``timestamps`` and ``confidence`` -- are those of the best hypothesis after any rescoring.
+
+  ``hotwords`` (a `hotwords.Hotwords`, or a list of phrases for one with the default weight): the beam search is biased towards the
+  phrases (a contact list, product names).  It needs a beam search: beam 16 if neither ``beam_width`` nor a model is given.  The
+  biased searches are the N-best kernels, so the serial loop runs with ``n_best = nbest or 1``; the lists are returned only with
+  ``nbest``, and their hypotheses then carry 'bias'.  None changes nothing."""
+  want_lists = nbest is not None
+  if hotwords is not None:
+    from .hotwords import Hotwords
+    if not isinstance(hotwords, Hotwords):
+      hotwords = Hotwords(hotwords)
+    if not beam_width and language_model is None:
+      beam_width = 16
+    nbest = nbest or 1
   if nbest is not None:
     if not (beam_width or language_model is not None):
       raise ValueError('transcribe: nbest needs a beam search (beam_width or language_model)')
@@ -94,7 +107,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
     raise ValueError('transcribe: rescore applies to N-best lists (nbest=N)')
   forward = (lambda: engine.forward(mask_padding=True)) if mask_padding else engine.forward
   if not features:
-    return ([], []) + (([],) if timestamps else ()) + (([],) if confidence else ()) + (([],) if nbest is not None else ())
+    return ([], []) + (([],) if timestamps else ()) + (([],) if confidence else ()) + (([],) if want_lists else ())
   if pipeline is None:
     pipeline = DEFAULT_PIPELINE
   if timestamps or confidence or nbest is not None:
@@ -124,11 +137,12 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   def decode_nbest():
     """The lists of the batch the engine holds, split into their parts and re-ranked if asked, each hypothesis with its text."""
     from . import nbest as nbest_lists
+    bias = dict(hotwords=hotwords) if hotwords is not None else {}
     if language_model is not None:
-      lists = engine.lm_beam_search_decode_nbest(language_model, nbest, beam_width, **lm_opts)
+      lists = engine.lm_beam_search_decode_nbest(language_model, nbest, beam_width, **dict(lm_opts, **bias))
     else:
-      lists = engine.beam_search_decode_nbest(nbest, beam_width)
-    lists = nbest_lists.components(engine, language_model, lists, first_pass)
+      lists = engine.beam_search_decode_nbest(nbest, beam_width, **bias)
+    lists = nbest_lists.components(engine, language_model, lists, first_pass, **bias)
     if rescore is not None:
       shared = first_pass if language_model is not None else (0.0, 0.0, 0.0)
       lists = nbest_lists.rescored(lists, engine, rescore['language_model'], rescore.get('lm_weight', first_pass[0]),
@@ -175,7 +189,7 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
           conf_out[i] = conf[row]
     texts = [vocabulary.ids_to_sentence(s) for s in ids_out]
     return (ids_out, texts) + ((spans_out,) if timestamps else ()) + ((conf_out,) if confidence else ()) + \
-        ((nbest_out,) if nbest is not None else ())
+        ((nbest_out,) if want_lists else ())
 
   def collect(handle, idx):
     res = handle.result()

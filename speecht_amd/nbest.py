@@ -15,7 +15,7 @@ import numpy as np
 
 class Hypothesis(dict):
   """One entry of an N-best list: {'ids', 'log_prob'} and, after `components`, {'acoustic', 'lm_log10', 'words', 'valid_words'}
-  (the last three only when a model was involved)."""
+  (the last three only when a model was involved) and 'bias' (only when the first pass had hotwords)."""
 
 
 def as_lists(lists):
@@ -34,23 +34,30 @@ def _scores(engine, lm, lists):
   return out
 
 
-def components(engine, lm, lists, first_pass_weights=None):
+def components(engine, lm, lists, first_pass_weights=None, hotwords=None):
   """Attaches to each hypothesis of ``lists`` (per utterance [(ids, log_prob), ...] or Hypothesis dicts) its parts under the
   first pass: ``lm_log10`` = G, ``words``, ``valid_words`` under ``lm``, and ``acoustic`` = log_prob - lm_weight * (G +
   word_count_weight * words + valid_word_count_weight * valid_words), computed in double, with ``first_pass_weights`` =
   (lm_weight, word_count_weight, valid_word_count_weight) of the search that made the lists.  ``lm=None`` (an LM-free first
-  pass): ``acoustic`` = log_prob and nothing else is attached.  Returns the lists as Hypothesis dicts."""
+  pass): ``acoustic`` = log_prob and nothing else is attached.  ``hotwords`` (the `hotwords.Hotwords` of a biased first pass): each
+  hypothesis also gets ``bias``, its final hotword credit with the weight included, and ``acoustic`` is without it -- so that rescoring
+  under a second model keeps the first pass's bias out of the acoustic part.  Returns the lists as Hypothesis dicts."""
   lists = as_lists(lists)
+  bias = (lambda h: float(hotwords.score(h['ids'])[1])) if hotwords is not None else (lambda h: 0.0)
   if lm is None:
     for hyps in lists:
       for h in hyps:
-        h['acoustic'] = float(h['log_prob'])
-    return lists
-  lw, wc, vwc = (float(x) for x in first_pass_weights)
-  for hyps, parts in zip(lists, _scores(engine, lm, lists)):
-    for h, (g, n_words, n_valid) in zip(hyps, parts):
-      h.update(lm_log10=g, words=n_words, valid_words=n_valid,
-               acoustic=float(h['log_prob']) - lw * (g + wc * n_words + vwc * n_valid))
+        h['acoustic'] = float(h['log_prob']) - bias(h)
+  else:
+    lw, wc, vwc = (float(x) for x in first_pass_weights)
+    for hyps, parts in zip(lists, _scores(engine, lm, lists)):
+      for h, (g, n_words, n_valid) in zip(hyps, parts):
+        h.update(lm_log10=g, words=n_words, valid_words=n_valid,
+                 acoustic=float(h['log_prob']) - lw * (g + wc * n_words + vwc * n_valid) - bias(h))
+  if hotwords is not None:
+    for hyps in lists:
+      for h in hyps:
+        h['bias'] = bias(h)
   return lists
 
 

@@ -193,7 +193,7 @@ def transcribe_audio(engine, signals, rates, feature_type='power', sample_rate=2
   Resampling (to ``sample_rate``, default 22 050 Hz as librosa.load; None or 'native' keeps each signal's rate) and the
   features run on the engine's device; the features must match the engine's input width (power: 128, mfcc: 39).
   ``decode``: inference.transcribe's decoding arguments -- none (greedy), ``beam_width``, or ``language_model`` with
-  ``lm_options``.
+  ``lm_options``; and ``hotwords``, which biases the beam search towards given phrases.
 
   ``batch_size=1`` (default): every signal is one [1, T, C] batch without padding, the semantics of the reference's `record`.
   ``batch_size > 1``: signals are bucketed by length into padded batches for throughput; nothing in the network is masked,
@@ -230,7 +230,9 @@ def transcribe_files(engine, paths, feature_type='power', sample_rate=22050, bat
   it is per segment and the words of ``segments`` carry `confidence`.
   ``nbest=N`` (with a beam search; not with ``segment``: per-segment lists do not join into file lists) adds ``nbest``: the file's up
   to N best hypotheses, best first (inference.transcribe: dicts with 'text', 'log_prob', 'acoustic' and the LM parts); ``rescore``
-  re-ranks them under a second model first, and ``text`` / ``ids`` are the best hypothesis after that."""
+  re-ranks them under a second model first, and ``text`` / ``ids`` are the best hypothesis after that.
+  ``hotwords`` (among ``decode``; a `hotwords.Hotwords` or a list of phrases): the beam search is biased towards the phrases
+  (inference.transcribe); it composes with ``segment``, ``timestamps``, ``confidence`` and ``nbest``, whose hypotheses then carry 'bias'."""
   if nbest is not None and segment is not None:
     raise ValueError('transcribe_files: nbest is not available with segment (per-segment lists do not join into file lists)')
   results = []
@@ -306,6 +308,10 @@ def run_cli(flags):
                                   valid_word_count_weight=model.valid_word_count_weight))
   elif model.beam_width:
     decode = dict(beam_width=model.beam_width)
+  from . import hotwords
+  bias = hotwords.from_flags(flags)
+  if bias is not None:
+    decode['hotwords'] = bias                           # (inference.transcribe: beam 16 when no beam search was asked for)
   with Session(flags.device) as sess:
     with contextlib.redirect_stdout(sys.stderr):
       model.restore(sess, flags.run_train_dir)          # FileNotFoundError('No checkpoint for evaluation found'), as evaluate
@@ -337,7 +343,7 @@ def run_cli(flags):
       print('{}\t{}'.format(r['path'], r['text']), flush=True)
       line = dict(path=r['path'], seconds=r['seconds'], text=r['text'])
       if r.get('nbest') is not None:
-        parts = ('text', 'log_prob', 'acoustic', 'lm_log10', 'words', 'valid_words')
+        parts = ('text', 'log_prob', 'acoustic', 'lm_log10', 'words', 'valid_words', 'bias')
         line['nbest'] = [{k: h[k] for k in parts if k in h} for h in r['nbest']]
         for rank, h in enumerate(r['nbest'], 1):
           print('{}\t{}\t{:.4f}\t{}'.format(r['path'], rank, h['log_prob'], h['text']), flush=True)
