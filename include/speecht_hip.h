@@ -923,6 +923,60 @@ int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_widt
                             float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
                             int32_t* tail, int max_tail, int32_t* result, void* stream);
 
+/* ---- Endpointing of live streams (csrc/stream_endpoint.hip, csrc/stream_endpoint_core.h; specification: tests/endpoint_oracle.py; no
+ * reference counterpart).  The device notices that a speaker has stopped, closes the utterance and steers the decoders above, so that
+ * a stream of any length is a sequence of utterances decoded like files.  The rule is a pure function of a stream's logits rows:
+ * row t is SILENT when its argmax -- computed as st_ctc_greedy_stream computes it -- is the blank (num_classes - 1) or space_id (-1: no
+ * such class), SPEECH otherwise.  With R = silence_frames >= 1, L = lead_frames >= 1, M = max_frames >= L: row t always joins the open
+ * utterance [u0, ...); a speech row sets started and run = 0, a silent row increments run; then, with len = t + 1 - u0, the first of
+ *   1 silence: started && run >= R;   2 length: started && len >= M;   3 discard: !started && len >= L
+ * that applies fires; 1 and 2 make the utterance [u0, t + 1) final, 3 drops the rows (no utterance), and after any of them u0 = t + 1,
+ * started = false, run = 0.  When the stream finishes (limit >= 0; rows at or past the limit are not consumed) a non-empty open stretch
+ * ends with event 4 (end of stream) if it has started and with event 3 otherwise.  No stretch is longer than M rows.
+ * st_stream_endpoint_pieces: P = 2 + (max_rows - 1) / min(L, R + 1, M), the event and piece slots per stream for steps of at most
+ *   max_rows rows per stream (0: bad arguments); st_stream_endpoint_state_bytes / _score_bytes: bytes of one stream's record / score.
+ * st_ctc_greedy_endpoint_stream: one wavefront per stream, in the place of st_ctc_greedy_stream (same logits, rows and table).  Greedy
+ *   decoding restarts at every event, so an utterance's ids and sum are those of its rows alone.
+ *   state   int32 [max_streams][8] {u0, started, run, first_speech, last_speech, finals so far, last argmax id, rows consumed} and
+ *           score float [max_streams][256] (the open utterance's chosen logits: row i of the utterance is added to slot i % 256, and a
+ *           sum is the binary tree of neighbours over the slots -- the order of st_ctc_greedy_decode, whose neg_sum_logits on an
+ *           utterance's rows a final's therefore equals bit for bit) persist between calls; any content before a stream's first step,
+ *           which carries reset = 1 (frames count from 0 then).
+ *   ids     [max_streams][max_new]: all new ids of the step, the utterances' concatenated; new_count[s] their number;
+ *           neg_sum_logits[s] the negative sum of the utterance still open.
+ *   events  int32 [max_streams][n_pieces][8] = {kind (0 ends the list; all n_pieces slots may be in use), u0, end, first_speech or -1,
+ *           last_speech or -1, ids_end: this step's ids up to the end of this stretch, negative sum of its chosen logits (float bits),
+ *           utterance index (of a discard: the index the next final will get)}
+ *   pieces  int32 [n_pieces][max_streams][4], each pieces[p] a table {first row, rows, limit, reset} of the streaming decoders: the
+ *           step's rows of one stretch.  The piece that ends a final utterance carries limit = its end frame (absolute, as the rows
+ *           table counts), every other one -1; the piece after an event -- and the first one of a step the host marked reset --
+ *           carries reset = 1, also when it has no rows yet (an event on a step's last row: {0, 0, -1, 1}); a final at the end of the
+ *           stream whose rows all came earlier is {0, 0, end, 0}; a stream without rows and unused slots are {0, 0, -1, 0}.  Pieces
+ *           lie inside the host's [first, first + rows).  Slots from n_pieces on are never written; n_pieces below
+ *           st_stream_endpoint_pieces(max_rows, ...) is refused, and a table row with more than max_rows rows loses its later events.
+ * st_stream_endpoint_host: the same on HOST pointers, bit-identical to the kernel (one walk, csrc/stream_endpoint_core.h).  No GPU.
+ * st_ctc_beam_stream_step_pieces (csrc/ctc_beam.hip): st_ctc_beam_stream_step's log-softmax of the step's rows once, then for p = 0 ..
+ *   n_pieces - 1 the search of st_ctc_beam_stream_step with table = pieces[p] followed by the read-out of st_ctc_beam_stream_read into
+ *   result[p] ([n_pieces][max_streams][4]) and tail[p] ([n_pieces][max_streams][max_tail]; relative to the stable length the read
+ *   before it stored, 0 after a reset).  The tables are read on the device: no host wait.  A final piece's read-out is the
+ *   whole-utterance search on the utterance's rows, bit for bit; with max_frames = M the pool-full status bit never sets. */
+size_t st_stream_endpoint_state_bytes(void);
+size_t st_stream_endpoint_score_bytes(void);
+int st_stream_endpoint_pieces(int max_rows, int silence_frames, int lead_frames, int max_frames);
+int st_ctc_greedy_endpoint_stream(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table,
+                                  int max_streams, int space_id, int silence_frames, int lead_frames, int max_frames, int max_rows,
+                                  int32_t* state, float* score, int32_t* ids, int max_new, int32_t* new_count, float* neg_sum_logits,
+                                  int32_t* events, int32_t* pieces, int n_pieces, void* stream);
+int st_stream_endpoint_host(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int max_streams,
+                            int space_id, int silence_frames, int lead_frames, int max_frames, int max_rows, int32_t* state,
+                            float* score, int32_t* ids, int max_new, int32_t* new_count, float* neg_sum_logits, int32_t* events,
+                            int32_t* pieces, int n_pieces);
+int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                   int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                   float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score, void* state,
+                                   void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
+                                   int32_t* result, void* stream);
+
 /* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
  * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
  * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are

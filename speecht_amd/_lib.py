@@ -239,6 +239,16 @@ _SIGNATURES = {
                                         c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'st_ctc_beam_stream_read': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
                                         c_void_p, c_int, c_void_p, c_void_p]),
+    'st_stream_endpoint_state_bytes': (c_size_t, []),
+    'st_stream_endpoint_score_bytes': (c_size_t, []),
+    'st_stream_endpoint_pieces': (c_int, [c_int, c_int, c_int, c_int]),
+    'st_ctc_greedy_endpoint_stream': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'st_stream_endpoint_host': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    'st_ctc_beam_stream_step_pieces': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                               c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                               c_int, c_void_p, c_void_p]),
     'st_spec_augment_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
                                     c_int, _T3P, c_void_p, c_void_p]),
     'st_spec_augment_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,

@@ -1378,11 +1378,9 @@ static int beam_stream_common(const char* who, const int32_t* table, int max_str
   return ST_OK;
 }
 
-int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
-                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
-                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  const char* who = "beam stream step";
+// the checks of a step's own arguments (st_ctc_beam_stream_step, st_ctc_beam_stream_step_pieces)
+static int beam_stream_step_args(const char* who, const float* logits, int pitch, int num_classes, const int32_t* rows, int n_rows,
+                                 int input_transform, void* lm) {
   ST_REQUIRE(logits && rows, "%s: null argument", who);
   ST_REQUIRE(input_transform == 0 || input_transform == 1, "%s: input_transform 0 (logits) or 1 (log10(softmax + 1e-8)), got %d", who,
              input_transform);
@@ -1392,20 +1390,13 @@ int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, con
   ST_REQUIRE(num_classes >= 2 && num_classes <= kMaxClasses && pitch >= num_classes, "%s: 2..%d classes at a pitch >= classes, got %d at %d",
              who, kMaxClasses, num_classes, pitch);
   ST_REQUIRE(n_rows >= 0, "%s: negative row count %d", who, n_rows);
-  LmArgs lma;
-  if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
-                                 state, pool, max_frames, stream, &lma))
-    return e;
-  const size_t need = st_ctc_beam_stream_ws(n_rows);
-  if (need && (!workspace || workspace_bytes < need)) {
-    st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    return ST_EWORKSPACE;
-  }
-  hipStream_t s = st::as_stream(stream);
-  float* lp_rows = reinterpret_cast<float*>(workspace);
-  if (n_rows > 0)
-    hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
-                       input_transform, lp_rows);
+  return ST_OK;
+}
+
+// one launch of the search over all streams, their work taken from `table` (device memory)
+static void launch_beam_stream(const float* lp_rows, int num_classes, const int32_t* rows, const int32_t* table, int n_rows, int max_streams,
+                               int beam_width, int input_transform, bool lm, const LmArgs& lma, void* state, void* pool, int max_frames,
+                               hipStream_t s) {
   const bool wide = beam_width > 64;
   if (lm)
     st::trace("ctc_beam_stream_lm<%s> beam=%d transform=%d order=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width,
@@ -1413,7 +1404,7 @@ int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, con
   else
     st::trace("ctc_beam_stream<%s> beam=%d transform=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width, input_transform,
               max_streams, n_rows);
-  const StreamArgs<true> sx{rows, table, static_cast<char*>(state), (long)st_ctc_beam_stream_state_bytes(beam_width, lm != nullptr),
+  const StreamArgs<true> sx{rows, table, static_cast<char*>(state), (long)st_ctc_beam_stream_state_bytes(beam_width, lm),
                             max_frames};
   const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));   // pairs per stream
   const int per_lane = st::ceil_div(beam_width * num_classes, 64);
@@ -1433,6 +1424,46 @@ int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, con
   else ST_LAUNCH_STREAM(32, 64);
 #undef ST_LAUNCH_STREAM
 #undef ST_LAUNCH_STREAM_AS
+}
+
+// one launch of the read-out over all streams
+static void launch_beam_stream_read(const int32_t* table, int max_streams, int beam_width, bool lm, const LmArgs& lma, void* state,
+                                    const void* pool, int max_frames, int32_t* tail, int max_tail, int32_t* result, hipStream_t s) {
+  const bool wide = beam_width > 64;
+  st::trace("ctc_beam_stream_read<%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", beam_width, max_streams);
+  const long stride = (long)st_ctc_beam_stream_state_bytes(beam_width, lm);
+  const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));
+#define ST_LAUNCH_READ(MAXB, LM)                                                                                      \
+  hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM>), dim3(max_streams), dim3(64), 0, s, table, beam_width, \
+                     static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
+                     tail, max_tail, result, lma)
+  if (wide) { if (lm) ST_LAUNCH_READ(128, true); else ST_LAUNCH_READ(128, false); }
+  else { if (lm) ST_LAUNCH_READ(64, true); else ST_LAUNCH_READ(64, false); }
+#undef ST_LAUNCH_READ
+}
+
+int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  const char* who = "beam stream step";
+  if (int e = beam_stream_step_args(who, logits, pitch, num_classes, rows, n_rows, input_transform, lm)) return e;
+  LmArgs lma;
+  if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
+                                 state, pool, max_frames, stream, &lma))
+    return e;
+  const size_t need = st_ctc_beam_stream_ws(n_rows);
+  if (need && (!workspace || workspace_bytes < need)) {
+    st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    return ST_EWORKSPACE;
+  }
+  hipStream_t s = st::as_stream(stream);
+  float* lp_rows = reinterpret_cast<float*>(workspace);
+  if (n_rows > 0)
+    hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
+                       input_transform, lp_rows);
+  launch_beam_stream(lp_rows, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm != nullptr, lma, state, pool,
+                     max_frames, s);
   return st::check_launch("ctc_beam_stream_step");
 }
 
@@ -1446,18 +1477,46 @@ int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_widt
   if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
                                  state, pool, max_frames, stream, &lma))
     return e;
-  const bool wide = beam_width > 64;
-  st::trace("ctc_beam_stream_read<%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", beam_width, max_streams);
-  const long stride = (long)st_ctc_beam_stream_state_bytes(beam_width, lm != nullptr);
-  const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));
-#define ST_LAUNCH_READ(MAXB, LM)                                                                                      \
-  hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM>), dim3(max_streams), dim3(64), 0, st::as_stream(stream), table, beam_width, \
-                     static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
-                     tail, max_tail, result, lma)
-  if (wide) { if (lm) ST_LAUNCH_READ(128, true); else ST_LAUNCH_READ(128, false); }
-  else { if (lm) ST_LAUNCH_READ(64, true); else ST_LAUNCH_READ(64, false); }
-#undef ST_LAUNCH_READ
+  launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames, tail, max_tail, result,
+                          st::as_stream(stream));
   return st::check_launch("ctc_beam_stream_read");
+}
+
+// An endpointed step (stream_endpoint.hip wrote `pieces` [n_pieces][max_streams][4] on this stream): the log-softmax of the step's
+// rows once, then for every piece in order the search and its read-out, each taking its work from pieces[p] -- device memory, so
+// nothing waits for the host.  A slot {0, 0, -1, 0} makes both kernels leave at once.
+int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                   int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                   float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score, void* state,
+                                   void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
+                                   int32_t* result, void* stream) {
+  const char* who = "beam stream step pieces";
+  if (int e = beam_stream_step_args(who, logits, pitch, num_classes, rows, n_rows, input_transform, lm)) return e;
+  ST_REQUIRE(n_pieces >= 1, "%s: n_pieces must be positive, got %d", who, n_pieces);
+  ST_REQUIRE(tail && result, "%s: null argument", who);
+  ST_REQUIRE(max_tail >= 1, "%s: max_tail must be positive, got %d", who, max_tail);
+  LmArgs lma;
+  if (int e = beam_stream_common(who, pieces, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
+                                 state, pool, max_frames, stream, &lma))
+    return e;
+  const size_t need = st_ctc_beam_stream_ws(n_rows);
+  if (need && (!workspace || workspace_bytes < need)) {
+    st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    return ST_EWORKSPACE;
+  }
+  hipStream_t s = st::as_stream(stream);
+  float* lp_rows = reinterpret_cast<float*>(workspace);
+  if (n_rows > 0)
+    hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
+                       input_transform, lp_rows);
+  for (int p = 0; p < n_pieces; ++p) {
+    const int32_t* table = pieces + (long)p * max_streams * 4;
+    launch_beam_stream(lp_rows, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm != nullptr, lma, state, pool,
+                       max_frames, s);
+    launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames,
+                            tail + (long)p * max_streams * max_tail, max_tail, result + (long)p * max_streams * 4, s);
+  }
+  return st::check_launch("ctc_beam_stream_step_pieces");
 }
 
 }  // extern "C"

@@ -20,6 +20,11 @@ steps.  A chunked search is the whole-utterance search: after `finish` the hypot
 ``engine.beam_search_decode`` / ``lm_beam_search_decode`` return on the stream's logits, bit for bit and however the audio was cut.
 Before that a step reports the best hypothesis so far and how many of its leading ids are final (the common prefix of all live
 entries).  Such a stream can decode ``StreamBeam.max_seconds`` of audio: its node pool is sized when the recogniser is built.
+
+With ``endpoint=Endpointing(...)`` the device also cuts every stream into utterances (csrc/stream_endpoint.hip): once silence has
+followed speech, or an utterance has reached its longest length, the step hands back a final -- the offline decoder's result on
+that utterance's rows alone -- and the decoders start again, so a stream may run for any length on a node pool of one utterance.
+The logits are the same with and without it; the rule is a pure function of a stream's logits rows (tests/endpoint_oracle.py).
 """
 import ctypes
 
@@ -161,15 +166,69 @@ class StreamBeam:
       raise StreamError('max_seconds and max_tail must be positive')
 
 
+class Endpointing:
+  """Endpointing of a `StreamingRecognizer` (st_ctc_greedy_endpoint_stream; the rule: include/speecht_hip.h, tests/endpoint_oracle.py):
+  the device closes an utterance once ``silence`` seconds of rows whose best class is the blank or the space have followed speech, or
+  when it reaches ``max_utterance`` seconds, and drops ``lead`` seconds that hold no speech at all; the decoders start again after
+  each.  A beam search's node pool then holds ``max_utterance`` seconds, whatever the stream's length.  ``space_id``: the class that
+  counts as silent beside the blank ('auto': 27 with the 29 classes a-z ' space blank, none otherwise; -1: none).  The 0.5 s default
+  of ``silence`` is a guess, not tuned on data."""
+
+  KINDS = {1: 'silence', 2: 'length', 4: 'end'}
+
+  def __init__(self, silence=0.5, lead=1.0, max_utterance=30.0, space_id='auto'):
+    self.silence, self.lead, self.max_utterance = float(silence), float(lead), float(max_utterance)
+    for name in ('silence', 'lead', 'max_utterance'):
+      v = getattr(self, name)
+      if not (np.isfinite(v) and v > 0):
+        raise StreamError('endpointing: {} must be a positive number of seconds, got {!r}'.format(name, v))
+    if self.lead > self.max_utterance:
+      raise StreamError('endpointing: lead ({} s) must not exceed max_utterance ({} s): a stretch without speech could outgrow the '
+                        'node pool'.format(self.lead, self.max_utterance))
+    if space_id != 'auto' and (not isinstance(space_id, (int, np.integer)) or space_id < -1):
+      raise StreamError('endpointing: space_id must be \'auto\', -1 or a class index, got {!r}'.format(space_id))
+    self.space_id = space_id
+
+  def frames(self, total_stride, num_classes):
+    """Seconds -> output frames of a model whose layers' strides multiply to ``total_stride`` (10 ms hop):
+    ``(silence_frames, lead_frames, max_frames, space_id)``, each count rounded up and at least 1."""
+    count = lambda seconds: max(int(np.ceil(seconds * 100.0 / total_stride - 1e-9)), 1)
+    R, L, M = count(self.silence), count(self.lead), count(self.max_utterance)
+    space = (27 if num_classes == 29 else -1) if self.space_id == 'auto' else int(self.space_id)
+    if space >= num_classes:
+      raise StreamError('endpointing: space_id {} is no class of a model with {} classes'.format(space, num_classes))
+    return R, L, max(M, L), space
+
+
+class Utterance:
+  """A final of an endpointed stream: utterance ``index`` of its stream, closed by ``kind`` ('silence', 'length' or, at `finish`, 'end'),
+  the logits rows ``[start_frame, end_frame)`` with speech from ``first_speech`` to ``last_speech``.  ``ids``: the beam search's result on
+  those rows alone with its log-probability ``logp`` -- what the whole-utterance search returns on them -- or, without a beam search,
+  the greedy ids; ``greedy_ids`` and ``score`` (the negative sum of the chosen logits) are the greedy decoder's either way."""
+  __slots__ = ('index', 'kind', 'start_frame', 'end_frame', 'first_speech', 'last_speech', 'ids', 'logp', 'greedy_ids', 'score')
+
+  def __init__(self, index, kind, start_frame, end_frame, first_speech, last_speech, greedy_ids, score):
+    self.index, self.kind, self.start_frame, self.end_frame = index, kind, start_frame, end_frame
+    self.first_speech, self.last_speech = first_speech, last_speech
+    self.greedy_ids, self.score, self.ids, self.logp = greedy_ids, score, greedy_ids, None
+
+  def __repr__(self):
+    return 'Utterance({}, {!r}, rows [{}, {}), speech {}..{}, ids={}, logp={}, score={})'.format(
+        self.index, self.kind, self.start_frame, self.end_frame, self.first_speech, self.last_speech, self.ids, self.logp, self.score)
+
+
 class StepResult:
   """What one `step` / `finish` produced: ``ids[slot]`` new label ids, ``logits[slot]`` new rows [r, C] (on request),
   ``score[slot]`` the running negative sum of the chosen logits.  With a beam search also ``hyp[slot]``, all ids of the best
   hypothesis so far, ``stable[slot]``, how many of its leading ids are final, and ``logp[slot]``, its log-probability (after
-  `finish`: what the whole-utterance search returns); ``ids`` and ``score`` stay the greedy ones."""
+  `finish`: what the whole-utterance search returns); ``ids`` and ``score`` stay the greedy ones.  With endpointing ``finals[slot]``
+  lists the `Utterance`s the step closed, in order; ``hyp`` / ``stable`` / ``logp`` / ``score`` and ``open_ids[slot]`` (the greedy ids
+  so far) then describe the utterance still open, and ``ids`` stays every new greedy id of the step."""
 
   def __init__(self):
     self.ids, self.logits, self.score = {}, {}, {}
     self.hyp, self.stable, self.logp = {}, {}, {}
+    self.finals, self.open_ids = {}, {}
 
 
 class StreamingRecognizer:
@@ -178,12 +237,14 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None):
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None):
     """``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
-    ``logp``); None: greedy decoding only."""
+    ``logp``); None: greedy decoding only.  ``endpoint``: an `Endpointing` -- the device cuts every stream into utterances
+    (`StepResult.finals`) and restarts the decoders after each; a beam search's node pool then holds ``endpoint.max_utterance``
+    seconds (``beam.max_seconds`` is ignored) and a stream may run for any length."""
     if max_streams < 1 or max_chunk_frames < 1:
       raise StreamError('max_streams and max_chunk_frames must be positive')
-    self.beam = beam
+    self.beam, self.endpoint = beam, endpoint
     self.engine, self.device = engine, engine.device
     self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
     self.layers = engine.layers
@@ -209,18 +270,34 @@ class StreamingRecognizer:
       self.dec_score = torch.zeros(S, dtype=torch.float64, device=dev)
       # the decoder's outputs in one buffer, so that a step's results come back with one copy: [ids | counts | scores]
       # (with a beam search: ... | result [S][4] | tail [S][max_tail])
+      # (with endpointing: [ids | counts | scores | events [S][P][8] | pieces [P][S][4]], then result [P][S][4] | tail [P][S][max_tail])
       greedy_words = S * self.max_new + 2 * S
-      self.dec_out = torch.zeros(greedy_words + (S * (4 + beam.max_tail) if beam else 0), dtype=torch.int32, device=dev)
+      total_stride = int(np.prod([s for _, s in self.geo]))
+      self.n_pieces = 1
+      if endpoint is not None:
+        self.ep_frames = endpoint.frames(total_stride, self.num_classes)
+        if not 2 <= self.num_classes <= 64:
+          raise StreamError('endpointing supports 2..64 classes, the engine has {}'.format(self.num_classes))
+        self.n_pieces = P = int(lib.st_stream_endpoint_pieces(self.max_new, *self.ep_frames[:3]))
+        self.ep_state = torch.zeros(S * int(lib.st_stream_endpoint_state_bytes()) // 4, dtype=torch.int32, device=dev)
+        self.ep_score = torch.zeros(S * int(lib.st_stream_endpoint_score_bytes()) // 4, dtype=torch.float32, device=dev)
+        self.ep_words = S * P * 8 + P * S * 4
+        greedy_words += self.ep_words
+      self.dec_out = torch.zeros(greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0), dtype=torch.int32, device=dev)
       self.ids = self.dec_out[:S * self.max_new]
       self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
-      self.neg_sum = self.dec_out[S * self.max_new + S:greedy_words].view(torch.float32)
+      self.neg_sum = self.dec_out[S * self.max_new + S:S * self.max_new + 2 * S].view(torch.float32)
+      if endpoint is not None:
+        self.ep_events = self.dec_out[S * self.max_new + 2 * S:S * self.max_new + 2 * S + S * P * 8]
+        self.ep_pieces = self.dec_out[S * self.max_new + 2 * S + S * P * 8:greedy_words]
       if beam:
         if beam.lm is not None and self.num_classes != 29:
           raise StreamError('a language model needs the 29 classes a-z \' space blank, the engine has {}'.format(self.num_classes))
         if not 2 <= self.num_classes <= 32:
           raise StreamError('the beam search supports 2..32 classes, the engine has {}'.format(self.num_classes))
-        total_stride = int(np.prod([s for _, s in self.geo]))
         self.max_frames = int(np.ceil(beam.max_seconds * 100.0 / total_stride - 1e-9))   # output frames (10 ms hop)
+        if endpoint is not None:
+          self.max_frames = self.ep_frames[2]                        # no utterance is longer: the pool is never full
         self._lm_handle = beam.lm.device_handle(dev) if beam.lm is not None else None
         from .engine_decode import beam_input_transform
         self._transform = beam_input_transform(beam.input_transform)
@@ -230,8 +307,8 @@ class StreamingRecognizer:
         self.beam_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
         self.beam_pool = torch.empty(S * pool_bytes // 8, dtype=torch.int64, device=dev)     # (a chain only holds written nodes)
         self.beam_ws = torch.empty(self.beam_ws_bytes // 4, dtype=torch.float32, device=dev)
-        self.beam_result = self.dec_out[greedy_words:greedy_words + 4 * S]
-        self.beam_tail = self.dec_out[greedy_words + 4 * S:]
+        self.beam_result = self.dec_out[greedy_words:greedy_words + self.n_pieces * 4 * S]
+        self.beam_tail = self.dec_out[greedy_words + self.n_pieces * 4 * S:]
       table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
       for i, l in enumerate(self.layers):
         table[2 * i] = self.windows[i].data_ptr()
@@ -245,6 +322,7 @@ class StreamingRecognizer:
     # (its first `_stable` ids are final: the device reports only what follows them), and the streams a read-out gave up on
     self._frames, self._stable, self._failed = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64), np.zeros(S, dtype=bool)
     self._hyp, self._logp = [[] for _ in range(S)], np.zeros(S, dtype=np.float32)
+    self._open_ids = [[] for _ in range(S)]                      # endpointing: the greedy ids of the open utterance
     self._info = np.zeros((L, S, 4), dtype=np.int32)             # {base, n, base, 0} of every stream between steps
     self.launches = 0            # kernels enqueued by the last pass (products count two: slices + epilogue)
 
@@ -259,6 +337,7 @@ class StreamingRecognizer:
     self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
     self._info[:, i] = 0                                                       # [0, n) are never read
     self._frames[i], self._stable[i], self._failed[i], self._hyp[i], self._logp[i] = 0, 0, False, [], 0.0
+    self._open_ids[i] = []
     return i
 
   def close(self, slot):
@@ -278,7 +357,10 @@ class StreamingRecognizer:
 
   def step(self, feeds, return_logits=False, fetch=True):
     """``feeds``: {slot: float array [t, C]} (t may be 0).  A feed longer than ``max_chunk_frames`` is split into several passes.
-    ``fetch=False`` only enqueues (no host wait at all) and returns None: the new ids of such a step are dropped."""
+    ``fetch=False`` only enqueues (no host wait at all) and returns None: the new ids of such a step are dropped (with endpointing
+    it is refused: the finals would be lost)."""
+    if self.endpoint is not None and not fetch:
+      raise StreamError('fetch=False with endpointing: the utterances the step closes would be lost')
     return self._run(feeds, (), return_logits, fetch)
 
   def finish(self, slot, return_logits=False):
@@ -302,6 +384,8 @@ class StreamingRecognizer:
     result = StepResult()
     for slot in list(arrays) + [int(s) for s in finishing]:
       result.ids[slot], result.score[slot] = [], 0.0
+      if self.endpoint is not None:
+        result.finals[slot], result.open_ids[slot] = [], list(self._open_ids[slot])
       if self.beam:
         result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(self._logp[slot])
       if return_logits:
@@ -330,7 +414,7 @@ class StreamingRecognizer:
       raise StreamError('stream {}: layer {} would overrun its window ({} frames, capacity {})'.format(
           int(named[k]), int(l), int(n_after[k, l] - base[k, l]), self.cap[l]))
     limit = np.where(fin, (self._total[named] + new) // 2, -1)
-    if self.beam:
+    if self.beam and self.endpoint is None:
       # rows the searches will take (those at or past a finishing stream's limit are not decoded) against the pools' capacity
       taken = np.where(fin, np.clip(limit - first[:, -1], 0, count[:, -1]), count[:, -1])
       full = self._frames[named] + taken > self.max_frames
@@ -378,10 +462,13 @@ class StreamingRecognizer:
            spec.cout_pitch, None if lastl else info_ptr(l + 1), ptr(self.workspace), self.ws_bytes, sp)
       self.launches += 2
     call('st_stream_advance', ptr(self.layer_table), L, info_ptr(0), S, sp)
-    call('st_ctc_greedy_stream', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), S, ptr(self.dec_state),
-         ptr(self.dec_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum), sp)
+    if self.endpoint is not None:
+      self._launch_endpointed(tptr(L), tptr(L + 1), len(rows[-1]))
+    else:
+      call('st_ctc_greedy_stream', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), S, ptr(self.dec_state),
+           ptr(self.dec_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum), sp)
     self.launches += 2
-    if self.beam:
+    if self.beam and self.endpoint is None:
       # the beam searches take the same rows through the same table; the read-out only when its result is fetched (so that
       # the labels the device has declared final are exactly those the host holds)
       bm = self.beam
@@ -415,6 +502,8 @@ class StreamingRecognizer:
     for s in named.tolist():
       result.ids[s] += ids[s, :counts[s]].tolist()
       result.score[s] = float(score[s])
+    if self.endpoint is not None:
+      return self._read_endpointed(words, named.tolist(), fin, result)
     if self.beam:
       g = S * self.max_new + 2 * S
       res, tail = words[g:g + 4 * S].reshape(S, 4), words[g + 4 * S:].reshape(S, self.beam.max_tail)
@@ -435,6 +524,79 @@ class StreamingRecognizer:
       if failed is not None:
         failed.result = result                                    # the other streams' results of this step
         raise failed
+
+  def _launch_endpointed(self, rows_ptr, table_ptr, n_rows):
+    """The decoders of an endpointed step: the endpoint kernel in the greedy decoder's place -- it leaves the step's events and, per
+    utterance the step touches, a table of the decoders' own format on the device -- then the searches and their read-outs piece by
+    piece, all in one call and without a host wait in between."""
+    eng, S, P = self.engine, self.max_streams, self.n_pieces
+    ptr, sp = eng._ptr, eng.stream_ptr
+    R, L, M, space = self.ep_frames
+    call('st_ctc_greedy_endpoint_stream', ptr(self.logits), self.logits_pitch, self.num_classes, rows_ptr, table_ptr, S, space, R, L, M,
+         self.max_new, ptr(self.ep_state), ptr(self.ep_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum),
+         ptr(self.ep_events), ptr(self.ep_pieces), P, sp)
+    if self.beam:
+      bm = self.beam
+      call('st_ctc_beam_stream_step_pieces', ptr(self.logits), self.logits_pitch, self.num_classes, rows_ptr, ptr(self.ep_pieces), P, n_rows,
+           S, bm.beam_width, self._transform, self._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score,
+           ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws), self.beam_ws_bytes, ptr(self.beam_tail),
+           bm.max_tail, ptr(self.beam_result), sp)
+      self.launches += (1 if n_rows else 0) + 2 * P
+
+  def _read_endpointed(self, words, named, fin, result):
+    """The host's part of an endpointed step, from the step's one copy: the events close utterances in order, each with the greedy ids
+    up to its ``ids_end``; the pieces are walked in order -- a piece marked reset starts from an empty hypothesis, every read-out
+    appends its tail above the stable length the one before it stored, and a piece with a limit is a final."""
+    S, P = self.max_streams, self.n_pieces
+    ids, counts = words[:S * self.max_new].reshape(S, self.max_new), words[S * self.max_new:S * self.max_new + S]
+    g = S * self.max_new + 2 * S
+    events = words[g:g + S * P * 8].reshape(S, P, 8)
+    pieces = words[g + S * P * 8:g + self.ep_words].reshape(P, S, 4)
+    if self.beam:
+      g += self.ep_words
+      mt = self.beam.max_tail
+      res, tail = words[g:g + P * S * 4].reshape(P, S, 4), words[g + P * S * 4:].reshape(P, S, mt)
+    failed = None
+    for k, s in enumerate(named):
+      closed, prev, last_kind = [], 0, 0
+      for e in (events[s].tolist() if events[s, 0, 0] else ()):   # (most steps close nothing)
+        if e[0] == 0:
+          break
+        self._open_ids[s] += ids[s, prev:e[5]].tolist()
+        prev, last_kind = e[5], e[0]
+        if e[0] in Endpointing.KINDS:
+          closed.append(Utterance(e[7], Endpointing.KINDS[e[0]], e[1], e[2], e[3], e[4], self._open_ids[s],
+                                  float(np.asarray(e[6], np.int32).view(np.float32))))
+        self._open_ids[s] = []
+      self._open_ids[s] += ids[s, prev:counts[s]].tolist()
+      result.open_ids[s] = list(self._open_ids[s])
+      if self.beam:
+        at = 0
+        for p, (_, rows, limit, reset) in enumerate(pieces[:, s].tolist()):
+          if rows == 0 and limit < 0 and not reset:
+            continue
+          if reset:
+            self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
+          length, stable, old = int(res[p, s, 0]), int(res[p, s, 1]), int(self._stable[s])
+          if res[p, s, 3] != 0 or length - old > mt or length < old:
+            self._failed[s] = True
+            why = ('status {}'.format(int(res[p, s, 3])) if res[p, s, 3] != 0 else
+                   '{} labels are not final yet, max_tail = {}'.format(length - old, mt))
+            failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
+            break
+          self._hyp[s] = self._hyp[s][:old] + tail[p, s, :length - old].tolist()
+          self._stable[s], self._logp[s] = stable, res[p, s, 2:3].view(np.float32)[0]
+          if limit >= 0:                                          # a final: the whole-utterance search on its rows alone
+            closed[at].ids, closed[at].logp = self._hyp[s], float(self._logp[s])
+            at += 1
+            self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
+        if fin[k] and last_kind == 3:                             # what was open at the end held no speech: dropped like any discard
+          self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
+        result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
+      result.finals[s] += closed
+    if failed is not None:
+      failed.result = result
+      raise failed
 
   def _upload(self, array, dtype):
     """Host array -> device as a stream operation (pinned staging from torch's caching host allocator: no wait for the stream's
@@ -612,27 +774,36 @@ class StreamingFeatures:
         result[s].append(view[s, :count].cpu().numpy())
 
 
-def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False, beam=None):
+def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False, beam=None, endpoint=None):
   """One stream: feed the feature chunks ([t, C] each) in order, finish, and return ``(ids, partials)`` -- all label ids and the
   list of (input frames so far, ids so far) after every chunk that produced any -- plus the logits [T', C] on request.
   ``beam`` (a `StreamBeam`): the ids are the beam search's hypothesis -- at the end the whole-utterance search's result -- and a
-  partial is (input frames so far, hypothesis so far, how many of its leading ids are final) after every chunk that changed either."""
-  rec = StreamingRecognizer(engine, 1, max_chunk_frames, beam=beam)
+  partial is (input frames so far, hypothesis so far, how many of its leading ids are final) after every chunk that changed either.
+  ``endpoint`` (an `Endpointing`): the first value is the list of the stream's `Utterance`s instead, and the partials describe the
+  utterance open at the time."""
+  rec = StreamingRecognizer(engine, 1, max_chunk_frames, beam=beam, endpoint=endpoint)
   slot = rec.open()
-  ids, partials, rows, frames = [], [], [], 0
+  ids, partials, rows, frames, finals = [], [], [], 0, []
   for chunk in chunks:
     r = rec.step({slot: chunk}, return_logits=return_logits)
     frames += len(chunk)
+    if endpoint is not None:
+      finals += r.finals[slot]
     if beam:
       if not partials or (r.hyp[slot], r.stable[slot]) != partials[-1][1:]:
         partials.append((frames, r.hyp[slot], r.stable[slot]))
+    elif endpoint is not None:
+      if r.ids[slot]:
+        partials.append((frames, r.open_ids[slot]))
     elif r.ids[slot]:
       ids += r.ids[slot]
       partials.append((frames, list(ids)))
     if return_logits:
       rows.append(r.logits[slot])
   r = rec.finish(slot, return_logits=return_logits)
-  if beam:
+  if endpoint is not None:
+    ids = finals + r.finals[slot]
+  elif beam:
     ids = r.hyp[slot]
     partials.append((frames, ids, r.stable[slot]))
   else:
@@ -659,25 +830,41 @@ def _pcm_chunks(stream, samples_per_chunk):
       yield np.frombuffer(data, dtype='<i2').astype(np.float32) / 32768.0
 
 
-def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None):
+def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
+                 on_final=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
   ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
   which are then fed piece by piece -- not live; it yields what `transcribe --batch-size 1` yields and exists for comparison.
   ``beam`` (a `StreamBeam`): the ids are the beam search's -- at the end the whole-utterance search's result -- and
-  ``on_partial(seconds, hypothesis so far, how many of its leading ids are final)`` is called whenever either has changed."""
+  ``on_partial(seconds, hypothesis so far, how many of its leading ids are final)`` is called whenever either has changed.
+  ``endpoint`` (an `Endpointing`): the stream is cut into utterances; ``on_final(utterance)`` is called as each closes, the partials
+  describe the utterance open at the time, and the first value returned is the list of `Utterance`s."""
   hop = 160
   if normalize not in ('running', 'file'):
     raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
-  ids, fed, last = [], 0, [([], 0)]
+  ids, fed, last, finals = [], 0, [([], 0)], []
+
+  def closed(r, slot):
+    for u in r.finals[slot]:
+      finals.append(u)
+      if on_final:
+        on_final(u)
+    if r.finals[slot]:
+      last[0] = ([], 0)
 
   def feed(rec, slot, feats, seconds):
     r = rec.step({slot: feats})
+    if endpoint is not None:
+      closed(r, slot)
     if beam:
       if (r.hyp[slot], r.stable[slot]) != last[0]:
         last[0] = (r.hyp[slot], r.stable[slot])
         if on_partial:
           on_partial(seconds, list(r.hyp[slot]), r.stable[slot])
+    elif endpoint is not None:
+      if r.ids[slot] and r.open_ids[slot] and on_partial:
+        on_partial(seconds, list(r.open_ids[slot]))
     elif r.ids[slot]:
       ids.extend(r.ids[slot])
       if on_partial:
@@ -693,7 +880,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     front.step({slot: y})
     feats = front.finish(slot)
     per = max(max(len(p) for p in pieces) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint)
     rslot = rec.open()
     for at in range(0, len(feats), per):
       feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
@@ -702,7 +889,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     max_piece = int(max_piece or 16000)
     front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
     slot = front.open()
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint)
     rslot = rec.open()
     for p in pieces:
       p = np.asarray(p, np.float32)
@@ -712,17 +899,29 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
       raise StreamError('too short: {} samples (the features need more than {})'.format(fed, N_FFT // 2))
     feed(rec, rslot, front.finish(slot), fed / float(samplerate))
   r = rec.finish(rslot)
+  if endpoint is not None:
+    closed(r, rslot)
+    return finals, fed / float(samplerate)
   if beam:
     return r.hyp[rslot], fed / float(samplerate)
   ids.extend(r.ids[rslot])
   return ids, fed / float(samplerate)
 
 
+def endpoint_of(flags):
+  """The `Endpointing` the flags of `speecht-cli stream` ask for (None without --endpoint)."""
+  if not getattr(flags, 'endpoint', False):
+    return None
+  return Endpointing(silence=flags.endpoint_silence, lead=flags.endpoint_lead, max_utterance=flags.max_utterance)
+
+
 def run_cli(flags):
   """`speecht-cli stream PATH|-`: one line "seconds<TAB>transcript so far" per step that produced text, then the final transcript
   as `transcribe` prints it ("path<TAB>transcript").  With --language-model or --beam-width (the flags of `transcribe`, with their
   meaning there) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
-  leading characters that are final".  Creates no train / data / log directory."""
+  leading characters that are final".  With --endpoint the stream is cut into utterances: the partial lines describe the utterance that
+  is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
+  speech), and the closing line joins the finals' transcripts with spaces.  Creates no train / data / log directory."""
   import contextlib
   import sys
   from . import transcription, vocabulary
@@ -735,7 +934,7 @@ def run_cli(flags):
   with contextlib.redirect_stdout(sys.stderr):          # stdout carries the transcripts only
     model = create_default_model(flags, input_size, SingleInputLoader(input_size))
   try:
-    beam = None
+    beam, endpoint, on_final = None, endpoint_of(flags), None
     if getattr(flags, 'language_model', None) or getattr(flags, 'beam_width', 0):
       from .language_model import LanguageModel
       lm = LanguageModel.load(flags.language_model) if flags.language_model else None
@@ -753,16 +952,25 @@ def run_cli(flags):
     with Session(flags.device) as sess:
       with contextlib.redirect_stdout(sys.stderr):
         model.restore(sess, flags.run_train_dir)
+      extra = {}
+      if endpoint is not None:
+        frame_s = 0.01 * int(np.prod([l.stride for l in model.engine.layers]))
+        on_final = lambda u: print('utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s, (u.last_speech + 1) * frame_s,
+                                                                        vocabulary.ids_to_sentence(u.ids)), flush=True)
+        extra = dict(endpoint=endpoint, on_final=on_final)
       if beam:
         if flags.path != '-':
           beam['max_seconds'] = len(samples) / float(rate) + 1.0
         partial = lambda seconds, ids, stable: print('{:.2f}\t{}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids), stable), flush=True)
-        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per, beam=StreamBeam(**beam))
+        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per, beam=StreamBeam(**beam), **extra)
       else:
         partial = lambda seconds, ids: print('{:.2f}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids)), flush=True)
-        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per)
+        ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per, **extra)
   except (StreamError, transcription.TranscriptionError, ValueError) as e:
     print('stream: {}'.format(e), file=sys.stderr)
     return 1
+  if endpoint is not None:
+    print('{}\t{}'.format(flags.path, ' '.join(vocabulary.ids_to_sentence(u.ids) for u in ids)), flush=True)
+    return 0
   print('{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids)), flush=True)
   return 0
