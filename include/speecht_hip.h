@@ -977,6 +977,43 @@ int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_class
                                    void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
                                    int32_t* result, void* stream);
 
+/* ---- Hotword biasing of the streaming beam searches, with a phrase set per stream (csrc/ctc_beam.hip: ctc_beam_kernel<.., STREAM,
+ * BIAS>, ctc_beam_read_kernel<.., BIAS>).  The three entry points above with the second scorer of st_ctc_beam_search_decode_bias_nbest
+ * / _lm_bias_nbest: each takes the arguments of its unbiased form, then `bias` (the tables as there: device pointers, 1 <= n_states <=
+ * 2^20; a null struct or table and n_states < 1 are refused without a launch) and `roots`, a DEVICE array int32 [max_streams].  A
+ * stream decoded in steps is the biased whole-utterance search on the concatenated rows: ids, length and log_prob are those of the
+ * n_best = 1 list, bit for bit, however the rows were cut.  With a model the classes are the 28 labels and the blank, as above.
+ *   roots  A search that starts afresh -- table reset = 1: a stream's first step, or the piece after an endpoint event -- starts in
+ *          hotword state roots[s] (clamped to [0, n_states)) with no credit lent; roots[s] is read then and only then.  This is how
+ *          streams of one launch have phrase sets of their own: the caller concatenates the sets' tables, shifts set k's `next`
+ *          values by the row its states begin at, so that a match of set k that returns "to the root" returns to k's first row, and
+ *          names that row in roots[s] (speecht_amd/hotwords.py: HotwordSets; its set 0 is one state without gain, whose streams get
+ *          the unbiased search's bits).  One table of one set: roots all 0.
+ *   state  records of st_ctc_beam_stream_bias_state_bytes(beam_width, lm != NULL) bytes: the record of the unbiased search -- the same
+ *          layout at the same offsets -- followed by every entry's hotword state (int32 [64 or 128]) and bself, the gain it was
+ *          entered with (float [64 or 128]): 8 B per entry more.  The magic carries a bias bit (0x1000): a record last reset by an
+ *          unbiased step is left alone by a biased one and the reverse, and the read-out of the other kind reports status bit 1.
+ *   read   While a stream is open the reported hypothesis is entry 0 with its running total, which includes the credit lent to the
+ *          open match.  Once limit >= 0 every live entry adds fin[state] -- after the LM's end-of-utterance terms if there is a
+ *          model, and also without one -- and the best total wins, ties to the lower rank: the tail of the biased whole-utterance
+ *          searches.  A final of an endpointed piece therefore forfeits the credit of a phrase the cut leaves unfinished, and the
+ *          next utterance starts at roots[s] again.  stable_len is computed as above.
+ * st_ctc_beam_stream_state_bytes, the unbiased entry points, their launches and their records are unchanged. */
+size_t st_ctc_beam_stream_bias_state_bytes(int beam_width, int lm);
+int st_ctc_beam_stream_step_bias(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                                 int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                                 float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                                 size_t workspace_bytes, void* stream, const st_bias_tables* bias, const int32_t* roots);
+int st_ctc_beam_stream_read_bias(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                                 float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                                 int32_t* tail, int max_tail, int32_t* result, void* stream, const st_bias_tables* bias,
+                                 const int32_t* roots);
+int st_ctc_beam_stream_step_pieces_bias(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                        int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                        float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                        void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
+                                        int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots);
+
 /* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
  * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
  * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are

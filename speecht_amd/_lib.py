@@ -249,6 +249,16 @@ _SIGNATURES = {
     'st_ctc_beam_stream_step_pieces': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
                                                c_int, c_void_p, c_void_p]),
+    # ... biased by hotwords: the same arguments, then the st_bias_tables and the roots
+    'st_ctc_beam_stream_bias_state_bytes': (c_size_t, [c_int, c_int]),
+    'st_ctc_beam_stream_step_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
+                                             c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                             c_void_p]),
+    'st_ctc_beam_stream_read_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                             c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'st_ctc_beam_stream_step_pieces_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                    c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'st_spec_augment_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
                                     c_int, _T3P, c_void_p, c_void_p]),
     'st_spec_augment_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,

@@ -5,6 +5,8 @@
 // st_ctc_beam_stream_step / _read): the same frame loop between a load and a save of the beam's state.
 // Hotword biasing (ctc_beam_kernel<.., BIAS = true>, st_ctc_beam_search_decode_bias_nbest / _lm_bias_nbest) is a second scorer of the
 // LM's shape: a table-driven automaton over the labels whose state is a function of the prefix alone (BiasArgs below).
+// The biased searches run carried across steps too (ctc_beam_kernel<.., STREAM, BIAS>, ctc_beam_read_kernel<.., BIAS>;
+// st_ctc_beam_stream_step_bias / _read_bias / _step_pieces_bias), each stream starting in a root state of its own (roots[]).
 //
 // The reference reaches a beam search only through its KenLM TensorFlow fork (speech_model.py:101-111);
 // this kernel follows the stock tf.nn.ctc_beam_search_decoder recursion, with the candidate order of
@@ -332,11 +334,18 @@ struct StreamHeader {     // the first kStateHeader bytes of a state record
 constexpr int kStateHeader = 32;
 constexpr int kPoolFull = 1;
 static_assert(sizeof(StreamHeader) == kStateHeader, "state record header");
-__host__ __device__ constexpr int stream_magic(int W, bool lm) { return 0x53420000 | (W << 1) | (lm ? 1 : 0); }
-// record: [header | BeamSet<MAXB> | LM: LmSet<MAXB>, deltas [MAXB][kDeltaPitch]]
+// (bit 12: a hotword-biased search -- its records carry two more arrays, and neither kind continues the other's)
+__host__ __device__ constexpr int stream_magic(int W, bool lm, bool bias = false) {
+  return 0x53420000 | (bias ? 0x1000 : 0) | (W << 1) | (lm ? 1 : 0);
+}
+// record: [header | BeamSet<MAXB> | LM: LmSet<MAXB>, deltas [MAXB][kDeltaPitch] | BIAS: hotword states int [MAXB], bself float [MAXB]]
 template <int MAXB>
 constexpr size_t stream_state_bytes(bool lm) {
   return kStateHeader + sizeof(BeamSet<MAXB>) + (lm ? sizeof(LmSet<MAXB>) + sizeof(float) * MAXB * kDeltaPitch : 0);
+}
+template <int MAXB>
+constexpr size_t stream_bias_state_bytes(bool lm) {
+  return stream_state_bytes<MAXB>(lm) + (sizeof(int) + sizeof(float)) * MAXB;
 }
 
 template <bool STREAM>
@@ -359,14 +368,21 @@ struct StreamArgs<true> {
 // as the LM deltas have, would cost 32 KB more at MAXB = 128 and a 128-byte copy per entry and frame for a row that, unlike the LM's,
 // costs nothing to look up again.  Every state written to LDS is clamped to [0, n_states): a malformed table gives wrong text, never
 // a read outside the tables.  BIAS = false compiles to the kernels above (its BiasArgs is empty).
-template <bool BIAS>
+// STREAM && BIAS: the entries' states and bself are saved in the record behind the other parts and restored from it; a search that
+// starts afresh (the stream's first step, a reset of an endpointed piece) starts in state roots[stream], not 0 -- the tables may hold
+// several phrase sets one after the other, each set's `next` pointing into its own rows, and roots[s] is the first row of stream s's.
+template <bool BIAS, bool STREAM = false>
 struct BiasArgs {};
 template <>
-struct BiasArgs<true> {
+struct BiasArgs<true, false> {
   const int* next;        // [n_states][kBiasPitch]
   const float* gain;      // [n_states][kBiasPitch]
   const float* fin;       // [n_states]
   int n_states;
+};
+template <>
+struct BiasArgs<true, true> : BiasArgs<true, false> {
+  const int* roots;       // [streams]
 };
 constexpr int kBiasPitch = 32;
 
@@ -383,9 +399,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
                                                       int2* __restrict__ node_pool, long pool_stride,
                                                       int* __restrict__ ids, int max_out,
                                                       int* __restrict__ out_lens, float* __restrict__ out_logp, LmArgs lma,
-                                                      NbestArgs<NBEST> nx, StreamArgs<STREAM> sx = {}, BiasArgs<BIAS> bx = {}) {
+                                                      NbestArgs<NBEST> nx, StreamArgs<STREAM> sx = {},
+                                                      BiasArgs<BIAS, BIAS && STREAM> bx = {}) {
   static_assert(!(NBEST && STREAM), "a stream has no N-best lists");
-  static_assert(!BIAS || (NBEST && !STREAM), "hotwords: the N-best instantiations only (the top path is the n_best = 1 list)");
+  static_assert(!BIAS || NBEST || STREAM, "hotwords: the N-best and the stream instantiations only (the top path is the n_best = 1 list)");
   constexpr bool WIDE = MAXB > 64;
   constexpr int SURV = WIDE ? 256 : 128;             // capacity of the fast selection; more survivors take the sequential rounds
   static_assert(MAXB == 64 || (MAXB == 128 && CPL == 64), "wide beams: 128 entries x 32 class slots = 64 candidates per lane");
@@ -423,7 +440,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     first = sx.table[4 * b];
     const int count = sx.table[4 * b + 1], limit = sx.table[4 * b + 2];
     fresh = sx.table[4 * b + 3] != 0;
-    if (!fresh && hdr->magic != stream_magic(W, LM)) return;     // never reset for this search: nothing to continue
+    if (!fresh && hdr->magic != stream_magic(W, LM, BIAS)) return;     // never reset for this search: nothing to continue
     if (!fresh) { t0 = hdr->frames; status = hdr->status; }
     Tb = count;
     if (limit >= 0 && count > 0) Tb = max(min(count, limit - sx.rows[2 * first + 1]), 0);   // rows at or past the limit
@@ -465,13 +482,24 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         copy_words(&delta_s[0][0][0], rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>),
                    sizeof(float) * MAXB * kDeltaPitch, lane);
       }
+      if constexpr (BIAS) {
+        // (clamped like every state written to LDS: whatever the record holds, no read leaves the tables)
+        const int* saved = reinterpret_cast<const int*>(rec + stream_state_bytes<MAXB>(LM));
+        for (int e = lane; e < MAXB; e += 64) bstate_s[0][e] = min(max(saved[e], 0), bx.n_states - 1);
+        copy_words(&bself_s[0][0], rec + stream_state_bytes<MAXB>(LM) + sizeof(int) * MAXB, sizeof(float) * MAXB, lane);
+      }
     }
   }
   if (lane == 0 && fresh) {
     BeamSet<MAXB>& s = sets[0];
     s.hash[0] = kRootHash; s.parent_hash[0] = 0; s.len[0] = 0; s.last[0] = -1; s.node[0] = 0;
     s.pb[0] = 0.f; s.pl[0] = -INFINITY; s.total[0] = 0.f;
-    if constexpr (BIAS) { bstate_s[0][0] = 0; bself_s[0][0] = 0.f; }
+    if constexpr (BIAS) {
+      int root = 0;
+      if constexpr (STREAM) root = min(max(bx.roots[b], 0), bx.n_states - 1);
+      bstate_s[0][0] = root;
+      bself_s[0][0] = 0.f;
+    }
     if constexpr (LM) {
       // root: context <s>, the trie root, lm_score = score = 0
       LmSet<LMB>& L = lms[0];
@@ -884,8 +912,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       copy_words(rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>), &delta_s[cur][0][0],
                  sizeof(float) * MAXB * kDeltaPitch, lane);
     }
+    if constexpr (BIAS) {
+      copy_words(rec + stream_state_bytes<MAXB>(LM), &bstate_s[cur][0], sizeof(int) * MAXB, lane);
+      copy_words(rec + stream_state_bytes<MAXB>(LM) + sizeof(int) * MAXB, &bself_s[cur][0], sizeof(float) * MAXB, lane);
+    }
     if (lane == 0) {
-      hdr->magic = stream_magic(W, LM);
+      hdr->magic = stream_magic(W, LM, BIAS);
       hdr->nb = nb;
       hdr->frames = t0 + Tb;
       hdr->status = status;
@@ -996,13 +1028,17 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
 //    the stored stable_len -- never to the root -- and stops early where the two chains join.
 //  - Hypothesis: open stream: entry 0 (running total).  Finishing (limit >= 0): the whole-utterance tail -- with the LM every entry
 //    gains its end-of-utterance terms (lm_final_total) and the best total wins, ties to the lower rank; LM-free entry 0.
+//    BIAS (a record of ctc_beam_kernel<.., STREAM, BIAS>): a finishing stream resolves every entry's open hotword match -- fin[state(e)]
+//    is added after the LM's terms, with or without a model, and the best total wins as above: the tail of the biased whole-utterance
+//    searches.  An open stream reports entry 0's running total, which carries the credit lent to its open match.
 // result[s] = {length of the hypothesis, new stable_len, log-probability (float bits), status}; tail[s][i] = label stable_len_old + i
 // of the hypothesis for i < max_tail.
 constexpr int kNoState = 2;
-template <int MAXB, bool LM>
+template <int MAXB, bool LM, bool BIAS = false>
 __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict__ table, int W, char* __restrict__ state, long state_stride,
                                                            const int2* __restrict__ node_pool, long pool_stride,
-                                                           int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma) {
+                                                           int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma,
+                                                           BiasArgs<BIAS> bx = {}) {
   __shared__ float fin[MAXB];
   const int s = blockIdx.x, lane = threadIdx.x;
   const int count = table[4 * s + 1], limit = table[4 * s + 2], reset = table[4 * s + 3];
@@ -1011,7 +1047,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict
   StreamHeader* hdr = reinterpret_cast<StreamHeader*>(rec);
   int* res = result + 4 * s;
   const int nb = min(max(hdr->nb, 0), W);
-  if (hdr->magic != stream_magic(W, LM) || nb == 0) {
+  if (hdr->magic != stream_magic(W, LM, BIAS) || nb == 0) {
     if (lane == 0) {
       res[0] = 0; res[1] = 0; res[2] = __float_as_int(-INFINITY); res[3] = kNoState;
     }
@@ -1023,12 +1059,20 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict
   // the reported entry and its total
   int e0 = 0;
   float v0 = S.total[0];
-  if constexpr (LM) {
+  if constexpr (LM || BIAS) {
     if (limit >= 0) {
-      const LmSet<MAXB>& L = *reinterpret_cast<const LmSet<MAXB>*>(rec + kStateHeader + sizeof(BeamSet<MAXB>));
-      const float* deltas = reinterpret_cast<const float*>(rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>));
-      const LmParams lmp{lma.v, lma.w[0][0], lma.w[0][1], lma.w[0][2], lma.oov_score};
-      for (int e = lane; e < nb; e += 64) fin[e] = lm_final_total(lmp, L, deltas + (long)e * kDeltaPitch, S.total[e], e);
+      [[maybe_unused]] const LmSet<MAXB>& L = *reinterpret_cast<const LmSet<MAXB>*>(rec + kStateHeader + sizeof(BeamSet<MAXB>));
+      [[maybe_unused]] const float* deltas =
+          reinterpret_cast<const float*>(rec + kStateHeader + sizeof(BeamSet<MAXB>) + sizeof(LmSet<MAXB>));
+      [[maybe_unused]] const LmParams lmp{lma.v, lma.w[0][0], lma.w[0][1], lma.w[0][2], lma.oov_score};
+      [[maybe_unused]] const int* bstate = reinterpret_cast<const int*>(rec + stream_state_bytes<MAXB>(LM));
+      for (int e = lane; e < nb; e += 64) {
+        float v;
+        if constexpr (LM) v = lm_final_total(lmp, L, deltas + (long)e * kDeltaPitch, S.total[e], e);
+        else v = S.total[e];
+        if constexpr (BIAS) v += bx.fin[min(max(bstate[e], 0), bx.n_states - 1)];
+        fin[e] = v;
+      }
       __syncthreads();
       for (int e = 1; e < nb; ++e)
         if (fin[e] > fin[e0]) e0 = e;
@@ -1341,6 +1385,12 @@ size_t st_ctc_beam_stream_state_bytes(int beam_width, int lm) {
   return st::round_up(beam_width > 64 ? stream_state_bytes<128>(lm != 0) : stream_state_bytes<64>(lm != 0), 64);
 }
 
+// the record of a hotword-biased search: the same, then the entries' hotword states and bself (8 B per entry)
+size_t st_ctc_beam_stream_bias_state_bytes(int beam_width, int lm) {
+  if (beam_width < 1 || beam_width > kMaxBeam) return 0;
+  return st::round_up(beam_width > 64 ? stream_bias_state_bytes<128>(lm != 0) : stream_bias_state_bytes<64>(lm != 0), 64);
+}
+
 size_t st_ctc_beam_stream_pool_bytes(int max_frames, int beam_width) {
   if (max_frames < 1 || beam_width < 1 || beam_width > kMaxBeam) return 0;
   return st::round_up(((size_t)max_frames * beam_width + 1) * sizeof(int2), 64);
@@ -1393,65 +1443,103 @@ static int beam_stream_step_args(const char* who, const float* logits, int pitch
   return ST_OK;
 }
 
-// one launch of the search over all streams, their work taken from `table` (device memory)
+// the hotword tables and roots of a biased stream search (bias_args' checks; `roots` is the device's, nothing is read here)
+static int beam_stream_bias_args(const char* who, const st_bias_tables* bias, const int32_t* roots, BiasArgs<true, true>* sbx) {
+  BiasArgs<true> bx{};
+  if (int e = bias_args(who, bias, &bx)) return e;
+  ST_REQUIRE(roots, "%s: null argument", who);
+  *sbx = BiasArgs<true, true>{bx, roots};
+  return ST_OK;
+}
+
+// one launch of the search over all streams, their work taken from `table` (device memory); sbx: the hotword-biased search
 static void launch_beam_stream(const float* lp_rows, int num_classes, const int32_t* rows, const int32_t* table, int n_rows, int max_streams,
                                int beam_width, int input_transform, bool lm, const LmArgs& lma, void* state, void* pool, int max_frames,
-                               hipStream_t s) {
+                               hipStream_t s, const BiasArgs<true, true>* sbx = nullptr) {
   const bool wide = beam_width > 64;
-  if (lm)
+  const int per_lane = st::ceil_div(beam_width * num_classes, 64);
+  // (the biased lines also name the dispatch: cpl = candidates per lane of the instantiation launched)
+  const int cpl = wide ? 64 : per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : per_lane <= 16 ? 16 : 32;
+  if (sbx && lm)
+    st::trace("ctc_beam_stream_lm_bias<%s> beam=%d transform=%d order=%d states=%d streams=%d rows=%d cpl=%d", wide ? "wide" : "wave",
+              beam_width, input_transform, lma.v.order, sbx->n_states, max_streams, n_rows, cpl);
+  else if (sbx)
+    st::trace("ctc_beam_stream_bias<%s> beam=%d transform=%d states=%d streams=%d rows=%d cpl=%d", wide ? "wide" : "wave", beam_width,
+              input_transform, sbx->n_states, max_streams, n_rows, cpl);
+  else if (lm)
     st::trace("ctc_beam_stream_lm<%s> beam=%d transform=%d order=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width,
               input_transform, lma.v.order, max_streams, n_rows);
   else
     st::trace("ctc_beam_stream<%s> beam=%d transform=%d streams=%d rows=%d", wide ? "wide" : "wave", beam_width, input_transform,
               max_streams, n_rows);
-  const StreamArgs<true> sx{rows, table, static_cast<char*>(state), (long)st_ctc_beam_stream_state_bytes(beam_width, lm),
-                            max_frames};
+  const long stride = (long)(sbx ? st_ctc_beam_stream_bias_state_bytes(beam_width, lm) : st_ctc_beam_stream_state_bytes(beam_width, lm));
+  const StreamArgs<true> sx{rows, table, static_cast<char*>(state), stride, max_frames};
   const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));   // pairs per stream
-  const int per_lane = st::ceil_div(beam_width * num_classes, 64);
 #define ST_LAUNCH_STREAM_AS(CPL, MAXB, LM)                                                                            \
   hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, LM, false, true>), dim3(max_streams), dim3(64), 0, s, lp_rows, 0, num_classes, \
                      (const int*)nullptr, beam_width, reinterpret_cast<int2*>(pool), pool_stride, \
                      (int*)nullptr, 0, (int*)nullptr, (float*)nullptr, lma, NbestArgs<false>{}, sx)
+#define ST_LAUNCH_STREAM_BIAS(CPL, MAXB, LM)                                                                          \
+  hipLaunchKernelGGL((ctc_beam_kernel<CPL, MAXB, LM, false, true, true>), dim3(max_streams), dim3(64), 0, s, lp_rows, 0, num_classes, \
+                     (const int*)nullptr, beam_width, reinterpret_cast<int2*>(pool), pool_stride, \
+                     (int*)nullptr, 0, (int*)nullptr, (float*)nullptr, lma, NbestArgs<false>{}, sx, *sbx)
 #define ST_LAUNCH_STREAM(CPL, MAXB)                                                                                   \
   do {                                                                                                                \
-    if (lm) ST_LAUNCH_STREAM_AS(CPL, MAXB, true);                                                                      \
+    if (sbx && lm) ST_LAUNCH_STREAM_BIAS(CPL, MAXB, true);                                                             \
+    else if (sbx) ST_LAUNCH_STREAM_BIAS(CPL, MAXB, false);                                                             \
+    else if (lm) ST_LAUNCH_STREAM_AS(CPL, MAXB, true);                                                                 \
     else ST_LAUNCH_STREAM_AS(CPL, MAXB, false);                                                                        \
   } while (0)
-  if (wide) ST_LAUNCH_STREAM(64, 128);
-  else if (per_lane <= 4) ST_LAUNCH_STREAM(4, 64);
-  else if (per_lane <= 8) ST_LAUNCH_STREAM(8, 64);
-  else if (per_lane <= 16) ST_LAUNCH_STREAM(16, 64);
+  if (cpl == 64) ST_LAUNCH_STREAM(64, 128);
+  else if (cpl == 4) ST_LAUNCH_STREAM(4, 64);
+  else if (cpl == 8) ST_LAUNCH_STREAM(8, 64);
+  else if (cpl == 16) ST_LAUNCH_STREAM(16, 64);
   else ST_LAUNCH_STREAM(32, 64);
 #undef ST_LAUNCH_STREAM
+#undef ST_LAUNCH_STREAM_BIAS
 #undef ST_LAUNCH_STREAM_AS
 }
 
 // one launch of the read-out over all streams
 static void launch_beam_stream_read(const int32_t* table, int max_streams, int beam_width, bool lm, const LmArgs& lma, void* state,
-                                    const void* pool, int max_frames, int32_t* tail, int max_tail, int32_t* result, hipStream_t s) {
+                                    const void* pool, int max_frames, int32_t* tail, int max_tail, int32_t* result, hipStream_t s,
+                                    const BiasArgs<true, true>* sbx = nullptr) {
   const bool wide = beam_width > 64;
-  st::trace("ctc_beam_stream_read<%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", beam_width, max_streams);
-  const long stride = (long)st_ctc_beam_stream_state_bytes(beam_width, lm);
+  st::trace("ctc_beam_stream_read<%s%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", sbx ? ", bias" : "", beam_width,
+            max_streams);
+  const long stride = (long)(sbx ? st_ctc_beam_stream_bias_state_bytes(beam_width, lm) : st_ctc_beam_stream_state_bytes(beam_width, lm));
   const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));
 #define ST_LAUNCH_READ(MAXB, LM)                                                                                      \
   hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM>), dim3(max_streams), dim3(64), 0, s, table, beam_width, \
                      static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
                      tail, max_tail, result, lma)
-  if (wide) { if (lm) ST_LAUNCH_READ(128, true); else ST_LAUNCH_READ(128, false); }
+#define ST_LAUNCH_READ_BIAS(MAXB, LM)                                                                                 \
+  hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM, true>), dim3(max_streams), dim3(64), 0, s, table, beam_width, \
+                     static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
+                     tail, max_tail, result, lma, static_cast<const BiasArgs<true>&>(*sbx))
+  if (sbx) {
+    if (wide) { if (lm) ST_LAUNCH_READ_BIAS(128, true); else ST_LAUNCH_READ_BIAS(128, false); }
+    else { if (lm) ST_LAUNCH_READ_BIAS(64, true); else ST_LAUNCH_READ_BIAS(64, false); }
+  } else if (wide) { if (lm) ST_LAUNCH_READ(128, true); else ST_LAUNCH_READ(128, false); }
   else { if (lm) ST_LAUNCH_READ(64, true); else ST_LAUNCH_READ(64, false); }
+#undef ST_LAUNCH_READ_BIAS
 #undef ST_LAUNCH_READ
 }
 
-int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
-                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
-                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  const char* who = "beam stream step";
+// the three entry points and their hotword-biased forms (`biased`: bias and roots are checked and the BIAS instantiations launched)
+static int beam_stream_step(const char* who, const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table,
+                            int n_rows, int max_streams, int beam_width, int input_transform, void* lm, float lm_weight,
+                            float word_count_weight, float valid_word_count_weight, float oov_score, void* state, void* pool,
+                            int max_frames, void* workspace, size_t workspace_bytes, void* stream, bool biased, const st_bias_tables* bias,
+                            const int32_t* roots) {
   if (int e = beam_stream_step_args(who, logits, pitch, num_classes, rows, n_rows, input_transform, lm)) return e;
   LmArgs lma;
   if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
                                  state, pool, max_frames, stream, &lma))
     return e;
+  BiasArgs<true, true> sbx{};
+  if (biased)
+    if (int e = beam_stream_bias_args(who, bias, roots, &sbx)) return e;
   const size_t need = st_ctc_beam_stream_ws(n_rows);
   if (need && (!workspace || workspace_bytes < need)) {
     st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
@@ -1463,34 +1551,37 @@ int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, con
     hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
                        input_transform, lp_rows);
   launch_beam_stream(lp_rows, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm != nullptr, lma, state, pool,
-                     max_frames, s);
+                     max_frames, s, biased ? &sbx : nullptr);
   return st::check_launch("ctc_beam_stream_step");
 }
 
-int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
-                            float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
-                            int32_t* tail, int max_tail, int32_t* result, void* stream) {
-  const char* who = "beam stream read";
+static int beam_stream_read(const char* who, const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight,
+                            float word_count_weight, float valid_word_count_weight, float oov_score, void* state, const void* pool,
+                            int max_frames, int32_t* tail, int max_tail, int32_t* result, void* stream, bool biased,
+                            const st_bias_tables* bias, const int32_t* roots) {
   ST_REQUIRE(tail && result, "%s: null argument", who);
   ST_REQUIRE(max_tail >= 1, "%s: max_tail must be positive, got %d", who, max_tail);
   LmArgs lma;
   if (int e = beam_stream_common(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
                                  state, pool, max_frames, stream, &lma))
     return e;
+  BiasArgs<true, true> sbx{};
+  if (biased)
+    if (int e = beam_stream_bias_args(who, bias, roots, &sbx)) return e;
   launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames, tail, max_tail, result,
-                          st::as_stream(stream));
+                          st::as_stream(stream), biased ? &sbx : nullptr);
   return st::check_launch("ctc_beam_stream_read");
 }
 
 // An endpointed step (stream_endpoint.hip wrote `pieces` [n_pieces][max_streams][4] on this stream): the log-softmax of the step's
 // rows once, then for every piece in order the search and its read-out, each taking its work from pieces[p] -- device memory, so
 // nothing waits for the host.  A slot {0, 0, -1, 0} makes both kernels leave at once.
-int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
-                                   int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
-                                   float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score, void* state,
-                                   void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
-                                   int32_t* result, void* stream) {
-  const char* who = "beam stream step pieces";
+static int beam_stream_step_pieces(const char* who, const float* logits, int pitch, int num_classes, const int32_t* rows,
+                                   const int32_t* pieces, int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform,
+                                   void* lm, float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                   void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
+                                   int max_tail, int32_t* result, void* stream, bool biased, const st_bias_tables* bias,
+                                   const int32_t* roots) {
   if (int e = beam_stream_step_args(who, logits, pitch, num_classes, rows, n_rows, input_transform, lm)) return e;
   ST_REQUIRE(n_pieces >= 1, "%s: n_pieces must be positive, got %d", who, n_pieces);
   ST_REQUIRE(tail && result, "%s: null argument", who);
@@ -1499,6 +1590,9 @@ int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_class
   if (int e = beam_stream_common(who, pieces, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score,
                                  state, pool, max_frames, stream, &lma))
     return e;
+  BiasArgs<true, true> sbx{};
+  if (biased)
+    if (int e = beam_stream_bias_args(who, bias, roots, &sbx)) return e;
   const size_t need = st_ctc_beam_stream_ws(n_rows);
   if (need && (!workspace || workspace_bytes < need)) {
     st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
@@ -1512,11 +1606,67 @@ int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_class
   for (int p = 0; p < n_pieces; ++p) {
     const int32_t* table = pieces + (long)p * max_streams * 4;
     launch_beam_stream(lp_rows, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm != nullptr, lma, state, pool,
-                       max_frames, s);
+                       max_frames, s, biased ? &sbx : nullptr);
     launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames,
-                            tail + (long)p * max_streams * max_tail, max_tail, result + (long)p * max_streams * 4, s);
+                            tail + (long)p * max_streams * max_tail, max_tail, result + (long)p * max_streams * 4, s,
+                            biased ? &sbx : nullptr);
   }
   return st::check_launch("ctc_beam_stream_step_pieces");
+}
+
+int st_ctc_beam_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  return beam_stream_step("beam stream step", logits, pitch, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm,
+                          lm_weight, word_count_weight, valid_word_count_weight, oov_score, state, pool, max_frames, workspace,
+                          workspace_bytes, stream, false, nullptr, nullptr);
+}
+
+int st_ctc_beam_stream_read(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                            float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                            int32_t* tail, int max_tail, int32_t* result, void* stream) {
+  return beam_stream_read("beam stream read", table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight,
+                          oov_score, state, pool, max_frames, tail, max_tail, result, stream, false, nullptr, nullptr);
+}
+
+int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                   int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                   float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score, void* state,
+                                   void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
+                                   int32_t* result, void* stream) {
+  return beam_stream_step_pieces("beam stream step pieces", logits, pitch, num_classes, rows, pieces, n_pieces, n_rows, max_streams,
+                                 beam_width, input_transform, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score, state,
+                                 pool, max_frames, workspace, workspace_bytes, tail, max_tail, result, stream, false, nullptr, nullptr);
+}
+
+// ... biased by hotwords: the records are those of st_ctc_beam_stream_bias_state_bytes, a fresh search starts in state roots[stream]
+int st_ctc_beam_stream_step_bias(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                                 int max_streams, int beam_width, int input_transform, void* lm, float lm_weight, float word_count_weight,
+                                 float valid_word_count_weight, float oov_score, void* state, void* pool, int max_frames, void* workspace,
+                                 size_t workspace_bytes, void* stream, const st_bias_tables* bias, const int32_t* roots) {
+  return beam_stream_step("beam stream step (hotwords)", logits, pitch, num_classes, rows, table, n_rows, max_streams, beam_width,
+                          input_transform, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score, state, pool, max_frames,
+                          workspace, workspace_bytes, stream, true, bias, roots);
+}
+
+int st_ctc_beam_stream_read_bias(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                                 float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                                 int32_t* tail, int max_tail, int32_t* result, void* stream, const st_bias_tables* bias,
+                                 const int32_t* roots) {
+  return beam_stream_read("beam stream read (hotwords)", table, max_streams, beam_width, lm, lm_weight, word_count_weight,
+                          valid_word_count_weight, oov_score, state, pool, max_frames, tail, max_tail, result, stream, true, bias, roots);
+}
+
+int st_ctc_beam_stream_step_pieces_bias(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                        int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                        float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                        void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
+                                        int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots) {
+  return beam_stream_step_pieces("beam stream step pieces (hotwords)", logits, pitch, num_classes, rows, pieces, n_pieces, n_rows,
+                                 max_streams, beam_width, input_transform, lm, lm_weight, word_count_weight, valid_word_count_weight,
+                                 oov_score, state, pool, max_frames, workspace, workspace_bytes, tail, max_tail, result, stream, true, bias,
+                                 roots);
 }
 
 }  // extern "C"

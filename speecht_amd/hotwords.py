@@ -164,6 +164,45 @@ class Hotwords:
     return self._device[key]
 
 
+class HotwordSets:
+  """``HotwordSets(sets)``: several phrase sets (each a `Hotwords`, with a weight of its own, or a list of phrases) in ONE table, for
+  searches that run side by side with a set each -- the streams of a `streaming.StreamingRecognizer`.  Set 0 is always the empty set
+  (one state, every gain 0: a search rooted there returns the unbiased search's bits); the given sets follow as 1, 2, ...  Set k's
+  states are the rows ``base[k] .. base[k + 1]`` of ``next`` / ``gain`` / ``fin``, its ``next`` values shifted by ``base[k]`` -- a
+  match that returns to the root returns to row ``base[k]``, set k's own -- so a search that STARTS in state ``base[k]`` never leaves
+  set k's rows.  At most MAX_STATES states in all."""
+
+  def __init__(self, sets):
+    if isinstance(sets, (str, Hotwords)):
+      raise HotwordError('hotword sets: give a list of Hotwords')
+    self.sets = [Hotwords([])] + [s if isinstance(s, Hotwords) else Hotwords(s) for s in sets]
+    counts = [s.n_states for s in self.sets]
+    self.base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    self.n_states = int(self.base[-1])
+    if self.n_states > MAX_STATES:
+      raise HotwordError('hotword sets: {} trie nodes in all, at most {}'.format(self.n_states, MAX_STATES))
+    self.next = np.concatenate([s.next + np.int32(b) for s, b in zip(self.sets, self.base)])
+    self.gain = np.concatenate([s.gain for s in self.sets])
+    self.fin = np.concatenate([s.fin for s in self.sets])
+    self._device = {}
+
+  def __len__(self):
+    return len(self.sets)
+
+  def root(self, index):
+    """The state a search of set ``index`` starts in."""
+    if not isinstance(index, (int, np.integer)) or not 0 <= index < len(self.sets):
+      raise HotwordError('hotword set {!r}: sets 0..{} exist'.format(index, len(self.sets) - 1))
+    return int(self.base[index])
+
+  def tables(self, index):
+    """Set ``index`` alone, as the whole-utterance searches take it: its `Hotwords`."""
+    self.root(index)
+    return self.sets[index]
+
+  device_tables = Hotwords.device_tables
+
+
 def from_flags(flags):
   """The `Hotwords` of ``--hotwords FILE`` / ``--hotword TEXT`` / ``--hotword-weight X``, or None when neither list is given."""
   phrases = []

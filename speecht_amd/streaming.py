@@ -20,6 +20,9 @@ steps.  A chunked search is the whole-utterance search: after `finish` the hypot
 ``engine.beam_search_decode`` / ``lm_beam_search_decode`` return on the stream's logits, bit for bit and however the audio was cut.
 Before that a step reports the best hypothesis so far and how many of its leading ids are final (the common prefix of all live
 entries).  Such a stream can decode ``StreamBeam.max_seconds`` of audio: its node pool is sized when the recogniser is built.
+``StreamBeam(hotwords=...)`` biases that search towards phrases as ``transcribe(hotwords=)`` does (speecht_amd/hotwords.py), with one
+phrase set for all streams or -- `hotwords.HotwordSets`, ``open(hotwords=k)`` -- a set per stream; `finish` then returns what
+``engine.beam_search_decode_nbest(1, ..., hotwords=)`` returns on the stream's logits with the stream's set.
 
 With ``endpoint=Endpointing(...)`` the device also cuts every stream into utterances (csrc/stream_endpoint.hip): once silence has
 followed speech, or an utterance has reached its longest length, the step hands back a final -- the offline decoder's result on
@@ -145,10 +148,22 @@ class StreamBeam:
   ``engine.beam_search_decode`` -- with ``lm`` (a `language_model.LanguageModel` or the path of an ARPA file) that of
   ``engine.lm_beam_search_decode`` -- carried across steps, with those methods' defaults: beam 16 on the logits without a model,
   beam 100 on log10(softmax + 1e-8) with one.  ``max_seconds`` sizes every stream's node pool (8 B x beam x 50 output frames per
-  second of audio); ``max_tail`` is the longest run of not yet final labels a step can report."""
+  second of audio); ``max_tail`` is the longest run of not yet final labels a step can report.  ``hotwords``: the search biased
+  towards phrases, as ``engine.beam_search_decode_nbest(..., hotwords=)`` is (st_ctc_beam_stream_step_bias / _read_bias /
+  _step_pieces_bias) -- a `hotwords.Hotwords`, which every stream then uses, or a `hotwords.HotwordSets`, of which every stream
+  names one when it is opened (`StreamingRecognizer.open(hotwords=index)`; set 0, the empty one, by default)."""
 
   def __init__(self, beam_width=None, lm=None, lm_weight=0.8, word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0,
-               input_transform='default', max_seconds=120.0, max_tail=256):
+               input_transform='default', max_seconds=120.0, max_tail=256, hotwords=None):
+    self.hotwords, self.default_set = None, 0
+    if hotwords is not None:
+      from .hotwords import Hotwords, HotwordSets
+      if isinstance(hotwords, Hotwords):
+        self.hotwords, self.default_set = HotwordSets([hotwords]), 1
+      elif isinstance(hotwords, HotwordSets):
+        self.hotwords = hotwords
+      else:
+        raise StreamError('hotwords must be a Hotwords or a HotwordSets, got {!r}'.format(type(hotwords).__name__))
     if isinstance(lm, str):
       from .language_model import LanguageModel
       lm = LanguageModel.load(lm)
@@ -302,6 +317,13 @@ class StreamingRecognizer:
         from .engine_decode import beam_input_transform
         self._transform = beam_input_transform(beam.input_transform)
         state_bytes = int(lib.st_ctc_beam_stream_state_bytes(beam.beam_width, int(beam.lm is not None)))
+        self._bias = ()                                              # the `_bias` entry points' two last arguments
+        if beam.hotwords is not None:
+          state_bytes = int(lib.st_ctc_beam_stream_bias_state_bytes(beam.beam_width, int(beam.lm is not None)))
+          nxt, gain, fin = self._bias_tables = beam.hotwords.device_tables(dev)
+          self._bias_struct = _lib.BiasTables(nxt.data_ptr(), gain.data_ptr(), fin.data_ptr(), beam.hotwords.n_states)
+          self.beam_roots = torch.zeros(S, dtype=torch.int32, device=dev)
+          self._bias = (ctypes.byref(self._bias_struct), ctypes.c_void_p(self.beam_roots.data_ptr()))
         pool_bytes = int(lib.st_ctc_beam_stream_pool_bytes(self.max_frames, beam.beam_width))
         self.beam_ws_bytes = int(lib.st_ctc_beam_stream_ws(self.max_rows[-1]))
         self.beam_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
@@ -328,11 +350,24 @@ class StreamingRecognizer:
 
   # -- slots --
 
-  def open(self):
+  def open(self, hotwords=None):
+    """-> a free slot.  ``hotwords``: the index of the stream's phrase set in the beam search's `hotwords.HotwordSets` (default: the
+    one set when the search was given a single `Hotwords`, else set 0, the empty one); its root is written to the slot's entry of the
+    device's roots on the engine's stream, ahead of the slot's first step."""
+    sets = self.beam.hotwords if self.beam else None
+    if hotwords is not None and sets is None:
+      raise StreamError('open(hotwords={!r}): the recognizer has no beam search with hotwords'.format(hotwords))
+    if sets is not None:
+      index = self.beam.default_set if hotwords is None else hotwords
+      if not isinstance(index, (int, np.integer)) or isinstance(index, bool) or not 0 <= index < len(sets):
+        raise StreamError('open(hotwords={!r}): the sets 0..{} exist'.format(hotwords, len(sets) - 1))
     free = np.flatnonzero(~self._open)
     if not len(free):
       raise StreamError('all {} streams are open'.format(self.max_streams))
     i = int(free[0])
+    if sets is not None:
+      with torch.cuda.stream(self.engine.stream):
+        self.beam_roots[i:i + 1].fill_(sets.root(int(index)))
     self._open[i], self._fresh[i], self._finished[i] = True, True, False     # the first step resets the slot's decoder state;
     self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
     self._info[:, i] = 0                                                       # [0, n) are never read
@@ -473,13 +508,14 @@ class StreamingRecognizer:
       # the labels the device has declared final are exactly those the host holds)
       bm = self.beam
       lm_args = (self._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score)
-      call('st_ctc_beam_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]), S,
-           bm.beam_width, self._transform, *lm_args, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
-           self.beam_ws_bytes, sp)
+      biased = '_bias' if self._bias else ''
+      call('st_ctc_beam_stream_step' + biased, ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]),
+           S, bm.beam_width, self._transform, *lm_args, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
+           self.beam_ws_bytes, sp, *self._bias)
       self.launches += 2 if len(rows[-1]) else 1
       if fetch:
-        call('st_ctc_beam_stream_read', tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
-             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp)
+        call('st_ctc_beam_stream_read' + biased, tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
+             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._bias)
         self.launches += 1
       read = (count[:, -1] > 0) | fin | self._fresh[named]       # the streams the read-out reports on
       self._frames[named] = np.where(self._fresh[named], 0, self._frames[named]) + taken
@@ -537,10 +573,10 @@ class StreamingRecognizer:
          ptr(self.ep_events), ptr(self.ep_pieces), P, sp)
     if self.beam:
       bm = self.beam
-      call('st_ctc_beam_stream_step_pieces', ptr(self.logits), self.logits_pitch, self.num_classes, rows_ptr, ptr(self.ep_pieces), P, n_rows,
-           S, bm.beam_width, self._transform, self._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score,
-           ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws), self.beam_ws_bytes, ptr(self.beam_tail),
-           bm.max_tail, ptr(self.beam_result), sp)
+      call('st_ctc_beam_stream_step_pieces' + ('_bias' if self._bias else ''), ptr(self.logits), self.logits_pitch, self.num_classes,
+           rows_ptr, ptr(self.ep_pieces), P, n_rows, S, bm.beam_width, self._transform, self._lm_handle, bm.lm_weight, bm.word_count_weight,
+           bm.valid_word_count_weight, bm.oov_score, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
+           self.beam_ws_bytes, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._bias)
       self.launches += (1 if n_rows else 0) + 2 * P
 
   def _read_endpointed(self, words, named, fin, result):
@@ -918,7 +954,8 @@ def endpoint_of(flags):
 def run_cli(flags):
   """`speecht-cli stream PATH|-`: one line "seconds<TAB>transcript so far" per step that produced text, then the final transcript
   as `transcribe` prints it ("path<TAB>transcript").  With --language-model or --beam-width (the flags of `transcribe`, with their
-  meaning there) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
+  meaning there) or hotwords (--hotwords / --hotword / --hotword-weight, as `transcribe` takes them: the beam search biased towards
+  the phrases) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
   leading characters that are final".  With --endpoint the stream is cut into utterances: the partial lines describe the utterance that
   is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
   speech), and the closing line joins the finals' transcripts with spaces.  Creates no train / data / log directory."""
@@ -935,12 +972,16 @@ def run_cli(flags):
     model = create_default_model(flags, input_size, SingleInputLoader(input_size))
   try:
     beam, endpoint, on_final = None, endpoint_of(flags), None
-    if getattr(flags, 'language_model', None) or getattr(flags, 'beam_width', 0):
+    from . import hotwords
+    hot = hotwords.from_flags(flags)
+    # (hotwords need a beam search: as in `transcribe`, beam 16 unless --beam-width or --language-model says otherwise)
+    if getattr(flags, 'language_model', None) or getattr(flags, 'beam_width', 0) or hot is not None:
       from .language_model import LanguageModel
-      lm = LanguageModel.load(flags.language_model) if flags.language_model else None
+      lm = LanguageModel.load(flags.language_model) if getattr(flags, 'language_model', None) else None
       # a stream's length is not known when it starts: an hour of node pool unless the file says less
       beam = dict(beam_width=flags.beam_width or None, lm=lm, lm_weight=flags.lm_weight, word_count_weight=flags.word_count_weight,
-                  valid_word_count_weight=flags.valid_word_count_weight, input_transform=flags.beam_input or 'default', max_seconds=3600.0)
+                  valid_word_count_weight=flags.valid_word_count_weight, input_transform=flags.beam_input or 'default', max_seconds=3600.0,
+                  hotwords=hot)
     if flags.path == '-':
       rate = int(flags.sample_rate)
       per = max(int(rate * flags.chunk_ms / 1000.0), 1)
