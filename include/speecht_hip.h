@@ -1014,6 +1014,60 @@ int st_ctc_beam_stream_step_pieces_bias(const float* logits, int pitch, int num_
                                         void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
                                         int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots);
 
+/* ---- Keyword spotting in live streams: lattices carried across steps, packed into waves (csrc/ctc_spot_stream.hip,
+ * csrc/ctc_spot_stream_core.h; specification: tests/spot_stream_oracle.py; no reference counterpart).  Every step tells which of the
+ * given keywords have just been said in each stream.  The rule is a pure function of a stream's logits rows, however they are cut
+ * into steps and whatever the other streams do.
+ *
+ * The lattice, d_t(c), the cell, the tie order and end_t / s_t(2L-1) are those of st_ctc_spot_f32 above, unchanged (the arithmetic
+ * is csrc/ctc_spot_core.h's: sp_ratio, sp_column, sp_cell), with t the stream's ABSOLUTE output-frame index (int32, the frame the
+ * rows table names for the stream's first row of a step; the following rows of the step are the following frames).  t + 1 must
+ * stay an int32: a stream may run for 2^31 - 2 frames (about 497 days at 20 ms per frame) before it has to be reset.
+ * Each (stream, keyword) pair keeps across steps its 2L+1 values and starts, a pending hit {score, start, end} or none, and
+ * last_end, initially 0.  With threshold a double <= 0 or -inf (NaN is refused) and hold an int32 >= 1, after the lattice update
+ * of frame t, with e = end_t and a = s_t(2L-1):
+ *   1. cand = e > -inf && a >= last_end && e >= threshold * (double)(t + 1 - a)     (one IEEE multiply, contraction off);
+ *   2. a pending hit, cand and a >= pending.end: the pending hit is EMITTED, last_end = pending.end, nothing is pending;
+ *   3. cand and (nothing pending or e >= pending.score): pending = {e, a, t + 1} -- the later frame wins among equals;
+ *   4. a pending hit and t + 1 - pending.end >= hold: it is emitted, last_end = pending.end, nothing is pending.
+ * When the stream finishes (the table's limit >= 0; rows at or past the limit are not consumed) a pending hit is emitted with kind 1
+ * (flushed).  hold exists because the end state can stay on the last character indefinitely with the old start: "no live path
+ * overlaps any more" would never fire.  Hits of one keyword never overlap; of overlapping candidates the better one stays (the
+ * causal counterpart of spotting.pick_hits); every emitted (start, end, score) is a point of the offline trace: score ==
+ * trace_score[end - 1], start == trace_start[end - 1].  Endpointing does NOT reset spotting: it runs on the stream's rows as they
+ * are, and its frames are the stream's, not an utterance's.
+ *
+ * st_ctc_spot_stream_plan_bytes / st_ctc_spot_stream_plan (HOST): pack the keywords (CSR as above: ids 0 .. num_classes - 2, 1 <= L
+ *   <= 511, 2 <= num_classes <= 32, n_keywords >= 1; anything else is an error / 0 bytes) into waves of 64 * KPL states, KPL =
+ *   the states-per-lane dispatch of the longest keyword.  Each keyword begins on a lane boundary and never straddles waves; its two
+ *   dead outer states separate it from its neighbours.  pack = 1: keywords fill a wave in order while they fit; pack = 0: one
+ *   keyword per wave.  The plan is a block of int32 words (header, per wave a table of state descriptors, per keyword its place) the
+ *   caller uploads, 4-byte aligned, and then names to the host copy: st_ctc_spot_stream_plan_bind(plan, device_copy).  The step
+ *   functions take the HOST copy (its header gives them the dispatch and the device address without a wait); the kernel believes only
+ *   a device copy whose header carries the magic value and the classes, KPL and waves it was launched for, and does nothing otherwise.
+ * st_ctc_spot_stream_state_bytes(plan): bytes of one stream's state (per wave 64 * (12 KPL + 20)), 0 for no plan.  state holds
+ *   max_streams of them, 8-byte aligned; any content before a stream's first step, which carries reset = 1.
+ * st_ctc_spot_stream_step: logits, pitch, rows and table as st_ctc_greedy_stream takes them ({first row, rows, limit or -1, reset};
+ *   only columns < num_classes are read).  A memset of counts and ONE launch, one wave per (stream, wave of the plan); enqueues only,
+ *   never allocates.  A stream without rows, reset and limit is not touched: n_rows = 0 with no finishing stream changes no state.
+ *   events  int32 [max_streams][max_events][8] = {keyword, start, end, kind (0, or 1: flushed), score bits lo, hi, 0, 0}, in no
+ *           particular order within a stream (sort by (end, keyword)).
+ *   counts  int32 [max_streams]: the TRUE number of the stream's events of this step, whatever was there before, 0 for a stream
+ *           that sat out.  Beyond max_events the surplus is not written; nothing is written outside the buffers.
+ * st_ctc_spot_stream_host: the same on HOST pointers (the plan needs no device copy), bit-identical events and state; it walks the
+ *   keywords one by one on their own states, which cross-checks the packing.  No GPU. */
+size_t st_ctc_spot_stream_plan_bytes(const int32_t* kw_ids, const int32_t* kw_offsets, int n_keywords, int num_classes, int pack);
+int st_ctc_spot_stream_plan(const int32_t* kw_ids, const int32_t* kw_offsets, int n_keywords, int num_classes, int pack, void* plan,
+                            int* n_waves);
+int st_ctc_spot_stream_plan_bind(void* plan, const void* device_copy);
+size_t st_ctc_spot_stream_state_bytes(const void* plan);
+int st_ctc_spot_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, const void* plan, double threshold, int hold, void* state, int32_t* events,
+                            int max_events, int32_t* counts, void* stream);
+int st_ctc_spot_stream_host(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                            int max_streams, const void* plan, double threshold, int hold, void* state, int32_t* events,
+                            int max_events, int32_t* counts);
+
 /* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
  * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
  * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are

@@ -259,6 +259,15 @@ _SIGNATURES = {
     'st_ctc_beam_stream_step_pieces_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                     c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # keyword spotting in live streams: the plan is made and read on the host, the step names its device copy through it
+    'st_ctc_spot_stream_plan_bytes': (c_size_t, [c_void_p, c_void_p, c_int, c_int, c_int]),
+    'st_ctc_spot_stream_plan': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'st_ctc_spot_stream_plan_bind': (c_int, [c_void_p, c_void_p]),
+    'st_ctc_spot_stream_state_bytes': (c_size_t, [c_void_p]),
+    'st_ctc_spot_stream_step': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'st_ctc_spot_stream_host': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int,
+                                        c_void_p, c_void_p, c_int, c_void_p]),
     'st_spec_augment_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
                                     c_int, _T3P, c_void_p, c_void_p]),
     'st_spec_augment_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,

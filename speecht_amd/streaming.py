@@ -28,6 +28,11 @@ With ``endpoint=Endpointing(...)`` the device also cuts every stream into uttera
 followed speech, or an utterance has reached its longest length, the step hands back a final -- the offline decoder's result on
 that utterance's rows alone -- and the decoders start again, so a stream may run for any length on a node pool of one utterance.
 The logits are the same with and without it; the rule is a pure function of a stream's logits rows (tests/endpoint_oracle.py).
+
+With ``spot=StreamSpotter(...)`` every step also tells which of the given words and phrases have just been said in each stream
+(csrc/ctc_spot_stream.hip): the lattices of `speecht-cli spot` carried across steps, all keywords of a stream packed into a few
+waves, and a causal rule that lets a hit go once nothing better can replace it (include/speecht_hip.h,
+tests/spot_stream_oracle.py).  It runs on the stream's rows as they are: decoding and endpointing neither see nor reset it.
 """
 import ctypes
 
@@ -232,18 +237,113 @@ class Utterance:
         self.index, self.kind, self.start_frame, self.end_frame, self.first_speech, self.last_speech, self.ids, self.logp, self.score)
 
 
+class StreamSpotter:
+  """Keyword spotting of a `StreamingRecognizer` (st_ctc_spot_stream_step; the rule: include/speecht_hip.h,
+  tests/spot_stream_oracle.py).  ``keywords``: the words and phrases, as texts (`spotting.keyword_ids`: letters, apostrophe, space).
+  A stretch of frames read as a keyword is a candidate when its score per frame reaches ``threshold`` (<= 0 or -inf; the score of
+  `speecht-cli spot`); of overlapping candidates the best stays, and it is reported once a later candidate lies behind it or
+  ``hold`` seconds have passed without a better one -- or when the stream finishes (`Hit.flushed`).  The 0.3 s default of ``hold``
+  is a guess, not tuned on data.  A step hands back at most ``max_events`` hits per stream; the rest is counted in
+  `StepResult.hits_lost`.  One keyword set for all streams."""
+
+  def __init__(self, keywords, threshold=None, hold=0.3, max_events=64):
+    from . import spotting
+    if isinstance(keywords, str) or not all(isinstance(k, str) for k in keywords):
+      raise StreamError('spotting: keywords must be a list of texts')
+    self.keywords = [k.lower() for k in keywords]
+    if not self.keywords:
+      raise StreamError('spotting: no keywords given')
+    if len(set(self.keywords)) != len(self.keywords):
+      raise StreamError('spotting: a keyword is given twice')
+    try:
+      self.ids = [spotting.keyword_ids(k) for k in self.keywords]
+    except spotting.TranscriptionError as e:
+      raise StreamError('spotting: {}'.format(e))
+    self.threshold = float(spotting.DEFAULT_THRESHOLD if threshold is None else threshold)
+    if np.isnan(self.threshold) or self.threshold > 0:
+      raise StreamError('spotting: threshold must be <= 0 or -inf (a score per frame), got {!r}'.format(threshold))
+    self.hold = float(hold)
+    if not (np.isfinite(self.hold) and self.hold > 0):
+      raise StreamError('spotting: hold must be a positive number of seconds, got {!r}'.format(hold))
+    if not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool) or max_events < 1:
+      raise StreamError('spotting: max_events must be a positive integer, got {!r}'.format(max_events))
+    self.max_events = int(max_events)
+
+  def frames(self, total_stride):
+    """``hold`` in output frames of a model whose layers' strides multiply to ``total_stride`` (10 ms hop), counted as
+    `Endpointing.frames` counts: rounded up, at least 1."""
+    return max(int(np.ceil(self.hold * 100.0 / total_stride - 1e-9)), 1)
+
+  def plan(self, num_classes, pack=1):
+    """-> (the plan of st_ctc_spot_stream_plan as an int32 array, its waves).  Runs on the host."""
+    if not 2 <= num_classes <= 32:
+      raise StreamError('spotting supports 2..32 classes, the engine has {}'.format(num_classes))
+    if max(max(i) for i in self.ids) > num_classes - 2:
+      raise StreamError('spotting: a keyword has a character the model\'s {} classes do not hold'.format(num_classes))
+    lib = _lib.load()
+    ids = np.asarray([i for k in self.ids for i in k], dtype=np.int32)
+    offs = np.cumsum([0] + [len(k) for k in self.ids]).astype(np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    size = int(lib.st_ctc_spot_stream_plan_bytes(p(ids), p(offs), len(self.ids), num_classes, pack))
+    if not size:
+      raise StreamError('spotting: {}'.format(lib.st_last_error().decode()))
+    words, waves = np.zeros(size // 4, dtype=np.int32), ctypes.c_int(0)
+    call('st_ctc_spot_stream_plan', p(ids), p(offs), len(self.ids), num_classes, pack, p(words), ctypes.byref(waves))
+    return words, waves.value
+
+
+class Hit:
+  """A keyword a step has found: ``keyword`` (the text) and its ``index`` in the spotter's list, the stream's logits rows
+  ``[start_frame, end_frame)`` (absolute: they count from the stream's start, whatever endpointing cut), ``score`` (<= 0, as
+  `speecht-cli spot` reports it) and ``flushed`` -- the stream finished while the hit was still waiting for a better one."""
+  __slots__ = ('keyword', 'index', 'start_frame', 'end_frame', 'score', 'flushed')
+
+  def __init__(self, keyword, index, start_frame, end_frame, score, flushed):
+    self.keyword, self.index, self.start_frame, self.end_frame = keyword, int(index), int(start_frame), int(end_frame)
+    self.score, self.flushed = float(score), bool(flushed)
+
+  @property
+  def score_per_frame(self):
+    return self.score / (self.end_frame - self.start_frame)
+
+  def __eq__(self, other):
+    return isinstance(other, Hit) and all(getattr(self, n) == getattr(other, n) for n in Hit.__slots__)
+
+  def __repr__(self):
+    return 'Hit({!r}, {}, rows [{}, {}), score={!r}{})'.format(self.keyword, self.index, self.start_frame, self.end_frame, self.score,
+                                                             ', flushed' if self.flushed else '')
+
+
+def read_hits(keywords, events, counts, max_events):
+  """The host's part of a spotting step: ``events`` int32 [S, max_events, 8] and ``counts`` [S] as the device left them ->
+  per stream (hits sorted by (end_frame, index), hits lost: the events beyond ``max_events``)."""
+  out = []
+  for ev, count in zip(events, counts.tolist()):
+    if count == 0:                                                # (most streams, most steps)
+      out.append(([], 0))
+      continue
+    kept = ev[:min(count, max_events)]
+    score = np.ascontiguousarray(kept[:, 4:6]).view(np.float64).reshape(-1)
+    hits = [Hit(keywords[k], k, a, e, sc, kind == 1) for (k, a, e, kind), sc in zip(kept[:, :4].tolist(), score.tolist())]
+    out.append((sorted(hits, key=lambda h: (h.end_frame, h.index)), max(count - max_events, 0)))
+  return out
+
+
 class StepResult:
   """What one `step` / `finish` produced: ``ids[slot]`` new label ids, ``logits[slot]`` new rows [r, C] (on request),
   ``score[slot]`` the running negative sum of the chosen logits.  With a beam search also ``hyp[slot]``, all ids of the best
   hypothesis so far, ``stable[slot]``, how many of its leading ids are final, and ``logp[slot]``, its log-probability (after
   `finish`: what the whole-utterance search returns); ``ids`` and ``score`` stay the greedy ones.  With endpointing ``finals[slot]``
   lists the `Utterance`s the step closed, in order; ``hyp`` / ``stable`` / ``logp`` / ``score`` and ``open_ids[slot]`` (the greedy ids
-  so far) then describe the utterance still open, and ``ids`` stays every new greedy id of the step."""
+  so far) then describe the utterance still open, and ``ids`` stays every new greedy id of the step.  With a spotter ``hits[slot]``
+  lists the `Hit`s the step found, sorted by (end_frame, index), and ``hits_lost[slot]`` counts those that did not fit the
+  spotter's ``max_events`` (0 as a rule: raise ``max_events`` otherwise)."""
 
   def __init__(self):
     self.ids, self.logits, self.score = {}, {}, {}
     self.hyp, self.stable, self.logp = {}, {}, {}
     self.finals, self.open_ids = {}, {}
+    self.hits, self.hits_lost = {}, {}
 
 
 class StreamingRecognizer:
@@ -252,14 +352,16 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None):
-    """``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None):
+    """``spot``: a `StreamSpotter` -- every step then also reports the keywords it has found (`StepResult.hits`), with or without
+    a beam search and endpointing, whose results it does not change: one launch more per step (and the memset of its counts).
+    ``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
     ``logp``); None: greedy decoding only.  ``endpoint``: an `Endpointing` -- the device cuts every stream into utterances
     (`StepResult.finals`) and restarts the decoders after each; a beam search's node pool then holds ``endpoint.max_utterance``
     seconds (``beam.max_seconds`` is ignored) and a stream may run for any length."""
     if max_streams < 1 or max_chunk_frames < 1:
       raise StreamError('max_streams and max_chunk_frames must be positive')
-    self.beam, self.endpoint = beam, endpoint
+    self.beam, self.endpoint, self.spot = beam, endpoint, spot
     self.engine, self.device = engine, engine.device
     self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
     self.layers = engine.layers
@@ -298,7 +400,18 @@ class StreamingRecognizer:
         self.ep_score = torch.zeros(S * int(lib.st_stream_endpoint_score_bytes()) // 4, dtype=torch.float32, device=dev)
         self.ep_words = S * P * 8 + P * S * 4
         greedy_words += self.ep_words
-      self.dec_out = torch.zeros(greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0), dtype=torch.int32, device=dev)
+      # (with a spotter, behind everything else: counts [S] | events [S][max_events][8])
+      self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
+      self.dec_out = torch.zeros(self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0), dtype=torch.int32, device=dev)
+      if spot is not None:
+        self.spot_hold = spot.frames(total_stride)
+        self.spot_plan, self.spot_waves = spot.plan(self.num_classes)      # the host copy: the step reads its header
+        self.spot_plan_dev = torch.from_numpy(self.spot_plan).to(dev)
+        call('st_ctc_spot_stream_plan_bind', self.spot_plan.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.spot_plan_dev.data_ptr()))
+        state_bytes = int(lib.st_ctc_spot_stream_state_bytes(self.spot_plan.ctypes.data_as(ctypes.c_void_p)))
+        self.spot_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
+        self.spot_counts = self.dec_out[self.spot_at:self.spot_at + S]
+        self.spot_events = self.dec_out[self.spot_at + S:]
       self.ids = self.dec_out[:S * self.max_new]
       self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
       self.neg_sum = self.dec_out[S * self.max_new + S:S * self.max_new + 2 * S].view(torch.float32)
@@ -330,7 +443,7 @@ class StreamingRecognizer:
         self.beam_pool = torch.empty(S * pool_bytes // 8, dtype=torch.int64, device=dev)     # (a chain only holds written nodes)
         self.beam_ws = torch.empty(self.beam_ws_bytes // 4, dtype=torch.float32, device=dev)
         self.beam_result = self.dec_out[greedy_words:greedy_words + self.n_pieces * 4 * S]
-        self.beam_tail = self.dec_out[greedy_words + self.n_pieces * 4 * S:]
+        self.beam_tail = self.dec_out[greedy_words + self.n_pieces * 4 * S:self.spot_at]
       table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
       for i, l in enumerate(self.layers):
         table[2 * i] = self.windows[i].data_ptr()
@@ -396,6 +509,8 @@ class StreamingRecognizer:
     it is refused: the finals would be lost)."""
     if self.endpoint is not None and not fetch:
       raise StreamError('fetch=False with endpointing: the utterances the step closes would be lost')
+    if self.spot is not None and not fetch:
+      raise StreamError('fetch=False with a spotter: the hits the step finds would be lost')
     return self._run(feeds, (), return_logits, fetch)
 
   def finish(self, slot, return_logits=False):
@@ -423,6 +538,8 @@ class StreamingRecognizer:
         result.finals[slot], result.open_ids[slot] = [], list(self._open_ids[slot])
       if self.beam:
         result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(self._logp[slot])
+      if self.spot is not None:
+        result.hits[slot], result.hits_lost[slot] = [], 0
       if return_logits:
         result.logits[slot] = []
     longest = max([a.shape[0] for a in arrays.values()] + [0])
@@ -430,6 +547,8 @@ class StreamingRecognizer:
     for p in range(passes):
       part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
       self._pass(part, finishing if p == passes - 1 else (), result, return_logits, fetch)
+    for hits in result.hits.values():                            # (several passes: a later pass may report an earlier end)
+      hits.sort(key=lambda h: (h.end_frame, h.index))
     if return_logits:
       for slot, parts in result.logits.items():
         rows = [t.cpu().numpy() for t in parts]
@@ -519,6 +638,12 @@ class StreamingRecognizer:
         self.launches += 1
       read = (count[:, -1] > 0) | fin | self._fresh[named]       # the streams the read-out reports on
       self._frames[named] = np.where(self._fresh[named], 0, self._frames[named]) + taken
+    if self.spot is not None:
+      # the keywords' lattices take the same rows through the host's table (not the endpointer's pieces: spotting is not reset)
+      call('st_ctc_spot_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]), S,
+           self.spot_plan.ctypes.data_as(ctypes.c_void_p), self.spot.threshold, self.spot_hold, ptr(self.spot_state), ptr(self.spot_events),
+           self.spot.max_events, ptr(self.spot_counts), sp)
+      self.launches += 2                                          # the memset of the counts and the lattices
     # 4. the host's counters follow; nothing above waited
     self._n[named], self._e[named] = n_after, first + count
     self._total[named] += new
@@ -533,6 +658,13 @@ class StreamingRecognizer:
           if count[k, -1]:
             result.logits[s].append(view[int(row0[k]):int(row0[k] + count[k, -1]), :self.num_classes].clone())
       words = self.dec_out.cpu().numpy()                         # the step's one wait
+    if self.spot is not None:
+      me = self.spot.max_events
+      found = read_hits(self.spot.keywords, words[self.spot_at + S:].reshape(S, me, 8), words[self.spot_at:self.spot_at + S], me)
+      for s in named.tolist():
+        result.hits[s] += found[s][0]
+        result.hits_lost[s] += found[s][1]
+      words = words[:self.spot_at]
     ids, counts = words[:S * self.max_new].reshape(S, self.max_new), words[S * self.max_new:S * self.max_new + S]
     score = words[S * self.max_new + S:].view(np.float32)
     for s in named.tolist():
@@ -867,7 +999,7 @@ def _pcm_chunks(stream, samples_per_chunk):
 
 
 def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
-                 on_final=None):
+                 on_final=None, spot=None, on_hit=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
   ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
@@ -875,7 +1007,9 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
   ``beam`` (a `StreamBeam`): the ids are the beam search's -- at the end the whole-utterance search's result -- and
   ``on_partial(seconds, hypothesis so far, how many of its leading ids are final)`` is called whenever either has changed.
   ``endpoint`` (an `Endpointing`): the stream is cut into utterances; ``on_final(utterance)`` is called as each closes, the partials
-  describe the utterance open at the time, and the first value returned is the list of `Utterance`s."""
+  describe the utterance open at the time, and the first value returned is the list of `Utterance`s.
+  ``spot`` (a `StreamSpotter`): ``on_hit(hit)`` is called for every `Hit` as its step finds it; hits a step could not hand back
+  (more than ``spot.max_events``) raise a RuntimeWarning."""
   hop = 160
   if normalize not in ('running', 'file'):
     raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
@@ -889,8 +1023,20 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     if r.finals[slot]:
       last[0] = ([], 0)
 
+  def found(r, slot):
+    if spot is None:
+      return
+    for h in r.hits[slot]:
+      if on_hit:
+        on_hit(h)
+    if r.hits_lost[slot]:
+      import warnings
+      warnings.warn('keyword spotting: {} hits of one step were lost (max_events = {})'.format(r.hits_lost[slot], spot.max_events),
+                    RuntimeWarning)
+
   def feed(rec, slot, feats, seconds):
     r = rec.step({slot: feats})
+    found(r, slot)
     if endpoint is not None:
       closed(r, slot)
     if beam:
@@ -916,7 +1062,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     front.step({slot: y})
     feats = front.finish(slot)
     per = max(max(len(p) for p in pieces) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot)
     rslot = rec.open()
     for at in range(0, len(feats), per):
       feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
@@ -925,7 +1071,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     max_piece = int(max_piece or 16000)
     front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
     slot = front.open()
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot)
     rslot = rec.open()
     for p in pieces:
       p = np.asarray(p, np.float32)
@@ -935,6 +1081,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
       raise StreamError('too short: {} samples (the features need more than {})'.format(fed, N_FFT // 2))
     feed(rec, rslot, front.finish(slot), fed / float(samplerate))
   r = rec.finish(rslot)
+  found(r, rslot)
   if endpoint is not None:
     closed(r, rslot)
     return finals, fed / float(samplerate)
@@ -951,6 +1098,26 @@ def endpoint_of(flags):
   return Endpointing(silence=flags.endpoint_silence, lead=flags.endpoint_lead, max_utterance=flags.max_utterance)
 
 
+def spotter_of(flags):
+  """The `StreamSpotter` the flags of `speecht-cli stream` ask for (None without --keywords / --keyword): the keywords of the file,
+  then those given one by one, duplicates dropped in order."""
+  if getattr(flags, 'keywords', None) is None and not getattr(flags, 'keyword', None):
+    return None
+  from . import spotting
+  keywords = spotting.read_keywords(flags.keywords) if getattr(flags, 'keywords', None) else []
+  for k in getattr(flags, 'keyword', None) or []:
+    if k.lower() not in keywords:
+      keywords.append(k.lower())
+  return StreamSpotter(keywords, threshold=getattr(flags, 'spot_threshold', None), hold=getattr(flags, 'spot_hold', 0.3))
+
+
+def hit_line(hit, rate, duration=None):
+  """The line `speecht-cli stream` prints per hit: start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame (seconds, nominal)."""
+  from . import alignment
+  sec = lambda f: alignment.frames_to_seconds(f, rate, alignment.HOP_LENGTH, duration)
+  return '{:.3f}\t{:.3f}\t{}\t{:.4f}\t{:.4f}'.format(sec(hit.start_frame), sec(hit.end_frame), hit.keyword, hit.score, hit.score_per_frame)
+
+
 def run_cli(flags):
   """`speecht-cli stream PATH|-`: one line "seconds<TAB>transcript so far" per step that produced text, then the final transcript
   as `transcribe` prints it ("path<TAB>transcript").  With --language-model or --beam-width (the flags of `transcribe`, with their
@@ -958,7 +1125,9 @@ def run_cli(flags):
   the phrases) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
   leading characters that are final".  With --endpoint the stream is cut into utterances: the partial lines describe the utterance that
   is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
-  speech), and the closing line joins the finals' transcripts with spaces.  Creates no train / data / log directory."""
+  speech), and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
+  "start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame" (`hit_line`) as soon as its step has found it, between the other lines;
+  hits a step could not hand back are a warning on stderr.  Creates no train / data / log directory."""
   import contextlib
   import sys
   from . import transcription, vocabulary
@@ -972,6 +1141,7 @@ def run_cli(flags):
     model = create_default_model(flags, input_size, SingleInputLoader(input_size))
   try:
     beam, endpoint, on_final = None, endpoint_of(flags), None
+    spot = spotter_of(flags)
     from . import hotwords
     hot = hotwords.from_flags(flags)
     # (hotwords need a beam search: as in `transcribe`, beam 16 unless --beam-width or --language-model says otherwise)
@@ -994,11 +1164,13 @@ def run_cli(flags):
       with contextlib.redirect_stdout(sys.stderr):
         model.restore(sess, flags.run_train_dir)
       extra = {}
+      if spot is not None:
+        extra = dict(spot=spot, on_hit=lambda h: print(hit_line(h, rate), flush=True))
       if endpoint is not None:
         frame_s = 0.01 * int(np.prod([l.stride for l in model.engine.layers]))
         on_final = lambda u: print('utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s, (u.last_speech + 1) * frame_s,
                                                                         vocabulary.ids_to_sentence(u.ids)), flush=True)
-        extra = dict(endpoint=endpoint, on_final=on_final)
+        extra.update(endpoint=endpoint, on_final=on_final)
       if beam:
         if flags.path != '-':
           beam['max_seconds'] = len(samples) / float(rate) + 1.0
@@ -1007,7 +1179,7 @@ def run_cli(flags):
       else:
         partial = lambda seconds, ids: print('{:.2f}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids)), flush=True)
         ids, _ = stream_audio(model.engine, pieces, rate, input_size, flags.normalize, partial, max_piece=per, **extra)
-  except (StreamError, transcription.TranscriptionError, ValueError) as e:
+  except (StreamError, transcription.TranscriptionError, ValueError, OSError) as e:
     print('stream: {}'.format(e), file=sys.stderr)
     return 1
   if endpoint is not None:
