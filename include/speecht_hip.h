@@ -977,6 +977,59 @@ int st_ctc_beam_stream_step_pieces(const float* logits, int pitch, int num_class
                                    void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail, int max_tail,
                                    int32_t* result, void* stream);
 
+/* ---- Word times and confidences for the finals of live streams (csrc/stream_words.hip, csrc/stream_ring.h, and the ring entry
+ * points in csrc/ctc_align.hip / csrc/ctc_conf.hip; no reference counterpart).  A stream's logits buffer holds one step's rows, so the
+ * rows of an utterance the endpointer closes are gone by then.  The recogniser keeps them in a ring per stream,
+ *   ring   float [max_streams][cap][32]: frame f of stream s at ring[s][f % cap]; columns at and past num_classes are never read,
+ * and the alignment and confidence lattices read a final's rows back from there: what they return is what st_ctc_align_f32 /
+ * st_ctc_word_conf_f32 return on the utterance's rows alone, bit for bit.
+ * st_stream_keep_rows: cap = max_frames + max_rows, the rows per stream the ring must hold for utterances of at most max_frames rows
+ *   (the endpointer's M) and passes of at most max_rows rows per stream; 0 on bad arguments (either below 1).  Why that is enough: no
+ *   stretch is longer than M rows (the endpoint rule), so a final is [u0, end) with end - u0 <= M; finals are aligned in the pass that
+ *   closes them, before the next pass keeps anything; and that pass holds at least the row end - 1, so it has kept fewer than max_rows
+ *   rows behind end.  The newest frame kept is therefore below u0 + M + max_rows - 1 = u0 + cap - 1: no slot of [u0, end) has been
+ *   written twice.
+ * st_stream_keep_f32: one launch; for every entry (stream, frame) of the step's last-layer `rows` table (int32 [n_rows][2], the table
+ *   of st_ctc_greedy_stream) row i of logits -- logits[i * pitch + 0 .. num_classes) -- goes to ring[stream][frame % cap].  Frame
+ *   numbers are the table's own, the ones the endpoint events report; they start at 0 after a reset, so a reused slot needs no
+ *   clearing.  1 <= num_classes <= 32, pitch >= num_classes.  An entry with a stream outside 0 .. max_streams - 1 or a negative
+ *   frame is skipped.  n_rows = 0 is valid and launches nothing.  Enqueues only, never allocates; ordinary vector loads and stores,
+ *   one lane per float.
+ * st_ctc_align_ring_f32: the semantics of st_ctc_align_f32 for a batch of n_jobs utterances whose rows live in the ring.
+ *   jobs   DEVICE int32 [n_jobs][3] = {stream, u0, n_rows}: row t of job j is ring[stream_j][(u0_j + t) % cap], seq_lens[j] = n_rows_j,
+ *          frames = max_rows (given by the caller: the pitch of `states` and of the workspace).
+ *   Labels CSR over the jobs, 2 <= num_classes <= 32; spans, states (may be null), score, status and the workspace,
+ *   st_ctc_align_ws(n_jobs, max_rows, max_label_len) bytes, exactly as there.  A job with stream outside 0 .. max_streams - 1,
+ *   n_rows outside 0 .. max_rows or u0 < 0 gets status != 0 (score -inf, spans {-1, -1}, states -2) and reads nothing outside the
+ *   ring.  Rows t >= n_rows_j are read from the ring -- defined memory -- and ignored by the lattice, as padding rows are there.
+ *   Three launches: the ring-mapped ln-softmax stage (the row offset comes from the job table and a wrap; same arithmetic, same
+ *   butterfly order, so the double rows have the same bits -- this stage IS the gather, there is no copy pass), then the lattice and
+ *   the back-trace kernels of st_ctc_align_f32, which read the workspace only.
+ * st_ctc_word_conf_ring_f32: the same for st_ctc_word_conf_f32: jobs, space_id and word_spans (whose first column is now the job),
+ *   2 <= num_classes <= 30; log_prob [n_jobs], log_conf [n_words], status [n_jobs] as there (a job the ring cannot serve: status != 0,
+ *   log_prob -inf, its words NaN); workspace st_ctc_word_conf_ws(n_jobs, max_rows, max_label_len, n_jobs + n_words) bytes.
+ * st_ctc_align_ring_host / st_ctc_word_conf_ring_host: the same on a HOST ring and a HOST job table: each gathers the jobs' rows
+ *   through the index function the kernels use (csrc/stream_ring.h) and runs st_ctc_align_host / st_ctc_word_conf_host on them:
+ *   bit-identical to the device entry points and to the dense host forms on the utterance's rows.  They need no device (and, unlike
+ *   the device entry points, allocate the gathered rows). */
+int st_stream_keep_rows(int max_frames, int max_rows);
+int st_stream_keep_f32(const float* logits, int pitch, int num_classes, const int32_t* rows, int n_rows, int max_streams, float* ring,
+                       int cap, void* stream);
+int st_ctc_align_ring_f32(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs, int max_rows,
+                          const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int32_t* spans, int32_t* states,
+                          float* score, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_align_ring_host(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs, int max_rows,
+                           const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int32_t* spans, int32_t* states,
+                           float* score, int32_t* status, void* workspace, size_t workspace_bytes);
+int st_ctc_word_conf_ring_f32(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs,
+                              int max_rows, const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int space_id,
+                              const int32_t* word_spans, int n_words, double* log_prob, double* log_conf, int32_t* status,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_word_conf_ring_host(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs,
+                               int max_rows, const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int space_id,
+                               const int32_t* word_spans, int n_words, double* log_prob, double* log_conf, int32_t* status,
+                               void* workspace, size_t workspace_bytes);
+
 /* ---- Hotword biasing of the streaming beam searches, with a phrase set per stream (csrc/ctc_beam.hip: ctc_beam_kernel<.., STREAM,
  * BIAS>, ctc_beam_read_kernel<.., BIAS>).  The three entry points above with the second scorer of st_ctc_beam_search_decode_bias_nbest
  * / _lm_bias_nbest: each takes the arguments of its unbiased form, then `bias` (the tables as there: device pointers, 1 <= n_states <=

@@ -259,6 +259,17 @@ _SIGNATURES = {
     'st_ctc_beam_stream_step_pieces_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                     c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # word times and confidences of finals: a ring of logits rows per stream, the two lattices reading from it
+    'st_stream_keep_rows': (c_int, [c_int, c_int]),
+    'st_stream_keep_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'st_ctc_align_ring_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_align_ring_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_size_t]),
+    'st_ctc_word_conf_ring_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_word_conf_ring_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     # keyword spotting in live streams: the plan is made and read on the host, the step names its device copy through it
     'st_ctc_spot_stream_plan_bytes': (c_size_t, [c_void_p, c_void_p, c_int, c_int, c_int]),
     'st_ctc_spot_stream_plan': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

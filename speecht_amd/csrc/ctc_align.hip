@@ -13,12 +13,15 @@
 //  3. align_backtrace<KPL>: one wave per utterance walks the back-pointers from the end state; the rows come through LDS in
 //     64-frame chunks (prefetched), so the walk is a chain of LDS reads, not of global loads.  The path of a chunk is kept in
 //     LDS and `states` / `spans` are then written by all lanes with plain vector stores.
+// st_ctc_align_ring_f32 (the finals of live streams, stream_ring.h) runs 2 and 3 as they are behind a ring-mapped form of 1: the rows of
+// its utterances come from a stream's ring through a job table, and the lattices ask that table for an utterance's frames.
 #include <algorithm>
 
 #include "ctc_align_core.h"
 #include "ctc_align_softmax.h"
 #include "ctc_lattice.h"
 #include "st_common.h"
+#include "stream_ring.h"
 
 namespace {
 
@@ -29,11 +32,17 @@ constexpr int TC = st::LATTICE_TC;   // frames per LDS chunk
 constexpr int BPW = 64;        // back-pointer words per frame (one per lane)
 #define NEG_INF_F (-__builtin_inff())
 
-template <int KPL>
+// the first stage of st_ctc_align_ring_f32: row t of job b comes from the stream's ring (the job table and a wrap); same arithmetic
+__global__ __launch_bounds__(256) void align_logsoftmax_ring_kernel(const float* __restrict__ ring, st::RingMap map, int B, int T, int C,
+                                                                    double* __restrict__ ly) {
+  st::align_logsoftmax_rows(ring, map, B, T, C, ly);
+}
+
+// (Lens: the frames of each utterance -- st::DenseLens, a seq_lens array, or st::RingLens, the job table of the ring entry point)
+template <int KPL, typename Lens>
 __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restrict__ ly, int T, int C,
                                                            const int* __restrict__ label_ids,
-                                                           const int* __restrict__ label_off,
-                                                           const int* __restrict__ seq_lens,
+                                                           const int* __restrict__ label_off, Lens seq_lens,
                                                            unsigned int* __restrict__ bp, int* __restrict__ end_state,
                                                            float* __restrict__ score, int* __restrict__ status) {
   constexpr int UP = KPL * 64;
@@ -45,7 +54,7 @@ __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restr
   const int* lab = label_ids + label_off[b];
   const int L = label_off[b + 1] - label_off[b];
   const int U = 2 * L + 1;
-  const int Tb = seq_lens[b];
+  const int Tb = seq_lens(b);
 
   // "Not enough time for target transition sequence": L + #adjacent repeats must fit in Tb
   const int rep = st::lattice_repeats(lab, L, lane);
@@ -126,10 +135,9 @@ __global__ __launch_bounds__(64) void align_viterbi_kernel(const double* __restr
   }
 }
 
-template <int KPL>
+template <int KPL, typename Lens>
 __global__ __launch_bounds__(64) void align_backtrace_kernel(const unsigned int* __restrict__ bp, int T,
-                                                             const int* __restrict__ label_off,
-                                                             const int* __restrict__ seq_lens,
+                                                             const int* __restrict__ label_off, Lens seq_lens,
                                                              const int* __restrict__ end_state,
                                                              const int* __restrict__ status, int* __restrict__ spans,
                                                              int* __restrict__ states) {
@@ -145,7 +153,7 @@ __global__ __launch_bounds__(64) void align_backtrace_kernel(const unsigned int*
     if (st_out) for (int t = lane; t < T; t += 64) st_out[t] = -2;
     return;
   }
-  const int Tb = seq_lens[b];
+  const int Tb = seq_lens(b);
   if (st_out) for (int t = Tb + lane; t < T; t += 64) st_out[t] = -2;
   if (Tb == 0) return;
 
@@ -253,6 +261,29 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
   }
 }
 
+// the three stages on B utterances of T rows each: `map` names a row for the softmax stage (which is also the gather), `lens` the
+// frames of an utterance for the lattice and the back-trace, which read the workspace only
+template <typename Map, typename Lens>
+void launch_align(const float* base, Map map, Lens lens, int B, int T, int C, int kpl, const int* label_ids, const int* label_offsets,
+                  int* spans, int* states, float* score, int* status, void* workspace, hipStream_t s) {
+  const size_t rows = (size_t)B * T;
+  double* ly = reinterpret_cast<double*>(workspace);
+  unsigned int* bp = reinterpret_cast<unsigned int*>(ly + rows * CP);
+  int* end_state = reinterpret_cast<int*>(bp + rows * BPW);
+  const dim3 grid((unsigned)((rows + 7) / 8));
+  if constexpr (std::is_same<Map, RowMap>::value) {
+    hipLaunchKernelGGL(st::align_logsoftmax_kernel, grid, dim3(256), 0, s, base, map, B, T, C, ly);
+  } else {
+    hipLaunchKernelGGL(align_logsoftmax_ring_kernel, grid, dim3(256), 0, s, base, map, B, T, C, ly);
+  }
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL((align_viterbi_kernel<k(), Lens>), dim3(B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets, lens, bp,
+                       end_state, score, status);
+    hipLaunchKernelGGL((align_backtrace_kernel<k(), Lens>), dim3(B), dim3(64), 0, s, bp, T, label_offsets, lens, end_state, status,
+                       spans, states);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,21 +309,25 @@ int st_ctc_align_f32(const st_tensor3* logits, const int32_t* label_ids, const i
   ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(logits->batch, logits->frames, max_label_len),
              "ctc_align: workspace too small");
   ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_align: workspace must be 16-byte aligned");
-  hipStream_t s = st::as_stream(stream);
-  const int B = logits->batch, T = logits->frames, C = logits->channels;
-  const size_t rows = (size_t)B * T;
-  double* ly = reinterpret_cast<double*>(workspace);
-  unsigned int* bp = reinterpret_cast<unsigned int*>(ly + rows * CP);
-  int* end_state = reinterpret_cast<int*>(bp + rows * BPW);
-  hipLaunchKernelGGL(st::align_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
-                     st::row_map(*logits), B, T, C, ly);
-  st::dispatch_kpl(kpl, [&](auto k) {
-    hipLaunchKernelGGL(align_viterbi_kernel<k()>, dim3(B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets, seq_lens, bp,
-                       end_state, score, status);
-    hipLaunchKernelGGL(align_backtrace_kernel<k()>, dim3(B), dim3(64), 0, s, bp, T, label_offsets, seq_lens, end_state, status,
-                       spans, states);
-  });
+  launch_align(logits->base, st::row_map(*logits), st::DenseLens{seq_lens}, logits->batch, logits->frames, logits->channels, kpl,
+               label_ids, label_offsets, spans, states, score, status, workspace, st::as_stream(stream));
   return st::check_launch("ctc_align");
+}
+
+int st_ctc_align_ring_f32(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs, int max_rows,
+                          const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int32_t* spans, int32_t* states,
+                          float* score, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(ring && jobs && label_ids && label_offsets && spans && score && status && workspace, "ctc_align_ring: null argument");
+  ST_REQUIRE(max_streams >= 1 && cap >= 1 && n_jobs >= 1 && max_rows >= 1, "ctc_align_ring: bad ring or job shape");
+  ST_REQUIRE(num_classes >= 2 && num_classes <= CP, "ctc_align_ring: num_classes must be 2..32");
+  const int kpl = st::lattice_kpl(max_label_len);
+  ST_REQUIRE(kpl > 0, "ctc_align_ring: label length %d outside 0..511", max_label_len);
+  ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(n_jobs, max_rows, max_label_len), "ctc_align_ring: workspace too small");
+  ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_align_ring: workspace must be 16-byte aligned");
+  st::trace("ctc_align_ring<%d> jobs=%d rows=%d cap=%d", kpl, n_jobs, max_rows, cap);
+  launch_align(ring, st::RingMap{jobs, max_streams, max_rows, cap}, st::RingLens{jobs, max_streams, max_rows}, n_jobs, max_rows,
+               num_classes, kpl, label_ids, label_offsets, spans, states, score, status, workspace, st::as_stream(stream));
+  return st::check_launch("ctc_align_ring");
 }
 
 int st_ctc_align_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,

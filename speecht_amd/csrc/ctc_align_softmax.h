@@ -8,9 +8,11 @@
 
 namespace st {
 
-// ln softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum)
-static __global__ __launch_bounds__(256) void align_logsoftmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T,
-                                                                      int C, double* __restrict__ ly) {
+// ln softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum).  `map` names
+// the row: a RowMap for a padded NWC tensor, a RingMap (stream_ring.h) for utterances kept in a stream's ring.
+template <typename Map>
+__device__ __forceinline__ void align_logsoftmax_rows(const float* __restrict__ logits, const Map& map, int B, int T, int C,
+                                                      double* __restrict__ ly) {
   const int lane = threadIdx.x & 63, c = lane & 31;
   const long i = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
   const bool row_ok = i < (long)B * T;
@@ -24,6 +26,11 @@ static __global__ __launch_bounds__(256) void align_logsoftmax_kernel(const floa
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
   if (row_ok) ly[i * AL_CP + c] = al_log_softmax(v, m, s);
+}
+
+static __global__ __launch_bounds__(256) void align_logsoftmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T,
+                                                                      int C, double* __restrict__ ly) {
+  align_logsoftmax_rows(logits, map, B, T, C, ly);
 }
 
 }  // namespace st

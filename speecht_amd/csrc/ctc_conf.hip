@@ -14,11 +14,14 @@
 //     register arithmetic plus four cross-lane shifts (DPP); softmax rows come through LDS in 64-frame chunks, prefetched one
 //     chunk ahead.  No transcendental on the frame chain.  Leaves ln P of the job in the workspace.
 //  3. conf_finish: one thread per output, forms log_prob and the differences.
+// st_ctc_word_conf_ring_f32 (the finals of live streams, stream_ring.h) runs 2 and 3 as they are behind a ring-mapped form of 1: the rows
+// of its utterances come from a stream's ring through a job table, and the lattices ask that table for an utterance's frames.
 #include <algorithm>
 
 #include "ctc_conf_core.h"
 #include "ctc_lattice.h"
 #include "st_common.h"
+#include "stream_ring.h"
 
 namespace {
 
@@ -31,9 +34,11 @@ constexpr int LMAX = 512;              // label ids a job's LDS array holds (lab
 #define NEG_INF_F (-__builtin_inff())
 #define CF_NAN ST_CF_NAN
 
-// softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum)
-__global__ __launch_bounds__(256) void conf_softmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T, int C,
-                                                           int space_id, double* __restrict__ rows) {
+// softmax of every (b, t) row, two rows per wavefront; sums by a 32-lane xor butterfly (the order of st::al_row_sum).  `map` names
+// the row: a RowMap for a padded NWC tensor, a RingMap (stream_ring.h) for utterances kept in a stream's ring.
+template <typename Map>
+__device__ __forceinline__ void conf_softmax_rows(const float* __restrict__ logits, const Map& map, int B, int T, int C, int space_id,
+                                                  double* __restrict__ rows) {
   const int lane = threadIdx.x & 63, c = lane & 31;
   const long i = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
   const bool row_ok = i < (long)B * T;
@@ -54,6 +59,16 @@ __global__ __launch_bounds__(256) void conf_softmax_kernel(const float* __restri
   if (row_ok) rows[i * CP + c] = c == st::CF_STAR ? star : p;          // (column 31: p = 0)
 }
 
+__global__ __launch_bounds__(256) void conf_softmax_kernel(const float* __restrict__ logits, RowMap map, int B, int T, int C,
+                                                           int space_id, double* __restrict__ rows) {
+  conf_softmax_rows(logits, map, B, T, C, space_id, rows);
+}
+// the first stage of st_ctc_word_conf_ring_f32: row t of job b comes from the stream's ring (the job table and a wrap); same arithmetic
+__global__ __launch_bounds__(256) void conf_softmax_ring_kernel(const float* __restrict__ ring, st::RingMap map, int B, int T, int C,
+                                                                int space_id, double* __restrict__ rows) {
+  conf_softmax_rows(ring, map, B, T, C, space_id, rows);
+}
+
 // what a job is: its utterance and, for a word's job, the run of label ids it replaces (first < 0: the full label)
 struct Job {
   int b, first, last;
@@ -69,11 +84,11 @@ __host__ __device__ inline Job conf_job(int job, int B, const int* __restrict__ 
   return j;
 }
 
-template <int KPL>
+// (Lens: the frames of each utterance -- st::DenseLens, a seq_lens array, or st::RingLens, the job table of the ring entry point)
+template <int KPL, typename Lens>
 __global__ __launch_bounds__(64) void conf_lattice_kernel(const double* __restrict__ softmax_rows, int B, int T, int C,
                                                           const int* __restrict__ label_ids,
-                                                          const int* __restrict__ label_off,
-                                                          const int* __restrict__ seq_lens,
+                                                          const int* __restrict__ label_off, Lens seq_lens,
                                                           const int* __restrict__ word_spans, double* __restrict__ ln_p,
                                                           int* __restrict__ status) {
   constexpr int UP = KPL * 64;
@@ -92,7 +107,7 @@ __global__ __launch_bounds__(64) void conf_lattice_kernel(const double* __restri
   const int b = jb.b;
   const int* lab = label_ids + label_off[b];
   const int L = label_off[b + 1] - label_off[b];
-  const int Tb = seq_lens[b];
+  const int Tb = seq_lens(b);
 
   // "Not enough time for target transition sequence", decided on the full label for all of the utterance's jobs
   const int rep = st::lattice_repeats(lab, (unsigned)(2 * L + 1) <= (unsigned)UP ? L : 0, lane);
@@ -222,6 +237,30 @@ bool conf_args_ok(int batch, int frames, int classes, int max_label_len, int spa
          n_words >= 0 && st::lattice_kpl(max_label_len) > 0;
 }
 
+// the three stages on B utterances of T rows each: `map` names a row for the softmax stage (which is also the gather), `lens` the
+// frames of an utterance for the lattices, which read the workspace only
+template <typename Map, typename Lens>
+void launch_conf(const float* base, Map map, Lens lens, int B, int T, int C, int max_label_len, const int* label_ids,
+                 const int* label_offsets, int space_id, const int* word_spans, int n_words, double* log_prob, double* log_conf,
+                 int* status, void* workspace, hipStream_t s) {
+  const size_t nrows = (size_t)B * T;
+  const int jobs = B + n_words;
+  double* rows = reinterpret_cast<double*>(workspace);
+  double* ln_p = rows + nrows * CP;
+  const dim3 grid((unsigned)((nrows + 7) / 8));
+  if constexpr (std::is_same<Map, RowMap>::value) {
+    hipLaunchKernelGGL(conf_softmax_kernel, grid, dim3(256), 0, s, base, map, B, T, C, space_id, rows);
+  } else {
+    hipLaunchKernelGGL(conf_softmax_ring_kernel, grid, dim3(256), 0, s, base, map, B, T, C, space_id, rows);
+  }
+  st::dispatch_kpl(st::lattice_kpl(max_label_len), [&](auto k) {
+    hipLaunchKernelGGL((conf_lattice_kernel<k(), Lens>), dim3(jobs), dim3(64), 0, s, rows, B, T, C, label_ids, label_offsets, lens,
+                       word_spans, ln_p, status);
+  });
+  hipLaunchKernelGGL(conf_finish_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, ln_p, B, n_words, word_spans, status, log_prob,
+                     log_conf);
+}
+
 }  // namespace
 
 extern "C" {
@@ -247,20 +286,30 @@ int st_ctc_word_conf_f32(const st_tensor3* logits, const int32_t* label_ids, con
   ST_REQUIRE((long)B + n_words <= 0x7fffffffL, "ctc_word_conf: too many jobs");
   ST_REQUIRE(workspace_bytes >= st_ctc_word_conf_ws(B, T, max_label_len, B + n_words), "ctc_word_conf: workspace too small");
   ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_word_conf: workspace must be 16-byte aligned");
-  hipStream_t s = st::as_stream(stream);
-  const size_t nrows = (size_t)B * T;
-  const int jobs = B + n_words;
-  double* rows = reinterpret_cast<double*>(workspace);
-  double* ln_p = rows + nrows * CP;
-  hipLaunchKernelGGL(conf_softmax_kernel, dim3((unsigned)((nrows + 7) / 8)), dim3(256), 0, s, logits->base, st::row_map(*logits),
-                     B, T, C, space_id, rows);
-  st::dispatch_kpl(st::lattice_kpl(max_label_len), [&](auto k) {
-    hipLaunchKernelGGL(conf_lattice_kernel<k()>, dim3(jobs), dim3(64), 0, s, rows, B, T, C, label_ids, label_offsets, seq_lens,
-                       word_spans, ln_p, status);
-  });
-  hipLaunchKernelGGL(conf_finish_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, ln_p, B, n_words, word_spans, status, log_prob,
-                     log_conf);
+  launch_conf(logits->base, st::row_map(*logits), st::DenseLens{seq_lens}, B, T, C, max_label_len, label_ids, label_offsets, space_id,
+              word_spans, n_words, log_prob, log_conf, status, workspace, st::as_stream(stream));
   return st::check_launch("ctc_word_conf");
+}
+
+int st_ctc_word_conf_ring_f32(const float* ring, int max_streams, int cap, int num_classes, const int32_t* jobs, int n_jobs,
+                              int max_rows, const int32_t* label_ids, const int32_t* label_offsets, int max_label_len, int space_id,
+                              const int32_t* word_spans, int n_words, double* log_prob, double* log_conf, int32_t* status,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(ring && jobs && label_ids && label_offsets && log_prob && status && workspace, "ctc_word_conf_ring: null argument");
+  ST_REQUIRE(n_words == 0 || (word_spans && log_conf), "ctc_word_conf_ring: null argument");
+  ST_REQUIRE(max_streams >= 1 && cap >= 1, "ctc_word_conf_ring: bad ring shape");
+  ST_REQUIRE(conf_args_ok(n_jobs, max_rows, num_classes, max_label_len, space_id, n_words),
+             "ctc_word_conf_ring: needs n_jobs, max_rows >= 1, 2 <= num_classes <= 30, 0 <= space_id < num_classes - 1, "
+             "0 <= max_label_len <= 511, n_words >= 0");
+  ST_REQUIRE((long)n_jobs + n_words <= 0x7fffffffL, "ctc_word_conf_ring: too many jobs");
+  ST_REQUIRE(workspace_bytes >= st_ctc_word_conf_ws(n_jobs, max_rows, max_label_len, n_jobs + n_words),
+             "ctc_word_conf_ring: workspace too small");
+  ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_word_conf_ring: workspace must be 16-byte aligned");
+  st::trace("ctc_word_conf_ring<%d> jobs=%d words=%d rows=%d cap=%d", st::lattice_kpl(max_label_len), n_jobs, n_words, max_rows, cap);
+  launch_conf(ring, st::RingMap{jobs, max_streams, max_rows, cap}, st::RingLens{jobs, max_streams, max_rows}, n_jobs, max_rows,
+              num_classes, max_label_len, label_ids, label_offsets, space_id, word_spans, n_words, log_prob, log_conf, status, workspace,
+              st::as_stream(stream));
+  return st::check_launch("ctc_word_conf_ring");
 }
 
 int st_ctc_word_conf_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,

@@ -29,6 +29,10 @@ followed speech, or an utterance has reached its longest length, the step hands 
 that utterance's rows alone -- and the decoders start again, so a stream may run for any length on a node pool of one utterance.
 The logits are the same with and without it; the rule is a pure function of a stream's logits rows (tests/endpoint_oracle.py).
 
+With ``words=FinalWords(...)`` (and endpointing) every final also carries its words' times and confidences: each pass copies its logits
+rows into a ring per stream (csrc/stream_words.hip), and the pass that closes an utterance runs the lattices of ``engine.align`` and
+``engine.word_confidence`` on the utterance's rows in that ring -- what those calls return on the rows alone, bit for bit.
+
 With ``spot=StreamSpotter(...)`` every step also tells which of the given words and phrases have just been said in each stream
 (csrc/ctc_spot_stream.hip): the lattices of `speecht-cli spot` carried across steps, all keywords of a stream packed into a few
 waves, and a causal rule that lets a hit go once nothing better can replace it (include/speecht_hip.h,
@@ -220,17 +224,77 @@ class Endpointing:
     return R, L, max(M, L), space
 
 
+class FinalWords:
+  """Word times and confidences for the finals of an endpointed `StreamingRecognizer` (st_stream_keep_f32, st_ctc_align_ring_f32,
+  st_ctc_word_conf_ring_f32; include/speecht_hip.h): the recogniser keeps every stream's recent logits rows in a ring on the device,
+  and the pass that closes an utterance runs the lattices of ``engine.align`` (``timestamps``) and ``engine.word_confidence``
+  (``confidence``) on the utterance's rows with the final's ids.  What a final then carries is what those offline calls return on its
+  rows alone, bit for bit, however the audio was cut into steps.  ``confidence`` needs a space class -- the endpointing's
+  ``space_id``, which must be the vocabulary's, whose helpers cut the ids into words -- and at most 30 classes.  One setting serves all
+  streams."""
+
+  def __init__(self, timestamps=True, confidence=False):
+    self.timestamps, self.confidence = bool(timestamps), bool(confidence)
+    if not (self.timestamps or self.confidence):
+      raise StreamError('words: neither timestamps nor confidence is asked for')
+
+  def check(self, endpoint, num_classes, space_id):
+    """Refuses what the recogniser cannot serve; ``space_id``: the endpointing's, resolved for ``num_classes`` (-1: none)."""
+    from . import vocabulary
+    if endpoint is None:
+      raise StreamError('words: word times and confidences need endpoint=Endpointing(...): the utterance of a stream that is not '
+                        'endpointed has no bound')
+    if not 2 <= num_classes <= 32:
+      raise StreamError('words: the alignment supports 2..32 classes, the engine has {}'.format(num_classes))
+    if self.confidence:
+      if space_id < 0:
+        raise StreamError('words: confidence needs a space class, the endpointing names none (space_id)')
+      if num_classes > 30:
+        raise StreamError('words: confidence supports at most 30 classes, the engine has {}'.format(num_classes))
+      if space_id != vocabulary.SPACE_ID:
+        raise StreamError('words: confidence cuts words at the vocabulary\'s space ({}), the endpointing names {}'.format(
+            vocabulary.SPACE_ID, space_id))
+
+
+def final_jobs(finals, space_id=None, max_labels=511):
+  """The host's table for the lattices of a pass's finals.  ``finals``: [(stream, start_frame, end_frame, ids)] in any order; those with
+  1 .. ``max_labels`` ids become jobs, in order.  -> dict: ``index`` (position in ``finals`` of every job), ``jobs`` int32 [n, 3] =
+  {stream, u0, rows}, ``ids`` / ``offsets`` (the labels, CSR over the jobs), ``word_spans`` int32 [W, 3] = {job, first id, one past the
+  last} from `alignment.word_runs` (empty without ``space_id``), ``words`` (how many words each job has), ``max_len`` and ``max_rows``
+  (the longest label and utterance among the jobs)."""
+  from . import alignment
+  index = [i for i, f in enumerate(finals) if 1 <= len(f[3]) <= max_labels]
+  jobs = np.asarray([(finals[i][0], finals[i][1], finals[i][2] - finals[i][1]) for i in index], dtype=np.int32).reshape(-1, 3)
+  labels = [list(finals[i][3]) for i in index]
+  offsets = np.zeros(len(index) + 1, dtype=np.int32)
+  offsets[1:] = np.cumsum([len(l) for l in labels])
+  runs = [alignment.word_runs(l, space_id) if space_id is not None else [] for l in labels]
+  return dict(index=index, jobs=jobs, ids=np.asarray([i for l in labels for i in l], dtype=np.int32), offsets=offsets,
+              word_spans=np.asarray([(j, a, e) for j, r in enumerate(runs) for a, e in r], dtype=np.int32).reshape(-1, 3),
+              words=[len(r) for r in runs], max_len=max([len(l) for l in labels] + [0]),
+              max_rows=int(jobs[:, 2].max()) if len(index) else 0)
+
+
 class Utterance:
   """A final of an endpointed stream: utterance ``index`` of its stream, closed by ``kind`` ('silence', 'length' or, at `finish`, 'end'),
   the logits rows ``[start_frame, end_frame)`` with speech from ``first_speech`` to ``last_speech``.  ``ids``: the beam search's result on
   those rows alone with its log-probability ``logp`` -- what the whole-utterance search returns on them -- or, without a beam search,
-  the greedy ids; ``greedy_ids`` and ``score`` (the negative sum of the chosen logits) are the greedy decoder's either way."""
-  __slots__ = ('index', 'kind', 'start_frame', 'end_frame', 'first_speech', 'last_speech', 'ids', 'logp', 'greedy_ids', 'score')
+  the greedy ids; ``greedy_ids`` and ``score`` (the negative sum of the chosen logits) are the greedy decoder's either way.
+
+  With ``words=FinalWords(...)``: ``spans`` ([L, 2] int32, the first row and one past the last row of every id, relative to
+  ``start_frame``) and ``align_score`` -- what ``engine.align`` returns on the utterance's rows --, ``confidence`` ({'log_prob', 'words'}
+  as `inference.transcribe(confidence=True)` shapes it) and ``words``, a list of {word, start, end[, confidence]} with times in seconds
+  from the stream's start (without ``timestamps``: {word, confidence}).  A final without ids has ``words == []`` and empty spans; one
+  with more than ``engine_decode.MAX_ALIGN_LABELS`` ids, or whose ids do not fit its rows (a beam hypothesis with adjacent repeats
+  can do that), has None for all four, as offline.  Without ``words`` -- and a field its `FinalWords` does not ask for -- None."""
+  __slots__ = ('index', 'kind', 'start_frame', 'end_frame', 'first_speech', 'last_speech', 'ids', 'logp', 'greedy_ids', 'score',
+               'spans', 'align_score', 'confidence', 'words')
 
   def __init__(self, index, kind, start_frame, end_frame, first_speech, last_speech, greedy_ids, score):
     self.index, self.kind, self.start_frame, self.end_frame = index, kind, start_frame, end_frame
     self.first_speech, self.last_speech = first_speech, last_speech
     self.greedy_ids, self.score, self.ids, self.logp = greedy_ids, score, greedy_ids, None
+    self.spans = self.align_score = self.confidence = self.words = None
 
   def __repr__(self):
     return 'Utterance({}, {!r}, rows [{}, {}), speech {}..{}, ids={}, logp={}, score={})'.format(
@@ -352,8 +416,10 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None):
-    """``spot``: a `StreamSpotter` -- every step then also reports the keywords it has found (`StepResult.hits`), with or without
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None, words=None):
+    """``words``: a `FinalWords` (needs ``endpoint``) -- every final then also carries its words' times and / or confidences
+    (`Utterance.spans` / ``align_score`` / ``confidence`` / ``words``): one launch more per pass, and in a pass that closes an utterance
+    one upload, the lattices' launches and a second wait.  None: nothing changes.  ``spot``: a `StreamSpotter` -- every step then also reports the keywords it has found (`StepResult.hits`), with or without
     a beam search and endpointing, whose results it does not change: one launch more per step (and the memset of its counts).
     ``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
     ``logp``); None: greedy decoding only.  ``endpoint``: an `Endpointing` -- the device cuts every stream into utterances
@@ -361,7 +427,7 @@ class StreamingRecognizer:
     seconds (``beam.max_seconds`` is ignored) and a stream may run for any length."""
     if max_streams < 1 or max_chunk_frames < 1:
       raise StreamError('max_streams and max_chunk_frames must be positive')
-    self.beam, self.endpoint, self.spot = beam, endpoint, spot
+    self.beam, self.endpoint, self.spot, self.words = beam, endpoint, spot, words
     self.engine, self.device = engine, engine.device
     self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
     self.layers = engine.layers
@@ -370,6 +436,11 @@ class StreamingRecognizer:
       if not pad_left_fixed(w, s):
         raise StreamError('a layer of width {} and stride {} has no length-independent left padding'.format(w, s))
     self.num_classes = engine.num_classes
+    self.total_stride = int(np.prod([s for _, s in self.geo]))
+    if words is not None:                                        # (refused before anything is allocated)
+      if not isinstance(words, FinalWords):
+        raise StreamError('words must be a FinalWords, got {!r}'.format(type(words).__name__))
+      words.check(endpoint, self.num_classes, endpoint.frames(self.total_stride, self.num_classes)[3] if endpoint is not None else -1)
     L, S = len(self.layers), self.max_streams
     self.in_max = max_new_frames(self.geo, self.max_chunk)
     self.cap = [l.width + self.in_max[i] for i, l in enumerate(self.layers)]            # retained (< width) + new
@@ -389,7 +460,7 @@ class StreamingRecognizer:
       # (with a beam search: ... | result [S][4] | tail [S][max_tail])
       # (with endpointing: [ids | counts | scores | events [S][P][8] | pieces [P][S][4]], then result [P][S][4] | tail [P][S][max_tail])
       greedy_words = S * self.max_new + 2 * S
-      total_stride = int(np.prod([s for _, s in self.geo]))
+      total_stride = self.total_stride
       self.n_pieces = 1
       if endpoint is not None:
         self.ep_frames = endpoint.frames(total_stride, self.num_classes)
@@ -400,6 +471,10 @@ class StreamingRecognizer:
         self.ep_score = torch.zeros(S * int(lib.st_stream_endpoint_score_bytes()) // 4, dtype=torch.float32, device=dev)
         self.ep_words = S * P * 8 + P * S * 4
         greedy_words += self.ep_words
+      if words is not None:
+        # the ring of logits rows per stream the finals' lattices read (st_stream_keep_rows: M + the rows of a pass)
+        self.ring_cap = int(lib.st_stream_keep_rows(self.ep_frames[2], self.max_new))
+        self.ring = torch.zeros(S * self.ring_cap * 32, dtype=torch.float32, device=dev)
       # (with a spotter, behind everything else: counts [S] | events [S][max_events][8])
       self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
       self.dec_out = torch.zeros(self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0), dtype=torch.int32, device=dev)
@@ -615,6 +690,10 @@ class StreamingRecognizer:
            ptr(pb), spec.width, spec.stride, spec.cout, int(spec.relu), ptr(out), self.max_rows[-1] if lastl else self.cap[l + 1],
            spec.cout_pitch, None if lastl else info_ptr(l + 1), ptr(self.workspace), self.ws_bytes, sp)
       self.launches += 2
+    if self.words is not None and len(rows[-1]):
+      call('st_stream_keep_f32', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), len(rows[-1]), S, ptr(self.ring),
+           self.ring_cap, sp)
+      self.launches += 1
     call('st_stream_advance', ptr(self.layer_table), L, info_ptr(0), S, sp)
     if self.endpoint is not None:
       self._launch_endpointed(tptr(L), tptr(L + 1), len(rows[-1]))
@@ -724,7 +803,7 @@ class StreamingRecognizer:
       g += self.ep_words
       mt = self.beam.max_tail
       res, tail = words[g:g + P * S * 4].reshape(P, S, 4), words[g + P * S * 4:].reshape(P, S, mt)
-    failed = None
+    failed, new_finals = None, []
     for k, s in enumerate(named):
       closed, prev, last_kind = [], 0, 0
       for e in (events[s].tolist() if events[s, 0, 0] else ()):   # (most steps close nothing)
@@ -762,9 +841,76 @@ class StreamingRecognizer:
           self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
         result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
       result.finals[s] += closed
+      new_finals += [(s, u) for u in closed]
+    if self.words is not None:
+      self._final_words(new_finals)
     if failed is not None:
       failed.result = result
       raise failed
+
+  def _final_words(self, finals):
+    """The word times and confidences of the finals a pass closed, ``[(slot, Utterance)]``: one table (`final_jobs`), one upload, the
+    ring alignment and / or the ring confidences for all of them together, one copy back -- the pass's second wait.  Runs inside the
+    pass: the next pass's keep overwrites the ring."""
+    from . import alignment
+    from .engine_decode import MAX_ALIGN_LABELS
+    want = self.words
+    for _, u in finals:
+      if len(u.ids) == 0:
+        u.words = []
+        if want.timestamps:
+          u.spans = np.zeros((0, 2), dtype=np.int32)
+    space = self.ep_frames[3] if want.confidence else None
+    tab = final_jobs([(s, u.start_frame, u.end_frame, u.ids) for s, u in finals], space, MAX_ALIGN_LABELS)
+    J = len(tab['index'])
+    if not J:
+      return
+    lib = _lib.load()
+    eng, S, C = self.engine, self.max_streams, self.num_classes
+    N, W, T, max_len = int(tab['offsets'][-1]), len(tab['word_spans']), tab['max_rows'], tab['max_len']
+    parts = [tab['jobs'].reshape(-1), tab['ids'], tab['offsets'], tab['word_spans'].reshape(-1), np.zeros(1, np.int32)]
+    offs = np.cumsum([0] + [p.size for p in parts])
+    table = self._upload(np.concatenate(parts), torch.int32)
+    tptr = lambda i: ctypes.c_void_p(table.data_ptr() + 4 * int(offs[i]))
+    ptr, sp = eng._ptr, eng.stream_ptr
+    with torch.cuda.stream(eng.stream):
+      # the outputs in one buffer, one copy back: log_conf [W] | log_prob [J] (doubles) | spans [N][2] | score [J] | status [J] | status [J]
+      out = torch.zeros(2 * (W + J) + 2 * N + 3 * J, dtype=torch.int32, device=self.device)
+      at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+      o_spans = 2 * (W + J)
+      o_score, o_st_align, o_st_conf = o_spans + 2 * N, o_spans + 2 * N + J, o_spans + 2 * N + 2 * J
+      if want.timestamps:
+        need = int(lib.st_ctc_align_ws(J, T, max_len))
+        ws = torch.empty(need // 4 + 16, dtype=torch.int32, device=self.device)
+        call('st_ctc_align_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, at(o_spans), None,
+             at(o_score), at(o_st_align), ptr(ws), ws.numel() * 4, sp)
+        self.launches += 3
+      if want.confidence:
+        need = int(lib.st_ctc_word_conf_ws(J, T, max_len, J + W))
+        ws2 = torch.empty(need // 4 + 16, dtype=torch.int32, device=self.device)
+        call('st_ctc_word_conf_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, space, tptr(3), W,
+             at(2 * W), at(0), at(o_st_conf), ptr(ws2), ws2.numel() * 4, sp)
+        self.launches += 3
+      host = out.cpu().numpy()                                     # the second wait of a pass that closed something
+    log_conf, log_prob = host[:2 * W].view(np.float64), host[2 * W:o_spans].view(np.float64)
+    spans, score = host[o_spans:o_score].reshape(N, 2), host[o_score:o_st_align].view(np.float32)
+    first_word = np.concatenate([[0], np.cumsum(tab['words'])]).astype(np.int64)
+    rate = 2.0 * alignment.HOP_LENGTH * 100.0 / self.total_stride   # frames_to_seconds(f, rate) = f * total_stride * 10 ms
+    for j, i in enumerate(tab['index']):
+      u = finals[i][1]
+      if host[o_st_align + j] != 0 or host[o_st_conf + j] != 0:     # the ids do not fit the rows: nothing, as offline
+        continue
+      probs = None
+      if want.timestamps:
+        u.spans = spans[tab['offsets'][j]:tab['offsets'][j + 1]].copy()
+        u.align_score = float(score[j])
+      if want.confidence:
+        probs = np.exp(log_conf[first_word[j]:first_word[j + 1]]).tolist()
+        u.confidence = dict(log_prob=float(log_prob[j]), words=probs)
+      if want.timestamps:
+        u.words = alignment.timed_words(u.ids, u.spans + u.start_frame, rate, confidence=probs)
+      else:
+        u.words = alignment.confident_words(u.ids, probs)
 
   def _upload(self, array, dtype):
     """Host array -> device as a stream operation (pinned staging from torch's caching host allocator: no wait for the stream's
@@ -942,14 +1088,14 @@ class StreamingFeatures:
         result[s].append(view[s, :count].cpu().numpy())
 
 
-def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False, beam=None, endpoint=None):
+def transcribe_stream(engine, chunks, max_chunk_frames=64, return_logits=False, beam=None, endpoint=None, words=None):
   """One stream: feed the feature chunks ([t, C] each) in order, finish, and return ``(ids, partials)`` -- all label ids and the
   list of (input frames so far, ids so far) after every chunk that produced any -- plus the logits [T', C] on request.
   ``beam`` (a `StreamBeam`): the ids are the beam search's hypothesis -- at the end the whole-utterance search's result -- and a
   partial is (input frames so far, hypothesis so far, how many of its leading ids are final) after every chunk that changed either.
   ``endpoint`` (an `Endpointing`): the first value is the list of the stream's `Utterance`s instead, and the partials describe the
-  utterance open at the time."""
-  rec = StreamingRecognizer(engine, 1, max_chunk_frames, beam=beam, endpoint=endpoint)
+  utterance open at the time; ``words`` (a `FinalWords`): every `Utterance` carries its words' times and / or confidences."""
+  rec = StreamingRecognizer(engine, 1, max_chunk_frames, beam=beam, endpoint=endpoint, words=words)
   slot = rec.open()
   ids, partials, rows, frames, finals = [], [], [], 0, []
   for chunk in chunks:
@@ -999,7 +1145,7 @@ def _pcm_chunks(stream, samples_per_chunk):
 
 
 def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
-                 on_final=None, spot=None, on_hit=None):
+                 on_final=None, spot=None, on_hit=None, words=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
   ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
@@ -1008,6 +1154,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
   ``on_partial(seconds, hypothesis so far, how many of its leading ids are final)`` is called whenever either has changed.
   ``endpoint`` (an `Endpointing`): the stream is cut into utterances; ``on_final(utterance)`` is called as each closes, the partials
   describe the utterance open at the time, and the first value returned is the list of `Utterance`s.
+  ``words`` (a `FinalWords`, with ``endpoint``): every `Utterance` carries its words' times and / or confidences.
   ``spot`` (a `StreamSpotter`): ``on_hit(hit)`` is called for every `Hit` as its step finds it; hits a step could not hand back
   (more than ``spot.max_events``) raise a RuntimeWarning."""
   hop = 160
@@ -1062,7 +1209,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     front.step({slot: y})
     feats = front.finish(slot)
     per = max(max(len(p) for p in pieces) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot, words=words)
     rslot = rec.open()
     for at in range(0, len(feats), per):
       feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
@@ -1071,7 +1218,7 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     max_piece = int(max_piece or 16000)
     front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
     slot = front.open()
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot, words=words)
     rslot = rec.open()
     for p in pieces:
       p = np.asarray(p, np.float32)
@@ -1096,6 +1243,23 @@ def endpoint_of(flags):
   if not getattr(flags, 'endpoint', False):
     return None
   return Endpointing(silence=flags.endpoint_silence, lead=flags.endpoint_lead, max_utterance=flags.max_utterance)
+
+
+def words_of(flags):
+  """The `FinalWords` the flags of `speecht-cli stream` ask for (None without --timestamps / --confidence)."""
+  stamps, conf = bool(getattr(flags, 'timestamps', False)), bool(getattr(flags, 'confidence', False))
+  return FinalWords(timestamps=stamps, confidence=conf) if stamps or conf else None
+
+
+def final_word_lines(path, utterance):
+  """The lines `speecht-cli stream` prints behind a final's line, one per word, in the format of `transcribe --timestamps`:
+  path<TAB>start<TAB>end<TAB>word, and <TAB>confidence when the words carry one (start and end are `-` without times)."""
+  out = []
+  for w in utterance.words or []:
+    times = '{:.3f}\t{:.3f}'.format(w['start'], w['end']) if 'start' in w else '-\t-'
+    tail = '\t{:.4f}'.format(w['confidence']) if 'confidence' in w else ''
+    out.append('{}\t{}\t{}{}'.format(path, times, w['word'], tail))
+  return out
 
 
 def spotter_of(flags):
@@ -1125,7 +1289,7 @@ def run_cli(flags):
   the phrases) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
   leading characters that are final".  With --endpoint the stream is cut into utterances: the partial lines describe the utterance that
   is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
-  speech), and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
+  speech) -- with --timestamps / --confidence followed by a line per word (`final_word_lines`) --, and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
   "start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame" (`hit_line`) as soon as its step has found it, between the other lines;
   hits a step could not hand back are a warning on stderr.  Creates no train / data / log directory."""
   import contextlib
@@ -1142,6 +1306,7 @@ def run_cli(flags):
   try:
     beam, endpoint, on_final = None, endpoint_of(flags), None
     spot = spotter_of(flags)
+    words = words_of(flags)
     from . import hotwords
     hot = hotwords.from_flags(flags)
     # (hotwords need a beam search: as in `transcribe`, beam 16 unless --beam-width or --language-model says otherwise)
@@ -1168,9 +1333,11 @@ def run_cli(flags):
         extra = dict(spot=spot, on_hit=lambda h: print(hit_line(h, rate), flush=True))
       if endpoint is not None:
         frame_s = 0.01 * int(np.prod([l.stride for l in model.engine.layers]))
-        on_final = lambda u: print('utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s, (u.last_speech + 1) * frame_s,
-                                                                        vocabulary.ids_to_sentence(u.ids)), flush=True)
-        extra.update(endpoint=endpoint, on_final=on_final)
+        on_final = lambda u: print('\n'.join(['utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s,
+                                                                                 (u.last_speech + 1) * frame_s,
+                                                                                 vocabulary.ids_to_sentence(u.ids))] +
+                                             final_word_lines(flags.path, u)), flush=True)
+        extra.update(endpoint=endpoint, on_final=on_final, words=words)
       if beam:
         if flags.path != '-':
           beam['max_seconds'] = len(samples) / float(rate) + 1.0
