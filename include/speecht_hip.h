@@ -802,6 +802,44 @@ int st_resample_kaiser_f32(const float* in, const int64_t* in_offsets, int n_utt
 int st_resample_kaiser_host(const float* in, const int64_t* in_offsets, int n_utts, const int32_t* rates, int sr_new,
                             const int64_t* out_offsets, const int64_t* out_valid, const double* win, int64_t win_len, double* out);
 
+/* ---- kaiser_best resampling of live streams (csrc/resample_stream.hip) ------------------------------------------------------
+ * One step for all streams; the concatenated outputs of a stream's steps are st_resample_kaiser_f32's samples of the whole
+ * signal, bit for bit, however the audio was cut (the arithmetic and its order are csrc/resample_map.h's, shared).  With
+ * ratio = sr_new / rate and L = 32 769 / int(min(1, ratio) * 512), the most taps of a wing (64 when up-sampling, 139 for
+ * 48 000 -> 22 050), output i of a stream that has received N samples is final iff int((double)i / ratio) + 1 + L <= N; once m
+ * outputs are out the first sample still needed is max(int(m / ratio) - L, 0).  A finished stream emits the rest up to
+ * out_valid = min(int(n_orig * ratio), target) and zeros up to target = ceil(n_orig * sr_new / rate) (audio_io.resample_lengths).
+ * rate == sr_new: a copy, L = 0.  The host keeps the counters (audio_io.resample_ready / resample_need) and passes
+ *   table int64 [max_streams][16], a HOST pointer (the launch is sized from it -- LDS from the ratios, grid from the counts -- and
+ *   it is copied to the head of `state` in stream order; pinned memory keeps that copy asynchronous):
+ *     {source rate (fixed per stream; 0: the stream sits this step out and is not touched),
+ *      base0: absolute sample at position 0 of the current window, base1: of the window the step leaves,
+ *      n0: samples received before the step, offset of the new samples in `samples`, their count,
+ *      first output index, outputs, their offset in `out`,
+ *      finished (0 / 1), n_orig, out_valid, target (read when finished),
+ *      parity: which of the stream's two windows is current (the step leaves the other one current), 0, 0}
+ *   state: st_resample_stream_state_bytes(max_streams, cap_samples) bytes, 8-byte aligned: the table's device copy, then two windows
+ *     of cap_samples floats per stream, used in turn.  A step reads the samples [base0, n0) from the current window and the new ones
+ *     from `samples`, and writes [base1, n0 + count) to the other window: no workgroup writes what another reads, nothing moves in
+ *     place.  At most 2 L + 1 samples are retained, whatever the feed.  Any content before a stream's first step (n0 = base0 = 0).
+ *   status int32 [max_streams]: 0, or why the row was refused -- 1 a negative or oversized field, 2 a window that would overrun
+ *     cap_samples or bases out of order, 3 outputs that need samples before base0 (or a base1 the next step would miss), 4 counts
+ *     that contradict the readiness rule, 5 outputs past out_capacity, 6 a tile span the LDS cannot hold.  A refused row writes no
+ *     output and no state; the other rows are served.  No read leaves the windows whatever a row says; `samples` must hold
+ *     [offset, offset + count) of every row.
+ *   out float32 [out_capacity]: laid out as the `samples` argument of st_melspec_stream_f32, which can read it in place.
+ * One launch: a workgroup per (stream, 256 outputs) stages the tile's source span (ceil(256 / ratio) + 2 L + 2 floats) in LDS, one
+ * thread per output walks its wings against it; a stream whose span exceeds 64 KiB is an error and nothing is launched.
+ * st_resample_stream_host: the same step on HOST pointers (state included), no GPU; it also writes the float64 sums to out64, which
+ * compare with st_resample_kaiser_host. */
+size_t st_resample_stream_state_bytes(int max_streams, int cap_samples);
+int st_resample_stream_f32(const float* samples, const int64_t* table, int max_streams, int sr_new, const double* win, int64_t win_len,
+                           void* state, size_t state_bytes, int cap_samples, float* out, int64_t out_capacity, int32_t* status,
+                           void* stream);
+int st_resample_stream_host(const float* samples, const int64_t* table, int max_streams, int sr_new, const double* win, int64_t win_len,
+                            void* state, size_t state_bytes, int cap_samples, float* out, double* out64, int64_t out_capacity,
+                            int32_t* status);
+
 /* ---- Silence segmentation: cut recordings into utterances (csrc/segment.hip) ------------------------------------------------
  * The endpointing of the reference's `record` (record_utils.AudioRecorder: normalise the peak to 0.5, trim samples with
  * abs(x) <= threshold from both ends, add 0.1 s of zeros on each side) applied to whole recordings.  Input layout of

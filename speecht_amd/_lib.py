@@ -214,6 +214,11 @@ _SIGNATURES = {
     'st_resample_kaiser_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                        c_void_p, c_void_p]),
     'st_resample_kaiser_host': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'st_resample_stream_state_bytes': (c_size_t, [c_int, c_int]),
+    'st_resample_stream_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int64,
+                                       c_void_p, c_void_p]),
+    'st_resample_stream_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
+                                        c_int64, c_void_p]),
     'st_segment_chunks_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     'st_segment_runs': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

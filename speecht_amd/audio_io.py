@@ -305,6 +305,68 @@ def plan_resample(lengths, rates, sr_new):
   return offsets, np.minimum(np.asarray(n_out, dtype=np.int64), np.asarray(target, dtype=np.int64))
 
 
+# ---- the rule of streamed resampling (csrc/resample_stream.hip, streaming.StreamingResampler) --------------------------------
+
+def resample_taps(sr_orig, sr_new):
+  """L: the most taps a wing of resample_kaiser_best can have, nwin // index_step -- 64 when up-sampling, 139 for 48 000 -> 22 050.
+  Equal rates resample nothing: 0."""
+  if sr_orig == sr_new:
+    return 0
+  nwin = (2 ** _KAISER_BEST['precision']) * _KAISER_BEST['num_zeros'] + 1
+  index_step = int(min(1.0, float(sr_new) / float(sr_orig)) * 2 ** _KAISER_BEST['precision'])
+  if index_step < 1:
+    raise ValueError('resampling {} -> {} Hz is outside the filter table'.format(sr_orig, sr_new))
+  return nwin // index_step
+
+
+def _source_index(i, sr_orig, sr_new):
+  return i if sr_orig == sr_new else int(float(i) / (float(sr_new) / float(sr_orig)))
+
+
+def resample_ready(n, sr_orig, sr_new):
+  """How many leading outputs of an open stream are final once it has received ``n`` source samples: output i is final iff
+  int(float(i) / ratio) + 1 + L <= n (wing 1 then has all the taps the table allows whatever arrives later; wing 0 only looks
+  back).  The left side is monotone in i; the count is found by bisection on the very float64 division the kernel performs, not from
+  a closed form.  Equal rates: every sample at once."""
+  if sr_orig == sr_new:
+    return n
+  taps = resample_taps(sr_orig, sr_new)
+  ratio = float(sr_new) / float(sr_orig)
+  final = lambda i: int(float(i) / ratio) + 1 + taps <= n
+  if not final(0):
+    return 0
+  lo = max(int((n - taps - 1) * ratio) - 4, 0)        # a guess only sets where the search starts: `final` decides
+  if not final(lo):
+    lo = 0
+  step = 8                                            # output lo is final; find an output lo + step that is not, then bisect
+  while final(lo + step):
+    lo, step = lo + step, 2 * step
+  hi = lo + step
+  while hi - lo > 1:
+    mid = (lo + hi) // 2
+    if final(mid):
+      lo = mid
+    else:
+      hi = mid
+  return hi
+
+
+def resample_need(m, sr_orig, sr_new):
+  """First source sample still needed once ``m`` outputs are out: max(int(float(m) / ratio) - L, 0)."""
+  return max(_source_index(m, sr_orig, sr_new) - resample_taps(sr_orig, sr_new), 0)
+
+
+def resample_stream_step(n, m, new, finished, sr_orig, sr_new):
+  """The counts of one step of a streamed resampling: a stream with ``n`` samples in and ``m`` outputs out receives ``new`` samples
+  and is ``finished`` or not -> (outputs of the step, n_orig, out_valid, target); the last three are 0 for an open stream.  A
+  finished stream emits the rest up to out_valid = min(int(n_orig * ratio), target) and zeros up to target (`resample_lengths`)."""
+  n1 = n + new
+  if not finished:
+    return max(resample_ready(n1, sr_orig, sr_new) - m, 0), 0, 0, 0
+  n_out, target = resample_lengths(n1, sr_orig, sr_new)
+  return target - m, n1, min(n_out, target), target
+
+
 _device_filters = {}
 
 

@@ -72,9 +72,11 @@ ST_RS_HD double rs_weight(const double* win, int64_t k, double eta, double ratio
   return a + eta * (b - a);
 }
 
-// output sample i (< the resampled length int(n_orig * ratio)) of the signal y[0 .. n_orig): the two wings' sums, added as the
-// host adds them (sum of wing 0, then + sum of wing 1); the taps in order, product rounded before the add
-ST_RS_HD double rs_output(const float* y, int64_t n_orig, const RsParams& p, int64_t i, const double* win) {
+// output sample i (< the resampled length int(n_orig * ratio)) of a signal of n_orig samples whose sample j is src(j): the two
+// wings' sums, added as the host adds them (sum of wing 0, then + sum of wing 1); the taps in order, product rounded before the
+// add.  Only where sample j is read from differs between the callers (a whole signal in memory; a live stream's staged window).
+template <class Src>
+ST_RS_HD double rs_output_src(const Src& src, int64_t n_orig, const RsParams& p, int64_t i, const double* win) {
 #pragma clang fp contract(off)
   double out = 0.0;
   for (int wing = 0; wing < 2; ++wing) {
@@ -83,12 +85,21 @@ ST_RS_HD double rs_output(const float* y, int64_t n_orig, const RsParams& p, int
     if (w.n >= 0 && w.n < n_orig) {                  // always true for i < int(n_orig * ratio); keeps every read in bounds
       for (int64_t k = 0; k < w.count; ++k) {
         const double wt = rs_weight(win, w.offset + k * p.index_step, w.eta, p.ratio);
-        acc += wt * (double)y[wing == 0 ? w.n - k : w.n + k + 1];
+        acc += wt * (double)src(wing == 0 ? w.n - k : w.n + k + 1);
       }
     }
     out += acc;
   }
   return out;
+}
+
+struct RsSignal {                                    // the signal y[0 .. n_orig) in memory
+  const float* y;
+  ST_RS_HD float operator()(int64_t j) const { return y[j]; }
+};
+
+ST_RS_HD double rs_output(const float* y, int64_t n_orig, const RsParams& p, int64_t i, const double* win) {
+  return rs_output_src(RsSignal{y}, n_orig, p, i, win);
 }
 
 }  // namespace st

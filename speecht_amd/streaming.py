@@ -37,6 +37,14 @@ With ``spot=StreamSpotter(...)`` every step also tells which of the given words 
 (csrc/ctc_spot_stream.hip): the lattices of `speecht-cli spot` carried across steps, all keywords of a stream packed into a few
 waves, and a causal rule that lets a hit go once nothing better can replace it (include/speecht_hip.h,
 tests/spot_stream_oracle.py).  It runs on the stream's rows as they are: decoding and endpointing neither see nor reset it.
+
+A model trained by this project expects 22 050 Hz audio (`preprocessing.LIBROSA_RATE`); live audio rarely has that rate.
+`StreamingResampler` brings streams of any source rates to the model's as the samples arrive (csrc/resample_stream.hip): band-limited
+interpolation has finite support, so an output sample is final (L + 1) / source_rate seconds after its time, and the streamed samples
+are the offline resampler's of the whole signal, bit for bit.  `StreamingFeatures(model_rate, ..., source_rate=)` puts it in front of
+the mel kernel without a trip through the host, `stream_audio(..., model_rate=)` and `speecht-cli stream --model-rate` use that, and
+the seconds of endpointing, spotting, the beam's pool and the words' times then count frames of hop / model_rate seconds
+(``frame_rate``) instead of assuming 10 ms.
 """
 import ctypes
 
@@ -213,10 +221,13 @@ class Endpointing:
       raise StreamError('endpointing: space_id must be \'auto\', -1 or a class index, got {!r}'.format(space_id))
     self.space_id = space_id
 
-  def frames(self, total_stride, num_classes):
-    """Seconds -> output frames of a model whose layers' strides multiply to ``total_stride`` (10 ms hop):
-    ``(silence_frames, lead_frames, max_frames, space_id)``, each count rounded up and at least 1."""
-    count = lambda seconds: max(int(np.ceil(seconds * 100.0 / total_stride - 1e-9)), 1)
+  def frames(self, total_stride, num_classes, frame_rate=None):
+    """Seconds -> output frames of a model whose layers' strides multiply to ``total_stride``:
+    ``(silence_frames, lead_frames, max_frames, space_id)``, each count rounded up and at least 1.  ``frame_rate``: feature frames
+    per second, sample rate / hop (137.8125 for 22 050 Hz); None: the 10 ms hop of 16 kHz audio, a guess where nothing says
+    otherwise."""
+    per_second = 100.0 if frame_rate is None else float(frame_rate)
+    count = lambda seconds: max(int(np.ceil(seconds * per_second / total_stride - 1e-9)), 1)
     R, L, M = count(self.silence), count(self.lead), count(self.max_utterance)
     space = (27 if num_classes == 29 else -1) if self.space_id == 'auto' else int(self.space_id)
     if space >= num_classes:
@@ -333,10 +344,11 @@ class StreamSpotter:
       raise StreamError('spotting: max_events must be a positive integer, got {!r}'.format(max_events))
     self.max_events = int(max_events)
 
-  def frames(self, total_stride):
-    """``hold`` in output frames of a model whose layers' strides multiply to ``total_stride`` (10 ms hop), counted as
-    `Endpointing.frames` counts: rounded up, at least 1."""
-    return max(int(np.ceil(self.hold * 100.0 / total_stride - 1e-9)), 1)
+  def frames(self, total_stride, frame_rate=None):
+    """``hold`` in output frames of a model whose layers' strides multiply to ``total_stride``, counted as `Endpointing.frames`
+    counts: rounded up, at least 1.  ``frame_rate``: feature frames per second (None: the 10 ms hop)."""
+    per_second = 100.0 if frame_rate is None else float(frame_rate)
+    return max(int(np.ceil(self.hold * per_second / total_stride - 1e-9)), 1)
 
   def plan(self, num_classes, pack=1):
     """-> (the plan of st_ctc_spot_stream_plan as an int32 array, its waves).  Runs on the host."""
@@ -416,8 +428,9 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None, words=None):
-    """``words``: a `FinalWords` (needs ``endpoint``) -- every final then also carries its words' times and / or confidences
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None, words=None, frame_rate=None):
+    """``frame_rate``: feature frames per second, the features' sample rate / hop -- what turns the seconds of ``endpoint``, ``spot``,
+    ``beam.max_seconds`` and the words' times into frames and back; None: 100, the 10 ms hop of 16 kHz audio.  ``words``: a `FinalWords` (needs ``endpoint``) -- every final then also carries its words' times and / or confidences
     (`Utterance.spans` / ``align_score`` / ``confidence`` / ``words``): one launch more per pass, and in a pass that closes an utterance
     one upload, the lattices' launches and a second wait.  None: nothing changes.  ``spot``: a `StreamSpotter` -- every step then also reports the keywords it has found (`StepResult.hits`), with or without
     a beam search and endpointing, whose results it does not change: one launch more per step (and the memset of its counts).
@@ -437,10 +450,13 @@ class StreamingRecognizer:
         raise StreamError('a layer of width {} and stride {} has no length-independent left padding'.format(w, s))
     self.num_classes = engine.num_classes
     self.total_stride = int(np.prod([s for _, s in self.geo]))
+    if frame_rate is not None and not (np.isfinite(frame_rate) and frame_rate > 0):
+      raise StreamError('frame_rate must be a positive number of frames per second, got {!r}'.format(frame_rate))
+    self.frame_rate = None if frame_rate is None else float(frame_rate)
     if words is not None:                                        # (refused before anything is allocated)
       if not isinstance(words, FinalWords):
         raise StreamError('words must be a FinalWords, got {!r}'.format(type(words).__name__))
-      words.check(endpoint, self.num_classes, endpoint.frames(self.total_stride, self.num_classes)[3] if endpoint is not None else -1)
+      words.check(endpoint, self.num_classes, endpoint.frames(self.total_stride, self.num_classes, self.frame_rate)[3] if endpoint is not None else -1)
     L, S = len(self.layers), self.max_streams
     self.in_max = max_new_frames(self.geo, self.max_chunk)
     self.cap = [l.width + self.in_max[i] for i, l in enumerate(self.layers)]            # retained (< width) + new
@@ -463,7 +479,7 @@ class StreamingRecognizer:
       total_stride = self.total_stride
       self.n_pieces = 1
       if endpoint is not None:
-        self.ep_frames = endpoint.frames(total_stride, self.num_classes)
+        self.ep_frames = endpoint.frames(total_stride, self.num_classes, self.frame_rate)
         if not 2 <= self.num_classes <= 64:
           raise StreamError('endpointing supports 2..64 classes, the engine has {}'.format(self.num_classes))
         self.n_pieces = P = int(lib.st_stream_endpoint_pieces(self.max_new, *self.ep_frames[:3]))
@@ -479,7 +495,7 @@ class StreamingRecognizer:
       self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
       self.dec_out = torch.zeros(self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0), dtype=torch.int32, device=dev)
       if spot is not None:
-        self.spot_hold = spot.frames(total_stride)
+        self.spot_hold = spot.frames(total_stride, self.frame_rate)
         self.spot_plan, self.spot_waves = spot.plan(self.num_classes)      # the host copy: the step reads its header
         self.spot_plan_dev = torch.from_numpy(self.spot_plan).to(dev)
         call('st_ctc_spot_stream_plan_bind', self.spot_plan.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.spot_plan_dev.data_ptr()))
@@ -498,7 +514,8 @@ class StreamingRecognizer:
           raise StreamError('a language model needs the 29 classes a-z \' space blank, the engine has {}'.format(self.num_classes))
         if not 2 <= self.num_classes <= 32:
           raise StreamError('the beam search supports 2..32 classes, the engine has {}'.format(self.num_classes))
-        self.max_frames = int(np.ceil(beam.max_seconds * 100.0 / total_stride - 1e-9))   # output frames (10 ms hop)
+        per_second = 100.0 if self.frame_rate is None else self.frame_rate               # (10 ms hop unless told)
+        self.max_frames = int(np.ceil(beam.max_seconds * per_second / total_stride - 1e-9))   # output frames
         if endpoint is not None:
           self.max_frames = self.ep_frames[2]                        # no utterance is longer: the pool is never full
         self._lm_handle = beam.lm.device_handle(dev) if beam.lm is not None else None
@@ -895,7 +912,8 @@ class StreamingRecognizer:
     log_conf, log_prob = host[:2 * W].view(np.float64), host[2 * W:o_spans].view(np.float64)
     spans, score = host[o_spans:o_score].reshape(N, 2), host[o_score:o_st_align].view(np.float32)
     first_word = np.concatenate([[0], np.cumsum(tab['words'])]).astype(np.int64)
-    rate = 2.0 * alignment.HOP_LENGTH * 100.0 / self.total_stride   # frames_to_seconds(f, rate) = f * total_stride * 10 ms
+    per_second = 100.0 if self.frame_rate is None else self.frame_rate
+    rate = 2.0 * alignment.HOP_LENGTH * per_second / self.total_stride   # frames_to_seconds(f, rate) = f * total_stride / per_second
     for j, i in enumerate(tab['index']):
       u = finals[i][1]
       if host[o_st_align + j] != 0 or host[o_st_conf + j] != 0:     # the ids do not fit the rows: nothing, as offline
@@ -918,6 +936,236 @@ class StreamingRecognizer:
     host = torch.from_numpy(array).pin_memory()
     with torch.cuda.stream(self.engine.stream):
       return host.to(self.device, non_blocking=True)
+
+
+# ---- resampling live streams (csrc/resample_stream.hip) -------------------------------------------------------------------------
+
+RS_ROW = 16                     # int64 words per row of st_resample_stream_f32's table
+RS_STATUS = {1: 'a field is negative or too large', 2: 'the window would overrun', 3: 'samples before the window would be needed',
+             4: 'the counts contradict the readiness rule', 5: 'the outputs do not fit', 6: 'a tile\'s span does not fit the LDS'}
+
+
+class _ResampleSlot:
+  __slots__ = ('rate', 'n', 'm', 'base', 'parity', 'finished')
+
+  def __init__(self, rate):
+    self.rate, self.n, self.m, self.base, self.parity, self.finished = int(rate), 0, 0, 0, 0, False
+
+
+class StreamingResampler:
+  """Up to ``max_streams`` sample streams, each of its own source rate, resampled to ``model_rate`` as the samples arrive
+  (st_resample_stream_f32): the concatenated outputs of a stream are `audio_io.resample_kaiser_best_batch`'s samples of the whole
+  signal (librosa's resample + fix_length), bit for bit, however the audio was cut.  An output appears once the samples of its right
+  wing are in -- (L + 1) / rate seconds after its time, L = `audio_io.resample_taps` -- and `finish` emits the rest.  The host keeps
+  every counter (`audio_io.resample_ready` / ``resample_need`` / ``resample_stream_step``) and checks what the kernel checks before
+  it launches.  ``max_source_rate`` sizes the streams' windows (2 L + 2 samples each, twice); ``device='cpu'`` runs the host form
+  st_resample_stream_host with the same table (no GPU), whose float64 sums of the last pass are in ``last64``."""
+
+  def __init__(self, model_rate, max_streams=1, max_chunk_samples=16000, device='cuda:0', max_source_rate=48000):
+    from . import audio_io
+    if max_streams < 1 or max_chunk_samples < 1 or int(model_rate) < 1 or int(max_source_rate) < 1:
+      raise StreamError('bad StreamingResampler sizes')
+    self.model_rate, self.max_streams, self.max_chunk = int(model_rate), int(max_streams), int(max_chunk_samples)
+    self.host = str(device) == 'cpu'
+    taps = max(audio_io.resample_taps(int(max_source_rate), self.model_rate), audio_io.resample_taps(1, 2))
+    self.cap = 2 * taps + 2
+    lib = _lib.load()
+    self.state_bytes = int(lib.st_resample_stream_state_bytes(self.max_streams, self.cap))
+    self.win = np.ascontiguousarray(audio_io._kaiser_best_filter()[0], dtype=np.float64)
+    self.slots = [None] * self.max_streams
+    self.launches = 0            # passes enqueued (one kernel each)
+    if self.host:
+      self.device = None
+      self.state = np.zeros(self.state_bytes // 8 + 1, dtype=np.int64)
+      self.last64 = {}
+    else:
+      self.device = torch.device(device)
+      self.state = torch.zeros(self.state_bytes // 8 + 1, dtype=torch.int64, device=self.device)
+      self.status = torch.zeros(self.max_streams, dtype=torch.int32, device=self.device)
+      self.out = torch.zeros(1, dtype=torch.float32, device=self.device)
+      self._win = audio_io._device_filter(self.device)
+      # the table is read by the host function and copied from there in stream order: a ring of pinned rows, each reused only
+      # once the copy that read it is done
+      self._tables = [torch.zeros(self.max_streams * RS_ROW, dtype=torch.int64).pin_memory() for _ in range(4)]
+      self._table_done = [None] * len(self._tables)
+      self._turn = 0
+
+  # -- slots --
+
+  def open(self, rate, slot=None):
+    """-> a free slot (``slot``: that one) for a stream of ``rate`` Hz.  Nothing is cleared: a stream's first step reads no state."""
+    from . import audio_io
+    if not isinstance(rate, (int, np.integer)) or isinstance(rate, bool) or not 0 < rate < 2 ** 31:
+      raise StreamError('the source rate must be a positive integer, got {!r}'.format(rate))
+    try:
+      taps = audio_io.resample_taps(int(rate), self.model_rate)
+    except ValueError as e:
+      raise StreamError(str(e))
+    if 2 * taps + 2 > self.cap:
+      raise StreamError('{} -> {} Hz keeps {} samples between steps, the windows hold {} (max_source_rate)'.format(
+          rate, self.model_rate, 2 * taps + 2, self.cap))
+    if rate != self.model_rate and (int(np.ceil(256.0 * rate / self.model_rate)) + 2 * taps + 2) * 4 > 65536:
+      raise StreamError('{} -> {} Hz: a tile\'s source span does not fit the LDS'.format(rate, self.model_rate))
+    for i, s in enumerate(self.slots):
+      if s is None and slot in (None, i):
+        self.slots[i] = _ResampleSlot(rate)
+        return i
+    raise StreamError('all {} streams are open'.format(self.max_streams) if slot is None else 'stream {} is not free'.format(slot))
+
+  def close(self, slot):
+    self._slot(slot, True)
+    self.slots[slot] = None
+
+  def _slot(self, slot, allow_finished=False):
+    if not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.max_streams or self.slots[slot] is None:
+      raise StreamError('stream {} is not open'.format(slot))
+    if self.slots[slot].finished and not allow_finished:
+      raise StreamError('stream {} has been finished: close it and open a new one'.format(slot))
+    return self.slots[slot]
+
+  # -- steps --
+
+  def step(self, feeds):
+    """``feeds``: {slot: float samples [n] at the slot's rate} -> {slot: new samples at ``model_rate``} (float32 numpy, may be empty).
+    Feeds longer than ``max_chunk_samples`` are cut into passes."""
+    return self._run(feeds, ())
+
+  def finish(self, slot):
+    """Flush: the outputs up to the fix_length target of everything the slot was fed.  Returns the rest of the slot's samples."""
+    self._slot(slot)
+    return self._run({}, (slot,))[slot]
+
+  def _arrays(self, feeds, finishing):
+    arrays = {}
+    for slot, y in feeds.items():
+      self._slot(slot)
+      y = np.ascontiguousarray(np.asarray(y, dtype=np.float32))
+      if y.ndim != 1:
+        raise StreamError('stream {}: samples must be a one-dimensional array, got shape {}'.format(slot, tuple(y.shape)))
+      arrays[int(slot)] = y
+    for slot in finishing:
+      self._slot(slot)
+    return arrays
+
+  def _run(self, feeds, finishing):
+    arrays = self._arrays(feeds, finishing)
+    result = {s: [] for s in list(arrays) + [int(s) for s in finishing]}
+    sums = {s: [] for s in result}
+    longest = max([len(a) for a in arrays.values()] + [0])
+    passes = max(-(-longest // self.max_chunk), 1)
+    for p in range(passes):
+      part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
+      out, where = self.step_device(part, finishing if p == passes - 1 else ())
+      host = out if self.host else out.cpu().numpy()
+      if not self.host:
+        self._raise_status(self.status.cpu().numpy())
+      for s, (at, count) in where.items():
+        if count:
+          result[s].append(host[at:at + count].copy())
+          if self.host:
+            sums[s].append(self._pass64[at:at + count].copy())
+    if self.host:
+      self.last64 = {s: (np.concatenate(r) if r else np.zeros(0, np.float64)) for s, r in sums.items()}
+    return {s: (np.concatenate(r) if r else np.zeros(0, np.float32)) for s, r in result.items()}
+
+  def step_device(self, feeds, finishing=()):
+    """One pass without a read-back: ``feeds`` {slot: float samples [n <= max_chunk_samples]} and the slots to finish -> (the float32
+    device buffer of the pass's outputs, {slot: (offset, count)}); the buffer is laid out as the ``samples`` argument of
+    st_melspec_stream_f32, ready on the current stream and valid until the next pass.  A feed longer than ``max_chunk_samples`` is
+    refused before anything is launched."""
+    arrays = self._arrays(feeds, finishing)
+    table, where, after, total = self.plan({s: len(a) for s, a in arrays.items()}, finishing)
+    chunks = [arrays[s] for s in sorted(arrays) if len(arrays[s])]
+    samples = np.concatenate(chunks) if chunks else np.zeros(1, np.float32)
+    if self.host:
+      out, self._pass64 = self._launch_host(table, samples, total)
+      self._raise_status(self._host_status)
+    else:
+      d_samples = torch.from_numpy(samples).pin_memory().to(self.device, non_blocking=True)
+      out = self.launch(table, d_samples, total)
+    self.commit(after)
+    return out, where
+
+  def plan(self, news, finishing=()):
+    """The table of one pass, from counts alone: ``news`` {slot: new samples} (their samples concatenated in slot order) and the slots
+    to finish -> (table int64 [max_streams, 16], {slot: (offset in the outputs, count)}, the counters to `commit` once the pass is
+    launched, total outputs).  Refuses (StreamError) what the kernel would refuse by status; changes nothing."""
+    from . import audio_io
+    table = np.zeros((self.max_streams, RS_ROW), dtype=np.int64)
+    where, after, src, total = {}, {}, 0, 0
+    finishing = set(int(x) for x in finishing)
+    for s in sorted(set(int(x) for x in news) | finishing):
+      st = self._slot(s)
+      new, fin = int(news.get(s, 0)), s in finishing
+      if new > self.max_chunk:
+        raise StreamError('stream {}: {} new samples, a pass takes {} (max_chunk_samples)'.format(s, new, self.max_chunk))
+      count, n_orig, valid, target = audio_io.resample_stream_step(st.n, st.m, new, fin, st.rate, self.model_rate)
+      n1, m1 = st.n + new, st.m + count
+      base1 = n1 if fin else min(audio_io.resample_need(m1, st.rate, self.model_rate), n1)
+      if st.n - st.base > self.cap or n1 - base1 > self.cap or base1 < st.base:
+        raise StreamError('stream {}: {} samples would overrun the window'.format(s, max(st.n - st.base, n1 - base1)))
+      if count and st.m < (valid if fin else m1) and audio_io.resample_need(st.m, st.rate, self.model_rate) < st.base:
+        raise StreamError('stream {}: output {} needs samples the window has dropped'.format(s, st.m))
+      table[s, :14] = (st.rate, st.base, base1, st.n, src, new, st.m, count, total, int(fin), n_orig, valid, target, st.parity)
+      where[s] = (total, count)
+      after[s] = (n1, m1, base1, fin)
+      src += new
+      total += count
+    return table, where, after, total
+
+  def commit(self, after):
+    """Move the counters of the streams of a launched pass on (``after`` from `plan`)."""
+    for s, (n1, m1, base1, fin) in after.items():
+      st = self.slots[s]
+      st.n, st.m, st.base, st.finished, st.parity = n1, m1, base1, fin, st.parity ^ 1
+
+  def launch(self, table, d_samples, total):
+    """Enqueue one pass: ``table`` from `plan` (or made by hand), ``d_samples`` the concatenated new samples on the device -> the
+    device buffer of the ``total`` outputs.  ``status`` (device int32 [max_streams]) tells which rows the kernel refused."""
+    if total > self.out.numel():
+      self.out = torch.zeros(total + total // 2, dtype=torch.float32, device=self.device)
+    k = self._turn
+    self._turn = (k + 1) % len(self._tables)
+    if self._table_done[k] is not None:
+      self._table_done[k].synchronize()
+    self._tables[k].copy_(torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64).reshape(-1)))
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = torch.cuda.current_stream(self.device)
+    call('st_resample_stream_f32', P(d_samples), P(self._tables[k]), self.max_streams, self.model_rate, P(self._win), self._win.numel(),
+         P(self.state), self.state_bytes, self.cap, P(self.out), int(total), P(self.status), ctypes.c_void_p(stream.cuda_stream))
+    self._table_done[k] = torch.cuda.Event()
+    self._table_done[k].record(stream)
+    self.launches += 1
+    return self.out[:total]
+
+  def _launch_host(self, table, samples, total, out=None):
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    table = np.ascontiguousarray(table, dtype=np.int64)
+    samples = np.ascontiguousarray(samples, dtype=np.float32)
+    out = np.zeros(max(total, 1), np.float32) if out is None else out
+    out64 = np.zeros(len(out), np.float64)
+    self._host_status = np.zeros(self.max_streams, np.int32)
+    call('st_resample_stream_host', p(samples), p(table), self.max_streams, self.model_rate, p(self.win), len(self.win), p(self.state),
+         self.state_bytes, self.cap, p(out), p(out64), len(out), p(self._host_status))
+    return out[:total], out64[:total]
+
+  def run_table(self, table, samples, total, fill=0.0):
+    """A hand-made table, as it is: -> (outputs [total] float32 numpy, status int32 [max_streams]).  The counters are not touched;
+    the output buffer holds ``fill`` wherever the pass wrote nothing.  For tests of the kernel's own checks."""
+    samples = np.array(samples, dtype=np.float32)
+    if self.host:
+      out, _ = self._launch_host(table, samples, total, out=np.full(max(total, 1), fill, np.float32))
+      return out.copy(), self._host_status.copy()
+    if total > self.out.numel():
+      self.out = torch.zeros(total + total // 2, dtype=torch.float32, device=self.device)
+    self.out.fill_(fill)
+    out = self.launch(table, torch.from_numpy(samples).to(self.device), total)
+    return out.cpu().numpy(), self.status.cpu().numpy()
+
+  def _raise_status(self, status):
+    bad = [(s, int(c)) for s, c in enumerate(status) if c]
+    if bad:
+      raise StreamError('the resampler refused ' + ', '.join('stream {}: {}'.format(s, RS_STATUS.get(c, c)) for s, c in bad))
 
 
 # ---- the mel front end -------------------------------------------------------------------------------------------------------
@@ -943,10 +1191,10 @@ def sample_base(f, hop):
 
 
 class _FeatSlot:
-  __slots__ = ('n', 'f', 'fresh', 'finished')
+  __slots__ = ('n', 'f', 'fresh', 'finished', 'chunk')
 
-  def __init__(self):
-    self.n, self.f, self.fresh, self.finished = 0, 0, True, False
+  def __init__(self, chunk=None):
+    self.n, self.f, self.fresh, self.finished, self.chunk = 0, 0, True, False, chunk    # chunk: source samples per pass
 
 
 class StreamingFeatures:
@@ -955,9 +1203,16 @@ class StreamingFeatures:
   ``stats=None``: causal normalisation -- the first ``warm`` frames appear together with the reference and the statistics of frame
   ``warm - 1`` (the network waits 99 frames for its first output anyway), every later frame with the running ones; an utterance of at
   most ``warm`` frames gets the whole-utterance features.  ``stats=(ref, mean, std)`` (largest mel power, mean and deviation of the dB
-  values): fixed statistics, every utterance gets the features those constants give.  Mel features only."""
+  values): fixed statistics, every utterance gets the features those constants give.  Mel features only.
 
-  def __init__(self, samplerate, n_mels, max_streams=1, max_chunk_samples=16000, warm=100, stats=None, hop_length=160, device='cuda:0'):
+  ``source_rate`` (here, or per stream in `open`): the streams deliver samples at that rate and the front end brings them to
+  ``samplerate`` on the device first (a `StreamingResampler` of its own; its outputs are the mel kernel's input in place, only
+  features are read back).  The features are then those of `audio_io.resample_kaiser_best_batch`'s samples of the whole signal fed
+  at ``samplerate``, bit for bit and however the audio was cut; they lag (L + 1) / source_rate seconds more.  ``max_chunk_samples``
+  stays a count at ``samplerate``.  Without any source rate, calls, tables and launches are what they are without the argument."""
+
+  def __init__(self, samplerate, n_mels, max_streams=1, max_chunk_samples=16000, warm=100, stats=None, hop_length=160, device='cuda:0',
+               source_rate=None):
     from .preprocessing import mel_filterbank
     if max_streams < 1 or max_chunk_samples < 1 or warm < 1 or not 0 < n_mels <= 256:
       raise StreamError('bad StreamingFeatures sizes')
@@ -981,6 +1236,9 @@ class StreamingFeatures:
     self.workspace = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
     self.out = torch.zeros(self.max_streams * self.out_cap * self.n_mels, dtype=torch.float32, device=dev)
     self.slots = [None] * self.max_streams
+    self.samplerate, self.source_rate, self.resampler = int(samplerate), source_rate, None
+    if source_rate is not None:
+      self._source_chunk(source_rate)                            # (refuses a rate the front end cannot serve)
     torch.cuda.current_stream(dev).synchronize()                 # (the basis may be freed once the plan is made)
 
   @staticmethod
@@ -991,16 +1249,55 @@ class StreamingFeatures:
   def _sp(self):
     return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-  def open(self):
-    for i, s in enumerate(self.slots):
-      if s is None:
-        self.slots[i] = _FeatSlot()
-        return i
-    raise StreamError('all {} streams are open'.format(self.max_streams))
+  def _source_chunk(self, rate):
+    """Source samples of ``rate`` Hz a pass may take so that its outputs, a finish's flush included, fit ``max_chunk_samples``."""
+    from . import audio_io
+    if not isinstance(rate, (int, np.integer)) or isinstance(rate, bool) or not 0 < rate < 2 ** 31:
+      raise StreamError('the source rate must be a positive integer, got {!r}'.format(rate))
+    try:
+      taps = audio_io.resample_taps(int(rate), self.samplerate)
+    except ValueError as e:
+      raise StreamError(str(e))
+    chunk = int((self.max_chunk - 2) * float(rate) / self.samplerate) - (taps + 2)
+    if chunk < 1:
+      raise StreamError('max_chunk_samples = {} is too small for a stream of {} Hz'.format(self.max_chunk, rate))
+    return chunk
+
+  def open(self, source_rate=None):
+    """-> a free slot.  ``source_rate``: the rate of this stream's samples (default: the front end's ``source_rate``; None: they are at
+    ``samplerate`` already)."""
+    rate = self.source_rate if source_rate is None else source_rate
+    if rate is None and self.resampler is None:
+      for i, s in enumerate(self.slots):
+        if s is None:
+          self.slots[i] = _FeatSlot()
+          return i
+      raise StreamError('all {} streams are open'.format(self.max_streams))
+    # once a stream is resampled every stream's samples pass through the resampler (equal rates: a copy, bit for bit), so that the
+    # mel kernel reads one buffer
+    rate = self.samplerate if rate is None else rate
+    chunk = self._source_chunk(rate)
+    free = [i for i, s in enumerate(self.slots) if s is None]
+    if not free:
+      raise StreamError('all {} streams are open'.format(self.max_streams))
+    if self.resampler is None:
+      resampler = StreamingResampler(self.samplerate, self.max_streams, max_chunk_samples=max(chunk, self.max_chunk), device=self.device,
+                                     max_source_rate=max(int(rate), 48000))
+      for i, s in enumerate(self.slots):
+        if s is not None:
+          resampler.open(self.samplerate, slot=i)
+          s.chunk = self._source_chunk(self.samplerate)
+      self.resampler = resampler
+    self.resampler.max_chunk = max(self.resampler.max_chunk, chunk)
+    self.resampler.open(int(rate), slot=free[0])
+    self.slots[free[0]] = _FeatSlot(chunk)
+    return free[0]
 
   def close(self, slot):
     self._slot(slot, True)
     self.slots[slot] = None
+    if self.resampler is not None:
+      self.resampler.close(slot)
 
   def _slot(self, slot, allow_finished=False):
     if not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.max_streams or self.slots[slot] is None:
@@ -1016,8 +1313,13 @@ class StreamingFeatures:
   def finish(self, slot):
     """Flush: the frames up to 1 + n // hop, reflected at the end.  Returns the rest of the slot's features."""
     st = self._slot(slot)
-    if st.n <= N_FFT // 2:
-      raise StreamError('stream {}: {} samples, the reflection at the ends needs more than {}'.format(slot, st.n, N_FFT // 2))
+    n = st.n
+    if self.resampler is not None:
+      from . import audio_io
+      rs = self.resampler.slots[slot]
+      n = audio_io.resample_lengths(rs.n, rs.rate, self.samplerate)[1]
+    if n <= N_FFT // 2:
+      raise StreamError('stream {}: {} samples, the reflection at the ends needs more than {}'.format(slot, n, N_FFT // 2))
     return self._run({}, (slot,))[slot]
 
   def _run(self, feeds, finishing):
@@ -1031,12 +1333,30 @@ class StreamingFeatures:
     for slot in finishing:
       self._slot(slot)
     result = {s: [] for s in list(arrays) + [int(s) for s in finishing]}
-    longest = max([len(a) for a in arrays.values()] + [0])
-    passes = max(-(-longest // self.max_chunk), 1)
-    for p in range(passes):
-      part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
-      self._pass(part, finishing if p == passes - 1 else (), result)
+    if self.resampler is None:
+      longest = max([len(a) for a in arrays.values()] + [0])
+      passes = max(-(-longest // self.max_chunk), 1)
+      for p in range(passes):
+        part = {s: a[p * self.max_chunk:(p + 1) * self.max_chunk] for s, a in arrays.items()}
+        self._pass(part, finishing if p == passes - 1 else (), result)
+    else:                                                        # a pass takes what resamples to at most max_chunk samples
+      per = {s: self.slots[s].chunk for s in arrays}
+      passes = max([-(-len(a) // per[s]) for s, a in arrays.items()] + [1])
+      for p in range(passes):
+        part = {s: a[p * per[s]:(p + 1) * per[s]] for s, a in arrays.items()}
+        self._pass(part, finishing if p == passes - 1 else (), result)
     return {s: (np.concatenate(r) if r else np.zeros((0, self.n_mels), np.float32)) for s, r in result.items()}
+
+  def _resample(self, part, finishing):
+    """The resampler's pass in front of the mel kernel's: -> ({slot: samples at ``samplerate`` this pass}, their device buffer)."""
+    rs = self.resampler
+    table, where, after, total = rs.plan({s: len(a) for s, a in part.items()}, finishing)
+    chunks = [part[s] for s in sorted(part) if len(part[s])]
+    source = np.concatenate(chunks) if chunks else np.zeros(1, np.float32)
+    d_source = torch.from_numpy(source).pin_memory().to(self.device, non_blocking=True)
+    out = rs.launch(table, d_source, total)
+    rs.commit(after)
+    return {s: count for s, (_, count) in where.items()}, (out if total else rs.out[:1])
 
   def _pass(self, part, finishing, result):
     S = self.max_streams
@@ -1047,9 +1367,10 @@ class StreamingFeatures:
         b = sample_base(st.f, self.hop)
         minfo[s] = (b, st.n, b, 0, 0, 0, st.f, 0)
     pairs, after, rows, src, chunks = [], {}, 0, 0, []
+    news, d_samples = (None, None) if self.resampler is None else self._resample(part, finishing)
     for s in sorted(set(part) | set(int(x) for x in finishing)):
       st = self.slots[s]
-      new = len(part[s]) if s in part else 0
+      new = (len(part[s]) if s in part else 0) if news is None else news.get(s, 0)
       fin = s in finishing
       n = st.n + new
       f_new = max(frames_ready(n, self.hop, fin), st.f)
@@ -1060,7 +1381,7 @@ class StreamingFeatures:
       minfo[s] = (base, n, sample_base(f_new, self.hop), int(fin), rows, m, st.f, int(st.fresh))
       feed[s] = (src, new, st.n - base, 0)
       pairs += [(s, t) for t in range(st.f, f_new, 2)]
-      if new:
+      if new and d_samples is None:
         chunks.append(part[s])
       if self.stats is not None:
         count = m
@@ -1073,8 +1394,9 @@ class StreamingFeatures:
       src += new
     table = np.concatenate([minfo.reshape(-1), feed.reshape(-1), np.asarray(pairs, dtype=np.int32).reshape(-1)]).astype(np.int32)
     d_table = torch.from_numpy(table).pin_memory().to(self.device, non_blocking=True)
-    samples = np.concatenate(chunks) if chunks else np.zeros(1, np.float32)
-    d_samples = torch.from_numpy(samples).pin_memory().to(self.device, non_blocking=True)
+    if d_samples is None:
+      samples = np.concatenate(chunks) if chunks else np.zeros(1, np.float32)
+      d_samples = torch.from_numpy(samples).pin_memory().to(self.device, non_blocking=True)
     fixed = self.stats is not None
     ref, mean, std = self.stats if fixed else (0.0, 0.0, 1.0)
     call('st_melspec_stream_f32', self._p(d_samples), self._p(d_table), len(pairs), S, self._p(self.plan), self.n_mels, self.hop, self.warm,
@@ -1145,9 +1467,12 @@ def _pcm_chunks(stream, samples_per_chunk):
 
 
 def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
-                 on_final=None, spot=None, on_hit=None, words=None):
+                 on_final=None, spot=None, on_hit=None, words=None, model_rate=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
-  ids so far)`` is called after every piece that produced new ids.  ``normalize='running'``: causal feature normalisation, live.
+  ids so far)`` is called after every piece that produced new ids.  ``model_rate``: the rate the model was trained at -- the pieces
+  are resampled to it on the device as they arrive (`StreamingFeatures(model_rate, source_rate=samplerate)`), and the seconds of
+  ``endpoint``, ``spot``, ``beam`` and the words' times count frames of hop / model_rate seconds; the seconds of the partials stay
+  those of the audio.  None: no resampling, the features run at ``samplerate`` with a 10 ms frame assumed, as before.  ``normalize='running'``: causal feature normalisation, live.
   ``normalize='file'``: the whole stream is read first and gets the features of the whole file (the statistics `transcribe` uses),
   which are then fed piece by piece -- not live; it yields what `transcribe --batch-size 1` yields and exists for comparison.
   ``beam`` (a `StreamBeam`): the ids are the beam search's -- at the end the whole-utterance search's result -- and
@@ -1161,6 +1486,9 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
   if normalize not in ('running', 'file'):
     raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
   ids, fed, last, finals = [], 0, [([], 0)], []
+  feature_rate, source = (samplerate, None) if model_rate is None else (int(model_rate), int(samplerate))
+  timing = {} if model_rate is None else dict(frame_rate=float(feature_rate) / hop)
+  ratio = float(feature_rate) / float(samplerate)
 
   def closed(r, slot):
     for u in r.finals[slot]:
@@ -1204,27 +1532,42 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     y = np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
     if len(y) <= N_FFT // 2:
       raise StreamError('too short: {} samples (the features need more than {})'.format(len(y), N_FFT // 2))
-    front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=16000, warm=1 + len(y) // hop, device=engine.device)
-    slot = front.open()
-    front.step({slot: y})
-    feats = front.finish(slot)
-    per = max(max(len(p) for p in pieces) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot, words=words)
+    if source is None:
+      front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=16000, warm=1 + len(y) // hop, device=engine.device)
+      slot = front.open()
+      front.step({slot: y})
+      feats = front.finish(slot)
+      total = len(y)
+    else:                                                        # the whole signal through the streaming resampler, piece by piece
+      from . import audio_io
+      total = audio_io.resample_lengths(len(y), source, feature_rate)[1]
+      if total <= N_FFT // 2:
+        raise StreamError('too short: {} samples at {} Hz (the features need more than {})'.format(total, feature_rate, N_FFT // 2))
+      front = StreamingFeatures(feature_rate, n_mels, 1, max_chunk_samples=16000, warm=1 + total // hop, device=engine.device,
+                                source_rate=source)
+      slot = front.open()
+      feats = [front.step({slot: p})[slot] for p in pieces]
+      feats = np.concatenate(feats + [front.finish(slot)])
+    per = max(int(max(len(p) for p in pieces) * ratio) // hop, 1)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot, words=words, **timing)
     rslot = rec.open()
     for at in range(0, len(feats), per):
-      feed(rec, rslot, feats[at:at + per], min((at + per) * hop, len(y)) / float(samplerate))
+      feed(rec, rslot, feats[at:at + per], min((at + per) * hop, total) / float(feature_rate))
     fed = len(y)
   else:
     max_piece = int(max_piece or 16000)
-    front = StreamingFeatures(samplerate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device)
+    if source is not None:                                       # a piece's outputs and a finish's flush in one pass
+      max_piece = int(max_piece * ratio) + 512
+    front = StreamingFeatures(feature_rate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device, source_rate=source)
     slot = front.open()
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot, words=words)
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot, words=words,
+                              **timing)
     rslot = rec.open()
     for p in pieces:
       p = np.asarray(p, np.float32)
       fed += len(p)
       feed(rec, rslot, front.step({slot: p})[slot], fed / float(samplerate))
-    if fed <= N_FFT // 2:
+    if source is None and fed <= N_FFT // 2:
       raise StreamError('too short: {} samples (the features need more than {})'.format(fed, N_FFT // 2))
     feed(rec, rslot, front.finish(slot), fed / float(samplerate))
   r = rec.finish(rslot)
@@ -1329,10 +1672,16 @@ def run_cli(flags):
       with contextlib.redirect_stdout(sys.stderr):
         model.restore(sess, flags.run_train_dir)
       extra = {}
+      model_rate = getattr(flags, 'model_rate', 'native')
+      model_rate = None if model_rate == 'native' else int(model_rate)
+      if model_rate is not None:
+        extra['model_rate'] = model_rate
       if spot is not None:
-        extra = dict(spot=spot, on_hit=lambda h: print(hit_line(h, rate), flush=True))
+        extra.update(spot=spot, on_hit=lambda h: print(hit_line(h, model_rate or rate), flush=True))
       if endpoint is not None:
         frame_s = 0.01 * int(np.prod([l.stride for l in model.engine.layers]))
+        if model_rate is not None:                               # the features' own frame: hop / rate
+          frame_s = 160.0 / model_rate * int(np.prod([l.stride for l in model.engine.layers]))
         on_final = lambda u: print('\n'.join(['utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s,
                                                                                  (u.last_speech + 1) * frame_s,
                                                                                  vocabulary.ids_to_sentence(u.ids))] +
