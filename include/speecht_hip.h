@@ -1105,6 +1105,43 @@ int st_ctc_beam_stream_step_pieces_bias(const float* logits, int pitch, int num_
                                         void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
                                         int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots);
 
+/* ---- N-best lists for the finals of live streams (csrc/ctc_beam.hip: ctc_beam_read_nbest_kernel).  The read-out of
+ * st_ctc_beam_stream_read_bias and the endpointed step of st_ctc_beam_stream_step_pieces_bias, each also writing, for every FINISHING
+ * read-out (limit >= 0: `finish`, or a final of an endpointed piece), the list "N-best lists from both beam searches" above defines:
+ * the list of st_ctc_beam_search_decode_nbest / _lm_nbest / _bias_nbest / _lm_bias_nbest on the utterance's rows alone -- the same
+ * ranking rules, n = min(n_best, entries alive), log_prob = (float)((double)final total + offset) -- bit for bit, however the rows were
+ * cut into steps.  An open stream's read-out writes no list.  Each takes the arguments of its `_bias` form, then the four below;
+ * `bias` and `roots` may both be NULL: the unbiased search with the records of st_ctc_beam_stream_state_bytes (one of them NULL is
+ * refused).  `result` and `tail` are written exactly as by the other forms; hypothesis 0 of a list is that top path.
+ *   n_best       1 <= n_best <= beam_width.
+ *   arena        DEVICE int32 [arena_words], arena_words >= 0: the records of one call, compact.  All live entries share the labels
+ *                below the stable_len the record stored BEFORE this read-out (the caller holds them: it has read every earlier
+ *                `tail`), so a hypothesis is stored as its labels from there on, as `tail` is, without a max_tail limit.  A record:
+ *                  {stream, piece, n, old stable_len, words of this record, 0}
+ *                  n pairs {length (the whole length in ids), log_prob (float bits)}, best first
+ *                  the n tails back to back, length_h - old stable_len labels each
+ *                piece: the index p of the piece (0 from st_ctc_beam_stream_read_nbest).  The records' order depends on arrival,
+ *                their content does not: sort by (piece, stream).
+ *   arena_used   DEVICE int32 [1]: zeroed by the entry point on `stream` ahead of the first launch (one more enqueue); every
+ *                finishing wave adds its record's words with one atomic and writes the record only if it lies inside
+ *                [0, arena_words) as a whole -- otherwise nothing of it -- so afterwards arena_used is the true demand and nothing
+ *                outside the arena is ever touched.  arena_used <= arena_words: the records lie back to back in [0, arena_used).
+ *                Otherwise the records that fit lie back to back from word 0 (once one reservation has passed the end, every later
+ *                one has too) and the words behind them are as the caller left them -- a caller that wants to tell where they end
+ *                fills the arena with a value no header has (word 5 of a header is 0) -- and the other lists are lost.  Worst case
+ *                per finishing read-out: 6 + n_best * (2 + longest tail).
+ * A bad argument returns the error without a launch.  The six entry points above keep their signatures, launches and records. */
+int st_ctc_beam_stream_read_nbest(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                                  float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                                  int32_t* tail, int max_tail, int32_t* result, void* stream, const st_bias_tables* bias,
+                                  const int32_t* roots, int n_best, int32_t* arena, int arena_words, int32_t* arena_used);
+int st_ctc_beam_stream_step_pieces_nbest(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                         int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                         float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                         void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
+                                         int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots,
+                                         int n_best, int32_t* arena, int arena_words, int32_t* arena_used);
+
 /* ---- Keyword spotting in live streams: lattices carried across steps, packed into waves (csrc/ctc_spot_stream.hip,
  * csrc/ctc_spot_stream_core.h; specification: tests/spot_stream_oracle.py; no reference counterpart).  Every step tells which of the
  * given keywords have just been said in each stream.  The rule is a pure function of a stream's logits rows, however they are cut

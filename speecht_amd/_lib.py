@@ -264,6 +264,15 @@ _SIGNATURES = {
     'st_ctc_beam_stream_step_pieces_bias': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                     c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... with the N-best lists of the finishing read-outs: the `_bias` arguments (bias and roots may be NULL), then n_best, the arena,
+    # its words and the counter
+    'st_ctc_beam_stream_read_nbest': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p]),
+    'st_ctc_beam_stream_step_pieces_nbest': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                     c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                                     c_void_p]),
     # word times and confidences of finals: a ring of logits rows per stream, the two lattices reading from it
     'st_stream_keep_rows': (c_int, [c_int, c_int]),
     'st_stream_keep_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),

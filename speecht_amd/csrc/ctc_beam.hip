@@ -1033,12 +1033,34 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
 //    searches.  An open stream reports entry 0's running total, which carries the credit lent to its open match.
 // result[s] = {length of the hypothesis, new stable_len, log-probability (float bits), status}; tail[s][i] = label stable_len_old + i
 // of the hypothesis for i < max_tail.
+//
+// NBEST (ctc_beam_read_nbest_kernel, st_ctc_beam_stream_read_nbest / _step_pieces_nbest): a FINISHING read-out (limit >= 0) also writes
+// the n = min(n_best, live entries) best final entries -- the list the whole-utterance N-best tail (write_nbest above) writes on the
+// same rows, ranked the same way: LM-free and unbiased the set's entries 0 .. n-1, else by (fin[] desc, rank in the set asc), counted
+// over LDS.  All live entries share the labels below the stored stable_len, which the host holds, so a hypothesis is its labels from
+// there on, as `tail` is -- but into a compact arena instead of a fixed [n_best][max_tail] block: the wave sums its record's words,
+// lane 0 reserves them with one atomicAdd on the launch's counter, and the record is written only if it lies inside the arena whole
+// (the counter advances either way: it reports the demand).  Record: {stream, piece, n, old stable_len, words of the record, 0}, n
+// pairs {length, log_prob bits}, the n tails back to back (length - old stable_len labels each).  One lane per hypothesis walks its
+// chain, two rounds above 64.  An open stream writes nothing.  NBEST = false compiles to the read-out above (its args are empty).
+template <bool NBEST>
+struct ReadNbestArgs {};
+template <>
+struct ReadNbestArgs<true> {
+  int n_best;             // 1 <= n_best <= W
+  int piece;              // stamped into the header
+  int* arena;             // [arena_words]
+  int arena_words;
+  int* used;              // the launch's counter: words asked for so far
+};
+constexpr int kNbestHeader = 6;
+
 constexpr int kNoState = 2;
-template <int MAXB, bool LM, bool BIAS = false>
-__global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict__ table, int W, char* __restrict__ state, long state_stride,
-                                                           const int2* __restrict__ node_pool, long pool_stride,
-                                                           int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma,
-                                                           BiasArgs<BIAS> bx = {}) {
+template <int MAXB, bool LM, bool BIAS, bool NBEST>
+__device__ __forceinline__ void beam_read(const int* __restrict__ table, int W, char* __restrict__ state, long state_stride,
+                                          const int2* __restrict__ node_pool, long pool_stride, int* __restrict__ tail, int max_tail,
+                                          int* __restrict__ result, const LmArgs& lma, BiasArgs<BIAS> bx,
+                                          const ReadNbestArgs<NBEST>& nx) {
   __shared__ float fin[MAXB];
   const int s = blockIdx.x, lane = threadIdx.x;
   const int count = table[4 * s + 1], limit = table[4 * s + 2], reset = table[4 * s + 3];
@@ -1101,10 +1123,12 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict
     }
   }
   const int stable = max((int)wave_min_u32((unsigned)lcp), stable0);
+  // (NBEST: a finishing read-out writes `tail` in the walk of hypothesis 0 below -- the same entry, the same chain, walked once)
+  const bool tail_here = !NBEST || limit < 0;
   if (lane == 0) {
     const int len0 = S.len[e0];
     int id = S.node[e0];
-    for (int p = len0 - 1; p >= stable0; --p) {
+    for (int p = len0 - 1; tail_here && p >= stable0; --p) {
       const int2 nd = nodes[id];
       if (p - stable0 < max_tail) tail[(long)s * max_tail + (p - stable0)] = nd.y;
       id = nd.x;
@@ -1115,6 +1139,98 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict
     res[3] = hdr->status;
     hdr->stable_len = stable;
   }
+  if constexpr (NBEST) {
+    if (limit < 0) return;                                         // (wave-uniform) an open stream has no list
+    __shared__ int rank_of[MAXB];
+    const int n = min(nx.n_best, nb);
+    if constexpr (LM || BIAS) {
+      // rank by (final total desc, rank in the set asc), by counting over LDS: entry e's place is the number of entries ahead of it
+      for (int e = lane; e < nb; e += 64) {
+        const float v = fin[e];
+        int r = 0;
+        for (int j = 0; j < nb; ++j) {
+          const float vj = fin[j];
+          r += (vj > v || (vj == v && j < e)) ? 1 : 0;
+        }
+        rank_of[r] = e;
+      }
+      __syncthreads();
+    }
+    // hypothesis h = lane + 64 k: its entry, its tail's length and the tail's place behind the pairs (a scan per round)
+    constexpr int ROUNDS = MAXB / 64;
+    int ent[ROUNDS], tlen[ROUNDS], toff[ROUNDS];
+    int tails = 0;
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {
+      const int h = lane + 64 * k;
+      ent[k] = 0;
+      tlen[k] = 0;
+      if (h < n) {
+        // (hypothesis 0 is the reported entry; a NaN total would leave places of rank_of unwritten: an entry of the set either way)
+        if constexpr (LM || BIAS) ent[k] = h == 0 ? e0 : min(max(rank_of[h], 0), nb - 1);
+        else ent[k] = h;
+        tlen[k] = max(S.len[ent[k]] - stable0, 0);
+      }
+      const int incl = wave_incl_scan_i32(tlen[k]);
+      toff[k] = tails + incl - tlen[k];
+      tails += __builtin_amdgcn_readlane(incl, 63);
+    }
+    const int words = kNbestHeader + 2 * n + tails;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(nx.used, words);
+    base = __builtin_amdgcn_readfirstlane(base);
+    // all of the record or nothing: every index into the arena below is base + (an offset < words), and only if the record fits
+    const bool fits = !(base < 0 || tails < 0 || words < 0 || (long)base + words > (long)nx.arena_words);
+    int* __restrict__ rec_out = nx.arena + (fits ? base : 0);
+    if (fits && lane == 0) {
+      rec_out[0] = s; rec_out[1] = nx.piece; rec_out[2] = n; rec_out[3] = stable0; rec_out[4] = words; rec_out[5] = 0;
+    }
+    const double offset = hdr->offset;
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {
+      const int h = lane + 64 * k;
+      if (h >= n || (!fits && h != 0)) continue;
+      const int e = ent[k], len = S.len[e];
+      float v;
+      if constexpr (LM || BIAS) v = fin[e];
+      else v = S.total[e];
+      if (fits) {
+        rec_out[kNbestHeader + 2 * h] = len;
+        rec_out[kNbestHeader + 2 * h + 1] = __float_as_int((float)((double)v + offset));
+      }
+      int* __restrict__ out = rec_out + kNbestHeader + 2 * n + toff[k];
+      int id = S.node[e];
+      const int lo = len - tlen[k];                                // stable0, or len when the tail is empty
+      for (int p = len - 1; p >= lo; --p) {
+        const int2 nd = nodes[id];
+        if (fits) out[p - lo] = nd.y;
+        // hypothesis 0 is the top path (the best total, ties to the lower rank: e0 above): its labels are `tail`, fit or not
+        if (h == 0 && p - lo < max_tail) tail[(long)s * max_tail + (p - lo)] = nd.y;
+        id = nd.x;
+      }
+    }
+  }
+}
+
+// the arena's counter back to 0 ahead of a call's read-outs: one more launch on the stream (a memset measured the same)
+__global__ void beam_zero_word_kernel(int* __restrict__ word) {
+  if (threadIdx.x == 0) *word = 0;
+}
+
+template <int MAXB, bool LM, bool BIAS = false>
+__global__ __launch_bounds__(64) void ctc_beam_read_kernel(const int* __restrict__ table, int W, char* __restrict__ state, long state_stride,
+                                                           const int2* __restrict__ node_pool, long pool_stride,
+                                                           int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma,
+                                                           BiasArgs<BIAS> bx = {}) {
+  beam_read<MAXB, LM, BIAS, false>(table, W, state, state_stride, node_pool, pool_stride, tail, max_tail, result, lma, bx, {});
+}
+
+template <int MAXB, bool LM, bool BIAS>
+__global__ __launch_bounds__(64) void ctc_beam_read_nbest_kernel(const int* __restrict__ table, int W, char* __restrict__ state,
+                                                                 long state_stride, const int2* __restrict__ node_pool, long pool_stride,
+                                                                 int* __restrict__ tail, int max_tail, int* __restrict__ result, LmArgs lma,
+                                                                 BiasArgs<BIAS> bx, ReadNbestArgs<true> nx) {
+  beam_read<MAXB, LM, BIAS, true>(table, W, state, state_stride, node_pool, pool_stride, tail, max_tail, result, lma, bx, nx);
 }
 
 }  // namespace
@@ -1503,12 +1619,32 @@ static void launch_beam_stream(const float* lp_rows, int num_classes, const int3
 // one launch of the read-out over all streams
 static void launch_beam_stream_read(const int32_t* table, int max_streams, int beam_width, bool lm, const LmArgs& lma, void* state,
                                     const void* pool, int max_frames, int32_t* tail, int max_tail, int32_t* result, hipStream_t s,
-                                    const BiasArgs<true, true>* sbx = nullptr) {
+                                    const BiasArgs<true, true>* sbx = nullptr, const ReadNbestArgs<true>* nx = nullptr) {
   const bool wide = beam_width > 64;
-  st::trace("ctc_beam_stream_read<%s%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", sbx ? ", bias" : "", beam_width,
-            max_streams);
   const long stride = (long)(sbx ? st_ctc_beam_stream_bias_state_bytes(beam_width, lm) : st_ctc_beam_stream_state_bytes(beam_width, lm));
   const long pool_stride = (long)(st_ctc_beam_stream_pool_bytes(max_frames, beam_width) / sizeof(int2));
+  if (nx) {
+    // the N-best read-out: the same eight record kinds, the unbiased ones with empty hotword arguments
+    st::trace("ctc_beam_stream_read_nbest<%s%s%s> beam=%d streams=%d n_best=%d piece=%d arena=%d", wide ? "wide" : "wave", lm ? ", lm" : "",
+              sbx ? ", bias" : "", beam_width, max_streams, nx->n_best, nx->piece, nx->arena_words);
+#define ST_LAUNCH_READ_NBEST(MAXB, LM, BIAS, BX)                                                                      \
+  hipLaunchKernelGGL((ctc_beam_read_nbest_kernel<MAXB, LM, BIAS>), dim3(max_streams), dim3(64), 0, s, table, beam_width, \
+                     static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
+                     tail, max_tail, result, lma, BX, *nx)
+    if (sbx) {
+      const BiasArgs<true>& bx = *sbx;
+      if (wide) { if (lm) ST_LAUNCH_READ_NBEST(128, true, true, bx); else ST_LAUNCH_READ_NBEST(128, false, true, bx); }
+      else { if (lm) ST_LAUNCH_READ_NBEST(64, true, true, bx); else ST_LAUNCH_READ_NBEST(64, false, true, bx); }
+    } else {
+      const BiasArgs<false> none{};
+      if (wide) { if (lm) ST_LAUNCH_READ_NBEST(128, true, false, none); else ST_LAUNCH_READ_NBEST(128, false, false, none); }
+      else { if (lm) ST_LAUNCH_READ_NBEST(64, true, false, none); else ST_LAUNCH_READ_NBEST(64, false, false, none); }
+    }
+#undef ST_LAUNCH_READ_NBEST
+    return;
+  }
+  st::trace("ctc_beam_stream_read<%s%s%s> beam=%d streams=%d", wide ? "wide" : "wave", lm ? ", lm" : "", sbx ? ", bias" : "", beam_width,
+            max_streams);
 #define ST_LAUNCH_READ(MAXB, LM)                                                                                      \
   hipLaunchKernelGGL((ctc_beam_read_kernel<MAXB, LM>), dim3(max_streams), dim3(64), 0, s, table, beam_width, \
                      static_cast<char*>(state), stride, reinterpret_cast<const int2*>(pool), pool_stride, \
@@ -1524,6 +1660,15 @@ static void launch_beam_stream_read(const int32_t* table, int max_streams, int b
   else { if (lm) ST_LAUNCH_READ(64, true); else ST_LAUNCH_READ(64, false); }
 #undef ST_LAUNCH_READ_BIAS
 #undef ST_LAUNCH_READ
+}
+
+// the list arguments of the N-best entry points (st_ctc_beam_stream_read_nbest / _step_pieces_nbest)
+static int beam_stream_nbest_args(const char* who, int beam_width, const ReadNbestArgs<true>* lists) {
+  ST_REQUIRE(lists->n_best >= 1 && lists->n_best <= beam_width, "%s: n_best must be 1..beam_width (%d), got %d", who, beam_width,
+             lists->n_best);
+  ST_REQUIRE(lists->arena && lists->used, "%s: null argument", who);
+  ST_REQUIRE(lists->arena_words >= 0, "%s: negative arena_words %d", who, lists->arena_words);
+  return ST_OK;
 }
 
 // the three entry points and their hotword-biased forms (`biased`: bias and roots are checked and the BIAS instantiations launched)
@@ -1558,7 +1703,7 @@ static int beam_stream_step(const char* who, const float* logits, int pitch, int
 static int beam_stream_read(const char* who, const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight,
                             float word_count_weight, float valid_word_count_weight, float oov_score, void* state, const void* pool,
                             int max_frames, int32_t* tail, int max_tail, int32_t* result, void* stream, bool biased,
-                            const st_bias_tables* bias, const int32_t* roots) {
+                            const st_bias_tables* bias, const int32_t* roots, const ReadNbestArgs<true>* lists = nullptr) {
   ST_REQUIRE(tail && result, "%s: null argument", who);
   ST_REQUIRE(max_tail >= 1, "%s: max_tail must be positive, got %d", who, max_tail);
   LmArgs lma;
@@ -1568,8 +1713,12 @@ static int beam_stream_read(const char* who, const int32_t* table, int max_strea
   BiasArgs<true, true> sbx{};
   if (biased)
     if (int e = beam_stream_bias_args(who, bias, roots, &sbx)) return e;
+  if (lists) {
+    if (int e = beam_stream_nbest_args(who, beam_width, lists)) return e;
+    hipLaunchKernelGGL(beam_zero_word_kernel, dim3(1), dim3(64), 0, st::as_stream(stream), lists->used);
+  }
   launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames, tail, max_tail, result,
-                          st::as_stream(stream), biased ? &sbx : nullptr);
+                          st::as_stream(stream), biased ? &sbx : nullptr, lists);
   return st::check_launch("ctc_beam_stream_read");
 }
 
@@ -1581,7 +1730,7 @@ static int beam_stream_step_pieces(const char* who, const float* logits, int pit
                                    void* lm, float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
                                    void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
                                    int max_tail, int32_t* result, void* stream, bool biased, const st_bias_tables* bias,
-                                   const int32_t* roots) {
+                                   const int32_t* roots, const ReadNbestArgs<true>* lists = nullptr) {
   if (int e = beam_stream_step_args(who, logits, pitch, num_classes, rows, n_rows, input_transform, lm)) return e;
   ST_REQUIRE(n_pieces >= 1, "%s: n_pieces must be positive, got %d", who, n_pieces);
   ST_REQUIRE(tail && result, "%s: null argument", who);
@@ -1598,7 +1747,10 @@ static int beam_stream_step_pieces(const char* who, const float* logits, int pit
     st::set_error("%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
     return ST_EWORKSPACE;
   }
+  if (lists)
+    if (int e = beam_stream_nbest_args(who, beam_width, lists)) return e;
   hipStream_t s = st::as_stream(stream);
+  if (lists) hipLaunchKernelGGL(beam_zero_word_kernel, dim3(1), dim3(64), 0, s, lists->used);
   float* lp_rows = reinterpret_cast<float*>(workspace);
   if (n_rows > 0)
     hipLaunchKernelGGL(logsoftmax_step_rows_kernel, dim3(st::ceil_div(n_rows, 4)), dim3(256), 0, s, logits, pitch, n_rows, num_classes,
@@ -1607,9 +1759,14 @@ static int beam_stream_step_pieces(const char* who, const float* logits, int pit
     const int32_t* table = pieces + (long)p * max_streams * 4;
     launch_beam_stream(lp_rows, num_classes, rows, table, n_rows, max_streams, beam_width, input_transform, lm != nullptr, lma, state, pool,
                        max_frames, s, biased ? &sbx : nullptr);
+    ReadNbestArgs<true> piece_lists{};
+    if (lists) {
+      piece_lists = *lists;
+      piece_lists.piece = p;
+    }
     launch_beam_stream_read(table, max_streams, beam_width, lm != nullptr, lma, state, pool, max_frames,
                             tail + (long)p * max_streams * max_tail, max_tail, result + (long)p * max_streams * 4, s,
-                            biased ? &sbx : nullptr);
+                            biased ? &sbx : nullptr, lists ? &piece_lists : nullptr);
   }
   return st::check_launch("ctc_beam_stream_step_pieces");
 }
@@ -1667,6 +1824,41 @@ int st_ctc_beam_stream_step_pieces_bias(const float* logits, int pitch, int num_
                                  max_streams, beam_width, input_transform, lm, lm_weight, word_count_weight, valid_word_count_weight,
                                  oov_score, state, pool, max_frames, workspace, workspace_bytes, tail, max_tail, result, stream, true, bias,
                                  roots);
+}
+
+// ... with the N-best list of every finishing read-out in a compact arena (ctc_beam_read_nbest_kernel).  bias and roots both NULL:
+// the unbiased record kind.
+static int nbest_kind(const char* who, const st_bias_tables* bias, const int32_t* roots, bool* biased) {
+  ST_REQUIRE((bias == nullptr) == (roots == nullptr), "%s: bias and roots must be given together, or both be null", who);
+  *biased = bias != nullptr;
+  return ST_OK;
+}
+
+int st_ctc_beam_stream_read_nbest(const int32_t* table, int max_streams, int beam_width, void* lm, float lm_weight, float word_count_weight,
+                                  float valid_word_count_weight, float oov_score, void* state, const void* pool, int max_frames,
+                                  int32_t* tail, int max_tail, int32_t* result, void* stream, const st_bias_tables* bias,
+                                  const int32_t* roots, int n_best, int32_t* arena, int arena_words, int32_t* arena_used) {
+  const char* who = "beam stream read (N best)";
+  bool biased = false;
+  if (int e = nbest_kind(who, bias, roots, &biased)) return e;
+  const ReadNbestArgs<true> lists{n_best, 0, arena, arena_words, arena_used};
+  return beam_stream_read(who, table, max_streams, beam_width, lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score, state,
+                          pool, max_frames, tail, max_tail, result, stream, biased, bias, roots, &lists);
+}
+
+int st_ctc_beam_stream_step_pieces_nbest(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* pieces,
+                                         int n_pieces, int n_rows, int max_streams, int beam_width, int input_transform, void* lm,
+                                         float lm_weight, float word_count_weight, float valid_word_count_weight, float oov_score,
+                                         void* state, void* pool, int max_frames, void* workspace, size_t workspace_bytes, int32_t* tail,
+                                         int max_tail, int32_t* result, void* stream, const st_bias_tables* bias, const int32_t* roots,
+                                         int n_best, int32_t* arena, int arena_words, int32_t* arena_used) {
+  const char* who = "beam stream step pieces (N best)";
+  bool biased = false;
+  if (int e = nbest_kind(who, bias, roots, &biased)) return e;
+  const ReadNbestArgs<true> lists{n_best, 0, arena, arena_words, arena_used};
+  return beam_stream_step_pieces(who, logits, pitch, num_classes, rows, pieces, n_pieces, n_rows, max_streams, beam_width, input_transform,
+                                 lm, lm_weight, word_count_weight, valid_word_count_weight, oov_score, state, pool, max_frames, workspace,
+                                 workspace_bytes, tail, max_tail, result, stream, biased, bias, roots, &lists);
 }
 
 }  // extern "C"

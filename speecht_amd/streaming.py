@@ -33,6 +33,12 @@ With ``words=FinalWords(...)`` (and endpointing) every final also carries its wo
 rows into a ring per stream (csrc/stream_words.hip), and the pass that closes an utterance runs the lattices of ``engine.align`` and
 ``engine.word_confidence`` on the utterance's rows in that ring -- what those calls return on the rows alone, bit for bit.
 
+With ``beam=StreamBeam(nbest=N)`` every final also carries the N best hypotheses of its search -- `Utterance.nbest`, or
+`StepResult.nbest` after `finish` without endpointing: the list the whole-utterance N-best searches return on the utterance's rows
+alone, bit for bit, written by the read-out kernel into a compact arena that only a pass with finals copies
+(st_ctc_beam_stream_read_nbest / _step_pieces_nbest, `nbest.read_arena`) -- and ``rescore=`` re-ranks the lists of a pass together
+under a second language model before the words are aligned: two-pass decoding, as ``transcribe(nbest=, rescore=)`` does offline.
+
 With ``spot=StreamSpotter(...)`` every step also tells which of the given words and phrases have just been said in each stream
 (csrc/ctc_spot_stream.hip): the lattices of `speecht-cli spot` carried across steps, all keywords of a stream packed into a few
 waves, and a causal rule that lets a hit go once nothing better can replace it (include/speecht_hip.h,
@@ -168,10 +174,49 @@ class StreamBeam:
   second of audio); ``max_tail`` is the longest run of not yet final labels a step can report.  ``hotwords``: the search biased
   towards phrases, as ``engine.beam_search_decode_nbest(..., hotwords=)`` is (st_ctc_beam_stream_step_bias / _read_bias /
   _step_pieces_bias) -- a `hotwords.Hotwords`, which every stream then uses, or a `hotwords.HotwordSets`, of which every stream
-  names one when it is opened (`StreamingRecognizer.open(hotwords=index)`; set 0, the empty one, by default)."""
+  names one when it is opened (`StreamingRecognizer.open(hotwords=index)`; set 0, the empty one, by default).
+
+  ``nbest`` (an int in 1..beam_width): every final -- an `Utterance` of an endpointed stream, or what `finish` returns -- also carries
+  the N best hypotheses of its search (st_ctc_beam_stream_read_nbest / _step_pieces_nbest): the list
+  ``engine.beam_search_decode_nbest`` / ``lm_beam_search_decode_nbest`` returns on the utterance's rows alone, bit for bit, with the
+  parts `nbest.components` attaches.  ``rescore`` (needs ``nbest``): the dict of `inference.transcribe` -- 'language_model' (a
+  `LanguageModel` or a path) and optionally 'lm_weight', 'word_count_weight', 'valid_word_count_weight', with the defaults there --
+  re-ranks every list under that model (`nbest.rescored`), and the final's ids are then the re-ranked first hypothesis's.
+  ``nbest_words``: the capacity, in int32 words, of the arena the device writes a step's lists into (default: one final per stream
+  with ``nbest`` tails of ``max_tail`` labels); lists beyond it are lost and counted (`StepResult.nbest_lost`)."""
 
   def __init__(self, beam_width=None, lm=None, lm_weight=0.8, word_count_weight=0.0, valid_word_count_weight=2.3, oov_score=-1000.0,
-               input_transform='default', max_seconds=120.0, max_tail=256, hotwords=None):
+               input_transform='default', max_seconds=120.0, max_tail=256, hotwords=None, nbest=None, rescore=None, nbest_words=None):
+    # (the list options first: a bad combination is refused before a model is loaded)
+    width = int(beam_width) if beam_width else (100 if lm is not None else 16)
+    if nbest is None:
+      if rescore is not None:
+        raise StreamError('rescore applies to N-best lists (nbest=N)')
+      if nbest_words is not None:
+        raise StreamError('nbest_words sizes the arena of N-best lists (nbest=N)')
+    else:
+      if not isinstance(nbest, (int, np.integer)) or isinstance(nbest, bool) or not 1 <= nbest <= width:
+        raise StreamError('nbest must be an integer in 1..beam_width ({}), got {!r}'.format(width, nbest))
+      if nbest_words is not None and (not isinstance(nbest_words, (int, np.integer)) or isinstance(nbest_words, bool)
+                                      or not 0 <= nbest_words < 2 ** 31):
+        raise StreamError('nbest_words must be a number of int32 words, got {!r}'.format(nbest_words))
+      if rescore is not None:
+        if not isinstance(rescore, dict) or rescore.get('language_model') is None:
+          raise StreamError("rescore needs a 'language_model'")
+        unknown = set(rescore) - {'language_model', 'lm_weight', 'word_count_weight', 'valid_word_count_weight'}
+        if unknown:
+          raise StreamError('rescore: unknown keys {}'.format(sorted(unknown)))
+    self.nbest = None if nbest is None else int(nbest)
+    self.nbest_words = None if nbest_words is None else int(nbest_words)
+    self.rescore = None
+    if rescore is not None:
+      from .language_model import LanguageModel
+      lm2 = rescore['language_model']
+      shared = (float(word_count_weight), float(valid_word_count_weight)) if lm is not None else (0.0, 0.0)
+      self.rescore = dict(language_model=lm2 if isinstance(lm2, LanguageModel) else LanguageModel.load(lm2),
+                          lm_weight=float(rescore.get('lm_weight', lm_weight)),
+                          word_count_weight=float(rescore.get('word_count_weight', shared[0])),
+                          valid_word_count_weight=float(rescore.get('valid_word_count_weight', shared[1])))
     self.hotwords, self.default_set = None, 0
     if hotwords is not None:
       from .hotwords import Hotwords, HotwordSets
@@ -297,15 +342,19 @@ class Utterance:
   as `inference.transcribe(confidence=True)` shapes it) and ``words``, a list of {word, start, end[, confidence]} with times in seconds
   from the stream's start (without ``timestamps``: {word, confidence}).  A final without ids has ``words == []`` and empty spans; one
   with more than ``engine_decode.MAX_ALIGN_LABELS`` ids, or whose ids do not fit its rows (a beam hypothesis with adjacent repeats
-  can do that), has None for all four, as offline.  Without ``words`` -- and a field its `FinalWords` does not ask for -- None."""
+  can do that), has None for all four, as offline.  Without ``words`` -- and a field its `FinalWords` does not ask for -- None.
+
+  With ``StreamBeam(nbest=N)``: ``nbest``, the list of `nbest.Hypothesis` of the search on the utterance's rows, best first, with the
+  parts `nbest.components` attaches -- re-ranked (`nbest.rescored`) with ``StreamBeam(rescore=...)``, and ``ids`` / ``logp`` are then
+  its first hypothesis's.  None without the option, and when the list did not fit the arena (`StepResult.nbest_lost`)."""
   __slots__ = ('index', 'kind', 'start_frame', 'end_frame', 'first_speech', 'last_speech', 'ids', 'logp', 'greedy_ids', 'score',
-               'spans', 'align_score', 'confidence', 'words')
+               'spans', 'align_score', 'confidence', 'words', 'nbest')
 
   def __init__(self, index, kind, start_frame, end_frame, first_speech, last_speech, greedy_ids, score):
     self.index, self.kind, self.start_frame, self.end_frame = index, kind, start_frame, end_frame
     self.first_speech, self.last_speech = first_speech, last_speech
     self.greedy_ids, self.score, self.ids, self.logp = greedy_ids, score, greedy_ids, None
-    self.spans = self.align_score = self.confidence = self.words = None
+    self.spans = self.align_score = self.confidence = self.words = self.nbest = None
 
   def __repr__(self):
     return 'Utterance({}, {!r}, rows [{}, {}), speech {}..{}, ids={}, logp={}, score={})'.format(
@@ -413,13 +462,16 @@ class StepResult:
   lists the `Utterance`s the step closed, in order; ``hyp`` / ``stable`` / ``logp`` / ``score`` and ``open_ids[slot]`` (the greedy ids
   so far) then describe the utterance still open, and ``ids`` stays every new greedy id of the step.  With a spotter ``hits[slot]``
   lists the `Hit`s the step found, sorted by (end_frame, index), and ``hits_lost[slot]`` counts those that did not fit the
-  spotter's ``max_events`` (0 as a rule: raise ``max_events`` otherwise)."""
+  spotter's ``max_events`` (0 as a rule: raise ``max_events`` otherwise).  With ``StreamBeam(nbest=N)`` ``nbest_lost[slot]`` counts the
+  finals of the step whose list did not fit the arena (raise ``nbest_words`` otherwise) and, without endpointing, ``nbest[slot]`` is
+  None until `finish` fills it with the stream's list (`Utterance.nbest` describes it; ``hyp`` / ``logp`` follow a rescoring)."""
 
   def __init__(self):
     self.ids, self.logits, self.score = {}, {}, {}
     self.hyp, self.stable, self.logp = {}, {}, {}
     self.finals, self.open_ids = {}, {}
     self.hits, self.hits_lost = {}, {}
+    self.nbest, self.nbest_lost = {}, {}
 
 
 class StreamingRecognizer:
@@ -457,6 +509,13 @@ class StreamingRecognizer:
       if not isinstance(words, FinalWords):
         raise StreamError('words must be a FinalWords, got {!r}'.format(type(words).__name__))
       words.check(endpoint, self.num_classes, endpoint.frames(self.total_stride, self.num_classes, self.frame_rate)[3] if endpoint is not None else -1)
+    if beam and beam.nbest is not None:
+      # the arena of a pass's lists: by default one final per stream, `nbest` hypotheses with tails of max_tail labels each
+      from .nbest import ARENA_HEADER
+      self.nbest_words = (self.max_streams * (ARENA_HEADER + beam.nbest * (2 + beam.max_tail)) if beam.nbest_words is None
+                          else beam.nbest_words)
+      if self.nbest_words >= 2 ** 31:
+        raise StreamError('the arena of the N-best lists would hold {} words (nbest_words)'.format(self.nbest_words))
     L, S = len(self.layers), self.max_streams
     self.in_max = max_new_frames(self.geo, self.max_chunk)
     self.cap = [l.width + self.in_max[i] for i, l in enumerate(self.layers)]            # retained (< width) + new
@@ -493,7 +552,10 @@ class StreamingRecognizer:
         self.ring = torch.zeros(S * self.ring_cap * 32, dtype=torch.float32, device=dev)
       # (with a spotter, behind everything else: counts [S] | events [S][max_events][8])
       self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
-      self.dec_out = torch.zeros(self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0), dtype=torch.int32, device=dev)
+      # (with N-best lists, the last word: the words the step's lists asked for -- the arena itself is copied only when that is not 0)
+      self.nbest_at = self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0)
+      lists = bool(beam) and beam.nbest is not None
+      self.dec_out = torch.zeros(self.nbest_at + (1 if lists else 0), dtype=torch.int32, device=dev)
       if spot is not None:
         self.spot_hold = spot.frames(total_stride, self.frame_rate)
         self.spot_plan, self.spot_waves = spot.plan(self.num_classes)      # the host copy: the step reads its header
@@ -502,7 +564,7 @@ class StreamingRecognizer:
         state_bytes = int(lib.st_ctc_spot_stream_state_bytes(self.spot_plan.ctypes.data_as(ctypes.c_void_p)))
         self.spot_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
         self.spot_counts = self.dec_out[self.spot_at:self.spot_at + S]
-        self.spot_events = self.dec_out[self.spot_at + S:]
+        self.spot_events = self.dec_out[self.spot_at + S:self.nbest_at]
       self.ids = self.dec_out[:S * self.max_new]
       self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
       self.neg_sum = self.dec_out[S * self.max_new + S:S * self.max_new + 2 * S].view(torch.float32)
@@ -536,6 +598,12 @@ class StreamingRecognizer:
         self.beam_ws = torch.empty(self.beam_ws_bytes // 4, dtype=torch.float32, device=dev)
         self.beam_result = self.dec_out[greedy_words:greedy_words + self.n_pieces * 4 * S]
         self.beam_tail = self.dec_out[greedy_words + self.n_pieces * 4 * S:self.spot_at]
+        if beam.nbest is not None:
+          # filled with a value no header holds, and again after every pass that wrote: behind the records that fit lies no stale one
+          self.nbest_arena = torch.full((max(self.nbest_words, 1),), -1, dtype=torch.int32, device=dev)
+          self.nbest_used = self.dec_out[self.nbest_at:]
+          self._nbest_args = (self._bias or (None, None)) + (beam.nbest, ctypes.c_void_p(self.nbest_arena.data_ptr()), self.nbest_words,
+                                                             ctypes.c_void_p(self.nbest_used.data_ptr()))
       table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
       for i, l in enumerate(self.layers):
         table[2 * i] = self.windows[i].data_ptr()
@@ -550,6 +618,7 @@ class StreamingRecognizer:
     self._frames, self._stable, self._failed = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64), np.zeros(S, dtype=bool)
     self._hyp, self._logp = [[] for _ in range(S)], np.zeros(S, dtype=np.float32)
     self._open_ids = [[] for _ in range(S)]                      # endpointing: the greedy ids of the open utterance
+    self._set = np.zeros(S, dtype=np.int64)                      # the hotword set every slot was opened with (the lists' `bias`)
     self._info = np.zeros((L, S, 4), dtype=np.int32)             # {base, n, base, 0} of every stream between steps
     self.launches = 0            # kernels enqueued by the last pass (products count two: slices + epilogue)
 
@@ -573,6 +642,7 @@ class StreamingRecognizer:
     if sets is not None:
       with torch.cuda.stream(self.engine.stream):
         self.beam_roots[i:i + 1].fill_(sets.root(int(index)))
+    self._set[i] = int(index) if sets is not None else 0
     self._open[i], self._fresh[i], self._finished[i] = True, True, False     # the first step resets the slot's decoder state;
     self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
     self._info[:, i] = 0                                                       # [0, n) are never read
@@ -728,7 +798,11 @@ class StreamingRecognizer:
            S, bm.beam_width, self._transform, *lm_args, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
            self.beam_ws_bytes, sp, *self._bias)
       self.launches += 2 if len(rows[-1]) else 1
-      if fetch:
+      if fetch and bm.nbest is not None:
+        call('st_ctc_beam_stream_read_nbest', tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
+             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._nbest_args)
+        self.launches += 2                                        # the counter's reset and the read-out
+      elif fetch:
         call('st_ctc_beam_stream_read' + biased, tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
              self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._bias)
         self.launches += 1
@@ -754,6 +828,14 @@ class StreamingRecognizer:
           if count[k, -1]:
             result.logits[s].append(view[int(row0[k]):int(row0[k] + count[k, -1]), :self.num_classes].clone())
       words = self.dec_out.cpu().numpy()                         # the step's one wait
+    arena = used = None
+    if self.beam and self.beam.nbest is not None:
+      used, words = int(words[-1]), words[:-1]
+      for s in named.tolist():
+        result.nbest.setdefault(s, None)
+        result.nbest_lost.setdefault(s, 0)
+      if used:                                                    # a pass with finals: their lists, one copy of what was written
+        arena = self._fetch_arena(used)
     if self.spot is not None:
       me = self.spot.max_events
       found = read_hits(self.spot.keywords, words[self.spot_at + S:].reshape(S, me, 8), words[self.spot_at:self.spot_at + S], me)
@@ -767,11 +849,11 @@ class StreamingRecognizer:
       result.ids[s] += ids[s, :counts[s]].tolist()
       result.score[s] = float(score[s])
     if self.endpoint is not None:
-      return self._read_endpointed(words, named.tolist(), fin, result)
+      return self._read_endpointed(words, named.tolist(), fin, result, arena, used)
     if self.beam:
       g = S * self.max_new + 2 * S
       res, tail = words[g:g + 4 * S].reshape(S, 4), words[g + 4 * S:].reshape(S, self.beam.max_tail)
-      failed = None
+      failed, listed, unwanted = None, [], set()
       for k, s in enumerate(named.tolist()):
         if read[k]:
           length, stable, old = int(res[s, 0]), int(res[s, 1]), int(self._stable[s])
@@ -780,11 +862,16 @@ class StreamingRecognizer:
             why = ('status {}'.format(int(res[s, 3])) if res[s, 3] != 0 else
                    '{} labels are not final yet, max_tail = {}'.format(length - old, self.beam.max_tail))
             failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
+            unwanted.add((0, s))                                  # (if it was finishing, the device wrote its record all the same)
             continue
+          if fin[k] and used is not None:
+            listed.append((s, (0, s), self._hyp[s][:old], None))
           self._hyp[s] = self._hyp[s][:old] + tail[s, :length - old].tolist()
           self._stable[s] = length if fin[k] else stable           # a finished stream's hypothesis is final as a whole
           self._logp[s] = res[s, 2:3].view(np.float32)[0]
         result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
+      if listed:
+        self._final_lists(arena, used, listed, result, unwanted)
       if failed is not None:
         failed.result = result                                    # the other streams' results of this step
         raise failed
@@ -801,13 +888,17 @@ class StreamingRecognizer:
          ptr(self.ep_events), ptr(self.ep_pieces), P, sp)
     if self.beam:
       bm = self.beam
-      call('st_ctc_beam_stream_step_pieces' + ('_bias' if self._bias else ''), ptr(self.logits), self.logits_pitch, self.num_classes,
+      name, extra = 'st_ctc_beam_stream_step_pieces' + ('_bias' if self._bias else ''), self._bias
+      if bm.nbest is not None:                                    # the finals' lists into the arena; one launch more (the counter's reset)
+        name, extra = 'st_ctc_beam_stream_step_pieces_nbest', self._nbest_args
+        self.launches += 1
+      call(name, ptr(self.logits), self.logits_pitch, self.num_classes,
            rows_ptr, ptr(self.ep_pieces), P, n_rows, S, bm.beam_width, self._transform, self._lm_handle, bm.lm_weight, bm.word_count_weight,
            bm.valid_word_count_weight, bm.oov_score, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
-           self.beam_ws_bytes, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._bias)
+           self.beam_ws_bytes, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *extra)
       self.launches += (1 if n_rows else 0) + 2 * P
 
-  def _read_endpointed(self, words, named, fin, result):
+  def _read_endpointed(self, words, named, fin, result, arena=None, used=None):
     """The host's part of an endpointed step, from the step's one copy: the events close utterances in order, each with the greedy ids
     up to its ``ids_end``; the pieces are walked in order -- a piece marked reset starts from an empty hypothesis, every read-out
     appends its tail above the stable length the one before it stored, and a piece with a limit is a final."""
@@ -820,7 +911,7 @@ class StreamingRecognizer:
       g += self.ep_words
       mt = self.beam.max_tail
       res, tail = words[g:g + P * S * 4].reshape(P, S, 4), words[g + P * S * 4:].reshape(P, S, mt)
-    failed, new_finals = None, []
+    failed, new_finals, listed, unwanted = None, [], [], set()
     for k, s in enumerate(named):
       closed, prev, last_kind = [], 0, 0
       for e in (events[s].tolist() if events[s, 0, 0] else ()):   # (most steps close nothing)
@@ -847,11 +938,15 @@ class StreamingRecognizer:
             why = ('status {}'.format(int(res[p, s, 3])) if res[p, s, 3] != 0 else
                    '{} labels are not final yet, max_tail = {}'.format(length - old, mt))
             failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
+            unwanted.update((q, s) for q in range(p, P))          # (the device wrote this final's record, and its later ones', all the same)
             break
-          self._hyp[s] = self._hyp[s][:old] + tail[p, s, :length - old].tolist()
+          head = self._hyp[s][:old]
+          self._hyp[s] = head + tail[p, s, :length - old].tolist()
           self._stable[s], self._logp[s] = stable, res[p, s, 2:3].view(np.float32)[0]
           if limit >= 0:                                          # a final: the whole-utterance search on its rows alone
             closed[at].ids, closed[at].logp = self._hyp[s], float(self._logp[s])
+            if used is not None:
+              listed.append((s, (p, s), head, closed[at]))
             at += 1
             self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
         if fin[k] and last_kind == 3:                             # what was open at the end held no speech: dropped like any discard
@@ -859,11 +954,61 @@ class StreamingRecognizer:
         result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
       result.finals[s] += closed
       new_finals += [(s, u) for u in closed]
+    if listed:                                                    # lists, then rescoring, then the words of the ids that are reported
+      self._final_lists(arena, used, listed, result, unwanted)
     if self.words is not None:
       self._final_words(new_finals)
     if failed is not None:
       failed.result = result
       raise failed
+
+  def _fetch_arena(self, used):
+    """The words a pass's lists wrote -- ``arena[:min(used, capacity)]``, the one additional copy (and wait) of a pass with finals -- and
+    the fill value back in their place, enqueued behind the copy."""
+    n = min(max(used, 0), self.nbest_words)
+    with torch.cuda.stream(self.engine.stream):
+      written = self.nbest_arena[:n]
+      host = written.cpu().numpy()
+      written.fill_(-1)
+    return host
+
+  def _final_lists(self, arena, used, listed, result, unwanted=()):
+    """The N-best lists of the finals a pass closed.  ``listed``: [(slot, (piece, slot), the ids the host holds below the record's stable
+    length, the `Utterance` or -- `finish` without endpointing -- None)].  The records of the arena become lists (`nbest.read_arena`), all
+    of them get their parts in one go (`nbest.components`: the first pass's model and weights, the slot's own hotword set), and with
+    ``rescore`` all are re-ranked together (`nbest.rescored`), the reported ids and log-probability becoming the first hypothesis's.  A
+    final whose record did not fit the arena keeps ``nbest = None`` and is counted in ``result.nbest_lost``.  ``unwanted``: the keys of
+    finishing read-outs the host gave up on (their streams have failed): their records are stepped over, so that one stream's failure
+    never costs the others their lists -- the pass still ends in that stream's `StreamError`, the others' results attached."""
+    from . import nbest as nb
+    bm = self.beam
+    found, _ = nb.read_arena(arena if arena is not None else np.zeros(0, np.int32), used if arena is not None else 0,
+                             {key: head for _, key, head, _ in listed}, skip=unwanted)
+    have = [f for f in listed if f[1] in found]
+    for slot, key, _, _ in listed:
+      if key not in found:
+        result.nbest_lost[slot] += 1
+    if not have:
+      return
+    hot = None
+    if bm.hotwords is not None:                                   # set 0 is the empty set: no bias
+      hot = [bm.hotwords.tables(int(self._set[slot])) if self._set[slot] else None for slot, _, _, _ in have]
+    lists = nb.components(self.engine, bm.lm, [found[key] for _, key, _, _ in have],
+                          (bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight), hotwords=hot)
+    if bm.rescore is not None:
+      r = bm.rescore
+      lists = nb.rescored(lists, self.engine, r['language_model'], r['lm_weight'], r['word_count_weight'], r['valid_word_count_weight'])
+    for (slot, _, _, utt), hyps in zip(have, lists):
+      if utt is not None:
+        utt.nbest = hyps
+        if bm.rescore is not None:
+          utt.ids, utt.logp = list(hyps[0]['ids']), float(hyps[0]['log_prob'])
+      else:
+        result.nbest[slot] = hyps
+        if bm.rescore is not None:
+          self._hyp[slot], self._logp[slot] = list(hyps[0]['ids']), hyps[0]['log_prob']
+          self._stable[slot] = len(self._hyp[slot])
+          result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(hyps[0]['log_prob'])
 
   def _final_words(self, finals):
     """The word times and confidences of the finals a pass closed, ``[(slot, Utterance)]``: one table (`final_jobs`), one upload, the
@@ -1467,7 +1612,7 @@ def _pcm_chunks(stream, samples_per_chunk):
 
 
 def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
-                 on_final=None, spot=None, on_hit=None, words=None, model_rate=None):
+                 on_final=None, spot=None, on_hit=None, words=None, model_rate=None, on_nbest=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``model_rate``: the rate the model was trained at -- the pieces
   are resampled to it on the device as they arrive (`StreamingFeatures(model_rate, source_rate=samplerate)`), and the seconds of
@@ -1481,7 +1626,9 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
   describe the utterance open at the time, and the first value returned is the list of `Utterance`s.
   ``words`` (a `FinalWords`, with ``endpoint``): every `Utterance` carries its words' times and / or confidences.
   ``spot`` (a `StreamSpotter`): ``on_hit(hit)`` is called for every `Hit` as its step finds it; hits a step could not hand back
-  (more than ``spot.max_events``) raise a RuntimeWarning."""
+  (more than ``spot.max_events``) raise a RuntimeWarning.
+  ``beam`` with ``nbest``: with ``endpoint`` every `Utterance` carries its list; without, ``on_nbest(hypotheses)`` is called once at
+  the end with the stream's list (None if it was lost), and the ids returned are its first hypothesis's after any rescoring."""
   hop = 160
   if normalize not in ('running', 'file'):
     raise StreamError('normalize must be running or file, got {!r}'.format(normalize))
@@ -1576,6 +1723,8 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     closed(r, rslot)
     return finals, fed / float(samplerate)
   if beam:
+    if on_nbest and rslot in r.nbest:
+      on_nbest(r.nbest[rslot])
     return r.hyp[rslot], fed / float(samplerate)
   ids.extend(r.ids[rslot])
   return ids, fed / float(samplerate)
@@ -1605,6 +1754,40 @@ def final_word_lines(path, utterance):
   return out
 
 
+def lists_of(flags):
+  """The N-best options of `StreamBeam` the flags of `speecht-cli stream` ask for ({} without --nbest): ``nbest`` and, with
+  --rescore-language-model, ``rescore`` with the weights `transcribe` gives it (--rescore-lm-weight, else --lm-weight; the word-count
+  weights of the first pass).  Refuses (StreamError) --nbest without a beam search or outside 1..the beam width, and the rescoring
+  flags without what they apply to; loads nothing."""
+  nbest, path = getattr(flags, 'nbest', None), getattr(flags, 'rescore_language_model', None)
+  if nbest is None:
+    if path is not None or hasattr(flags, 'rescore_lm_weight'):
+      raise StreamError('--rescore-language-model and --rescore-lm-weight apply with --nbest only')
+    return {}
+  if hasattr(flags, 'rescore_lm_weight') and path is None:
+    raise StreamError('--rescore-lm-weight applies with --rescore-language-model only')
+  model = getattr(flags, 'language_model', None)
+  biased = getattr(flags, 'hotwords', None) is not None or bool(getattr(flags, 'hotword', None))
+  if not (model or getattr(flags, 'beam_width', 0) or biased):
+    raise StreamError('--nbest needs a beam search (--beam-width, --language-model or hotwords)')
+  beam = getattr(flags, 'beam_width', 0) or (100 if model else 16)
+  if not 1 <= nbest <= beam:
+    raise StreamError('--nbest must lie in 1..the beam width ({}), got {}'.format(beam, nbest))
+  out = dict(nbest=int(nbest))
+  if path is not None:
+    out['rescore'] = dict(language_model=path, lm_weight=getattr(flags, 'rescore_lm_weight', flags.lm_weight),
+                          word_count_weight=flags.word_count_weight, valid_word_count_weight=flags.valid_word_count_weight)
+  return out
+
+
+def nbest_lines(path, hyps):
+  """The lines `speecht-cli stream --nbest` prints for a list, in the format of `transcribe --nbest`:
+  path<TAB>rank<TAB>log_prob<TAB>text for ranks 1..n (none for a list that was lost)."""
+  from . import vocabulary
+  return ['{}\t{}\t{:.4f}\t{}'.format(path, rank, h['log_prob'], vocabulary.ids_to_sentence(h['ids']))
+          for rank, h in enumerate(hyps or [], 1)]
+
+
 def spotter_of(flags):
   """The `StreamSpotter` the flags of `speecht-cli stream` ask for (None without --keywords / --keyword): the keywords of the file,
   then those given one by one, duplicates dropped in order."""
@@ -1632,7 +1815,7 @@ def run_cli(flags):
   the phrases) the transcripts are the beam search's and a partial line is "seconds<TAB>hypothesis so far<TAB>number of its
   leading characters that are final".  With --endpoint the stream is cut into utterances: the partial lines describe the utterance that
   is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
-  speech) -- with --timestamps / --confidence followed by a line per word (`final_word_lines`) --, and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
+  speech) -- with --nbest followed by a line per hypothesis (`nbest_lines`, re-ranked with --rescore-language-model, the final's transcript then being the first one's), with --timestamps / --confidence followed by a line per word (`final_word_lines`) --, and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
   "start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame" (`hit_line`) as soon as its step has found it, between the other lines;
   hits a step could not hand back are a warning on stderr.  Creates no train / data / log directory."""
   import contextlib
@@ -1659,7 +1842,7 @@ def run_cli(flags):
       # a stream's length is not known when it starts: an hour of node pool unless the file says less
       beam = dict(beam_width=flags.beam_width or None, lm=lm, lm_weight=flags.lm_weight, word_count_weight=flags.word_count_weight,
                   valid_word_count_weight=flags.valid_word_count_weight, input_transform=flags.beam_input or 'default', max_seconds=3600.0,
-                  hotwords=hot)
+                  hotwords=hot, **lists_of(flags))
     if flags.path == '-':
       rate = int(flags.sample_rate)
       per = max(int(rate * flags.chunk_ms / 1000.0), 1)
@@ -1685,9 +1868,12 @@ def run_cli(flags):
         on_final = lambda u: print('\n'.join(['utt\t{}\t{:.2f}\t{:.2f}\t{}'.format(u.index, u.first_speech * frame_s,
                                                                                  (u.last_speech + 1) * frame_s,
                                                                                  vocabulary.ids_to_sentence(u.ids))] +
-                                             final_word_lines(flags.path, u)), flush=True)
+                                             nbest_lines(flags.path, u.nbest) + final_word_lines(flags.path, u)), flush=True)
         extra.update(endpoint=endpoint, on_final=on_final, words=words)
+      closing = []
       if beam:
+        if beam.get('nbest') and endpoint is None:                # the stream's list, behind the closing line
+          extra['on_nbest'] = lambda hyps: closing.extend(nbest_lines(flags.path, hyps))
         if flags.path != '-':
           beam['max_seconds'] = len(samples) / float(rate) + 1.0
         partial = lambda seconds, ids, stable: print('{:.2f}\t{}\t{}'.format(seconds, vocabulary.ids_to_sentence(ids), stable), flush=True)
@@ -1701,5 +1887,5 @@ def run_cli(flags):
   if endpoint is not None:
     print('{}\t{}'.format(flags.path, ' '.join(vocabulary.ids_to_sentence(u.ids) for u in ids)), flush=True)
     return 0
-  print('{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids)), flush=True)
+  print('\n'.join(['{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids))] + closing), flush=True)
   return 0
