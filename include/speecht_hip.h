@@ -1196,6 +1196,65 @@ int st_ctc_spot_stream_host(const float* logits, int pitch, int num_classes, con
                             int max_streams, const void* plan, double threshold, int hold, void* state, int32_t* events,
                             int max_events, int32_t* counts);
 
+/* ---- Following a known script in live streams: one long alignment lattice per stream, carried across steps in tiles
+ * (csrc/ctc_follow_stream.hip, csrc/ctc_follow_core.h; specification: tests/follow_oracle.py; no reference counterpart).  Every step
+ * tells where in its script each stream's speaker is now and which words have just been reached.  The rule is a pure function of a
+ * stream's logits rows, however they are cut into steps and whatever the other streams do.
+ *
+ * A following stream has a script l of L ids, 1 <= L <= max_labels, ids 0 .. num_classes - 2, blank = num_classes - 1.  Its lattice
+ * is st_ctc_align_f32's: U = 2L+1 states, v_0(u) = ly_0(class(u)) for u < 2 and -inf otherwise, v_t(u) = al_cell(v_{t-1}(u),
+ * v_{t-1}(u-1), v_{t-1}(u-2), skip only between different labels, ly_t(class(u))) (csrc/ctc_align_core.h), ly_t the double ln-softmax
+ * row csrc/ctc_align_softmax.h forms (same arithmetic, same butterfly order), t the stream's ABSOLUTE output frame since its last
+ * reset (int32).  No back-pointers are kept.  After frame t:
+ *   1. b_t = max_u v_t(u), c_t the LOWEST state attaining it, c_t = -1 if b_t = -inf;
+ *   2. pos_t = (c_t + 1) >> 1, the labels the best state has entered (0 for c_t <= 0);
+ *   3. g_t = g_{t-1} + max_c ly_t(c), g_{-1} = 0, double adds in frame order; fit_t = b_t - g_t <= 0: how far the script's best
+ *      reading lies below the greedy reading of the same frames, and so whether the speaker is on script at all;
+ *   4. m_t = min(pos_{t-K+1} .. pos_t), frames before 0 counting as 0, K = confirm frames, 1 <= K <= 16: the cursor of a Viterbi filter
+ *      jumps back and forth on noise; the sliding minimum asks for K frames of agreement without depending on step boundaries;
+ *   5. the words are the maximal runs of ids other than the space, word j beginning at label a_j (word_starts, increasing): word j is
+ *      REACHED at the first frame t with m_t >= a_j + 1, its event {j, t}.  Several words may be reached at one frame; they are emitted
+ *      in word order, each once;
+ *   6. end_score_t = v_t(al_end_state(U, v_t(U-1), v_t(U-2))): what st_ctc_align_long_f32 returns as the score of rows 0 .. t, -inf
+ *      while the script does not fit.
+ * Rows at or past the table's limit are not consumed; nothing is flushed when a stream finishes.  Endpointing neither sees nor
+ * resets the follower.
+ *
+ * st_ctc_follow_stream_state_bytes(max_labels): bytes of one stream's state, a multiple of 16 (a header of 128 bytes, then two
+ *   columns of 896 NB + 128 doubles, NB = ceil((2 max_labels + 1) / 896)); 0 unless 1 <= max_labels <= 28671.  state holds max_streams
+ *   of them, 16-byte aligned; any content before a stream's first step, which carries reset = 1 and makes the 128 column elements
+ *   below state 0 -inf.  A run leaves its new column in the second buffer and its last launch copies it over the first: between
+ *   steps both hold the same, and a state's bytes depend on the stream's rows alone.
+ * st_ctc_follow_stream_ws(max_rows, max_labels, max_streams): bytes of the workspace (16-byte aligned) for steps of at most max_rows
+ *   rows in all: max_rows * 32 * 8 + max_streams * 64 * NB * 16 + max_streams * 32 + 256.
+ * st_ctc_follow_stream_step: logits, pitch, rows and table as st_ctc_greedy_stream takes them ({first row, rows, limit or -1, reset}).
+ *   script_ids / script_offsets [max_streams + 1] and word_starts / word_offsets [max_streams + 1]: DEVICE CSR arrays over the slots,
+ *   owned by the caller; a slot with an empty script sits out (status 2), one whose script is longer than max_labels is not followed
+ *   (status 1) -- neither reads or writes its state.  max_stream_rows: the most rows any one stream has in this step (the host knows
+ *   it; the tables live on the device): the step is cut into ceil(max_stream_rows / 64) runs, at least one; a stream with more rows
+ *   loses them (status 4).  One softmax launch, then per run the tile kernel (one wave per (state block, stream)) and the read-out;
+ *   enqueues only, never allocates.  Bad arguments return ST_EINVAL and enqueue nothing.
+ *   events  int32 [max_streams][max_events][2] = {word, frame}, in order, 8-byte aligned.  Beyond max_events the surplus is not
+ *           written; nothing is written outside the buffers.
+ *   result  int32 [max_streams][16] = {frames consumed, c of the last frame (-1 before the first), status, the TRUE number of this
+ *           step's events, fit (double bits lo, hi; -inf before the first frame), end_score (lo, hi), words reached so far, 0 ...},
+ *           written for every slot.
+ *   trace   NULL, or int32 [n_rows]: c_t of every consumed row, at the row's index in the launch.
+ * st_ctc_follow_stream_host: the same on HOST pointers with plain loops over the whole lattice, without tiles: results and state
+ *   bit-identical, which cross-checks the halo.  No GPU. */
+size_t st_ctc_follow_stream_state_bytes(int max_labels);
+size_t st_ctc_follow_stream_ws(int max_rows, int max_labels, int max_streams);
+int st_ctc_follow_stream_step(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                              int max_rows, int max_stream_rows, int max_streams, const int32_t* script_ids,
+                              const int32_t* script_offsets, const int32_t* word_starts, const int32_t* word_offsets, int max_labels,
+                              int confirm, void* state, int32_t* events, int max_events, int32_t* result, int32_t* trace,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_follow_stream_host(const float* logits, int pitch, int num_classes, const int32_t* rows, const int32_t* table, int n_rows,
+                              int max_rows, int max_stream_rows, int max_streams, const int32_t* script_ids,
+                              const int32_t* script_offsets, const int32_t* word_starts, const int32_t* word_offsets, int max_labels,
+                              int confirm, void* state, int32_t* events, int max_events, int32_t* result, int32_t* trace,
+                              void* workspace, size_t workspace_bytes);
+
 /* st_melspec_stream_f32: the mel front end, one step for all streams (csrc/melspec.hip).  Frame t needs samples t * hop - 256 ...
  * t * hop + 255, reflected at the start of the stream and, at the end, once the stream is finished; every stream's sample tail stays
  * in `state` (st_melspec_stream_state_bytes; any content before a stream's first step, which carries reset = 1).  Frames are

@@ -293,6 +293,15 @@ _SIGNATURES = {
                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'st_ctc_spot_stream_host': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int,
                                         c_void_p, c_void_p, c_int, c_void_p]),
+    # following a known script in live streams: scripts and word starts as device CSR arrays over the slots
+    'st_ctc_follow_stream_state_bytes': (c_size_t, [c_int]),
+    'st_ctc_follow_stream_ws': (c_size_t, [c_int, c_int, c_int]),
+    'st_ctc_follow_stream_step': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
+    'st_ctc_follow_stream_host': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_size_t]),
     'st_spec_augment_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
                                     c_int, _T3P, c_void_p, c_void_p]),
     'st_spec_augment_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,

@@ -454,6 +454,113 @@ def read_hits(keywords, events, counts, max_events):
   return out
 
 
+class ScriptFollower:
+  """Following a known script in the streams of a `StreamingRecognizer` (st_ctc_follow_stream_step; the rule: include/speecht_hip.h,
+  tests/follow_oracle.py): a stream opened with ``open(script=...)`` reports after every step where in its script the speaker is
+  (`StepResult.follow`) and which words have just been reached (`StepResult.reached`).  The script's alignment lattice is carried
+  across steps in tiles, so a script may be long: ``max_labels`` ids per stream (1 .. 28 671; the state of a stream is two columns
+  of that many label and blank states in double).  A word counts as reached once the best state has stayed at or behind its first
+  character for ``confirm`` seconds (1 .. 16 output frames: the cursor of a Viterbi filter jumps on noise); the 0.06 s default is a
+  guess, not tuned on data.  A step hands back at most ``max_events`` reached words per stream, the rest is counted in
+  `StepResult.reached_lost`.  ``trace``: every step also returns the best state of each of its rows (``follow[slot]['trace']``).
+  ``space_id``: the class that separates words ('auto': 27 with the 29 classes a-z ' space blank, none otherwise; -1: none -- the
+  script is one word).  Exact start and end times of the words are `speecht-cli align --segment`'s, on the recording."""
+
+  def __init__(self, max_labels=16384, confirm=0.06, max_events=64, trace=False, space_id='auto'):
+    if not isinstance(max_labels, (int, np.integer)) or isinstance(max_labels, bool) or not 1 <= max_labels <= 28671:
+      raise StreamError('following: max_labels must lie in 1..28671, got {!r}'.format(max_labels))
+    self.max_labels = int(max_labels)
+    self.confirm = float(confirm)
+    if not (np.isfinite(self.confirm) and self.confirm > 0):
+      raise StreamError('following: confirm must be a positive number of seconds, got {!r}'.format(confirm))
+    if not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool) or max_events < 1:
+      raise StreamError('following: max_events must be a positive integer, got {!r}'.format(max_events))
+    self.max_events, self.trace = int(max_events), bool(trace)
+    if space_id != 'auto' and (not isinstance(space_id, (int, np.integer)) or space_id < -1):
+      raise StreamError('following: space_id must be \'auto\', -1 or a class index, got {!r}'.format(space_id))
+    self.space_id = space_id
+
+  def frames(self, total_stride, frame_rate=None):
+    """``confirm`` in output frames, counted as `StreamSpotter.frames` counts ``hold``: rounded up, at least 1; more than 16 is
+    refused.  ``frame_rate``: feature frames per second (None: the 10 ms hop)."""
+    per_second = 100.0 if frame_rate is None else float(frame_rate)
+    k = max(int(np.ceil(self.confirm * per_second / total_stride - 1e-9)), 1)
+    if k > 16:
+      raise StreamError('following: confirm = {} s is {} output frames, at most 16 are kept'.format(self.confirm, k))
+    return k
+
+  def space(self, num_classes):
+    space = (27 if num_classes == 29 else -1) if self.space_id == 'auto' else int(self.space_id)
+    if space >= num_classes - 1:
+      raise StreamError('following: space_id {} is no label of a model with {} classes'.format(space, num_classes))
+    return space
+
+  def script(self, script, num_classes):
+    """A text (`vocabulary.sentence_to_ids` after lower-casing) or a list of ids -> (ids, the first label index of every word,
+    the words as texts).  Refuses an empty script, one without a word, one beyond ``max_labels`` and ids the model has no label
+    for."""
+    from . import vocabulary
+    if isinstance(script, str):
+      try:
+        ids = vocabulary.sentence_to_ids(script)
+      except Exception as e:
+        raise StreamError('following: the script has a character outside the vocabulary ({})'.format(e))
+    else:
+      try:
+        ids = [int(i) for i in script]
+      except (TypeError, ValueError):
+        raise StreamError('following: a script is a text or a list of ids, got {!r}'.format(type(script).__name__))
+    if not ids:
+      raise StreamError('following: the script is empty')
+    if len(ids) > self.max_labels:
+      raise StreamError('following: the script has {} ids, max_labels = {}'.format(len(ids), self.max_labels))
+    if min(ids) < 0 or max(ids) > num_classes - 2:
+      raise StreamError('following: the script has an id outside the model\'s labels 0..{}'.format(num_classes - 2))
+    space = self.space(num_classes)
+    starts = [i for i, l in enumerate(ids) if l != space and (i == 0 or ids[i - 1] == space)]
+    if not starts:
+      raise StreamError('following: the script has no word')
+    ends = [next((j for j in range(a, len(ids)) if ids[j] == space), len(ids)) for a in starts]
+    letter = (lambda i: vocabulary.id_to_letter(i)) if num_classes == vocabulary.SIZE + 1 else (lambda i: '<{}>'.format(i))
+    return ids, starts, [''.join(letter(i) for i in ids[a:e]) for a, e in zip(starts, ends)]
+
+
+class WordReached:
+  """A word of its script a followed stream has reached: its ``index`` among the script's words, its ``text`` and the output
+  ``frame`` (absolute, counted from the stream's start) at which the rule confirmed it."""
+  __slots__ = ('index', 'text', 'frame')
+
+  def __init__(self, index, text, frame):
+    self.index, self.text, self.frame = int(index), text, int(frame)
+
+  def __eq__(self, other):
+    return isinstance(other, WordReached) and (self.index, self.text, self.frame) == (other.index, other.text, other.frame)
+
+  def __repr__(self):
+    return 'WordReached({}, {!r}, frame {})'.format(self.index, self.text, self.frame)
+
+
+def read_follow(records, events, max_events, scripts, slots):
+  """The host's part of a following step: ``records`` int32 [S, 16] and ``events`` int32 [S, max_events, 2] as the device left them,
+  ``scripts`` per slot (ids, word starts, words) -> {slot: (dict frames / state / label / word / in_blank / fit / end_score /
+  complete / status, [WordReached], events lost)} for the ``slots`` asked for.  ``label``: the script's id index the best state
+  stands at or has last left (-1 before the first); ``word``: the index of the word that label belongs to or follows (-1 before the
+  first word); ``complete``: the end state is the best state."""
+  import bisect
+  heads = records[:, :4].tolist()                                # (one conversion for all streams: this runs in every step)
+  reals = np.ascontiguousarray(records[:, 4:8]).view(np.float64).tolist()
+  out = {}
+  for s in slots:
+    ids, starts, words = scripts[s]
+    (frames, c, status, count), (fit, end) = heads[s], reals[s]
+    label = (c - 1) >> 1 if c >= 1 else -1
+    state = dict(frames=frames, state=c, label=label, word=bisect.bisect_right(starts, label) - 1 if label >= 0 else -1,
+                 in_blank=c >= 0 and c % 2 == 0, fit=fit, end_score=end, complete=c >= 2 * len(ids) - 1, status=status)
+    reached = [WordReached(j, words[j], t) for j, t in events[s, :min(count, max_events)].tolist()] if count else []
+    out[s] = (state, reached, max(count - max_events, 0))
+  return out
+
+
 class StepResult:
   """What one `step` / `finish` produced: ``ids[slot]`` new label ids, ``logits[slot]`` new rows [r, C] (on request),
   ``score[slot]`` the running negative sum of the chosen logits.  With a beam search also ``hyp[slot]``, all ids of the best
@@ -464,7 +571,9 @@ class StepResult:
   lists the `Hit`s the step found, sorted by (end_frame, index), and ``hits_lost[slot]`` counts those that did not fit the
   spotter's ``max_events`` (0 as a rule: raise ``max_events`` otherwise).  With ``StreamBeam(nbest=N)`` ``nbest_lost[slot]`` counts the
   finals of the step whose list did not fit the arena (raise ``nbest_words`` otherwise) and, without endpointing, ``nbest[slot]`` is
-  None until `finish` fills it with the stream's list (`Utterance.nbest` describes it; ``hyp`` / ``logp`` follow a rescoring)."""
+  None until `finish` fills it with the stream's list (`Utterance.nbest` describes it; ``hyp`` / ``logp`` follow a rescoring).
+  With a `ScriptFollower`, for the streams opened with a script: ``follow[slot]`` where the speaker is (`read_follow`),
+  ``reached[slot]`` the `WordReached` of the step in order and ``reached_lost[slot]`` those beyond the follower's ``max_events``."""
 
   def __init__(self):
     self.ids, self.logits, self.score = {}, {}, {}
@@ -472,6 +581,7 @@ class StepResult:
     self.finals, self.open_ids = {}, {}
     self.hits, self.hits_lost = {}, {}
     self.nbest, self.nbest_lost = {}, {}
+    self.follow, self.reached, self.reached_lost = {}, {}, {}
 
 
 class StreamingRecognizer:
@@ -480,19 +590,25 @@ class StreamingRecognizer:
   ``open()`` -> slot; ``step({slot: features[t, C]})`` advances all named slots in one pass over the layers and returns the new
   ids per slot; ``finish(slot)`` flushes with the right padding; ``close(slot)`` frees the slot."""
 
-  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None, words=None, frame_rate=None):
+  def __init__(self, engine, max_streams, max_chunk_frames=64, beam=None, endpoint=None, spot=None, words=None, frame_rate=None,
+               follow=None):
     """``frame_rate``: feature frames per second, the features' sample rate / hop -- what turns the seconds of ``endpoint``, ``spot``,
     ``beam.max_seconds`` and the words' times into frames and back; None: 100, the 10 ms hop of 16 kHz audio.  ``words``: a `FinalWords` (needs ``endpoint``) -- every final then also carries its words' times and / or confidences
     (`Utterance.spans` / ``align_score`` / ``confidence`` / ``words``): one launch more per pass, and in a pass that closes an utterance
     one upload, the lattices' launches and a second wait.  None: nothing changes.  ``spot``: a `StreamSpotter` -- every step then also reports the keywords it has found (`StepResult.hits`), with or without
     a beam search and endpointing, whose results it does not change: one launch more per step (and the memset of its counts).
+    ``follow``: a `ScriptFollower` -- the streams opened with ``open(script=...)`` are followed through their scripts
+    (`StepResult.follow` / ``reached``), with or without the other options, whose results it does not change: one table upload at
+    `open`, and per pass the softmax launch and two launches per 64 rows of the longest stream; its record rides in the step's copy.
     ``beam``: a `StreamBeam` -- every step then also advances a beam search per stream (`StepResult.hyp` / ``stable`` /
     ``logp``); None: greedy decoding only.  ``endpoint``: an `Endpointing` -- the device cuts every stream into utterances
     (`StepResult.finals`) and restarts the decoders after each; a beam search's node pool then holds ``endpoint.max_utterance``
     seconds (``beam.max_seconds`` is ignored) and a stream may run for any length."""
     if max_streams < 1 or max_chunk_frames < 1:
       raise StreamError('max_streams and max_chunk_frames must be positive')
-    self.beam, self.endpoint, self.spot, self.words = beam, endpoint, spot, words
+    self.beam, self.endpoint, self.spot, self.words, self.follow = beam, endpoint, spot, words, follow
+    if follow is not None and not isinstance(follow, ScriptFollower):
+      raise StreamError('follow must be a ScriptFollower, got {!r}'.format(type(follow).__name__))
     self.engine, self.device = engine, engine.device
     self.max_streams, self.max_chunk = int(max_streams), int(max_chunk_frames)
     self.layers = engine.layers
@@ -553,7 +669,10 @@ class StreamingRecognizer:
       # (with a spotter, behind everything else: counts [S] | events [S][max_events][8])
       self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
       # (with N-best lists, the last word: the words the step's lists asked for -- the arena itself is copied only when that is not 0)
-      self.nbest_at = self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0)
+      self.spot_end = self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0)
+      # (with a follower, behind that from an even word on: records [S][16] | events [S][max_events][2] | with trace, c per row)
+      self.follow_at = self.spot_end + (self.spot_end & 1 if follow else 0)
+      self.nbest_at = self.follow_at + (S * (16 + 2 * follow.max_events) + (self.max_rows[-1] if follow.trace else 0) if follow else 0)
       lists = bool(beam) and beam.nbest is not None
       self.dec_out = torch.zeros(self.nbest_at + (1 if lists else 0), dtype=torch.int32, device=dev)
       if spot is not None:
@@ -565,6 +684,22 @@ class StreamingRecognizer:
         self.spot_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
         self.spot_counts = self.dec_out[self.spot_at:self.spot_at + S]
         self.spot_events = self.dec_out[self.spot_at + S:self.nbest_at]
+      if follow is not None:
+        if not 2 <= self.num_classes <= 32:
+          raise StreamError('following supports 2..32 classes, the engine has {}'.format(self.num_classes))
+        follow.space(self.num_classes)
+        self.follow_confirm = follow.frames(total_stride, self.frame_rate)
+        state_bytes = int(lib.st_ctc_follow_stream_state_bytes(follow.max_labels))
+        self.follow_state = torch.zeros(S * state_bytes // 8, dtype=torch.float64, device=dev)
+        self.follow_ws_bytes = int(lib.st_ctc_follow_stream_ws(self.max_rows[-1], follow.max_labels, S))
+        self.follow_ws = torch.empty(self.follow_ws_bytes // 8 + 1, dtype=torch.float64, device=dev)
+        at = self.follow_at
+        self.follow_result = self.dec_out[at:at + 16 * S]
+        self.follow_events = self.dec_out[at + 16 * S:at + S * (16 + 2 * follow.max_events)]
+        self.follow_trace = self.dec_out[at + S * (16 + 2 * follow.max_events):self.nbest_at] if follow.trace else None
+        self._scripts = [None] * S                                   # per slot (ids, word starts, words) or None
+        self._follow_frames = np.zeros(S, dtype=np.int64)            # rows each followed stream has consumed (for the trace)
+        self._set_scripts()
       self.ids = self.dec_out[:S * self.max_new]
       self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
       self.neg_sum = self.dec_out[S * self.max_new + S:S * self.max_new + 2 * S].view(torch.float32)
@@ -624,13 +759,31 @@ class StreamingRecognizer:
 
   # -- slots --
 
-  def open(self, hotwords=None):
-    """-> a free slot.  ``hotwords``: the index of the stream's phrase set in the beam search's `hotwords.HotwordSets` (default: the
+  def _set_scripts(self):
+    """The scripts of all slots as CSR arrays on the device: [script offsets S + 1 | word offsets S + 1 | ids | word starts], one
+    upload on the engine's stream (a slot without a script has an empty one and sits out)."""
+    S = self.max_streams
+    ids = [sc[0] if sc else [] for sc in self._scripts]
+    starts = [sc[1] if sc else [] for sc in self._scripts]
+    offs, woffs = np.cumsum([0] + [len(i) for i in ids]), np.cumsum([0] + [len(w) for w in starts])
+    flat = np.concatenate([offs, woffs, [i for l in ids for i in l], [0], [w for l in starts for w in l], [0]]).astype(np.int32)
+    self.follow_table = self._upload(flat, torch.int32)
+    base = self.follow_table.data_ptr()
+    at = [0, S + 1, 2 * (S + 1), 2 * (S + 1) + int(offs[-1]) + 1]
+    self._follow_ptrs = tuple(ctypes.c_void_p(base + 4 * a) for a in (at[2], at[0], at[3], at[1]))   # ids, offsets, starts, offsets
+
+  def open(self, hotwords=None, script=None):
+    """``script`` (with a `ScriptFollower`): the text, or the ids, the stream is to be followed through (`ScriptFollower.script`);
+    None: the stream is not followed.
+    -> a free slot.  ``hotwords``: the index of the stream's phrase set in the beam search's `hotwords.HotwordSets` (default: the
     one set when the search was given a single `Hotwords`, else set 0, the empty one); its root is written to the slot's entry of the
     device's roots on the engine's stream, ahead of the slot's first step."""
     sets = self.beam.hotwords if self.beam else None
     if hotwords is not None and sets is None:
       raise StreamError('open(hotwords={!r}): the recognizer has no beam search with hotwords'.format(hotwords))
+    if script is not None and self.follow is None:
+      raise StreamError('open(script=...): the recognizer has no ScriptFollower')
+    parsed = self.follow.script(script, self.num_classes) if script is not None else None
     if sets is not None:
       index = self.beam.default_set if hotwords is None else hotwords
       if not isinstance(index, (int, np.integer)) or isinstance(index, bool) or not 0 <= index < len(sets):
@@ -648,6 +801,9 @@ class StreamingRecognizer:
     self._info[:, i] = 0                                                       # [0, n) are never read
     self._frames[i], self._stable[i], self._failed[i], self._hyp[i], self._logp[i] = 0, 0, False, [], 0.0
     self._open_ids[i] = []
+    if self.follow is not None and (parsed is not None or self._scripts[i] is not None):
+      self._scripts[i], self._follow_frames[i] = parsed, 0
+      self._set_scripts()
     return i
 
   def close(self, slot):
@@ -673,6 +829,8 @@ class StreamingRecognizer:
       raise StreamError('fetch=False with endpointing: the utterances the step closes would be lost')
     if self.spot is not None and not fetch:
       raise StreamError('fetch=False with a spotter: the hits the step finds would be lost')
+    if self.follow is not None and not fetch:
+      raise StreamError('fetch=False with a follower: the words the step reaches would be lost')
     return self._run(feeds, (), return_logits, fetch)
 
   def finish(self, slot, return_logits=False):
@@ -702,6 +860,8 @@ class StreamingRecognizer:
         result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(self._logp[slot])
       if self.spot is not None:
         result.hits[slot], result.hits_lost[slot] = [], 0
+      if self.follow is not None and self._scripts[slot] is not None:
+        result.follow[slot], result.reached[slot], result.reached_lost[slot] = None, [], 0
       if return_logits:
         result.logits[slot] = []
     longest = max([a.shape[0] for a in arrays.values()] + [0])
@@ -814,6 +974,14 @@ class StreamingRecognizer:
            self.spot_plan.ctypes.data_as(ctypes.c_void_p), self.spot.threshold, self.spot_hold, ptr(self.spot_state), ptr(self.spot_events),
            self.spot.max_events, ptr(self.spot_counts), sp)
       self.launches += 2                                          # the memset of the counts and the lattices
+    if self.follow is not None:
+      # the scripts' lattices take the same rows through the host's table, as the spotter does: endpointing does not reset them
+      fw, longest = self.follow, int(count[:, -1].max()) if len(named) else 0
+      call('st_ctc_follow_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]),
+           self.max_rows[-1], longest, S, *self._follow_ptrs, fw.max_labels, self.follow_confirm,
+           ptr(self.follow_state), ptr(self.follow_events), fw.max_events, ptr(self.follow_result),
+           ptr(self.follow_trace) if fw.trace else None, ptr(self.follow_ws), self.follow_ws_bytes, sp)
+      self.launches += (1 if len(rows[-1]) else 0) + 2 * max(-(-longest // 64), 1)   # the softmax, then tiles and read-out per 64 rows
     # 4. the host's counters follow; nothing above waited
     self._n[named], self._e[named] = n_after, first + count
     self._total[named] += new
@@ -836,6 +1004,24 @@ class StreamingRecognizer:
         result.nbest_lost.setdefault(s, 0)
       if used:                                                    # a pass with finals: their lists, one copy of what was written
         arena = self._fetch_arena(used)
+    if self.follow is not None:
+      fw, at = self.follow, self.follow_at
+      rec = words[at:at + 16 * S].reshape(S, 16)
+      ev = words[at + 16 * S:at + S * (16 + 2 * fw.max_events)].reshape(S, fw.max_events, 2)
+      followed = read_follow(rec, ev, fw.max_events, self._scripts, [s for s in named.tolist() if self._scripts[s] is not None])
+      for k, s in enumerate(named.tolist()):
+        if s not in followed:
+          continue
+        state, reached, lost = followed[s]
+        if fw.trace:
+          took = state['frames'] - int(self._follow_frames[s])     # (rows at or past a finishing stream's limit are not consumed)
+          state['trace'] = (result.follow[s]['trace'] if result.follow.get(s) else []) + \
+              words[at + S * (16 + 2 * fw.max_events):][int(row0[k]):int(row0[k]) + took].tolist()
+        self._follow_frames[s] = state['frames']
+        result.follow[s] = state
+        result.reached[s] += reached
+        result.reached_lost[s] += lost
+      words = words[:self.spot_end]
     if self.spot is not None:
       me = self.spot.max_events
       found = read_hits(self.spot.keywords, words[self.spot_at + S:].reshape(S, me, 8), words[self.spot_at:self.spot_at + S], me)
@@ -1612,7 +1798,8 @@ def _pcm_chunks(stream, samples_per_chunk):
 
 
 def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_partial=None, max_piece=None, beam=None, endpoint=None,
-                 on_final=None, spot=None, on_hit=None, words=None, model_rate=None, on_nbest=None):
+                 on_final=None, spot=None, on_hit=None, words=None, model_rate=None, on_nbest=None, follow=None, script=None,
+                 on_reached=None, on_followed=None):
   """Recognise one stream of sample pieces (float32 arrays at ``samplerate``) -> (ids, seconds of audio).  ``on_partial(seconds,
   ids so far)`` is called after every piece that produced new ids.  ``model_rate``: the rate the model was trained at -- the pieces
   are resampled to it on the device as they arrive (`StreamingFeatures(model_rate, source_rate=samplerate)`), and the seconds of
@@ -1627,6 +1814,9 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
   ``words`` (a `FinalWords`, with ``endpoint``): every `Utterance` carries its words' times and / or confidences.
   ``spot`` (a `StreamSpotter`): ``on_hit(hit)`` is called for every `Hit` as its step finds it; hits a step could not hand back
   (more than ``spot.max_events``) raise a RuntimeWarning.
+  ``follow`` (a `ScriptFollower`) with ``script`` (a text or ids): the stream is followed through the script; ``on_reached(word)`` is
+  called for every `WordReached` as its step reports it, and ``on_followed(state)`` once at the end with the last
+  `StepResult.follow` entry; reached words a step could not hand back raise a RuntimeWarning.
   ``beam`` with ``nbest``: with ``endpoint`` every `Utterance` carries its list; without, ``on_nbest(hypotheses)`` is called once at
   the end with the stream's list (None if it was lost), and the ids returned are its first hypothesis's after any rescoring."""
   hop = 160
@@ -1646,6 +1836,14 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
       last[0] = ([], 0)
 
   def found(r, slot):
+    if follow is not None and slot in r.reached:
+      for w in r.reached[slot]:
+        if on_reached:
+          on_reached(w)
+      if r.reached_lost[slot]:
+        import warnings
+        warnings.warn('following: {} reached words of one step were lost (max_events = {})'.format(r.reached_lost[slot], follow.max_events),
+                      RuntimeWarning)
     if spot is None:
       return
     for h in r.hits[slot]:
@@ -1696,8 +1894,9 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
       feats = [front.step({slot: p})[slot] for p in pieces]
       feats = np.concatenate(feats + [front.finish(slot)])
     per = max(int(max(len(p) for p in pieces) * ratio) // hop, 1)
-    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot, words=words, **timing)
-    rslot = rec.open()
+    rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(per, 8), beam=beam, endpoint=endpoint, spot=spot, words=words, follow=follow,
+                              **timing)
+    rslot = rec.open(script=script)
     for at in range(0, len(feats), per):
       feed(rec, rslot, feats[at:at + per], min((at + per) * hop, total) / float(feature_rate))
     fed = len(y)
@@ -1708,8 +1907,8 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     front = StreamingFeatures(feature_rate, n_mels, 1, max_chunk_samples=max_piece, device=engine.device, source_rate=source)
     slot = front.open()
     rec = StreamingRecognizer(engine, 1, max_chunk_frames=max(max_piece // hop + 4, 8), beam=beam, endpoint=endpoint, spot=spot, words=words,
-                              **timing)
-    rslot = rec.open()
+                              follow=follow, **timing)
+    rslot = rec.open(script=script)
     for p in pieces:
       p = np.asarray(p, np.float32)
       fed += len(p)
@@ -1719,6 +1918,8 @@ def stream_audio(engine, pieces, samplerate, n_mels, normalize='running', on_par
     feed(rec, rslot, front.finish(slot), fed / float(samplerate))
   r = rec.finish(rslot)
   found(r, rslot)
+  if on_followed and r.follow.get(rslot) is not None:
+    on_followed(r.follow[rslot])
   if endpoint is not None:
     closed(r, rslot)
     return finals, fed / float(samplerate)
@@ -1801,6 +2002,35 @@ def spotter_of(flags):
   return StreamSpotter(keywords, threshold=getattr(flags, 'spot_threshold', None), hold=getattr(flags, 'spot_hold', 0.3))
 
 
+def follower_of(flags):
+  """The `ScriptFollower` and the script the flags of `speecht-cli stream` ask for ((None, None) without --script / --script-text):
+  the text of the file with its line ends and runs of blanks as single spaces, or the text given."""
+  path, text = getattr(flags, 'script', None), getattr(flags, 'script_text', None)
+  if path is None and text is None:
+    return None, None
+  if path is not None and text is not None:
+    raise StreamError('--script and --script-text exclude each other')
+  if path is not None:
+    with open(path) as f:
+      text = f.read()
+  text = ' '.join(text.split())
+  follower = ScriptFollower(max_labels=max(len(text), 1) if len(text) <= 28671 else 28671, confirm=getattr(flags, 'follow_confirm', 0.06))
+  follower.script(text, 29)                                      # (refused here, before a model is built)
+  return follower, text
+
+
+def reached_line(path, word, total_stride, hop, model_rate):
+  """The line `speecht-cli stream` prints per reached word: path<TAB>reached<TAB>index<TAB>word<TAB>time, the time being
+  frame * total_stride * hop / model_rate seconds."""
+  return '{}\treached\t{}\t{}\t{:.3f}'.format(path, word.index, word.text, word.frame * total_stride * hop / float(model_rate))
+
+
+def followed_line(path, state):
+  """The line `speecht-cli stream` prints at the end for a followed stream: path<TAB>followed<TAB>fit per frame<TAB>complete|open."""
+  per_frame = state['fit'] / state['frames'] if state['frames'] else float('nan')
+  return '{}\tfollowed\t{:.4f}\t{}'.format(path, per_frame, 'complete' if state['complete'] else 'open')
+
+
 def hit_line(hit, rate, duration=None):
   """The line `speecht-cli stream` prints per hit: start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame (seconds, nominal)."""
   from . import alignment
@@ -1817,7 +2047,9 @@ def run_cli(flags):
   is open, every final prints "utt<TAB>index<TAB>start<TAB>end<TAB>transcript" (seconds, from the first to behind the last row with
   speech) -- with --nbest followed by a line per hypothesis (`nbest_lines`, re-ranked with --rescore-language-model, the final's transcript then being the first one's), with --timestamps / --confidence followed by a line per word (`final_word_lines`) --, and the closing line joins the finals' transcripts with spaces.  With --keywords / --keyword every hit prints
   "start<TAB>end<TAB>keyword<TAB>score<TAB>score_per_frame" (`hit_line`) as soon as its step has found it, between the other lines;
-  hits a step could not hand back are a warning on stderr.  Creates no train / data / log directory."""
+  hits a step could not hand back are a warning on stderr.  With --script / --script-text the stream is followed through the given
+  text: every word prints "path<TAB>reached<TAB>index<TAB>word<TAB>time" (`reached_line`) as it is reached, and behind the closing
+  line comes "path<TAB>followed<TAB>fit per frame<TAB>complete|open" (`followed_line`).  Creates no train / data / log directory."""
   import contextlib
   import sys
   from . import transcription, vocabulary
@@ -1833,6 +2065,7 @@ def run_cli(flags):
     beam, endpoint, on_final = None, endpoint_of(flags), None
     spot = spotter_of(flags)
     words = words_of(flags)
+    follower, script = follower_of(flags)
     from . import hotwords
     hot = hotwords.from_flags(flags)
     # (hotwords need a beam search: as in `transcribe`, beam 16 unless --beam-width or --language-model says otherwise)
@@ -1854,13 +2087,18 @@ def run_cli(flags):
     with Session(flags.device) as sess:
       with contextlib.redirect_stdout(sys.stderr):
         model.restore(sess, flags.run_train_dir)
-      extra = {}
+      extra, closing = {}, []
       model_rate = getattr(flags, 'model_rate', 'native')
       model_rate = None if model_rate == 'native' else int(model_rate)
       if model_rate is not None:
         extra['model_rate'] = model_rate
       if spot is not None:
         extra.update(spot=spot, on_hit=lambda h: print(hit_line(h, model_rate or rate), flush=True))
+      if follower is not None:
+        stride = int(np.prod([l.stride for l in model.engine.layers]))
+        extra.update(follow=follower, script=script,
+                     on_reached=lambda w: print(reached_line(flags.path, w, stride, 160, model_rate or rate), flush=True),
+                     on_followed=lambda st: closing.append(followed_line(flags.path, st)))
       if endpoint is not None:
         frame_s = 0.01 * int(np.prod([l.stride for l in model.engine.layers]))
         if model_rate is not None:                               # the features' own frame: hop / rate
@@ -1870,7 +2108,6 @@ def run_cli(flags):
                                                                                  vocabulary.ids_to_sentence(u.ids))] +
                                              nbest_lines(flags.path, u.nbest) + final_word_lines(flags.path, u)), flush=True)
         extra.update(endpoint=endpoint, on_final=on_final, words=words)
-      closing = []
       if beam:
         if beam.get('nbest') and endpoint is None:                # the stream's list, behind the closing line
           extra['on_nbest'] = lambda hyps: closing.extend(nbest_lines(flags.path, hyps))
@@ -1885,7 +2122,7 @@ def run_cli(flags):
     print('stream: {}'.format(e), file=sys.stderr)
     return 1
   if endpoint is not None:
-    print('{}\t{}'.format(flags.path, ' '.join(vocabulary.ids_to_sentence(u.ids) for u in ids)), flush=True)
+    print('\n'.join(['{}\t{}'.format(flags.path, ' '.join(vocabulary.ids_to_sentence(u.ids) for u in ids))] + closing), flush=True)
     return 0
   print('\n'.join(['{}\t{}'.format(flags.path, vocabulary.ids_to_sentence(ids))] + closing), flush=True)
   return 0
