@@ -406,6 +406,48 @@ int st_ctc_align_long_f32(const float* logits, long frames, int classes, int row
 int st_ctc_align_long_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
                            int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- Forced alignment of transcripts that leave audio out: a wildcard label and a per-label fit ----
+ * st_ctc_align_wild_f32 and st_ctc_align_long_wild_f32 are st_ctc_align_f32 and st_ctc_align_long_f32 -- the same lattice and
+ * back-trace kernels, ties, end rule, fit rule, score, spans, workspace sizes (st_ctc_align_ws, st_ctc_align_long_ws) -- with two
+ * additions.  The float64 specification is tests/wildcard_align_oracle.py.
+ *
+ * The wildcard W is the id `classes`, one past the blank; ids are therefore in [0, classes - 1) or == classes, and
+ * 2 <= classes <= 31 (ST_EINVAL above): the ln-softmax rows are [32] wide and slot `classes`, -inf in the plain entry points,
+ * holds W's emission.  W is a label state like any other: it takes at least one frame, counts as one label in the fit rule
+ * frames >= L + adjacent repeats, and its class differs from every id, so the skip over the blank into it and out of it is
+ * allowed.  Its emission at frame t is the largest of the row's `classes` ln-softmax values, the blank included, plus
+ * wildcard_bias, in double: ly_t(W) = max_c ly_t(c) + wildcard_bias.  wildcard_bias is finite and <= 0 (ST_EINVAL otherwise).
+ * With a bias of 0 the wildcard ties with a label on every frame the greedy reading agrees with, and the tie rule hands such
+ * frames to the wildcard that follows; a negative bias is the price per frame of not reading the transcript.  The span of a
+ * wildcard is the stretch of audio the transcript leaves out.  Two ADJACENT wildcards are a bad argument: the host forms
+ * return ST_EINVAL; the device forms cannot read the labels where they validate, and, as for the range of the ids, the caller
+ * checks (engine.align does).  Without a wildcard among the labels the spans, states, score bits and status are those of the
+ * plain entry points, whatever the bias.
+ *
+ * fit (may be null; [label_offsets[B]] resp. [label_len] doubles): the best path gives label k of class c_k the frames [a, b);
+ * fit_k = sum over t = a .. b-1, in frame order, of ly_t(c_k) - max_c ly_t(c), in double: exactly 0 where the greedy reading
+ * spells the label on every one of its frames, negative otherwise.  For a wildcard fit_k = wildcard_bias * (b - a), one
+ * product.  Blank frames belong to no label.  The labels of an utterance with status != 0 get NaN.  The fit stage runs after
+ * the back-trace, on the rows still in the workspace: one pass turns slot `classes` of every row into the row's maximum, then
+ * one lane per label walks its span (a label forced over thousands of frames is a serial walk of that length).  With
+ * fit = null the stage is not launched.
+ *
+ * The host forms share the deciding arithmetic (csrc/ctc_align_core.h): identical spans, states, score bits, status and fit
+ * bits; they also check every id against 0 .. classes. */
+int st_ctc_align_wild_f32(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets,
+                          const int32_t* seq_lens, int max_label_len, double wildcard_bias, int32_t* spans, int32_t* states,
+                          float* score, int32_t* status, double* fit, void* workspace, size_t workspace_bytes, void* stream);
+int st_ctc_align_wild_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,
+                           const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, double wildcard_bias,
+                           int32_t* spans, int32_t* states, float* score, int32_t* status, double* fit, void* workspace,
+                           size_t workspace_bytes);
+int st_ctc_align_long_wild_f32(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                               double wildcard_bias, int32_t* spans, double* score, int32_t* status, double* fit, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int st_ctc_align_long_wild_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                                double wildcard_bias, int32_t* spans, double* score, int32_t* status, double* fit, void* workspace,
+                                size_t workspace_bytes);
+
 /* ---- Word confidences: exact CTC word posteriors of given labels (csrc/ctc_conf.hip) ----
  * Conventions of st_ctc_align_f32: logits [B, T', C] padded NWC, blank = C-1, labels CSR, labels up to 511 (max_label_len
  * picks the states-per-lane dispatch), seq_lens[b] frames are used, enqueues only, never allocates.  Here C <= 30 (two

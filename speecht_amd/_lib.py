@@ -4,7 +4,7 @@ There is deliberately NO fallback: if the HIP library is missing or a call fails
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_void_p
 
 from .build import LIB_PATH
 
@@ -123,6 +123,15 @@ _SIGNATURES = {
                                       c_size_t, c_void_p]),
     'st_ctc_align_long_host': (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_size_t]),
+    # the wildcard label and the per-label fit: the plain arguments plus `double wildcard_bias` and `double* fit`
+    'st_ctc_align_wild_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_align_wild_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    'st_ctc_align_long_wild_f32': (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    'st_ctc_align_long_wild_host': (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t]),
     'st_ctc_word_conf_ws': (c_size_t, [c_int, c_int, c_int, c_int]),
     'st_ctc_word_conf_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),

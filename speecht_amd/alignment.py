@@ -47,6 +47,37 @@ def word_spans(ids, spans):
   return [(vocabulary.ids_to_sentence(ids[a:b]), int(spans[a][0]), int(spans[b - 1][1])) for a, b in word_runs(ids)]
 
 
+WILDCARD = -1                         # engine_decode.WILDCARD (kept here so that this module imports without torch)
+WILDCARD_TOKEN = '*'                  # how a transcript writes it: a word of its own, outside the vocabulary
+WILDCARD_BIAS = -1.0                  # engine_decode.WILDCARD_BIAS: nats per frame, a guess that nobody has tuned on data
+
+
+def wild_word_runs(ids, space_id=vocabulary.SPACE_ID):
+  """`word_runs` for ids that may hold WILDCARD: a wildcard ends a word like a space and is never part of one
+  -> (word runs, indices of the wildcards)."""
+  ids = list(ids)
+  runs = word_runs([space_id if i == WILDCARD else i for i in ids], space_id)
+  return runs, [k for k, i in enumerate(ids) if i == WILDCARD]
+
+
+def wild_word_spans(ids, spans):
+  """`word_spans` for ids that may hold WILDCARD -> (words as (word, first frame, end frame), gaps as (first frame, end frame)
+  of every wildcard: the stretches of audio the transcript leaves out)."""
+  ids = list(ids)
+  runs, stars = wild_word_runs(ids)
+  return ([(vocabulary.ids_to_sentence(ids[a:b]), int(spans[a][0]), int(spans[b - 1][1])) for a, b in runs],
+          [(int(spans[k][0]), int(spans[k][1])) for k in stars])
+
+
+def word_fits(ids, spans, fit):
+  """The per-label fit of `engine.align(fit=True)` grouped into the words of `wild_word_runs`: for every word the sum of its
+  labels' fits over the frames those labels hold (blank frames inside the word belong to no label) -- nats per frame, 0 where
+  the greedy reading of the audio spells the word, the more negative the less the audio says it."""
+  runs, _ = wild_word_runs(ids)
+  return [float(sum(float(fit[k]) for k in range(a, b))) / max(sum(int(spans[k][1]) - int(spans[k][0]) for k in range(a, b)), 1)
+          for a, b in runs]
+
+
 def confident_words(ids, confidence):
   """The JSON form without times: [{word, confidence}], ``confidence`` one probability per word of `word_runs`."""
   ids = list(ids)
@@ -95,18 +126,28 @@ def concat_frame_seconds(frame_edges, segments, segment_frames, sample_rate, pad
   return out
 
 
-def timed_words(ids, spans, sample_rate, duration=None, chars=False, confidence=None, concat=None):
+def timed_words(ids, spans, sample_rate, duration=None, chars=False, confidence=None, concat=None, fit=None, gaps=False):
   """The JSON form: [{word, start, end}] in seconds (``chars``: of the single characters, as {char, start, end});
   ``confidence`` (one probability per word): each word also carries `confidence`.  ``concat``: (segments, segment_frames,
-  pad_seconds) of an entry whose spans are in concatenated frames -- the times then come from `concat_frame_seconds`."""
+  pad_seconds) of an entry whose spans are in concatenated frames -- the times then come from `concat_frame_seconds`.
+  Ids that hold WILDCARD: a wildcard is no word and no character; ``gaps=True`` returns their [{start, end}] instead.
+  ``fit`` (the per-label fit of `engine.align`): each word also carries `fit` (`word_fits`)."""
   if concat is None:
     sec = end_sec = lambda f: round(frames_to_seconds(f, sample_rate, HOP_LENGTH, duration), 4)
   else:
     sec = lambda f: round(concat_frame_seconds([f], concat[0], concat[1], sample_rate, concat[2], duration)[0], 4)
     end_sec = lambda f: round(concat_frame_seconds([f], concat[0], concat[1], sample_rate, concat[2], duration, end=True)[0], 4)
+  ids = list(ids)
+  if gaps:
+    return [dict(start=sec(a), end=end_sec(b)) for a, b in wild_word_spans(ids, spans)[1]]
   if chars:
-    return [dict(char=c, start=sec(a), end=end_sec(b)) for c, a, b in char_spans(ids, spans)]
-  words = [dict(word=w, start=sec(a), end=end_sec(b)) for w, a, b in word_spans(ids, spans)]
+    keep = [k for k, i in enumerate(ids) if i != WILDCARD]
+    return [dict(char=c, start=sec(a), end=end_sec(b)) for c, a, b in char_spans([ids[k] for k in keep], [spans[k] for k in keep])]
+  words = [dict(word=w, start=sec(a), end=end_sec(b))
+           for w, a, b in (wild_word_spans(ids, spans)[0] if WILDCARD in ids else word_spans(ids, spans))]
+  if fit is not None:
+    for w, f in zip(words, word_fits(ids, spans, fit)):
+      w['fit'] = round(f, 6)
   if confidence is not None:
     for w, c in zip(words, confident_words(ids, confidence)):
       w['confidence'] = c['confidence']
@@ -152,9 +193,25 @@ def find_transcripts(paths, transcripts_file=None):
   return out
 
 
-def transcript_ids(text):
+def transcript_ids(text, wildcard=None, ends=False):
   """Ids of a transcript as the corpus reader makes them (vocabulary.sentence_to_ids after lower-casing); raises
-  TranscriptionError for a character outside the vocabulary."""
+  TranscriptionError for a character outside the vocabulary.
+
+  ``wildcard`` (a token such as WILDCARD_TOKEN, outside the vocabulary): where it stands as a word of its own between spaces
+  (or at an end of the text) it becomes the id WILDCARD, audio the transcript leaves out; anywhere else its characters are the
+  vocabulary error they always were.  ``ends``: a wildcard and a space before the text and a space and a wildcard after it,
+  unless the text has one there already -- a recording that opens and closes with words the transcript does not have."""
+  if wildcard is not None:
+    if not wildcard or ' ' in wildcard or all(c in vocabulary._TO_ID for c in wildcard.lower()):
+      raise ValueError('the wildcard token must be a word outside the vocabulary, not {!r}'.format(wildcard))
+    pieces = text.lower().split(' ')
+    if ends and any(pieces):
+      pieces = ([] if pieces[0] == wildcard.lower() else [wildcard.lower()]) + pieces + \
+          ([] if pieces[-1] == wildcard.lower() else [wildcard.lower()])
+    ids = []
+    for k, piece in enumerate(pieces):
+      ids += ([vocabulary.SPACE_ID] if k else []) + ([WILDCARD] if piece == wildcard.lower() else transcript_ids(piece))
+    return ids
   ids = vocabulary.sentence_to_ids(text.lower())
   bad = sorted({ch for ch, i in zip(text.lower(), ids) if not 0 <= i < vocabulary.SIZE})
   if bad:
@@ -163,7 +220,7 @@ def transcript_ids(text):
 
 
 def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22050, batch_size=1, timings=None, mask_padding=False,
-                confidence=False, segment=None):
+                confidence=False, segment=None, wildcard=None, fit=False, ends=False, wildcard_bias=None):
   """Align audio files with their transcripts -> a list, in ``paths`` order, of dicts
   {path, seconds, sample_rate, text, ids, spans, score, frames, error}.  ``transcripts``: {path: text} (`find_transcripts`) or
   a list parallel to ``paths``; None = no transcript.  ``error`` is the message for a file that is unreadable, too short, has no
@@ -179,9 +236,26 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
   ``segments`` ([{start, end}] in seconds of the file), ``segment_frames`` (the output frames of each; 0 for a segment too short
   for the features) and ``segment_pad`` (seconds of zeros in front of a gathered segment); ``spans`` are in concatenated frames,
   ``frames`` is their number, and `concat_frame_seconds` -- through `timed_words`, `result_json`, `print_words` -- maps them to
-  seconds of the file.  Word confidences are not computed on this path."""
+  seconds of the file.  Word confidences are not computed on this path.
+
+  ``wildcard`` (a token, usually WILDCARD_TOKEN; ``ends=True`` implies that one): transcripts that leave audio out.  The token
+  as a word of its own in a transcript becomes a wildcard label (`transcript_ids`; ``ids`` then holds WILDCARD there), which the
+  best path gives the audio the text does not have, at ``wildcard_bias`` nats per frame (default WILDCARD_BIAS = -1.0, a guess
+  that nobody has tuned on data).  ``ends=True`` puts one before and after every transcript: recordings that open and close with
+  words the text lacks.  Aligned entries gain ``gaps``: [{start, end}] in seconds of the file, one per wildcard -- and, with
+  ``fit=True``, ``fit`` (one float per id: `engine.align`) and ``word_fit`` (`word_fits`: nats per frame for every word; a very
+  negative one marks text the audio does not say).  With and without ``segment``; not with ``confidence`` (the word-posterior
+  lattices do not know the wildcard)."""
   if segment is not None and confidence:
     raise ValueError('align_files: word confidences are not available with segment')
+  if ends and wildcard is None:
+    wildcard = WILDCARD_TOKEN
+  wild = wildcard is not None or bool(fit) or wildcard_bias is not None
+  if wild and confidence:
+    raise ValueError('align_files: word confidences are not available with a wildcard or the fit')
+  if wild and wildcard_bias is None:
+    wildcard_bias = WILDCARD_BIAS
+  wild_args = dict(wildcard_bias=wildcard_bias, fit=True) if wild else {}
   texts = [transcripts.get(p) for p in paths] if isinstance(transcripts, dict) else list(transcripts)
   if len(texts) != len(paths):
     raise ValueError('align_files: {} paths and {} transcripts'.format(len(paths), len(texts)))
@@ -198,7 +272,7 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
       if text is None:
         raise transcription.TranscriptionError('{}: no transcript'.format(path))
       try:
-        entry['ids'] = transcript_ids(text)
+        entry['ids'] = transcript_ids(text, wildcard, ends) if wildcard is not None else transcript_ids(text)
       except transcription.TranscriptionError as e:
         raise transcription.TranscriptionError('{}: {}'.format(path, e)) from e
       entry['text'] = text.lower()
@@ -222,8 +296,9 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
       rows = [s for s in range(len(table)) if table[s, 0] == i]
       entry['segments'] = [dict(start=int(table[s, 1]) / float(rate), end=int(table[s, 2]) / float(rate)) for s in rows]
       entry['segment_pad'] = segmentation.pad_samples(segment, rate) / float(rate)
-      spans, score, status, frames = inference.align_long(engine, [feats[s] for s in rows if feats[s] is not None], entry['ids'],
-                                                          batch_size=batch_size, mask_padding=mask_padding)
+      res = inference.align_long(engine, [feats[s] for s in rows if feats[s] is not None], entry['ids'],
+                                 batch_size=batch_size, mask_padding=mask_padding, **wild_args)
+      spans, score, status, frames = res[:4]
       frames = iter(frames)
       entry['segment_frames'] = [next(frames) if feats[s] is not None else 0 for s in rows]
       entry['frames'] = sum(entry['segment_frames'])
@@ -232,11 +307,13 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
             entry['path'], len(entry['ids']), entry['frames'])
       else:
         entry['spans'], entry['score'] = spans, score
+        if wild:
+          _wild_entry(entry, res[-1], fit)
   elif ok:
     feats = transcription.device_features(signals, rates, feature_type, sample_rate, engine.device)
     t2 = time.perf_counter()
     res = inference.align(engine, feats, [e['ids'] for e in ok], batch_size=batch_size, mask_padding=mask_padding,
-                          confidence=confidence)
+                          confidence=confidence, **wild_args)
     spans, scores, status = res[:3]
     if confidence:
       for entry, c in zip(ok, res[3]):
@@ -249,11 +326,23 @@ def align_files(engine, paths, transcripts, feature_type='power', sample_rate=22
             entry['path'], len(entry['ids']), entry['frames'])
       else:
         entry['spans'], entry['score'] = sp, sc
+    if wild:
+      for entry, f in zip(ok, res[-1]):
+        if entry['spans'] is not None:
+          _wild_entry(entry, f, fit)
   else:
     t2 = t1
   if timings is not None:
     timings.update(decode_host=t1 - t0, features=t2 - t1, align=time.perf_counter() - t2)
   return results
+
+
+def _wild_entry(entry, fits, want_fit):
+  """The ``gaps`` (and with ``want_fit`` the ``fit`` / ``word_fit``) of an aligned entry of `align_files`."""
+  entry['gaps'] = timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds'], concat=concat_of(entry), gaps=True)
+  if want_fit:
+    entry['fit'] = [float(f) for f in fits]
+    entry['word_fit'] = word_fits(entry['ids'], entry['spans'], fits)
 
 
 MAX_LABELS = 511                      # engine_decode.MAX_ALIGN_LABELS (kept here so that this module imports without torch)
@@ -287,7 +376,9 @@ def result_json(entry, chars=False):
     out['words'] = confident_words(entry['ids'], conf['words'])
     return out
   out['words'] = timed_words(entry['ids'], entry['spans'], rate, dur, confidence=conf['words'] if conf is not None else None,
-                             concat=concat)
+                             concat=concat, fit=entry.get('fit'))
+  if entry.get('gaps') is not None:
+    out['gaps'] = entry['gaps']
   if chars:
     out['chars'] = timed_words(entry['ids'], entry['spans'], rate, dur, chars=True, concat=concat)
   if concat is not None:
@@ -303,10 +394,14 @@ def print_words(entry, file=None):
     words = confident_words(entry['ids'], conf['words'])
   else:
     words = timed_words(entry['ids'], entry['spans'], entry['sample_rate'], entry['seconds'],
-                        confidence=conf['words'] if conf is not None else None, concat=concat_of(entry))
+                        confidence=conf['words'] if conf is not None else None, concat=concat_of(entry), fit=entry.get('fit'))
+    # the gaps of a wildcard entry are lines of their own, in time order among the words: the token in the word's column
+    words = sorted(words + [dict(g, word=WILDCARD_TOKEN) for g in entry.get('gaps') or []], key=lambda w: (w['start'], w['end']))
   for w in words:
     times = '{:.3f}\t{:.3f}'.format(w['start'], w['end']) if 'start' in w else '-\t-'
     tail = '\t{:.4f}'.format(w['confidence']) if conf is not None else ''
+    if entry.get('fit') is not None:
+      tail += '\t{:.4f}'.format(w['fit']) if 'fit' in w else '\t-'
     print('{}\t{}\t{}{}'.format(entry['path'], times, w['word'], tail), file=file or sys.stdout, flush=True)
 
 
@@ -320,6 +415,21 @@ def segment_options(flags):
   return segmentation.SegmentOptions(threshold=getattr(flags, 'segment_threshold', d.threshold),
                                      min_silence=getattr(flags, 'min_silence', d.min_silence),
                                      max_segment=getattr(flags, 'max_segment', d.max_segment))
+
+
+def wildcard_options(flags):
+  """The wildcard / fit arguments of `align_files` from `speecht-cli align --wildcard [TOKEN] --wildcard-ends --wildcard-bias X
+  --fit` (the flags are absent from the namespace unless given; none of them: {} -- a `*` in a transcript stays a vocabulary
+  error)."""
+  token = getattr(flags, 'wildcard', None)
+  ends = bool(getattr(flags, 'wildcard_ends', False))
+  bias = getattr(flags, 'wildcard_bias', None)
+  fit = bool(getattr(flags, 'fit', False))
+  if token is None and (ends or bias is not None):
+    token = WILDCARD_TOKEN
+  if token is None and not fit:
+    return {}
+  return dict(wildcard=token, ends=ends, wildcard_bias=WILDCARD_BIAS if bias is None else float(bias), fit=fit)
 
 
 def run_cli(flags):
@@ -345,7 +455,7 @@ def run_cli(flags):
       model.restore(sess, flags.run_train_dir)
     results = align_files(model.engine, paths, transcripts, flags.feature_type, flags.sample_rate, flags.batch_size,
                           mask_padding=bool(getattr(flags, 'mask_padding', False)),
-                          confidence=bool(getattr(flags, 'confidence', False)), segment=segment)
+                          confidence=bool(getattr(flags, 'confidence', False)), segment=segment, **wildcard_options(flags))
   out = open(flags.output, 'w') if flags.output else None
   status = 0
   try:

@@ -15,7 +15,12 @@
 //     LDS and `states` / `spans` are then written by all lanes with plain vector stores.
 // st_ctc_align_ring_f32 (the finals of live streams, stream_ring.h) runs 2 and 3 as they are behind a ring-mapped form of 1: the rows of
 // its utterances come from a stream's ring through a job table, and the lattices ask that table for an utterance's frames.
+// st_ctc_align_wild_f32 (transcripts that leave audio out) runs 2 and 3 as they are too: the WILD form of 1 writes the emission of
+// the wildcard id C into slot C of every row, which the lattice indexes like any class, and a fit stage follows the back-trace:
+//  4. align_rowmax (ctc_align_softmax.h): slot C of every row := the row's largest value; align_fit: one LANE per label walks
+//     its span through those rows and writes one double (a wildcard: bias * frames, no walk).
 #include <algorithm>
+#include <cmath>
 
 #include "ctc_align_core.h"
 #include "ctc_align_softmax.h"
@@ -202,9 +207,26 @@ __global__ __launch_bounds__(64) void align_backtrace_kernel(const unsigned int*
   }
 }
 
-// the host form of one utterance; ly: [T][32] doubles, bp: [T][UP / 16] words, 2 bits per state
+// the fit of every label (st_ctc_align_wild_f32): lane k of block (x, b) has label 64 x + k of utterance b; NaN where refused
+__global__ __launch_bounds__(64) void align_fit_kernel(const double* __restrict__ ly, int T, int C, const int* __restrict__ label_ids,
+                                                       const int* __restrict__ label_off, const int* __restrict__ seq_lens,
+                                                       const int* __restrict__ status, const int* __restrict__ spans, double bias,
+                                                       double* __restrict__ fit) {
+  const int b = blockIdx.y;
+  const int L = label_off[b + 1] - label_off[b];
+  const bool bad = status[b] != 0;
+  // (the stride: a refused label may be longer than the max_label_len the grid was sized for)
+  for (int k = (int)blockIdx.x * 64 + (int)threadIdx.x; k < L; k += (int)gridDim.x * 64) {
+    const long n = (long)label_off[b] + k;
+    fit[n] = bad ? __builtin_nan("")
+                 : st::al_label_fit(ly + (long)b * T * CP, label_ids[n], C, spans[2 * n], spans[2 * n + 1], seq_lens[b], bias);
+  }
+}
+
+// the host form of one utterance; ly: [T][32] doubles, bp: [T][UP / 16] words, 2 bits per state.  `bias` (null: the plain form):
+// the wildcard id C may appear in lab and slot C of the rows carries its emission; `fit` (may be null): [L], as align_fit_kernel
 void align_host_one(const float* logits, int T, int C, const int* lab, int L, int Tb, int UP, int* sp, int* st_out,
-                    float* score, int* status, double* ly, uint32_t* bp) {
+                    float* score, int* status, double* ly, uint32_t* bp, const double* bias = nullptr, double* fit = nullptr) {
   const int U = 2 * L + 1, blank = C - 1, words = UP / 16;
   int rep = 0;
   if (U <= UP) for (int i = 1; i < L; ++i) rep += lab[i] == lab[i - 1];
@@ -213,6 +235,7 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
   if (bad) {
     *score = NEG_INF_F;
     for (int i = 0; i < 2 * L; ++i) sp[i] = -1;
+    if (fit) for (int i = 0; i < L; ++i) fit[i] = __builtin_nan("");
     if (st_out) for (int t = 0; t < T; ++t) st_out[t] = -2;
     return;
   }
@@ -226,6 +249,7 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
     for (int c = 0; c < CP; ++c) e[c] = c < C ? st::al_exp((double)row[c] - (double)m) : 0.0;
     const double s = st::al_row_sum(e);
     for (int c = 0; c < C; ++c) ly[(long)t * CP + c] = st::al_log_softmax(row[c], m, s);
+    if (bias) ly[(long)t * CP + C] = st::al_wild_emission(m, s, *bias);
   }
   auto cls = [&](int u) { return st::lattice_class(u, lab, blank); };
   double col[2][1024];                    // the lattice columns of frames t-1 and t (U <= 1023)
@@ -259,20 +283,30 @@ void align_host_one(const float* logits, int T, int C, const int* lab, int L, in
     next = s;
     if (t > 0) u = std::max(u - (int)((bp[(long)t * words + (u >> 4)] >> (2 * (u & 15))) & 3u), 0);
   }
+  if (fit) {
+    for (int t = 0; t < Tb; ++t) ly[(long)t * CP + C] = st::al_row_max(ly + (long)t * CP, C);
+    for (int k = 0; k < L; ++k) fit[k] = st::al_label_fit(ly, lab[k], C, sp[2 * k], sp[2 * k + 1], Tb, *bias);
+  }
 }
 
 // the three stages on B utterances of T rows each: `map` names a row for the softmax stage (which is also the gather), `lens` the
-// frames of an utterance for the lattice and the back-trace, which read the workspace only
+// frames of an utterance for the lattice and the back-trace, which read the workspace only.  `bias` (null: the plain form, and
+// always null for a ring): the WILD softmax stage; `fit` (with a bias only, may be null): the fit stage after the back-trace
 template <typename Map, typename Lens>
 void launch_align(const float* base, Map map, Lens lens, int B, int T, int C, int kpl, const int* label_ids, const int* label_offsets,
-                  int* spans, int* states, float* score, int* status, void* workspace, hipStream_t s) {
+                  int* spans, int* states, float* score, int* status, void* workspace, hipStream_t s, const double* bias = nullptr,
+                  double* fit = nullptr, int max_label_len = 0) {
   const size_t rows = (size_t)B * T;
   double* ly = reinterpret_cast<double*>(workspace);
   unsigned int* bp = reinterpret_cast<unsigned int*>(ly + rows * CP);
   int* end_state = reinterpret_cast<int*>(bp + rows * BPW);
   const dim3 grid((unsigned)((rows + 7) / 8));
   if constexpr (std::is_same<Map, RowMap>::value) {
-    hipLaunchKernelGGL(st::align_logsoftmax_kernel, grid, dim3(256), 0, s, base, map, B, T, C, ly);
+    if (bias) {
+      hipLaunchKernelGGL(st::align_logsoftmax_wild_kernel, grid, dim3(256), 0, s, base, map, B, T, C, *bias, ly);
+    } else {
+      hipLaunchKernelGGL(st::align_logsoftmax_kernel, grid, dim3(256), 0, s, base, map, B, T, C, ly);
+    }
   } else {
     hipLaunchKernelGGL(align_logsoftmax_ring_kernel, grid, dim3(256), 0, s, base, map, B, T, C, ly);
   }
@@ -282,6 +316,13 @@ void launch_align(const float* base, Map map, Lens lens, int B, int T, int C, in
     hipLaunchKernelGGL((align_backtrace_kernel<k(), Lens>), dim3(B), dim3(64), 0, s, bp, T, label_offsets, lens, end_state, status,
                        spans, states);
   });
+  if constexpr (std::is_same<Lens, st::DenseLens>::value) {
+    if (bias && fit) {
+      hipLaunchKernelGGL(st::align_rowmax_kernel, grid, dim3(256), 0, s, ly, (long)rows, C);
+      hipLaunchKernelGGL(align_fit_kernel, dim3((std::max(max_label_len, 1) + 63) / 64, B), dim3(64), 0, s, ly, T, C, label_ids, label_offsets,
+                         lens.lens, status, spans, *bias, fit);
+    }
+  }
 }
 
 }  // namespace
@@ -349,6 +390,61 @@ int st_ctc_align_host(const float* logits, int batch, int frames, int classes, c
     align_host_one(logits + (size_t)b * frames * classes, frames, classes, label_ids + label_offsets[b], L, seq_lens[b],
                    kpl * 64, spans + 2 * (size_t)label_offsets[b], states ? states + (size_t)b * frames : nullptr, score + b,
                    status + b, ly, bp);
+  }
+  return ST_OK;
+}
+
+// ---- the wildcard forms: the id `classes` is the wildcard, slot `classes` of the rows its emission (so classes <= 31) ----
+
+int st_ctc_align_wild_f32(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets,
+                          const int32_t* seq_lens, int max_label_len, double wildcard_bias, int32_t* spans, int32_t* states,
+                          float* score, int32_t* status, double* fit, void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(logits && logits->base && label_ids && label_offsets && seq_lens && spans && score && status && workspace,
+             "ctc_align_wild: null argument");
+  ST_REQUIRE(logits->batch > 0 && logits->batch <= 65535 && logits->frames > 0 && logits->halo >= 0 &&
+                 logits->t_pitch >= logits->halo + logits->frames,
+             "ctc_align_wild: bad logits shape");
+  ST_REQUIRE(logits->channels >= 2 && logits->channels <= CP - 1 && logits->c_pitch >= logits->channels,
+             "ctc_align_wild: num_classes must be 2..31 (the wildcard takes the row's slot after the blank)");
+  ST_REQUIRE(std::isfinite(wildcard_bias) && wildcard_bias <= 0.0, "ctc_align_wild: wildcard_bias must be finite and <= 0");
+  const int kpl = st::lattice_kpl(max_label_len);
+  ST_REQUIRE(kpl > 0, "ctc_align_wild: label length %d outside 0..511", max_label_len);
+  ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(logits->batch, logits->frames, max_label_len),
+             "ctc_align_wild: workspace too small");
+  ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_align_wild: workspace must be 16-byte aligned");
+  launch_align(logits->base, st::row_map(*logits), st::DenseLens{seq_lens}, logits->batch, logits->frames, logits->channels, kpl,
+               label_ids, label_offsets, spans, states, score, status, workspace, st::as_stream(stream), &wildcard_bias, fit,
+               max_label_len);
+  return st::check_launch("ctc_align_wild");
+}
+
+int st_ctc_align_wild_host(const float* logits, int batch, int frames, int classes, const int32_t* label_ids,
+                           const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len, double wildcard_bias,
+                           int32_t* spans, int32_t* states, float* score, int32_t* status, double* fit, void* workspace,
+                           size_t workspace_bytes) {
+  ST_REQUIRE(logits && label_ids && label_offsets && seq_lens && spans && score && status && workspace,
+             "ctc_align_wild: null argument");
+  ST_REQUIRE(batch > 0 && frames > 0, "ctc_align_wild: bad logits shape");
+  ST_REQUIRE(classes >= 2 && classes <= CP - 1,
+             "ctc_align_wild: num_classes must be 2..31 (the wildcard takes the row's slot after the blank)");
+  ST_REQUIRE(std::isfinite(wildcard_bias) && wildcard_bias <= 0.0, "ctc_align_wild: wildcard_bias must be finite and <= 0");
+  const int kpl = st::lattice_kpl(max_label_len);
+  ST_REQUIRE(kpl > 0, "ctc_align_wild: label length %d outside 0..511", max_label_len);
+  ST_REQUIRE(workspace_bytes >= st_ctc_align_ws(batch, frames, max_label_len), "ctc_align_wild: workspace too small");
+  ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "ctc_align_wild: workspace must be 16-byte aligned");
+  for (int b = 0; b < batch; ++b)
+    for (int i = label_offsets[b]; i < label_offsets[b + 1]; ++i) {
+      ST_REQUIRE(label_ids[i] >= 0 && label_ids[i] <= classes, "ctc_align_wild: label id %d outside 0..%d", label_ids[i], classes);
+      ST_REQUIRE(i == label_offsets[b] || label_ids[i] != classes || label_ids[i - 1] != classes,
+                 "ctc_align_wild: two adjacent wildcards in utterance %d", b);
+    }
+  double* ly = reinterpret_cast<double*>(workspace);
+  uint32_t* bp = reinterpret_cast<uint32_t*>(ly + (size_t)frames * CP);
+  for (int b = 0; b < batch; ++b) {
+    const int L = label_offsets[b + 1] - label_offsets[b];
+    align_host_one(logits + (size_t)b * frames * classes, frames, classes, label_ids + label_offsets[b], L, seq_lens[b],
+                   kpl * 64, spans + 2 * (size_t)label_offsets[b], states ? states + (size_t)b * frames : nullptr, score + b,
+                   status + b, ly, bp, &wildcard_bias, fit && L > 0 ? fit + label_offsets[b] : nullptr);
   }
   return ST_OK;
 }

@@ -114,4 +114,36 @@ ST_AL_HD int al_end_state(int U, double last_blank, double last_label) {
 // what `states` holds for lattice state u: the label index, -1 for a blank
 ST_AL_HD int al_state_label(int u) { return (u & 1) ? (u >> 1) : -1; }
 
+// ---- the wildcard entry points (st_ctc_align_wild_f32 / st_ctc_align_long_wild_f32) ----
+// The wildcard is the id C, one past the blank: its emission is slot C of the [32] row, the row's largest ln-softmax value plus
+// the bias.  al_log_softmax(m, m, s) IS that largest value: the row maximum of the logits gives the maximum of the row.
+ST_AL_HD double al_wild_emission(float m, double s, double bias) {
+#pragma clang fp contract(off)
+  return al_log_softmax(m, m, s) + bias;
+}
+
+// The largest of the C ln-softmax values of one row (a selection: the same bits in any order of the comparisons, up to the
+// sign of a zero, which the sum below does not see).
+ST_AL_HD double al_row_max(const double* row, int C) {
+  double m = row[0];
+  for (int c = 1; c < C; ++c) m = row[c] > m ? row[c] : m;
+  return m;
+}
+
+// The fit of one label of class c whose span is frames [a, b) of `rows` ([frames][32], slot C = the row maximum, written by the
+// row-maximum pass after the back-trace): sum in frame order of ly_t(c) - max_c ly_t(c), 0 where the greedy reading agrees on
+// every frame, negative otherwise.  A wildcard (c == C) has the closed form bias * frames; an id outside 0..C gives NaN.
+// a and b are clipped to [0, frames_hi] by the caller's choice of frames_hi, so spans a lattice of score -inf left unspecified
+// read no row outside the utterance.
+ST_AL_HD double al_label_fit(const double* rows, int c, int C, int a, int b, int frames_hi, double bias) {
+#pragma clang fp contract(off)
+  a = a < 0 ? 0 : a;
+  b = b > frames_hi ? frames_hi : b;
+  if ((unsigned)c > (unsigned)C) return __builtin_nan("");
+  if (c == C) return bias * (double)(b > a ? b - a : 0);
+  double f = 0.0;
+  for (int t = a; t < b; ++t) f = f + (rows[(long)t * AL_CP + c] - rows[(long)t * AL_CP + C]);
+  return f;
+}
+
 }  // namespace st

@@ -16,7 +16,11 @@
 //  4. align_long_backtrace: one wave.  Inside a 64-frame chunk the path descends at most 126 states below the state it enters
 //     the chunk's last frame in, so the 16 back-pointer words per row that end at that state's word hold the whole walk of the
 //     chunk: they are brought to LDS, walked there, and the spans are written by all lanes with plain vector stores.
+// st_ctc_align_long_wild_f32 (transcripts that leave audio out): the WILD form of 1 writes the emission of the wildcard id C into
+// slot C of every row, 2-4 run as they are, and the fit stage follows: align_rowmax (slot C := the row's largest value), then
+// align_long_fit, one LANE per label walking its span through the rows (a wildcard: bias * frames, no walk).
 #include <algorithm>
+#include <cmath>
 
 #include "ctc_align_core.h"
 #include "ctc_align_softmax.h"
@@ -184,6 +188,15 @@ __global__ __launch_bounds__(64) void align_long_backtrace_kernel(const unsigned
   }
 }
 
+// the fit of every label (st_ctc_align_long_wild_f32), after align_rowmax: one lane per label; NaN where the label is refused
+__global__ __launch_bounds__(64) void align_long_fit_kernel(const double* __restrict__ ly, int T, int C, const int* __restrict__ lab,
+                                                            int L, const int* __restrict__ status, const int* __restrict__ spans,
+                                                            double bias, double* __restrict__ fit) {
+  const int k = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (k >= L) return;
+  fit[k] = *status != 0 ? __builtin_nan("") : st::al_label_fit(ly, lab[k], C, spans[2 * k], spans[2 * k + 1], T, bias);
+}
+
 struct Workspace {
   double* ly;          // [T][32]
   uint32_t* bp;        // [T][56 NB]
@@ -217,15 +230,21 @@ size_t st_ctc_align_long_ws(long frames, int label_len) {
   ST_REQUIRE(workspace_bytes >= st_ctc_align_long_ws(frames, label_len), NAME ": workspace too small");                      \
   ST_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, NAME ": workspace must be 16-byte aligned")
 
-int st_ctc_align_long_f32(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
-                          int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  ST_ALIGN_LONG_ARGS("ctc_align_long");
+// the launches of both device entry points; `bias` (null: the plain form): the WILD softmax stage, `fit` (with a bias only, may be
+// null): the fit stage after the back-trace
+static int align_long_launch(const char* name, const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids,
+                             int label_len, int32_t* spans, double* score, int32_t* status, void* workspace, void* stream,
+                             const double* bias, double* fit) {
   hipStream_t s = st::as_stream(stream);
   const int T = (int)frames, L = label_len, NB = state_blocks(L);
   const Workspace w = carve(workspace, T, NB);
-  hipLaunchKernelGGL(st::align_logsoftmax_kernel, dim3((unsigned)(((size_t)T + 7) / 8)), dim3(256), 0, s, logits,
-                     st::RowMap{0, 0, row_pitch}, 1, T, classes, w.ly);
+  const dim3 row_grid((unsigned)(((size_t)T + 7) / 8));
+  if (bias) {
+    hipLaunchKernelGGL(st::align_logsoftmax_wild_kernel, row_grid, dim3(256), 0, s, logits, st::RowMap{0, 0, row_pitch}, 1, T, classes,
+                       *bias, w.ly);
+  } else {
+    hipLaunchKernelGGL(st::align_logsoftmax_kernel, row_grid, dim3(256), 0, s, logits, st::RowMap{0, 0, row_pitch}, 1, T, classes, w.ly);
+  }
   const long n = 2 * (long)col_elems(NB);
   hipLaunchKernelGGL(align_long_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, label_ids, L, T, w.col[0], n,
                      status, score);
@@ -235,12 +254,17 @@ int st_ctc_align_long_f32(const float* logits, long frames, int classes, int row
     hipLaunchKernelGGL(align_long_tile_kernel, dim3(NB), dim3(64), 0, s, w.ly, T, classes, label_ids, L, fb, NB, w.col[fb & 1],
                        w.col[(fb & 1) ^ 1], w.bp, status);
   hipLaunchKernelGGL(align_long_backtrace_kernel, dim3(1), dim3(64), 0, s, w.bp, T, L, NB, w.col[nfb & 1], status, spans, score);
-  return st::check_launch("ctc_align_long");
+  if (bias && fit && L > 0) {
+    hipLaunchKernelGGL(st::align_rowmax_kernel, row_grid, dim3(256), 0, s, w.ly, (long)T, classes);
+    hipLaunchKernelGGL(align_long_fit_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, s, w.ly, T, classes, label_ids, L, status,
+                       spans, *bias, fit);
+  }
+  return st::check_launch(name);
 }
 
-int st_ctc_align_long_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
-                           int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes) {
-  ST_ALIGN_LONG_ARGS("ctc_align_long");
+// the loops of both host entry points (bias, fit: as above)
+static int align_long_host_run(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                               int32_t* spans, double* score, int32_t* status, void* workspace, const double* bias, double* fit) {
   const long T = frames;
   const int L = label_len, U = 2 * L + 1, blank = classes - 1, NB = state_blocks(L);
   const size_t pitch = (size_t)BPW * NB;
@@ -252,6 +276,7 @@ int st_ctc_align_long_host(const float* logits, long frames, int classes, int ro
   if (*status) {
     *score = ST_AL_NEG_INF;
     for (long i = 0; i < 2 * (long)L; ++i) spans[i] = -1;
+    if (fit) for (int i = 0; i < L; ++i) fit[i] = __builtin_nan("");
     return ST_OK;
   }
   for (long t = 0; t < T; ++t) {
@@ -262,6 +287,7 @@ int st_ctc_align_long_host(const float* logits, long frames, int classes, int ro
     for (int c = 0; c < CP; ++c) e[c] = c < classes ? st::al_exp((double)row[c] - (double)m) : 0.0;
     const double s = st::al_row_sum(e);
     for (int c = 0; c < classes; ++c) w.ly[t * CP + c] = st::al_log_softmax(row[c], m, s);
+    if (bias) w.ly[t * CP + classes] = st::al_wild_emission(m, s, *bias);
   }
   auto cls = [&](int u) { return st::lattice_class(u, lab, blank); };
   // plain loops over the whole lattice: the columns of frames t-1 and t, state u at element u
@@ -294,7 +320,51 @@ int st_ctc_align_long_host(const float* logits, long frames, int classes, int ro
     next = s;
     if (t > 0) u = std::max(u - (int)((w.bp[t * pitch + (u >> 4)] >> (2 * (u & 15))) & 3u), 0);
   }
+  if (fit) {
+    for (long t = 0; t < T; ++t) w.ly[t * CP + classes] = st::al_row_max(w.ly + t * CP, classes);
+    for (int k = 0; k < L; ++k) fit[k] = st::al_label_fit(w.ly, lab[k], classes, spans[2 * k], spans[2 * k + 1], (int)T, *bias);
+  }
   return ST_OK;
+}
+
+int st_ctc_align_long_f32(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                          int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  ST_ALIGN_LONG_ARGS("ctc_align_long");
+  return align_long_launch("ctc_align_long", logits, frames, classes, row_pitch, label_ids, label_len, spans, score, status, workspace,
+                           stream, nullptr, nullptr);
+}
+
+int st_ctc_align_long_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                           int32_t* spans, double* score, int32_t* status, void* workspace, size_t workspace_bytes) {
+  ST_ALIGN_LONG_ARGS("ctc_align_long");
+  return align_long_host_run(logits, frames, classes, row_pitch, label_ids, label_len, spans, score, status, workspace, nullptr, nullptr);
+}
+
+// ---- the wildcard forms: the id `classes` is the wildcard, slot `classes` of the rows its emission (so classes <= 31) ----
+#define ST_ALIGN_LONG_WILD_ARGS(NAME)                                                                                          \
+  ST_ALIGN_LONG_ARGS(NAME);                                                                                                    \
+  ST_REQUIRE(classes <= CP - 1, NAME ": num_classes must be 2..31 (the wildcard takes the row's slot after the blank)");      \
+  ST_REQUIRE(std::isfinite(wildcard_bias) && wildcard_bias <= 0.0, NAME ": wildcard_bias must be finite and <= 0")
+
+int st_ctc_align_long_wild_f32(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                               double wildcard_bias, int32_t* spans, double* score, int32_t* status, double* fit, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  ST_ALIGN_LONG_WILD_ARGS("ctc_align_long_wild");
+  return align_long_launch("ctc_align_long_wild", logits, frames, classes, row_pitch, label_ids, label_len, spans, score, status,
+                           workspace, stream, &wildcard_bias, fit);
+}
+
+int st_ctc_align_long_wild_host(const float* logits, long frames, int classes, int row_pitch, const int32_t* label_ids, int label_len,
+                                double wildcard_bias, int32_t* spans, double* score, int32_t* status, double* fit, void* workspace,
+                                size_t workspace_bytes) {
+  ST_ALIGN_LONG_WILD_ARGS("ctc_align_long_wild");
+  for (int i = 0; i < label_len; ++i) {
+    ST_REQUIRE(label_ids[i] >= 0 && label_ids[i] <= classes, "ctc_align_long_wild: label id %d outside 0..%d", label_ids[i], classes);
+    ST_REQUIRE(i == 0 || label_ids[i] != classes || label_ids[i - 1] != classes, "ctc_align_long_wild: two adjacent wildcards at label %d", i);
+  }
+  return align_long_host_run(logits, frames, classes, row_pitch, label_ids, label_len, spans, score, status, workspace, &wildcard_bias,
+                             fit);
 }
 
 }  // extern "C"

@@ -55,6 +55,34 @@ CANDIDATE_WORKSPACE_BYTES = 1 << 30
 MAX_ALIGN_LABELS = 511          # labels per utterance of st_ctc_align_f32 (the 16-states-per-lane lattice of st_ctc_loss_grad_f32)
 
 
+WILDCARD = -1                   # the wildcard label of `align` / `align_long`: audio the transcript leaves out (id num_classes in the C ABI)
+WILDCARD_BIAS = -1.0            # its default price per frame, in nats: a guess, not tuned on data
+MAX_WILDCARD_CLASSES = 31       # the wildcard takes the slot after the blank in the lattices' 32-wide rows
+
+
+def wildcard_ids(name, ids, num_classes, wild):
+  """The check every label goes through before a lattice kernel indexes rows with its ids: ids in [0, num_classes - 1), and --
+  ``wild`` -- WILDCARD, which becomes the id num_classes, never two of them in a row.  -> int32 array (a copy)."""
+  ids = np.array(ids, dtype=np.int32).reshape(-1)
+  star = ids == WILDCARD
+  if wild and num_classes > MAX_WILDCARD_CLASSES:
+    raise ValueError('{}: the wildcard needs num_classes <= {}, not {}'.format(name, MAX_WILDCARD_CLASSES, num_classes))
+  if ids.size and (not wild and star.any() or int(ids[~star].min(initial=0)) < 0 or int(ids[~star].max(initial=0)) >= num_classes - 1):
+    raise ValueError('{}: label ids must lie in [0, {}) (blank = {}){}'.format(
+        name, num_classes - 1, num_classes - 1, ' or be WILDCARD' if wild else ''))
+  if (star[1:] & star[:-1]).any():
+    raise ValueError('{}: two adjacent wildcards'.format(name))
+  ids[star] = num_classes
+  return ids
+
+
+def _wildcard_bias(name, wildcard_bias):
+  bias = WILDCARD_BIAS if wildcard_bias is None else float(wildcard_bias)
+  if not (np.isfinite(bias) and bias <= 0.0):
+    raise ValueError('{}: wildcard_bias must be finite and <= 0, not {}'.format(name, wildcard_bias))
+  return bias
+
+
 MAX_ALIGN_LONG_LABELS = 1048575   # labels of the one sequence of st_ctc_align_long_f32
 ALIGN_LONG_FRAME_BLOCK = 64       # frames per launch of its tile kernel (csrc/ctc_align_long.hip)
 ALIGN_LONG_STATE_BLOCK = 896      # lattice states one workgroup of it owns (plus a halo of 2 * ALIGN_LONG_FRAME_BLOCK)
@@ -176,13 +204,22 @@ class DecodeMixin:
       out = [merge_repeated_labels(seq) for seq in out]
     return out, sh.dec_score.cpu().numpy().reshape(-1, 1)
 
-  def align(self, labels, return_states=False):
+  def align(self, labels, return_states=False, *, wildcard_bias=None, fit=False):
     """Forced alignment (st_ctc_align_f32; semantics: include/speecht_hip.h, tests/align_oracle.py): the best CTC path of the
     given id lists, one per utterance of the batch, against the logits of the current shape
     -> (list of [L_b, 2] int32 arrays: first frame and one past the last frame of each label, score [B, 1] = ln p(best path),
     status [B]: != 0 where the label does not fit its utterance's frames -- then score = -inf and the spans are -1).
     ``return_states``: a fourth element, [B, T'] int32, the label index of every frame (-1 blank, -2 beyond the utterance).
-    Labels hold ids in [0, num_classes - 1) and at most MAX_ALIGN_LABELS of them."""
+    Labels hold ids in [0, num_classes - 1) and at most MAX_ALIGN_LABELS of them.
+
+    ``wildcard_bias`` (a float <= 0) or ``fit=True``: st_ctc_align_wild_f32 instead (tests/wildcard_align_oracle.py).  Labels may
+    then hold WILDCARD, a label for audio the transcript leaves out: a state like any other (at least one frame, never two in a
+    row) whose emission is the frame's largest ln-softmax value plus the bias -- WILDCARD_BIAS when ``wildcard_bias`` is None,
+    a guess that nobody has tuned on data; its span is the left-out stretch.  The tuple gains, as its LAST element, a list of
+    float64 arrays: the fit of every label, sum over its frames of ln p(its class) - ln p(the frame's best class): 0 where the
+    greedy reading spells the label on all its frames, negative otherwise, bias * frames for a wildcard, NaN where status != 0."""
+    wild = wildcard_bias is not None or bool(fit)
+    bias = _wildcard_bias('align', wildcard_bias) if wild else None
     lib = _lib.load()
     sh = self.shape
     xl = sh.X[-1]
@@ -195,27 +232,44 @@ class DecodeMixin:
     N, max_len = int(offs[-1]), int(max(lens + [0]))
     if max_len > MAX_ALIGN_LABELS:
       raise ValueError('align: label of length {} is too long for the alignment kernel (max {})'.format(max_len, MAX_ALIGN_LABELS))
-    ids = np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in labels] + [np.zeros(1, np.int32)])
-    # the kernel indexes LDS rows with the id: it must never see one outside the classes
-    if N and (int(ids.min()) < 0 or int(ids.max()) >= self.num_classes - 1):
-      raise ValueError('align: label ids must lie in [0, {}) (blank = {})'.format(self.num_classes - 1, self.num_classes - 1))
+    # the kernel indexes LDS rows with the id: it must never see one outside the classes (`wildcard_ids`)
+    if wild:
+      ids = np.concatenate([wildcard_ids('align', l, self.num_classes, True) for l in labels] + [np.zeros(1, np.int32)])
+    else:
+      ids = np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in labels] + [np.zeros(1, np.int32)])
+      if N and (int(ids.min()) < 0 or int(ids.max()) >= self.num_classes - 1):
+        raise ValueError('align: label ids must lie in [0, {}) (blank = {})'.format(self.num_classes - 1, self.num_classes - 1))
     need = lib.st_ctc_align_ws(B, T, max_len)
     ws = self._storage.view('align_ws', need // 4 + 16, torch.int32)[0]
-    # outputs in one buffer, one copy back: spans [N][2] | states [B][T] | status [B] | score [B] (float bits)
-    out = self._storage.view('align_out', 2 * N + B * T + 2 * B, torch.int32)[0]
+    # outputs in one buffer, one copy back: spans [N][2] | states [B][T] | status [B] | score [B] (float bits) | a word to
+    # bring the fits to 8 bytes | fit [N] (doubles, the wildcard form only)
+    words = 2 * N + B * T + 2 * B
+    fit0 = words + (words & 1)
+    out = self._storage.view('align_out', fit0 + 2 * N + 2, torch.int32)[0]
     at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
     d_ids, d_offs = self._upload_i32(ids), self._upload_i32(offs)
     self._wait_uploads()
-    call('st_ctc_align_f32', xl.ref, self._ptr(d_ids), self._ptr(d_offs), self._ptr(self.ctc_lens), max_len,
-         at(0), at(2 * N), at(2 * N + B * T + B), at(2 * N + B * T), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    if wild:
+      call('st_ctc_align_wild_f32', xl.ref, self._ptr(d_ids), self._ptr(d_offs), self._ptr(self.ctc_lens), max_len, bias,
+           at(0), at(2 * N), at(2 * N + B * T + B), at(2 * N + B * T), at(fit0), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+      words = fit0 + 2 * N
+    else:
+      call('st_ctc_align_f32', xl.ref, self._ptr(d_ids), self._ptr(d_offs), self._ptr(self.ctc_lens), max_len,
+           at(0), at(2 * N), at(2 * N + B * T + B), at(2 * N + B * T), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
     with torch.cuda.stream(self.stream):
-      host = out[:2 * N + B * T + 2 * B].cpu().numpy()
+      host = out[:words].cpu().numpy()
     spans = host[:2 * N].reshape(N, 2)
     res = ([spans[offs[b]:offs[b + 1]].copy() for b in range(B)],
-           host[2 * N + B * T + B:].view(np.float32).reshape(-1, 1).copy(), host[2 * N + B * T:2 * N + B * T + B].copy())
-    return res + (host[2 * N:2 * N + B * T].reshape(B, T).copy(),) if return_states else res
+           host[2 * N + B * T + B:2 * N + B * T + 2 * B].view(np.float32).reshape(-1, 1).copy(),
+           host[2 * N + B * T:2 * N + B * T + B].copy())
+    if return_states:
+      res = res + (host[2 * N:2 * N + B * T].reshape(B, T).copy(),)
+    if wild:
+      fits = host[fit0:fit0 + 2 * N].view(np.float64)
+      res = res + ([fits[offs[b]:offs[b + 1]].copy() for b in range(B)],)
+    return res
 
-  def align_long(self, logits, labels, max_workspace_bytes=ALIGN_LONG_WORKSPACE_BYTES):
+  def align_long(self, logits, labels, max_workspace_bytes=ALIGN_LONG_WORKSPACE_BYTES, *, wildcard_bias=None, fit=False):
     """Forced alignment of ONE long sequence (st_ctc_align_long_f32; the semantics of `align`, include/speecht_hip.h): the
     best CTC path of ``labels`` -- up to MAX_ALIGN_LONG_LABELS ids in [0, num_classes - 1) -- against ``logits``, a float32
     device tensor [T, C] or [T, pitch] (C = num_classes <= pitch) such as the concatenated output frames of a recording's
@@ -224,7 +278,12 @@ class DecodeMixin:
 
     The lattice runs in tiles of ALIGN_LONG_FRAME_BLOCK frames x ALIGN_LONG_STATE_BLOCK states, one launch per frame block.
     Its back-pointers take T * ceil((2 L + 1) / 896) * 224 bytes (an hour with 54 000 characters: 6.8 GB) in the engine's
-    storage; a workspace above ``max_workspace_bytes`` is refused with a ValueError that names its size."""
+    storage; a workspace above ``max_workspace_bytes`` is refused with a ValueError that names its size.
+
+    ``wildcard_bias`` / ``fit``: as in `align` -- st_ctc_align_long_wild_f32, labels may hold WILDCARD, and the tuple gains the
+    per-label fit, a float64 array [L], as its last element."""
+    wild = wildcard_bias is not None or bool(fit)
+    bias = _wildcard_bias('align_long', wildcard_bias) if wild else None
     lib = _lib.load()
     C = self.num_classes
     if not (torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_cuda):
@@ -236,8 +295,10 @@ class DecodeMixin:
     L = int(ids.shape[0])
     if L > MAX_ALIGN_LONG_LABELS:
       raise ValueError('align_long: label of length {} is too long for the alignment kernel (max {})'.format(L, MAX_ALIGN_LONG_LABELS))
-    # the kernel indexes LDS rows with the id: it must never see one outside the classes
-    if L and (int(ids.min()) < 0 or int(ids.max()) >= C - 1):
+    # the kernel indexes LDS rows with the id: it must never see one outside the classes (`wildcard_ids`)
+    if wild:
+      ids = wildcard_ids('align_long', ids, C, True)
+    elif L and (int(ids.min()) < 0 or int(ids.max()) >= C - 1):
       raise ValueError('align_long: label ids must lie in [0, {}) (blank = {})'.format(C - 1, C - 1))
     need = int(lib.st_ctc_align_long_ws(T, L))
     if need > max_workspace_bytes:
@@ -245,18 +306,24 @@ class DecodeMixin:
           T, L, need, need / 2.0 ** 30, int(max_workspace_bytes)))
     logits = logits.contiguous()
     ws = self._storage.view('align_long_ws', need // 4 + 16, torch.int32)[0]
-    # outputs in one buffer, one copy back: score (a double) | status, a spare word | spans [L][2]
-    out = self._storage.view('align_long_out', 4 + 2 * L, torch.int32)[0]
+    # outputs in one buffer, one copy back: score (a double) | status, a spare word | spans [L][2] | fit [L] (doubles, the
+    # wildcard form only)
+    out = self._storage.view('align_long_out', 4 + 4 * L + 2, torch.int32)[0]
     at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
     d_ids = self._upload_i32(np.concatenate([ids, np.zeros(1, np.int32)]))
     self._wait_uploads()
     self.stream.wait_stream(torch.cuda.current_stream(self.device))    # (the caller made ``logits`` on the current stream)
-    call('st_ctc_align_long_f32', self._ptr(logits), T, C, pitch, self._ptr(d_ids), L, at(4), at(0), at(2), self._ptr(ws),
-         ws.numel() * 4, self.stream_ptr)
+    if wild:
+      call('st_ctc_align_long_wild_f32', self._ptr(logits), T, C, pitch, self._ptr(d_ids), L, bias, at(4), at(0), at(2),
+           at(4 + 2 * L), self._ptr(ws), ws.numel() * 4, self.stream_ptr)
+    else:
+      call('st_ctc_align_long_f32', self._ptr(logits), T, C, pitch, self._ptr(d_ids), L, at(4), at(0), at(2), self._ptr(ws),
+           ws.numel() * 4, self.stream_ptr)
     with torch.cuda.stream(self.stream):
-      host = out[:4 + 2 * L].cpu().numpy()
+      host = out[:4 + (4 if wild else 2) * L].cpu().numpy()
     logits.record_stream(self.stream)
-    return host[4:].reshape(L, 2).copy(), float(host[:2].view(np.float64)[0]), int(host[2])
+    res = (host[4:4 + 2 * L].reshape(L, 2).copy(), float(host[:2].view(np.float64)[0]), int(host[2]))
+    return res + (host[4 + 2 * L:].view(np.float64).copy(),) if wild else res
 
   def word_confidence(self, labels, space_id=None):
     """Word confidences (st_ctc_word_conf_f32; semantics: include/speecht_hip.h, tests/conf_oracle.py): for the given id lists,

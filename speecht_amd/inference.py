@@ -230,16 +230,23 @@ def transcribe(engine, features, batch_size=64, bucket=True, pipeline=None, beam
   return ids_out, [vocabulary.ids_to_sentence(s) for s in ids_out]
 
 
-def _align_current(engine, labels):
+def _align_current(engine, labels, wildcard_bias=None, fit=False):
   """``engine.align`` on the batch the engine holds, with labels the kernel cannot take (longer than MAX_ALIGN_LABELS) left out:
-  their spans are None, their score -inf and their status 1."""
+  their spans are None, their score -inf and their status 1.  With a ``wildcard_bias`` or ``fit``: a fourth element, the fits
+  (None for a label left out)."""
   from .engine_decode import MAX_ALIGN_LABELS
   long = [len(l) > MAX_ALIGN_LABELS for l in labels]
-  spans, score, status = engine.align([[] if skip else l for l, skip in zip(labels, long)])
+  kept = [[] if skip else l for l, skip in zip(labels, long)]
+  if wildcard_bias is None and not fit:
+    spans, score, status = res = engine.align(kept)
+  else:
+    spans, score, status, fits = res = engine.align(kept, wildcard_bias=wildcard_bias, fit=fit)
   for row, skip in enumerate(long):
     if skip:
       spans[row], score[row, 0], status[row] = None, -np.inf, 1
-  return spans, score, status
+      if len(res) > 3:
+        fits[row] = None
+  return res
 
 
 def _confidence_current(engine, labels):
@@ -252,7 +259,7 @@ def _confidence_current(engine, labels):
           for row, skip in enumerate(long)]
 
 
-def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=False, confidence=False):
+def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=False, confidence=False, wildcard_bias=None, fit=False):
   """Forced alignment of known transcripts: features as for `transcribe`, ``labels`` one id list per utterance
   -> (spans, scores, status) in input order: spans[i] an [L_i, 2] int32 array (first output frame, one past the last output
   frame of each id on the best CTC path), scores[i] = ln p(that path), status[i] != 0 where the transcript does not fit the
@@ -263,13 +270,20 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
   times of its last words -- unless ``mask_padding`` is set, which masks the padding in the forward pass as in `transcribe`.
 
   ``confidence=True``: a fourth element, per utterance {'log_prob', 'words'} as `transcribe` returns it -- the confidences of the
-  GIVEN transcript's words (None where status != 0): a low one marks a word the audio contradicts."""
+  GIVEN transcript's words (None where status != 0): a low one marks a word the audio contradicts.
+
+  ``wildcard_bias`` / ``fit`` (``engine.align``): labels may hold ``engine_decode.WILDCARD`` for audio the transcript leaves out,
+  and the LAST element of the tuple is the list of per-label fits (float64 arrays; None for a transcript too long).  Not
+  together with ``confidence``: the word-posterior lattices do not know the wildcard."""
+  wild = wildcard_bias is not None or bool(fit)
+  if wild and confidence:
+    raise ValueError('align: word confidences are not available with a wildcard or the fit')
   if len(features) != len(labels):
     raise ValueError('align: {} feature arrays and {} label sequences'.format(len(features), len(labels)))
   n = len(features)
-  spans_out, score_out, status_out, conf_out = [None] * n, [float('-inf')] * n, [1] * n, [None] * n
+  spans_out, score_out, status_out, conf_out, fit_out = [None] * n, [float('-inf')] * n, [1] * n, [None] * n, [None] * n
   if not features:
-    return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
+    return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ()) + ((fit_out,) if wild else ())
   lengths, buckets = _plan(features, batch_size, bucket)
   for idx in buckets:
     max_t = max(lengths[i] for i in idx)
@@ -281,17 +295,20 @@ def align(engine, features, labels, batch_size=1, bucket=True, mask_padding=Fals
       engine.forward(mask_padding=True)
     else:
       engine.forward()
-    spans, score, status = _align_current(engine, [labels[i] for i in idx])
+    res = _align_current(engine, [labels[i] for i in idx], wildcard_bias, fit)
+    spans, score, status = res[:3]
     for row, i in enumerate(idx):
       spans_out[i], score_out[i], status_out[i] = spans[row], float(score[row, 0]), int(status[row])
+      if wild:
+        fit_out[i] = res[3][row]
     if confidence:
       conf = _confidence_current(engine, [labels[i] for i in idx])
       for row, i in enumerate(idx):
         conf_out[i] = conf[row]
-  return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ())
+  return (spans_out, score_out, status_out) + ((conf_out,) if confidence else ()) + ((fit_out,) if wild else ())
 
 
-def align_long(engine, features, labels, batch_size=1, mask_padding=False, return_logits=False):
+def align_long(engine, features, labels, batch_size=1, mask_padding=False, return_logits=False, wildcard_bias=None, fit=False):
   """Forced alignment of ONE recording given as its segments: ``features`` the list of the segments' feature arrays in time
   order, ``labels`` the id list of the whole transcript, of any length up to ``engine_decode.MAX_ALIGN_LONG_LABELS`` -- which part
   of the text belongs to which segment is what the alignment finds.  The segments go through the forward pass in the batches
@@ -299,14 +316,17 @@ def align_long(engine, features, labels, batch_size=1, mask_padding=False, retur
   one [sum T, C] device tensor, and ``engine.align_long`` aligns the transcript against it
   -> (spans [L, 2] int32 in CONCATENATED output frames, score = ln p(best path), status != 0 where the transcript does not fit
   the frames -- spans is None then --, frames: the output frames of each segment; `alignment.concat_frame_seconds` maps a
-  concatenated frame to seconds).  ``return_logits``: a fifth element, the gathered logits (None without frames)."""
+  concatenated frame to seconds).  ``return_logits``: a fifth element, the gathered logits (None without frames).
+  ``wildcard_bias`` / ``fit`` (``engine.align_long``): labels may hold ``engine_decode.WILDCARD``, and the LAST element of the
+  tuple is the per-label fit, a float64 array [L] (None where the transcript does not fit)."""
   import torch
+  wild = wildcard_bias is not None or bool(fit)
   lengths, buckets = _plan(features, batch_size, True) if features else ([], [])
   frames = [l // 2 for l in lengths]                               # the segments' output frames (engine.ctc_lens)
   first = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
   total = int(first[-1])
   if total == 0:
-    return (None, float('-inf'), 1, frames) + ((None,) if return_logits else ())
+    return (None, float('-inf'), 1, frames) + ((None,) if return_logits else ()) + ((None,) if wild else ())
   logits = torch.empty((total, engine.num_classes), dtype=torch.float32, device=engine.device)
   for idx in buckets:
     max_t = max(lengths[i] for i in idx)
@@ -323,8 +343,12 @@ def align_long(engine, features, labels, batch_size=1, mask_padding=False, retur
       for row, i in enumerate(idx):
         logits[int(first[i]):int(first[i + 1])].copy_(out[row, :frames[i]])
   logits.record_stream(engine.stream)
-  spans, score, status = engine.align_long(logits, labels)
-  return (spans if status == 0 else None, score, status, frames) + ((logits,) if return_logits else ())
+  if wild:
+    spans, score, status, fits = engine.align_long(logits, labels, wildcard_bias=wildcard_bias, fit=fit)
+  else:
+    spans, score, status = engine.align_long(logits, labels)
+  return (spans if status == 0 else None, score, status, frames) + ((logits,) if return_logits else ()) + \
+      (((fits if status == 0 else None),) if wild else ())
 
 
 def spot(engine, features, keywords, batch_size=1, bucket=True, mask_padding=False, trace=False):
