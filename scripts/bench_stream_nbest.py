@@ -95,12 +95,12 @@ def speech_engine():
 
 def read_call(eng, rec, S):
   """-> the arguments of st_ctc_beam_stream_read on ``rec``'s records with every stream finishing and no new rows."""
-  bm = rec.beam
+  bm, part = rec.beam, rec._beam
   table = np.zeros((S, 4), np.int32)
-  table[:, 2] = rec._frames
+  table[:, 2] = part.frames
   d_table = torch.from_numpy(table).to(dev)
-  return (eng._ptr(d_table), S, bm.beam_width, rec._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score,
-          eng._ptr(rec.beam_state), eng._ptr(rec.beam_pool), rec.max_frames, eng._ptr(rec.beam_tail), bm.max_tail, eng._ptr(rec.beam_result),
+  return (eng._ptr(d_table), S, bm.beam_width, part.lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score,
+          eng._ptr(part.state), eng._ptr(part.pool), rec.max_frames, eng._ptr(part.tail), bm.max_tail, eng._ptr(part.result),
           eng.stream_ptr), d_table
 
 
@@ -207,7 +207,7 @@ for name, make in (('beam100_lm', lambda: StreamBeam(lm=lm, max_seconds=30.0, ma
       if k != 'read':
         fn()
         demand[k] = int(used.item())
-  r = dict(decoder=name, streams=S, beam=W, frames=int(rec._frames[0]), read_us=spread(t['read']),
+  r = dict(decoder=name, streams=S, beam=W, frames=int(rec._beam.frames[0]), read_us=spread(t['read']),
            unstable_labels=dict(largest=unstable[-8:], median=unstable[len(unstable) // 2]))
   for k in forms:                                                 # per label of the longest unstable tail, which bounds the launch
     r.setdefault('us_per_label_of_the_longest_tail', {})[k] = round(sorted(t[k])[a.rounds // 2] / max(unstable[-1], 1), 4)

@@ -51,6 +51,9 @@ are the offline resampler's of the whole signal, bit for bit.  `StreamingFeature
 the mel kernel without a trip through the host, `stream_audio(..., model_rate=)` and `speecht-cli stream --model-rate` use that, and
 the seconds of endpointing, spotting, the beam's pool and the words' times then count frames of hop / model_rate seconds
 (``frame_rate``) instead of assuming 10 ms.
+
+On the host every option owns its part of a pass (`_EndpointPart`, `_BeamPart`, `_WordsPart`, `_SpotPart`, `_FollowPart`: state,
+launches, read-out), and `StepLayout` alone says where each of them finds its results in the step's one copy back.
 """
 import ctypes
 
@@ -166,6 +169,12 @@ def first_row_after(layers):
 
 # ---- the session ----------------------------------------------------------------------------------------------------------
 
+def seconds_to_frames(seconds, total_stride, frame_rate=None):
+  """Seconds -> output frames of a model whose layers' strides multiply to ``total_stride``, rounded up and at least 1.  ``frame_rate``:
+  feature frames per second, sample rate / hop (137.8125 for 22 050 Hz); None: 100, the 10 ms hop of 16 kHz audio, a guess."""
+  return max(int(np.ceil(seconds * (100.0 if frame_rate is None else float(frame_rate)) / total_stride - 1e-9)), 1)
+
+
 class StreamBeam:
   """The beam search of a `StreamingRecognizer` (st_ctc_beam_stream_step / _read): the prefix beam search of
   ``engine.beam_search_decode`` -- with ``lm`` (a `language_model.LanguageModel` or the path of an ARPA file) that of
@@ -242,6 +251,17 @@ class StreamBeam:
     if self.max_seconds <= 0 or self.max_tail < 1:
       raise StreamError('max_seconds and max_tail must be positive')
 
+  def arena_words(self, max_streams):
+    """The int32 words of the arena of a pass's lists: ``nbest_words``, or by default one final per stream, ``nbest`` hypotheses with
+    tails of ``max_tail`` labels each.  None without lists."""
+    if self.nbest is None:
+      return None
+    from .nbest import ARENA_HEADER
+    words = max_streams * (ARENA_HEADER + self.nbest * (2 + self.max_tail)) if self.nbest_words is None else self.nbest_words
+    if words >= 2 ** 31:
+      raise StreamError('the arena of the N-best lists would hold {} words (nbest_words)'.format(words))
+    return words
+
 
 class Endpointing:
   """Endpointing of a `StreamingRecognizer` (st_ctc_greedy_endpoint_stream; the rule: include/speecht_hip.h, tests/endpoint_oracle.py):
@@ -268,12 +288,9 @@ class Endpointing:
 
   def frames(self, total_stride, num_classes, frame_rate=None):
     """Seconds -> output frames of a model whose layers' strides multiply to ``total_stride``:
-    ``(silence_frames, lead_frames, max_frames, space_id)``, each count rounded up and at least 1.  ``frame_rate``: feature frames
-    per second, sample rate / hop (137.8125 for 22 050 Hz); None: the 10 ms hop of 16 kHz audio, a guess where nothing says
-    otherwise."""
-    per_second = 100.0 if frame_rate is None else float(frame_rate)
-    count = lambda seconds: max(int(np.ceil(seconds * per_second / total_stride - 1e-9)), 1)
-    R, L, M = count(self.silence), count(self.lead), count(self.max_utterance)
+    ``(silence_frames, lead_frames, max_frames, space_id)``, each count rounded up and at least 1 (`seconds_to_frames`).
+    ``frame_rate``: feature frames per second."""
+    R, L, M = (seconds_to_frames(v, total_stride, frame_rate) for v in (self.silence, self.lead, self.max_utterance))
     space = (27 if num_classes == 29 else -1) if self.space_id == 'auto' else int(self.space_id)
     if space >= num_classes:
       raise StreamError('endpointing: space_id {} is no class of a model with {} classes'.format(space, num_classes))
@@ -396,8 +413,7 @@ class StreamSpotter:
   def frames(self, total_stride, frame_rate=None):
     """``hold`` in output frames of a model whose layers' strides multiply to ``total_stride``, counted as `Endpointing.frames`
     counts: rounded up, at least 1.  ``frame_rate``: feature frames per second (None: the 10 ms hop)."""
-    per_second = 100.0 if frame_rate is None else float(frame_rate)
-    return max(int(np.ceil(self.hold * per_second / total_stride - 1e-9)), 1)
+    return seconds_to_frames(self.hold, total_stride, frame_rate)
 
   def plan(self, num_classes, pack=1):
     """-> (the plan of st_ctc_spot_stream_plan as an int32 array, its waves).  Runs on the host."""
@@ -483,8 +499,7 @@ class ScriptFollower:
   def frames(self, total_stride, frame_rate=None):
     """``confirm`` in output frames, counted as `StreamSpotter.frames` counts ``hold``: rounded up, at least 1; more than 16 is
     refused.  ``frame_rate``: feature frames per second (None: the 10 ms hop)."""
-    per_second = 100.0 if frame_rate is None else float(frame_rate)
-    k = max(int(np.ceil(self.confirm * per_second / total_stride - 1e-9)), 1)
+    k = seconds_to_frames(self.confirm, total_stride, frame_rate)
     if k > 16:
       raise StreamError('following: confirm = {} s is {} output frames, at most 16 are kept'.format(self.confirm, k))
     return k
@@ -584,6 +599,472 @@ class StepResult:
     self.follow, self.reached, self.reached_lost = {}, {}, {}
 
 
+class StepLayout:
+  """Where a step's results lie in its one buffer of int32 words (``dec_out``), so that they come back with one copy: the named
+  segments in order, ``segments[name] = (first word, length, shape)``, and their ``size`` in all -- no torch, no device.
+    ids [S][max_new] | counts [S] | scores [S] (float32)
+    with endpointing (``n_pieces`` = P; without it P = 1):  | events [S][P][8] | pieces [P][S][4]
+    with a beam search (``max_tail``):                      | result [P][S][4] | tail [P][S][max_tail]
+    with a spotter (``spot_events``):                       | spot_counts [S] | spot_events [S][spot_events][8]
+    with a follower (``follow_events``), from the next even word on (its records hold doubles):
+                                     | follow_records [S][16] | follow_events [S][follow_events][2] | follow_trace [``trace_rows``]
+    with N-best lists (``lists``), the last word: used, the words the step's lists asked for (the arena is copied only if not 0)
+  The options take their device views from it, and resolve once where a pass's read-outs find theirs in the host copy (`views`)."""
+
+  def __init__(self, S, max_new, n_pieces=None, max_tail=None, spot_events=None, follow_events=None, trace_rows=None, lists=False):
+    self.segments, self.size = {}, 0
+    P = 1 if n_pieces is None else n_pieces
+    self._add('ids', S, max_new), self._add('counts', S), self._add('scores', S)
+    if n_pieces is not None:
+      self._add('events', S, P, 8), self._add('pieces', P, S, 4)
+    if max_tail is not None:
+      self._add('result', P, S, 4), self._add('tail', P, S, max_tail)
+    if spot_events is not None:
+      self._add('spot_counts', S), self._add('spot_events', S, spot_events, 8)
+    if follow_events is not None:
+      self.size += self.size & 1
+      self._add('follow_records', S, 16), self._add('follow_events', S, follow_events, 2)
+      if trace_rows is not None:
+        self._add('follow_trace', trace_rows)
+    if lists:
+      self._add('used', 1)
+
+  def _add(self, name, *shape):
+    length = int(np.prod(shape))
+    self.segments[name] = (self.size, length, shape)
+    self.size += length
+
+  def views(self, *names):
+    """-> f(words): the named segments of ``words`` -- the device buffer or a host copy of it -- each in its shape."""
+    cuts = [(slice(first, first + length), shape) for first, length, shape in map(self.segments.get, names)]
+    return lambda words: [words[cut].reshape(shape) for cut, shape in cuts]
+
+
+def read_beam(hyp, stable, row, tail, max_tail, final):
+  """One read-out of a streamed beam search: ``hyp`` / ``stable``, the hypothesis the host holds and how many of its leading ids are
+  final; ``row`` = {length, stable, log-probability (float32 bits), status} and ``tail``, the labels above ``stable``, as the device left
+  them.  -> ``(hyp, stable, logp, head)``, the tail appended above ``head``, the ids that were final (a ``final`` read-out's hypothesis
+  is final as a whole) -- or the reason, a text, why the read-out gave up."""
+  length, old = int(row[0]), int(stable)
+  if row[3] != 0:
+    return 'status {}'.format(int(row[3]))
+  if length - old > max_tail or length < old:
+    return '{} labels are not final yet, max_tail = {}'.format(length - old, max_tail)
+  head = hyp[:old]
+  return head + tail[:length - old].tolist(), length if final else int(row[1]), row[2:3].view(np.float32)[0], head
+
+
+def _upload(engine, array, dtype):
+  """Host array -> device on the engine's stream (pinned staging from torch's caching host allocator: no wait for the stream's earlier
+  kernels, and the block is not reused before the copy has run)."""
+  host = torch.from_numpy(array).pin_memory()
+  with torch.cuda.stream(engine.stream):
+    return host.to(engine.device, non_blocking=True)
+
+
+# What an option adds to a `StreamingRecognizer`, made only when the option is given: its checks of the engine, its device state and
+# segments of the step's buffer, its state per slot, and the hooks the recogniser calls in a fixed order -- ``reset`` a slot at `open`,
+# ``seed`` the slots' entries of a fresh `StepResult`, ``launch`` for a pass (-> the kernels enqueued), ``read`` its share of the host copy.
+# ``src``: the pass's rows as every decoder takes them (logits, pitch, classes, the (stream, frame) of every row); ``table``: the
+# decoders' {first row, rows, limit, fresh} per stream.
+
+class _EndpointPart:
+  unfetched = 'endpointing: the utterances the step closes'          # what a step with fetch=False would lose
+
+  def __init__(self, rec, frames):                               # `Endpointing.frames`: (R, L, M, space)
+    lib, S, dev = _lib.load(), rec.max_streams, rec.device
+    self.engine, self.max_new, self.frames, self.n_pieces = rec.engine, rec.max_new, frames, rec.n_pieces
+    self.state = torch.zeros(S * int(lib.st_stream_endpoint_state_bytes()) // 4, dtype=torch.int32, device=dev)
+    self.score = torch.zeros(S * int(lib.st_stream_endpoint_score_bytes()) // 4, dtype=torch.float32, device=dev)
+    self.events, self.pieces = rec.layout.views('events', 'pieces')(rec.dec_out)
+    self.host = rec.layout.views('ids', 'counts', 'events', 'pieces')
+    self.open_ids = [[] for _ in range(S)]                       # the greedy ids of every slot's open utterance
+
+  def reset(self, slot):
+    self.open_ids[slot] = []
+
+  def seed(self, result, slots):
+    for s in slots:
+      result.finals[s], result.open_ids[s] = [], list(self.open_ids[s])
+
+  def launch(self, src, table, S, greedy_out):     # in the greedy decoder's place: events, and per utterance a table of its own (pieces)
+    ptr = self.engine._ptr
+    R, L, M, space = self.frames
+    call('st_ctc_greedy_endpoint_stream', *src, table, S, space, R, L, M, self.max_new, ptr(self.state), ptr(self.score), *greedy_out,
+         ptr(self.events), ptr(self.pieces), self.n_pieces, self.engine.stream_ptr)
+
+  def read(self, words, named, result):
+    """The events close utterances in order, each with the greedy ids up to its ``ids_end``.  -> ({slot: the `Utterance`s the pass
+    closed}, the slots whose last event dropped what was open: it held no speech, the pieces of the pass)."""
+    ids, counts, events, pieces = self.host(words)
+    closed, dropped = {}, set()
+    for s in named:
+      closed[s], prev, last_kind = [], 0, 0
+      for e in (events[s].tolist() if events[s, 0, 0] else ()):   # (most steps close nothing)
+        if e[0] == 0:
+          break
+        self.open_ids[s] += ids[s, prev:e[5]].tolist()
+        prev, last_kind = e[5], e[0]
+        if e[0] in Endpointing.KINDS:
+          closed[s].append(Utterance(e[7], Endpointing.KINDS[e[0]], e[1], e[2], e[3], e[4], self.open_ids[s],
+                                     float(np.asarray(e[6], np.int32).view(np.float32))))
+        self.open_ids[s] = []
+      self.open_ids[s] += ids[s, prev:counts[s]].tolist()
+      result.open_ids[s] = list(self.open_ids[s])
+      result.finals[s] += closed[s]
+      if last_kind == 3:
+        dropped.add(s)
+    return closed, dropped, pieces
+
+
+class _BeamPart:
+  def __init__(self, rec, endpoint, arena_words):                # the recogniser's `_EndpointPart` or None; `StreamBeam.arena_words`
+    beam, lib, S, dev, C = rec.beam, _lib.load(), rec.max_streams, rec.device, rec.num_classes
+    if beam.lm is not None and C != 29:
+      raise StreamError('a language model needs the 29 classes a-z \' space blank, the engine has {}'.format(C))
+    if not 2 <= C <= 32:
+      raise StreamError('the beam search supports 2..32 classes, the engine has {}'.format(C))
+    self.engine, self.beam, self.S = rec.engine, beam, S
+    self.lm_args = lambda: (self.lm_handle, beam.lm_weight, beam.word_count_weight, beam.valid_word_count_weight, beam.oov_score)
+    self.max_frames = seconds_to_frames(beam.max_seconds, rec.total_stride, rec.frame_rate)     # output frames a node pool holds
+    if endpoint is not None:
+      self.max_frames = endpoint.frames[2]                         # no utterance is longer: the pool is never full
+    self.lm_handle = beam.lm.device_handle(dev) if beam.lm is not None else None
+    from .engine_decode import beam_input_transform
+    self.transform = beam_input_transform(beam.input_transform)
+    state_bytes = int(lib.st_ctc_beam_stream_state_bytes(beam.beam_width, int(beam.lm is not None)))
+    self.bias = ()                                                 # the `_bias` entry points' two last arguments
+    if beam.hotwords is not None:
+      state_bytes = int(lib.st_ctc_beam_stream_bias_state_bytes(beam.beam_width, int(beam.lm is not None)))
+      nxt, gain, fin = self._bias_tables = beam.hotwords.device_tables(dev)
+      self._bias_struct = _lib.BiasTables(nxt.data_ptr(), gain.data_ptr(), fin.data_ptr(), beam.hotwords.n_states)
+      self.roots = torch.zeros(S, dtype=torch.int32, device=dev)
+      self.bias = (ctypes.byref(self._bias_struct), ctypes.c_void_p(self.roots.data_ptr()))
+    pool_bytes = int(lib.st_ctc_beam_stream_pool_bytes(self.max_frames, beam.beam_width))
+    self.ws_bytes = int(lib.st_ctc_beam_stream_ws(rec.max_rows[-1]))
+    self.state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
+    self.pool = torch.empty(S * pool_bytes // 8, dtype=torch.int64, device=dev)       # (a chain only holds written nodes)
+    self.ws = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
+    self.host = rec.layout.views('result', 'tail', *(('used',) if arena_words is not None else ()))
+    self.result, self.tail, *used = self.host(rec.dec_out)
+    self.arena_words = arena_words
+    if arena_words is not None:
+      # filled with a value no header holds, and again after every pass that wrote: behind the records that fit lies no stale one
+      self.arena = torch.full((max(arena_words, 1),), -1, dtype=torch.int32, device=dev)
+      self.nbest_args = (self.bias or (None, None)) + (beam.nbest, ctypes.c_void_p(self.arena.data_ptr()), arena_words,
+                                                       ctypes.c_void_p(used[0].data_ptr()))
+    # per slot: output frames decoded (checked against the pool before a launch), the last hypothesis read (its first `stable` ids are
+    # final: the device reports only what follows) and its log-probability, a read-out gave up, the hotword set (the lists' `bias`)
+    self.frames, self.stable, self.failed = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64), np.zeros(S, dtype=bool)
+    self.hyp, self.logp, self.slot_set = [[] for _ in range(S)], np.zeros(S, dtype=np.float32), np.zeros(S, dtype=np.int64)
+
+  def reset(self, slot, index):                                  # (the hotword set's root goes to the device ahead of the first step)
+    if self.beam.hotwords is not None:
+      with torch.cuda.stream(self.engine.stream):
+        self.roots[slot:slot + 1].fill_(self.beam.hotwords.root(index))
+    self.slot_set[slot] = index
+    self.frames[slot], self.failed[slot] = 0, False
+    self._clear(slot)
+
+  def _clear(self, slot):
+    self.hyp[slot], self.stable[slot], self.logp[slot] = [], 0, 0.0
+
+  def seed(self, result, slots):
+    for s in slots:
+      result.hyp[s], result.stable[s], result.logp[s] = list(self.hyp[s]), int(self.stable[s]), float(self.logp[s])
+      if self.arena_words is not None:
+        result.nbest[s], result.nbest_lost[s] = None, 0
+
+  def plan(self, named, fresh, fin, limit, first, count):
+    """Before a pass by table: the rows the searches will take (none at or past a finishing stream's limit) against the pools' capacity.
+    -> (the rows taken, the streams the read-out reports on)."""
+    taken = np.where(fin, np.clip(limit - first, 0, count), count)
+    full = self.frames[named] + taken > self.max_frames
+    if full.any():
+      k = int(np.flatnonzero(full)[0])
+      raise StreamError('stream {}: {} output frames would pass the beam search\'s node pool ({} frames, max_seconds = {})'.format(
+          int(named[k]), int(self.frames[named[k]] + taken[k]), self.max_frames, self.beam.max_seconds))
+    return taken, (count > 0) | fin | fresh
+
+  def launch_table(self, src, table, n_rows, fetch):             # the read-out only when fetched: what the device calls final, the host holds
+    bm, ptr, sp = self.beam, self.engine._ptr, self.engine.stream_ptr
+    biased = '_bias' if self.bias else ''
+    call('st_ctc_beam_stream_step' + biased, *src, table, n_rows, self.S, bm.beam_width, self.transform, *self.lm_args(),
+         ptr(self.state), ptr(self.pool), self.max_frames, ptr(self.ws), self.ws_bytes, sp, *self.bias)
+    if not fetch:
+      return 2 if n_rows else 1
+    name, extra = 'st_ctc_beam_stream_read' + biased, self.bias
+    if self.arena_words is not None:                               # one launch more: the counter's reset
+      name, extra = 'st_ctc_beam_stream_read_nbest', self.nbest_args
+    call(name, table, self.S, bm.beam_width, *self.lm_args(), ptr(self.state), ptr(self.pool), self.max_frames, ptr(self.tail),
+         bm.max_tail, ptr(self.result), sp, *extra)
+    return (2 if n_rows else 1) + (2 if self.arena_words is not None else 1)
+
+  def launch_pieces(self, src, pieces, n_pieces, n_rows):        # searches and read-outs piece by piece, no host wait in between
+    bm, ptr = self.beam, self.engine._ptr
+    name, extra = 'st_ctc_beam_stream_step_pieces' + ('_bias' if self.bias else ''), self.bias
+    if self.arena_words is not None:                               # the finals' lists into the arena; one launch more (the counter's reset)
+      name, extra = 'st_ctc_beam_stream_step_pieces_nbest', self.nbest_args
+    call(name, *src, ptr(pieces), n_pieces, n_rows, self.S, bm.beam_width, self.transform, *self.lm_args(), ptr(self.state),
+         ptr(self.pool), self.max_frames, ptr(self.ws), self.ws_bytes, ptr(self.tail), bm.max_tail, ptr(self.result),
+         self.engine.stream_ptr, *extra)
+    return (1 if self.arena_words is not None else 0) + (1 if n_rows else 0) + 2 * n_pieces
+
+  def read(self, words, named, fin, result, read=None, closed=None, dropped=(), pieces=None):
+    """The read-outs of a pass.  By table: one per stream that ``read`` names, a final where the stream finishes.  Endpointed (``closed`` /
+    ``dropped`` / ``pieces``: `_EndpointPart.read`): the pieces in order -- one marked reset starts from an empty hypothesis, every read-out
+    appends above the stable length the one before stored, one with a limit is a final, the next of ``closed[slot]``, and the search starts
+    again.  -> None, or the first `StreamError` of a search that gave up (the other streams' results are complete)."""
+    res, tail, *used = self.host(words)
+    arena, used = None, int(used[0][0]) if used else None
+    if used:                                                      # a pass with finals: one more copy (and wait) for what their lists wrote;
+      with torch.cuda.stream(self.engine.stream):                 # the fill value goes back in its place behind the copy
+        written = self.arena[:min(max(used, 0), self.arena_words)]
+        arena = written.cpu().numpy()
+        written.fill_(-1)
+    failed, listed, unwanted = None, [], set()
+    for k, s in enumerate(named):
+      if closed is None:                                          # {piece, final, reset} of every read-out the device made for the stream
+        walk = [(0, fin[k], False)] if read[k] else []
+      else:
+        walk = [(p, limit >= 0, reset) for p, (_, rows, limit, reset) in enumerate(pieces[:, s].tolist()) if rows or limit >= 0 or reset]
+      at = 0
+      for p, final, reset in walk:
+        if reset:
+          self._clear(s)
+        got = read_beam(self.hyp[s], self.stable[s], res[p, s], tail[p, s], self.beam.max_tail, final)
+        if isinstance(got, str):
+          self.failed[s] = True
+          failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, got))
+          unwanted.update((q, s) for q in range(p, len(res)))     # (the device wrote this final's record, and its later ones', all the same)
+          break
+        (self.hyp[s], self.stable[s], self.logp[s], head), utt = got, None
+        if final and closed is not None:                          # the whole-utterance search on the utterance's rows alone
+          utt, at = closed[s][at], at + 1
+          utt.ids, utt.logp = self.hyp[s], float(self.logp[s])
+          self._clear(s)
+        if final and used is not None:
+          listed.append((s, (p, s), head, utt))
+      if fin[k] and s in dropped:                                 # what was open at the end held no speech: dropped like any discard
+        self._clear(s)
+      result.hyp[s], result.stable[s], result.logp[s] = list(self.hyp[s]), int(self.stable[s]), float(self.logp[s])
+    if listed:                                                    # (lists, then rescoring: the words are those of the ids that are reported)
+      self.final_lists(arena, used, listed, result, unwanted)
+    return failed
+
+  def final_lists(self, arena, used, listed, result, unwanted=()):
+    """The N-best lists of the finals a pass closed, ``listed`` = [(slot, (piece, slot), the ids the host holds below the record's stable
+    length, the `Utterance` or -- `finish` without endpointing -- None)]: the arena's records become lists (`nbest.read_arena`), get
+    their parts together (`nbest.components`) and with ``rescore`` are re-ranked together, the reported ids and log-probability becoming
+    the first hypothesis's.  A record that did not fit counts in ``result.nbest_lost``.  ``unwanted``: the keys of finishing read-outs the
+    host gave up on; their records are stepped over, so that one stream's failure never costs the others their lists."""
+    from . import nbest as nb
+    bm = self.beam
+    found, _ = nb.read_arena(arena if arena is not None else np.zeros(0, np.int32), used if arena is not None else 0,
+                             {key: head for _, key, head, _ in listed}, skip=unwanted)
+    have = [f for f in listed if f[1] in found]
+    for slot, key, _, _ in listed:
+      if key not in found:
+        result.nbest_lost[slot] += 1
+    if not have:
+      return
+    hot = None
+    if bm.hotwords is not None:                                   # set 0 is the empty set: no bias
+      hot = [bm.hotwords.tables(int(self.slot_set[slot])) if self.slot_set[slot] else None for slot, _, _, _ in have]
+    lists = nb.components(self.engine, bm.lm, [found[key] for _, key, _, _ in have],
+                          (bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight), hotwords=hot)
+    if bm.rescore is not None:
+      r = bm.rescore
+      lists = nb.rescored(lists, self.engine, r['language_model'], r['lm_weight'], r['word_count_weight'], r['valid_word_count_weight'])
+    for (slot, _, _, utt), hyps in zip(have, lists):
+      if utt is not None:
+        utt.nbest = hyps
+        if bm.rescore is not None:
+          utt.ids, utt.logp = list(hyps[0]['ids']), float(hyps[0]['log_prob'])
+      else:
+        result.nbest[slot] = hyps
+        if bm.rescore is not None:
+          self.hyp[slot], self.logp[slot] = list(hyps[0]['ids']), hyps[0]['log_prob']
+          self.stable[slot] = len(self.hyp[slot])
+          result.hyp[slot], result.stable[slot], result.logp[slot] = list(self.hyp[slot]), int(self.stable[slot]), float(hyps[0]['log_prob'])
+
+
+class _WordsPart:
+  def __init__(self, rec, endpoint):                             # the recogniser's `_EndpointPart` (`FinalWords.check` made sure of it)
+    self.engine, self.want, self.S, self.C = rec.engine, rec.words, rec.max_streams, rec.num_classes
+    self.space = endpoint.frames[3]
+    from . import alignment                                        # frames_to_seconds(f, rate) = f * total_stride / frames per second
+    self.rate = 2.0 * alignment.HOP_LENGTH * (100.0 if rec.frame_rate is None else rec.frame_rate) / rec.total_stride
+    # the ring of logits rows per stream the finals' lattices read (st_stream_keep_rows: M + the rows of a pass)
+    self.ring_cap = int(_lib.load().st_stream_keep_rows(endpoint.frames[2], rec.max_new))
+    self.ring = torch.zeros(self.S * self.ring_cap * 32, dtype=torch.float32, device=rec.device)
+
+  def launch(self, src, n_rows):                                 # the pass's rows into the ring
+    call('st_stream_keep_f32', *src, n_rows, self.S, self.engine._ptr(self.ring), self.ring_cap, self.engine.stream_ptr)
+    return 1
+
+  def read(self, finals):
+    """The word times and confidences of the finals a pass closed, ``[(slot, Utterance)]``: one table (`final_jobs`), one upload, the ring
+    lattices for all of them, one copy back -- the pass's second wait (the next pass's keep overwrites the ring).  -> the kernels enqueued."""
+    from . import alignment
+    from .engine_decode import MAX_ALIGN_LABELS
+    want, launches = self.want, 0
+    for _, u in finals:
+      if len(u.ids) == 0:
+        u.words = []
+        if want.timestamps:
+          u.spans = np.zeros((0, 2), dtype=np.int32)
+    space = self.space if want.confidence else None
+    tab = final_jobs([(s, u.start_frame, u.end_frame, u.ids) for s, u in finals], space, MAX_ALIGN_LABELS)
+    J = len(tab['index'])
+    if not J:
+      return 0
+    lib = _lib.load()
+    eng, S, C = self.engine, self.S, self.C
+    N, W, T, max_len = int(tab['offsets'][-1]), len(tab['word_spans']), tab['max_rows'], tab['max_len']
+    parts = [tab['jobs'].reshape(-1), tab['ids'], tab['offsets'], tab['word_spans'].reshape(-1), np.zeros(1, np.int32)]
+    offs = np.cumsum([0] + [p.size for p in parts])
+    table = _upload(eng, np.concatenate(parts), torch.int32)
+    tptr = lambda i: ctypes.c_void_p(table.data_ptr() + 4 * int(offs[i]))
+    ptr, sp = eng._ptr, eng.stream_ptr
+    with torch.cuda.stream(eng.stream):
+      # the outputs in one buffer, one copy back: log_conf [W] | log_prob [J] (doubles) | spans [N][2] | score [J] | status [J] | status [J]
+      out = torch.zeros(2 * (W + J) + 2 * N + 3 * J, dtype=torch.int32, device=eng.device)
+      at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
+      o_spans = 2 * (W + J)
+      o_score, o_st_align, o_st_conf = o_spans + 2 * N, o_spans + 2 * N + J, o_spans + 2 * N + 2 * J
+      if want.timestamps:
+        need = int(lib.st_ctc_align_ws(J, T, max_len))
+        ws = torch.empty(need // 4 + 16, dtype=torch.int32, device=eng.device)
+        call('st_ctc_align_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, at(o_spans), None,
+             at(o_score), at(o_st_align), ptr(ws), ws.numel() * 4, sp)
+        launches += 3
+      if want.confidence:
+        need = int(lib.st_ctc_word_conf_ws(J, T, max_len, J + W))
+        ws2 = torch.empty(need // 4 + 16, dtype=torch.int32, device=eng.device)
+        call('st_ctc_word_conf_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, space, tptr(3), W,
+             at(2 * W), at(0), at(o_st_conf), ptr(ws2), ws2.numel() * 4, sp)
+        launches += 3
+      host = out.cpu().numpy()                                     # the second wait of a pass that closed something
+    log_conf, log_prob = host[:2 * W].view(np.float64), host[2 * W:o_spans].view(np.float64)
+    spans, score = host[o_spans:o_score].reshape(N, 2), host[o_score:o_st_align].view(np.float32)
+    first_word = np.concatenate([[0], np.cumsum(tab['words'])]).astype(np.int64)
+    for j, i in enumerate(tab['index']):
+      u = finals[i][1]
+      if host[o_st_align + j] != 0 or host[o_st_conf + j] != 0:     # the ids do not fit the rows: nothing, as offline
+        continue
+      probs = None
+      if want.timestamps:
+        u.spans = spans[tab['offsets'][j]:tab['offsets'][j + 1]].copy()
+        u.align_score = float(score[j])
+      if want.confidence:
+        probs = np.exp(log_conf[first_word[j]:first_word[j + 1]]).tolist()
+        u.confidence = dict(log_prob=float(log_prob[j]), words=probs)
+      if want.timestamps:
+        u.words = alignment.timed_words(u.ids, u.spans + u.start_frame, self.rate, confidence=probs)
+      else:
+        u.words = alignment.confident_words(u.ids, probs)
+    return launches
+
+
+class _SpotPart:
+  unfetched = 'a spotter: the hits the step finds'
+
+  def __init__(self, rec):
+    spot, lib, S, dev = rec.spot, _lib.load(), rec.max_streams, rec.device
+    self.engine, self.spot, self.S = rec.engine, spot, S
+    self.hold = spot.frames(rec.total_stride, rec.frame_rate)
+    self.plan, self.waves = spot.plan(rec.num_classes)             # the host copy: the step reads its header
+    self.plan_dev = torch.from_numpy(self.plan).to(dev)
+    self.plan_ptr = self.plan.ctypes.data_as(ctypes.c_void_p)
+    call('st_ctc_spot_stream_plan_bind', self.plan_ptr, ctypes.c_void_p(self.plan_dev.data_ptr()))
+    self.state = torch.zeros(S * int(lib.st_ctc_spot_stream_state_bytes(self.plan_ptr)) // 8, dtype=torch.int64, device=dev)
+    self.host = rec.layout.views('spot_events', 'spot_counts')
+    self.events, self.counts = self.host(rec.dec_out)
+
+  def seed(self, result, slots):
+    for s in slots:
+      result.hits[s], result.hits_lost[s] = [], 0
+
+  def launch(self, src, table, n_rows):                          # by the greedy decoder's table: endpointing does not reset spotting
+    ptr = self.engine._ptr
+    call('st_ctc_spot_stream_step', *src, table, n_rows, self.S, self.plan_ptr, self.spot.threshold, self.hold, ptr(self.state),
+         ptr(self.events), self.spot.max_events, ptr(self.counts), self.engine.stream_ptr)
+    return 2                                                       # the memset of the counts and the lattices
+
+  def read(self, words, named, result):
+    found = read_hits(self.spot.keywords, *self.host(words), self.spot.max_events)
+    for s in named:
+      result.hits[s] += found[s][0]
+      result.hits_lost[s] += found[s][1]
+
+
+class _FollowPart:
+  unfetched = 'a follower: the words the step reaches'
+
+  def __init__(self, rec):
+    fw, lib, S, dev = rec.follow, _lib.load(), rec.max_streams, rec.device
+    if not 2 <= rec.num_classes <= 32:
+      raise StreamError('following supports 2..32 classes, the engine has {}'.format(rec.num_classes))
+    fw.space(rec.num_classes)
+    self.engine, self.follow, self.S, self.max_rows = rec.engine, fw, S, rec.max_rows[-1]
+    self.confirm = fw.frames(rec.total_stride, rec.frame_rate)
+    self.state = torch.zeros(S * int(lib.st_ctc_follow_stream_state_bytes(fw.max_labels)) // 8, dtype=torch.float64, device=dev)
+    self.ws_bytes = int(lib.st_ctc_follow_stream_ws(self.max_rows, fw.max_labels, S))
+    self.ws = torch.empty(self.ws_bytes // 8 + 1, dtype=torch.float64, device=dev)
+    self.host = rec.layout.views('follow_records', 'follow_events', *(('follow_trace',) if fw.trace else ()))
+    self.records, self.events, self.trace = (self.host(rec.dec_out) + [None])[:3]
+    self.scripts = [None] * S                                      # per slot (ids, word starts, words) or None
+    self.frames = np.zeros(S, dtype=np.int64)                      # rows each followed stream has consumed (for the trace)
+    self._set_scripts()
+
+  def _set_scripts(self):
+    """The scripts of all slots as CSR arrays on the device: [script offsets S + 1 | word offsets S + 1 | ids | word starts], one
+    upload on the engine's stream (a slot without a script has an empty one and sits out)."""
+    S = self.S
+    ids = [sc[0] if sc else [] for sc in self.scripts]
+    starts = [sc[1] if sc else [] for sc in self.scripts]
+    offs, woffs = np.cumsum([0] + [len(i) for i in ids]), np.cumsum([0] + [len(w) for w in starts])
+    flat = np.concatenate([offs, woffs, [i for l in ids for i in l], [0], [w for l in starts for w in l], [0]]).astype(np.int32)
+    self.table = _upload(self.engine, flat, torch.int32)
+    base = self.table.data_ptr()
+    at = [0, S + 1, 2 * (S + 1), 2 * (S + 1) + int(offs[-1]) + 1]
+    self.script_ptrs = tuple(ctypes.c_void_p(base + 4 * a) for a in (at[2], at[0], at[3], at[1]))   # ids, offsets, starts, offsets
+
+  def reset(self, slot, parsed):                                 # `ScriptFollower.script` of the slot's script; None: not followed
+    if parsed is not None or self.scripts[slot] is not None:
+      self.scripts[slot], self.frames[slot] = parsed, 0
+      self._set_scripts()
+
+  def seed(self, result, slots):
+    for s in slots:
+      if self.scripts[s] is not None:
+        result.follow[s], result.reached[s], result.reached_lost[s] = None, [], 0
+
+  def launch(self, src, table, n_rows, longest):                 # as the spotter; ``longest``: the most rows of a stream in the pass
+    fw, ptr = self.follow, self.engine._ptr
+    call('st_ctc_follow_stream_step', *src, table, n_rows, self.max_rows, longest, self.S, *self.script_ptrs, fw.max_labels,
+         self.confirm, ptr(self.state), ptr(self.events), fw.max_events, ptr(self.records),
+         ptr(self.trace) if fw.trace else None, ptr(self.ws), self.ws_bytes, self.engine.stream_ptr)
+    return (1 if n_rows else 0) + 2 * max(-(-longest // 64), 1)    # the softmax, then tiles and read-out per 64 rows
+
+  def read(self, words, named, row0, result):                    # ``row0``: every named stream's first row in the pass (for the trace)
+    fw, (records, events, *trace) = self.follow, self.host(words)
+    followed = read_follow(records, events, fw.max_events, self.scripts, [s for s in named if self.scripts[s] is not None])
+    for k, s in enumerate(named):
+      if s not in followed:
+        continue
+      state, reached, lost = followed[s]
+      if fw.trace:
+        took = state['frames'] - int(self.frames[s])               # (rows at or past a finishing stream's limit are not consumed)
+        state['trace'] = (result.follow[s]['trace'] if result.follow.get(s) else []) + \
+            trace[0][int(row0[k]):int(row0[k]) + took].tolist()
+      self.frames[s] = state['frames']
+      result.follow[s] = state
+      result.reached[s] += reached
+      result.reached_lost[s] += lost
+
+
 class StreamingRecognizer:
   """Owns the per-layer windows, the workspace and the decoder state of up to ``max_streams`` streams on the engine's device.
 
@@ -625,19 +1106,14 @@ class StreamingRecognizer:
       if not isinstance(words, FinalWords):
         raise StreamError('words must be a FinalWords, got {!r}'.format(type(words).__name__))
       words.check(endpoint, self.num_classes, endpoint.frames(self.total_stride, self.num_classes, self.frame_rate)[3] if endpoint is not None else -1)
-    if beam and beam.nbest is not None:
-      # the arena of a pass's lists: by default one final per stream, `nbest` hypotheses with tails of max_tail labels each
-      from .nbest import ARENA_HEADER
-      self.nbest_words = (self.max_streams * (ARENA_HEADER + beam.nbest * (2 + beam.max_tail)) if beam.nbest_words is None
-                          else beam.nbest_words)
-      if self.nbest_words >= 2 ** 31:
-        raise StreamError('the arena of the N-best lists would hold {} words (nbest_words)'.format(self.nbest_words))
+    arena_words = beam.arena_words(self.max_streams) if beam is not None else None
     L, S = len(self.layers), self.max_streams
     self.in_max = max_new_frames(self.geo, self.max_chunk)
     self.cap = [l.width + self.in_max[i] for i, l in enumerate(self.layers)]            # retained (< width) + new
     self.max_rows = [S * self.in_max[i + 1] for i in range(L)]
     self.max_new = self.in_max[L]
     dev = self.device
+    self._endpoint = self._beam = self._spot = self._words = self._follow = None     # the options' parts
     with torch.cuda.stream(engine.stream):
       self.windows = [torch.zeros(S * self.cap[i] * l.cin_pitch, dtype=torch.float32, device=dev) for i, l in enumerate(self.layers)]
       self.logits_pitch = self.layers[-1].cout_pitch
@@ -647,130 +1123,48 @@ class StreamingRecognizer:
       self.workspace = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
       self.dec_state = torch.zeros(S * 4, dtype=torch.int32, device=dev)
       self.dec_score = torch.zeros(S, dtype=torch.float64, device=dev)
-      # the decoder's outputs in one buffer, so that a step's results come back with one copy: [ids | counts | scores]
-      # (with a beam search: ... | result [S][4] | tail [S][max_tail])
-      # (with endpointing: [ids | counts | scores | events [S][P][8] | pieces [P][S][4]], then result [P][S][4] | tail [P][S][max_tail])
-      greedy_words = S * self.max_new + 2 * S
-      total_stride = self.total_stride
       self.n_pieces = 1
-      if endpoint is not None:
-        self.ep_frames = endpoint.frames(total_stride, self.num_classes, self.frame_rate)
+      if endpoint is not None:                                     # (the pieces of a pass size the step's buffer)
+        ep_frames = endpoint.frames(self.total_stride, self.num_classes, self.frame_rate)
         if not 2 <= self.num_classes <= 64:
           raise StreamError('endpointing supports 2..64 classes, the engine has {}'.format(self.num_classes))
-        self.n_pieces = P = int(lib.st_stream_endpoint_pieces(self.max_new, *self.ep_frames[:3]))
-        self.ep_state = torch.zeros(S * int(lib.st_stream_endpoint_state_bytes()) // 4, dtype=torch.int32, device=dev)
-        self.ep_score = torch.zeros(S * int(lib.st_stream_endpoint_score_bytes()) // 4, dtype=torch.float32, device=dev)
-        self.ep_words = S * P * 8 + P * S * 4
-        greedy_words += self.ep_words
-      if words is not None:
-        # the ring of logits rows per stream the finals' lattices read (st_stream_keep_rows: M + the rows of a pass)
-        self.ring_cap = int(lib.st_stream_keep_rows(self.ep_frames[2], self.max_new))
-        self.ring = torch.zeros(S * self.ring_cap * 32, dtype=torch.float32, device=dev)
-      # (with a spotter, behind everything else: counts [S] | events [S][max_events][8])
-      self.spot_at = greedy_words + (self.n_pieces * S * (4 + beam.max_tail) if beam else 0)
-      # (with N-best lists, the last word: the words the step's lists asked for -- the arena itself is copied only when that is not 0)
-      self.spot_end = self.spot_at + (S * (1 + 8 * spot.max_events) if spot else 0)
-      # (with a follower, behind that from an even word on: records [S][16] | events [S][max_events][2] | with trace, c per row)
-      self.follow_at = self.spot_end + (self.spot_end & 1 if follow else 0)
-      self.nbest_at = self.follow_at + (S * (16 + 2 * follow.max_events) + (self.max_rows[-1] if follow.trace else 0) if follow else 0)
-      lists = bool(beam) and beam.nbest is not None
-      self.dec_out = torch.zeros(self.nbest_at + (1 if lists else 0), dtype=torch.int32, device=dev)
-      if spot is not None:
-        self.spot_hold = spot.frames(total_stride, self.frame_rate)
-        self.spot_plan, self.spot_waves = spot.plan(self.num_classes)      # the host copy: the step reads its header
-        self.spot_plan_dev = torch.from_numpy(self.spot_plan).to(dev)
-        call('st_ctc_spot_stream_plan_bind', self.spot_plan.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.spot_plan_dev.data_ptr()))
-        state_bytes = int(lib.st_ctc_spot_stream_state_bytes(self.spot_plan.ctypes.data_as(ctypes.c_void_p)))
-        self.spot_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
-        self.spot_counts = self.dec_out[self.spot_at:self.spot_at + S]
-        self.spot_events = self.dec_out[self.spot_at + S:self.nbest_at]
-      if follow is not None:
-        if not 2 <= self.num_classes <= 32:
-          raise StreamError('following supports 2..32 classes, the engine has {}'.format(self.num_classes))
-        follow.space(self.num_classes)
-        self.follow_confirm = follow.frames(total_stride, self.frame_rate)
-        state_bytes = int(lib.st_ctc_follow_stream_state_bytes(follow.max_labels))
-        self.follow_state = torch.zeros(S * state_bytes // 8, dtype=torch.float64, device=dev)
-        self.follow_ws_bytes = int(lib.st_ctc_follow_stream_ws(self.max_rows[-1], follow.max_labels, S))
-        self.follow_ws = torch.empty(self.follow_ws_bytes // 8 + 1, dtype=torch.float64, device=dev)
-        at = self.follow_at
-        self.follow_result = self.dec_out[at:at + 16 * S]
-        self.follow_events = self.dec_out[at + 16 * S:at + S * (16 + 2 * follow.max_events)]
-        self.follow_trace = self.dec_out[at + S * (16 + 2 * follow.max_events):self.nbest_at] if follow.trace else None
-        self._scripts = [None] * S                                   # per slot (ids, word starts, words) or None
-        self._follow_frames = np.zeros(S, dtype=np.int64)            # rows each followed stream has consumed (for the trace)
-        self._set_scripts()
-      self.ids = self.dec_out[:S * self.max_new]
-      self.new_count = self.dec_out[S * self.max_new:S * self.max_new + S]
-      self.neg_sum = self.dec_out[S * self.max_new + S:S * self.max_new + 2 * S].view(torch.float32)
+        self.n_pieces = int(lib.st_stream_endpoint_pieces(self.max_new, *ep_frames[:3]))
+      # the decoders' outputs in one buffer, so that a step's results come back with one copy
+      opt = lambda option, name: getattr(option, name) if option is not None else None
+      self.layout = StepLayout(S, self.max_new, n_pieces=self.n_pieces if endpoint is not None else None, max_tail=opt(beam, 'max_tail'),
+                               spot_events=opt(spot, 'max_events'), follow_events=opt(follow, 'max_events'),
+                               trace_rows=self.max_rows[-1] if opt(follow, 'trace') else None, lists=arena_words is not None)
+      self.dec_out = torch.zeros(self.layout.size, dtype=torch.int32, device=dev)
+      self._host = self.layout.views('ids', 'counts', 'scores')
+      ids, counts, scores = self._host(self.dec_out)
+      self._greedy_out = (engine._ptr(ids), self.max_new, engine._ptr(counts), engine._ptr(scores))   # as both greedy kernels take them
       if endpoint is not None:
-        self.ep_events = self.dec_out[S * self.max_new + 2 * S:S * self.max_new + 2 * S + S * P * 8]
-        self.ep_pieces = self.dec_out[S * self.max_new + 2 * S + S * P * 8:greedy_words]
-      if beam:
-        if beam.lm is not None and self.num_classes != 29:
-          raise StreamError('a language model needs the 29 classes a-z \' space blank, the engine has {}'.format(self.num_classes))
-        if not 2 <= self.num_classes <= 32:
-          raise StreamError('the beam search supports 2..32 classes, the engine has {}'.format(self.num_classes))
-        per_second = 100.0 if self.frame_rate is None else self.frame_rate               # (10 ms hop unless told)
-        self.max_frames = int(np.ceil(beam.max_seconds * per_second / total_stride - 1e-9))   # output frames
-        if endpoint is not None:
-          self.max_frames = self.ep_frames[2]                        # no utterance is longer: the pool is never full
-        self._lm_handle = beam.lm.device_handle(dev) if beam.lm is not None else None
-        from .engine_decode import beam_input_transform
-        self._transform = beam_input_transform(beam.input_transform)
-        state_bytes = int(lib.st_ctc_beam_stream_state_bytes(beam.beam_width, int(beam.lm is not None)))
-        self._bias = ()                                              # the `_bias` entry points' two last arguments
-        if beam.hotwords is not None:
-          state_bytes = int(lib.st_ctc_beam_stream_bias_state_bytes(beam.beam_width, int(beam.lm is not None)))
-          nxt, gain, fin = self._bias_tables = beam.hotwords.device_tables(dev)
-          self._bias_struct = _lib.BiasTables(nxt.data_ptr(), gain.data_ptr(), fin.data_ptr(), beam.hotwords.n_states)
-          self.beam_roots = torch.zeros(S, dtype=torch.int32, device=dev)
-          self._bias = (ctypes.byref(self._bias_struct), ctypes.c_void_p(self.beam_roots.data_ptr()))
-        pool_bytes = int(lib.st_ctc_beam_stream_pool_bytes(self.max_frames, beam.beam_width))
-        self.beam_ws_bytes = int(lib.st_ctc_beam_stream_ws(self.max_rows[-1]))
-        self.beam_state = torch.zeros(S * state_bytes // 8, dtype=torch.int64, device=dev)
-        self.beam_pool = torch.empty(S * pool_bytes // 8, dtype=torch.int64, device=dev)     # (a chain only holds written nodes)
-        self.beam_ws = torch.empty(self.beam_ws_bytes // 4, dtype=torch.float32, device=dev)
-        self.beam_result = self.dec_out[greedy_words:greedy_words + self.n_pieces * 4 * S]
-        self.beam_tail = self.dec_out[greedy_words + self.n_pieces * 4 * S:self.spot_at]
-        if beam.nbest is not None:
-          # filled with a value no header holds, and again after every pass that wrote: behind the records that fit lies no stale one
-          self.nbest_arena = torch.full((max(self.nbest_words, 1),), -1, dtype=torch.int32, device=dev)
-          self.nbest_used = self.dec_out[self.nbest_at:]
-          self._nbest_args = (self._bias or (None, None)) + (beam.nbest, ctypes.c_void_p(self.nbest_arena.data_ptr()), self.nbest_words,
-                                                             ctypes.c_void_p(self.nbest_used.data_ptr()))
+        self._endpoint = _EndpointPart(self, ep_frames)
+      if words is not None:
+        self._words = _WordsPart(self, self._endpoint)
+        self.ring_cap = self._words.ring_cap
+      if spot is not None:
+        self._spot = _SpotPart(self)
+        self.spot_waves = self._spot.waves
+      if follow is not None:
+        self._follow = _FollowPart(self)
+      if beam is not None:
+        self._beam = _BeamPart(self, self._endpoint, arena_words)
+        self.max_frames = self._beam.max_frames
       table = np.zeros(L * 2, dtype=np.int64)                                          # {float* windows, int32 cap, int32 c_pitch}
       for i, l in enumerate(self.layers):
         table[2 * i] = self.windows[i].data_ptr()
         table[2 * i + 1] = self.cap[i] | (l.cin_pitch << 32)
       self.layer_table = torch.from_numpy(table).to(dev)
+    self._seeders = [p for p in (self._endpoint, self._beam, self._spot, self._follow) if p is not None]
     # the host's counters: per stream and layer the frames received and emitted, per stream the input frames in all
     self._open, self._fresh, self._finished = (np.zeros(S, dtype=bool) for _ in range(3))
     self._n, self._e = np.zeros((S, L), dtype=np.int64), np.zeros((S, L), dtype=np.int64)
     self._total = np.zeros(S, dtype=np.int64)
-    # beam search: output frames decoded per stream (the pool's capacity is checked before a launch), the last hypothesis read
-    # (its first `_stable` ids are final: the device reports only what follows them), and the streams a read-out gave up on
-    self._frames, self._stable, self._failed = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64), np.zeros(S, dtype=bool)
-    self._hyp, self._logp = [[] for _ in range(S)], np.zeros(S, dtype=np.float32)
-    self._open_ids = [[] for _ in range(S)]                      # endpointing: the greedy ids of the open utterance
-    self._set = np.zeros(S, dtype=np.int64)                      # the hotword set every slot was opened with (the lists' `bias`)
     self._info = np.zeros((L, S, 4), dtype=np.int32)             # {base, n, base, 0} of every stream between steps
     self.launches = 0            # kernels enqueued by the last pass (products count two: slices + epilogue)
 
   # -- slots --
-
-  def _set_scripts(self):
-    """The scripts of all slots as CSR arrays on the device: [script offsets S + 1 | word offsets S + 1 | ids | word starts], one
-    upload on the engine's stream (a slot without a script has an empty one and sits out)."""
-    S = self.max_streams
-    ids = [sc[0] if sc else [] for sc in self._scripts]
-    starts = [sc[1] if sc else [] for sc in self._scripts]
-    offs, woffs = np.cumsum([0] + [len(i) for i in ids]), np.cumsum([0] + [len(w) for w in starts])
-    flat = np.concatenate([offs, woffs, [i for l in ids for i in l], [0], [w for l in starts for w in l], [0]]).astype(np.int32)
-    self.follow_table = self._upload(flat, torch.int32)
-    base = self.follow_table.data_ptr()
-    at = [0, S + 1, 2 * (S + 1), 2 * (S + 1) + int(offs[-1]) + 1]
-    self._follow_ptrs = tuple(ctypes.c_void_p(base + 4 * a) for a in (at[2], at[0], at[3], at[1]))   # ids, offsets, starts, offsets
 
   def open(self, hotwords=None, script=None):
     """``script`` (with a `ScriptFollower`): the text, or the ids, the stream is to be followed through (`ScriptFollower.script`);
@@ -792,18 +1186,15 @@ class StreamingRecognizer:
     if not len(free):
       raise StreamError('all {} streams are open'.format(self.max_streams))
     i = int(free[0])
-    if sets is not None:
-      with torch.cuda.stream(self.engine.stream):
-        self.beam_roots[i:i + 1].fill_(sets.root(int(index)))
-    self._set[i] = int(index) if sets is not None else 0
     self._open[i], self._fresh[i], self._finished[i] = True, True, False     # the first step resets the slot's decoder state;
     self._n[i], self._e[i], self._total[i] = 0, 0, 0                           # the windows need no clearing: frames outside
     self._info[:, i] = 0                                                       # [0, n) are never read
-    self._frames[i], self._stable[i], self._failed[i], self._hyp[i], self._logp[i] = 0, 0, False, [], 0.0
-    self._open_ids[i] = []
-    if self.follow is not None and (parsed is not None or self._scripts[i] is not None):
-      self._scripts[i], self._follow_frames[i] = parsed, 0
-      self._set_scripts()
+    if self._beam is not None:
+      self._beam.reset(i, int(index) if sets is not None else 0)
+    if self._endpoint is not None:
+      self._endpoint.reset(i)
+    if self._follow is not None:
+      self._follow.reset(i, parsed)
     return i
 
   def close(self, slot):
@@ -816,21 +1207,18 @@ class StreamingRecognizer:
       raise StreamError('stream {} is not open'.format(slot))
     if self._finished[slot] and not allow_finished:
       raise StreamError('stream {} has been finished: close it and open a new one'.format(slot))
-    if self._failed[slot] and not allow_finished:
+    if self._beam is not None and self._beam.failed[slot] and not allow_finished:
       raise StreamError('stream {}: its beam search has failed: close it and open a new one'.format(slot))
 
   # -- steps --
 
   def step(self, feeds, return_logits=False, fetch=True):
     """``feeds``: {slot: float array [t, C]} (t may be 0).  A feed longer than ``max_chunk_frames`` is split into several passes.
-    ``fetch=False`` only enqueues (no host wait at all) and returns None: the new ids of such a step are dropped (with endpointing
-    it is refused: the finals would be lost)."""
-    if self.endpoint is not None and not fetch:
-      raise StreamError('fetch=False with endpointing: the utterances the step closes would be lost')
-    if self.spot is not None and not fetch:
-      raise StreamError('fetch=False with a spotter: the hits the step finds would be lost')
-    if self.follow is not None and not fetch:
-      raise StreamError('fetch=False with a follower: the words the step reaches would be lost')
+    ``fetch=False`` only enqueues (no host wait at all) and returns None: the new ids of such a step are dropped (with endpointing,
+    a spotter or a follower it is refused: what they report would be lost)."""
+    for part in (self._endpoint, self._spot, self._follow):
+      if part is not None and not fetch:
+        raise StreamError('fetch=False with {} would be lost'.format(part.unfetched))
     return self._run(feeds, (), return_logits, fetch)
 
   def finish(self, slot, return_logits=False):
@@ -852,18 +1240,13 @@ class StreamingRecognizer:
     for slot in finishing:
       self._slot(slot)
     result = StepResult()
-    for slot in list(arrays) + [int(s) for s in finishing]:
+    slots = list(arrays) + [int(s) for s in finishing]
+    for slot in slots:
       result.ids[slot], result.score[slot] = [], 0.0
-      if self.endpoint is not None:
-        result.finals[slot], result.open_ids[slot] = [], list(self._open_ids[slot])
-      if self.beam:
-        result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(self._logp[slot])
-      if self.spot is not None:
-        result.hits[slot], result.hits_lost[slot] = [], 0
-      if self.follow is not None and self._scripts[slot] is not None:
-        result.follow[slot], result.reached[slot], result.reached_lost[slot] = None, [], 0
       if return_logits:
         result.logits[slot] = []
+    for part in self._seeders:
+      part.seed(result, slots)
     longest = max([a.shape[0] for a in arrays.values()] + [0])
     passes = max(-(-longest // self.max_chunk), 1)
     for p in range(passes):
@@ -880,24 +1263,18 @@ class StreamingRecognizer:
   def _pass(self, part, finishing, result, return_logits, fetch):
     eng, L, S = self.engine, len(self.layers), self.max_streams
     named = np.asarray(sorted(set(part) | set(int(s) for s in finishing)), dtype=np.int64)
-    # 1. size the step on the host (all named streams at once)
+    # 1. size the step on the host (all named streams at once); whatever is refused is refused here
     new = np.asarray([part[s].shape[0] if s in part else 0 for s in named], dtype=np.int64)
-    fin = np.isin(named, [int(s) for s in finishing])
+    fin, fresh = np.isin(named, [int(s) for s in finishing]), self._fresh[named]
     first, count, base, n_after, new_base = plan_many(self.geo, self._n[named], self._e[named], new, fin)
     over = (n_after - base > np.asarray(self.cap)) | (count > np.asarray(self.in_max[1:]))
     if over.any():
       k, l = np.argwhere(over)[0]
       raise StreamError('stream {}: layer {} would overrun its window ({} frames, capacity {})'.format(
           int(named[k]), int(l), int(n_after[k, l] - base[k, l]), self.cap[l]))
-    limit = np.where(fin, (self._total[named] + new) // 2, -1)
-    if self.beam and self.endpoint is None:
-      # rows the searches will take (those at or past a finishing stream's limit are not decoded) against the pools' capacity
-      taken = np.where(fin, np.clip(limit - first[:, -1], 0, count[:, -1]), count[:, -1])
-      full = self._frames[named] + taken > self.max_frames
-      if full.any():
-        k = int(np.flatnonzero(full)[0])
-        raise StreamError('stream {}: {} output frames would pass the beam search\'s node pool ({} frames, max_seconds = {})'.format(
-            int(named[k]), int(self._frames[named[k]] + taken[k]), self.max_frames, self.beam.max_seconds))
+    limit = np.where(fin, decode_limit(self._total[named] + new), -1)
+    by_table = self._beam is not None and self._endpoint is None   # the searches take the greedy decoder's table, not the endpointer's pieces
+    taken, read = self._beam.plan(named, fresh, fin, limit, first[:, -1], count[:, -1]) if by_table else (None, None)
     info = self._info.copy()                                     # streams that sit this step out keep their windows
     info[:, named, 0], info[:, named, 1], info[:, named, 2] = base.T, n_after.T, new_base.T
 
@@ -910,23 +1287,23 @@ class StreamingRecognizer:
     row0 = np.cumsum(count[:, -1]) - count[:, -1]
     dec = np.zeros((S, 4), dtype=np.int32)
     dec[:, 2] = -1
-    dec[named, 0], dec[named, 1], dec[named, 3] = row0, count[:, -1], self._fresh[named]
-    dec[named, 2] = np.where(fin, (self._total[named] + new) // 2, -1)
+    dec[named, 0], dec[named, 1], dec[named, 2], dec[named, 3] = row0, count[:, -1], limit, fresh
     feed_rows, _ = table_rows(new, self._n[named, 0] - base[:, 0])
     # 2. one table, one upload
     parts = [info.reshape(-1)] + [r.reshape(-1) for r in rows] + [dec.reshape(-1), feed_rows.reshape(-1)]
     offs = np.cumsum([0] + [p.size for p in parts])
-    table = self._upload(np.concatenate(parts), torch.int32)
+    table = _upload(eng, np.concatenate(parts), torch.int32)
     tptr = lambda i: ctypes.c_void_p(table.data_ptr() + 4 * int(offs[i]))
     info_ptr = lambda l: ctypes.c_void_p(table.data_ptr() + 4 * l * S * 4)
     ptr, sp = eng._ptr, eng.stream_ptr
     self.launches = 0
+    # 3. the new frames into the first layer's windows
     if len(feed_rows):
-      feat = self._upload(np.concatenate([part[s] for s in named.tolist() if s in part and part[s].shape[0]]), torch.float32)
+      feat = _upload(eng, np.concatenate([part[s] for s in named.tolist() if s in part and part[s].shape[0]]), torch.float32)
       call('st_stream_feed_f32', ptr(feat), self.layers[0].cin, tptr(L + 2), len(feed_rows), S, ptr(self.windows[0]), self.cap[0],
            self.layers[0].cin_pitch, sp)
       self.launches += 1
-    # 3. eleven products with their epilogues, one advance, one decode
+    # 4. eleven products with their epilogues
     for l, spec in enumerate(self.layers):
       if not len(rows[l]):
         continue
@@ -937,336 +1314,64 @@ class StreamingRecognizer:
            ptr(pb), spec.width, spec.stride, spec.cout, int(spec.relu), ptr(out), self.max_rows[-1] if lastl else self.cap[l + 1],
            spec.cout_pitch, None if lastl else info_ptr(l + 1), ptr(self.workspace), self.ws_bytes, sp)
       self.launches += 2
-    if self.words is not None and len(rows[-1]):
-      call('st_stream_keep_f32', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), len(rows[-1]), S, ptr(self.ring),
-           self.ring_cap, sp)
-      self.launches += 1
+    # 5. - 7. the words' ring keeps the new rows, the windows move on, and the decoders take the rows: the endpointer or the greedy
+    # decoder, the searches and their read-out, the spotter, the follower
+    src, dec_table, n_rows = (ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L)), tptr(L + 1), len(rows[-1])
+    if self._words is not None and n_rows:
+      self.launches += self._words.launch(src, n_rows)
     call('st_stream_advance', ptr(self.layer_table), L, info_ptr(0), S, sp)
-    if self.endpoint is not None:
-      self._launch_endpointed(tptr(L), tptr(L + 1), len(rows[-1]))
+    if self._endpoint is not None:
+      self._endpoint.launch(src, dec_table, S, self._greedy_out)
     else:
-      call('st_ctc_greedy_stream', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), S, ptr(self.dec_state),
-           ptr(self.dec_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum), sp)
+      call('st_ctc_greedy_stream', *src, dec_table, S, ptr(self.dec_state), ptr(self.dec_score), *self._greedy_out, sp)
     self.launches += 2
-    if self.beam and self.endpoint is None:
-      # the beam searches take the same rows through the same table; the read-out only when its result is fetched (so that
-      # the labels the device has declared final are exactly those the host holds)
-      bm = self.beam
-      lm_args = (self._lm_handle, bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight, bm.oov_score)
-      biased = '_bias' if self._bias else ''
-      call('st_ctc_beam_stream_step' + biased, ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]),
-           S, bm.beam_width, self._transform, *lm_args, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
-           self.beam_ws_bytes, sp, *self._bias)
-      self.launches += 2 if len(rows[-1]) else 1
-      if fetch and bm.nbest is not None:
-        call('st_ctc_beam_stream_read_nbest', tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
-             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._nbest_args)
-        self.launches += 2                                        # the counter's reset and the read-out
-      elif fetch:
-        call('st_ctc_beam_stream_read' + biased, tptr(L + 1), S, bm.beam_width, *lm_args, ptr(self.beam_state), ptr(self.beam_pool),
-             self.max_frames, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *self._bias)
-        self.launches += 1
-      read = (count[:, -1] > 0) | fin | self._fresh[named]       # the streams the read-out reports on
-      self._frames[named] = np.where(self._fresh[named], 0, self._frames[named]) + taken
-    if self.spot is not None:
-      # the keywords' lattices take the same rows through the host's table (not the endpointer's pieces: spotting is not reset)
-      call('st_ctc_spot_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]), S,
-           self.spot_plan.ctypes.data_as(ctypes.c_void_p), self.spot.threshold, self.spot_hold, ptr(self.spot_state), ptr(self.spot_events),
-           self.spot.max_events, ptr(self.spot_counts), sp)
-      self.launches += 2                                          # the memset of the counts and the lattices
-    if self.follow is not None:
-      # the scripts' lattices take the same rows through the host's table, as the spotter does: endpointing does not reset them
-      fw, longest = self.follow, int(count[:, -1].max()) if len(named) else 0
-      call('st_ctc_follow_stream_step', ptr(self.logits), self.logits_pitch, self.num_classes, tptr(L), tptr(L + 1), len(rows[-1]),
-           self.max_rows[-1], longest, S, *self._follow_ptrs, fw.max_labels, self.follow_confirm,
-           ptr(self.follow_state), ptr(self.follow_events), fw.max_events, ptr(self.follow_result),
-           ptr(self.follow_trace) if fw.trace else None, ptr(self.follow_ws), self.follow_ws_bytes, sp)
-      self.launches += (1 if len(rows[-1]) else 0) + 2 * max(-(-longest // 64), 1)   # the softmax, then tiles and read-out per 64 rows
-    # 4. the host's counters follow; nothing above waited
+    if by_table:
+      self.launches += self._beam.launch_table(src, dec_table, n_rows, fetch)
+    elif self._beam is not None:
+      self.launches += self._beam.launch_pieces(src, self._endpoint.pieces, self.n_pieces, n_rows)
+    if self._spot is not None:
+      self.launches += self._spot.launch(src, dec_table, n_rows)
+    if self._follow is not None:
+      self.launches += self._follow.launch(src, dec_table, n_rows, int(count[:, -1].max()) if len(named) else 0)
+    # 8. the host's counters follow; nothing above waited
+    if by_table:
+      self._beam.frames[named] = np.where(fresh, 0, self._beam.frames[named]) + taken
     self._n[named], self._e[named] = n_after, first + count
     self._total[named] += new
     self._fresh[named], self._finished[named] = False, fin
     self._info[:, named, 0], self._info[:, named, 1], self._info[:, named, 2] = new_base.T, n_after.T, new_base.T
     if not fetch:
       return
+    # 9. one copy: the step's one wait
     with torch.cuda.stream(eng.stream):
       if return_logits:
         view = self.logits.view(-1, self.logits_pitch)
         for k, s in enumerate(named.tolist()):
           if count[k, -1]:
             result.logits[s].append(view[int(row0[k]):int(row0[k] + count[k, -1]), :self.num_classes].clone())
-      words = self.dec_out.cpu().numpy()                         # the step's one wait
-    arena = used = None
-    if self.beam and self.beam.nbest is not None:
-      used, words = int(words[-1]), words[:-1]
-      for s in named.tolist():
-        result.nbest.setdefault(s, None)
-        result.nbest_lost.setdefault(s, 0)
-      if used:                                                    # a pass with finals: their lists, one copy of what was written
-        arena = self._fetch_arena(used)
-    if self.follow is not None:
-      fw, at = self.follow, self.follow_at
-      rec = words[at:at + 16 * S].reshape(S, 16)
-      ev = words[at + 16 * S:at + S * (16 + 2 * fw.max_events)].reshape(S, fw.max_events, 2)
-      followed = read_follow(rec, ev, fw.max_events, self._scripts, [s for s in named.tolist() if self._scripts[s] is not None])
-      for k, s in enumerate(named.tolist()):
-        if s not in followed:
-          continue
-        state, reached, lost = followed[s]
-        if fw.trace:
-          took = state['frames'] - int(self._follow_frames[s])     # (rows at or past a finishing stream's limit are not consumed)
-          state['trace'] = (result.follow[s]['trace'] if result.follow.get(s) else []) + \
-              words[at + S * (16 + 2 * fw.max_events):][int(row0[k]):int(row0[k]) + took].tolist()
-        self._follow_frames[s] = state['frames']
-        result.follow[s] = state
-        result.reached[s] += reached
-        result.reached_lost[s] += lost
-      words = words[:self.spot_end]
-    if self.spot is not None:
-      me = self.spot.max_events
-      found = read_hits(self.spot.keywords, words[self.spot_at + S:].reshape(S, me, 8), words[self.spot_at:self.spot_at + S], me)
-      for s in named.tolist():
-        result.hits[s] += found[s][0]
-        result.hits_lost[s] += found[s][1]
-      words = words[:self.spot_at]
-    ids, counts = words[:S * self.max_new].reshape(S, self.max_new), words[S * self.max_new:S * self.max_new + S]
-    score = words[S * self.max_new + S:].view(np.float32)
-    for s in named.tolist():
+      words = self.dec_out.cpu().numpy()
+    # 10. every option reads its segments of the copy; a search that gave up is reported after the others' results are in
+    slots, failed = named.tolist(), None
+    if self._follow is not None:
+      self._follow.read(words, slots, row0, result)
+    if self._spot is not None:
+      self._spot.read(words, slots, result)
+    ids, counts, score = self._host(words)
+    score = score.view(np.float32)
+    for s in slots:
       result.ids[s] += ids[s, :counts[s]].tolist()
       result.score[s] = float(score[s])
-    if self.endpoint is not None:
-      return self._read_endpointed(words, named.tolist(), fin, result, arena, used)
-    if self.beam:
-      g = S * self.max_new + 2 * S
-      res, tail = words[g:g + 4 * S].reshape(S, 4), words[g + 4 * S:].reshape(S, self.beam.max_tail)
-      failed, listed, unwanted = None, [], set()
-      for k, s in enumerate(named.tolist()):
-        if read[k]:
-          length, stable, old = int(res[s, 0]), int(res[s, 1]), int(self._stable[s])
-          if res[s, 3] != 0 or length - old > self.beam.max_tail or length < old:
-            self._failed[s] = True
-            why = ('status {}'.format(int(res[s, 3])) if res[s, 3] != 0 else
-                   '{} labels are not final yet, max_tail = {}'.format(length - old, self.beam.max_tail))
-            failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
-            unwanted.add((0, s))                                  # (if it was finishing, the device wrote its record all the same)
-            continue
-          if fin[k] and used is not None:
-            listed.append((s, (0, s), self._hyp[s][:old], None))
-          self._hyp[s] = self._hyp[s][:old] + tail[s, :length - old].tolist()
-          self._stable[s] = length if fin[k] else stable           # a finished stream's hypothesis is final as a whole
-          self._logp[s] = res[s, 2:3].view(np.float32)[0]
-        result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
-      if listed:
-        self._final_lists(arena, used, listed, result, unwanted)
-      if failed is not None:
-        failed.result = result                                    # the other streams' results of this step
-        raise failed
-
-  def _launch_endpointed(self, rows_ptr, table_ptr, n_rows):
-    """The decoders of an endpointed step: the endpoint kernel in the greedy decoder's place -- it leaves the step's events and, per
-    utterance the step touches, a table of the decoders' own format on the device -- then the searches and their read-outs piece by
-    piece, all in one call and without a host wait in between."""
-    eng, S, P = self.engine, self.max_streams, self.n_pieces
-    ptr, sp = eng._ptr, eng.stream_ptr
-    R, L, M, space = self.ep_frames
-    call('st_ctc_greedy_endpoint_stream', ptr(self.logits), self.logits_pitch, self.num_classes, rows_ptr, table_ptr, S, space, R, L, M,
-         self.max_new, ptr(self.ep_state), ptr(self.ep_score), ptr(self.ids), self.max_new, ptr(self.new_count), ptr(self.neg_sum),
-         ptr(self.ep_events), ptr(self.ep_pieces), P, sp)
-    if self.beam:
-      bm = self.beam
-      name, extra = 'st_ctc_beam_stream_step_pieces' + ('_bias' if self._bias else ''), self._bias
-      if bm.nbest is not None:                                    # the finals' lists into the arena; one launch more (the counter's reset)
-        name, extra = 'st_ctc_beam_stream_step_pieces_nbest', self._nbest_args
-        self.launches += 1
-      call(name, ptr(self.logits), self.logits_pitch, self.num_classes,
-           rows_ptr, ptr(self.ep_pieces), P, n_rows, S, bm.beam_width, self._transform, self._lm_handle, bm.lm_weight, bm.word_count_weight,
-           bm.valid_word_count_weight, bm.oov_score, ptr(self.beam_state), ptr(self.beam_pool), self.max_frames, ptr(self.beam_ws),
-           self.beam_ws_bytes, ptr(self.beam_tail), bm.max_tail, ptr(self.beam_result), sp, *extra)
-      self.launches += (1 if n_rows else 0) + 2 * P
-
-  def _read_endpointed(self, words, named, fin, result, arena=None, used=None):
-    """The host's part of an endpointed step, from the step's one copy: the events close utterances in order, each with the greedy ids
-    up to its ``ids_end``; the pieces are walked in order -- a piece marked reset starts from an empty hypothesis, every read-out
-    appends its tail above the stable length the one before it stored, and a piece with a limit is a final."""
-    S, P = self.max_streams, self.n_pieces
-    ids, counts = words[:S * self.max_new].reshape(S, self.max_new), words[S * self.max_new:S * self.max_new + S]
-    g = S * self.max_new + 2 * S
-    events = words[g:g + S * P * 8].reshape(S, P, 8)
-    pieces = words[g + S * P * 8:g + self.ep_words].reshape(P, S, 4)
-    if self.beam:
-      g += self.ep_words
-      mt = self.beam.max_tail
-      res, tail = words[g:g + P * S * 4].reshape(P, S, 4), words[g + P * S * 4:].reshape(P, S, mt)
-    failed, new_finals, listed, unwanted = None, [], [], set()
-    for k, s in enumerate(named):
-      closed, prev, last_kind = [], 0, 0
-      for e in (events[s].tolist() if events[s, 0, 0] else ()):   # (most steps close nothing)
-        if e[0] == 0:
-          break
-        self._open_ids[s] += ids[s, prev:e[5]].tolist()
-        prev, last_kind = e[5], e[0]
-        if e[0] in Endpointing.KINDS:
-          closed.append(Utterance(e[7], Endpointing.KINDS[e[0]], e[1], e[2], e[3], e[4], self._open_ids[s],
-                                  float(np.asarray(e[6], np.int32).view(np.float32))))
-        self._open_ids[s] = []
-      self._open_ids[s] += ids[s, prev:counts[s]].tolist()
-      result.open_ids[s] = list(self._open_ids[s])
-      if self.beam:
-        at = 0
-        for p, (_, rows, limit, reset) in enumerate(pieces[:, s].tolist()):
-          if rows == 0 and limit < 0 and not reset:
-            continue
-          if reset:
-            self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
-          length, stable, old = int(res[p, s, 0]), int(res[p, s, 1]), int(self._stable[s])
-          if res[p, s, 3] != 0 or length - old > mt or length < old:
-            self._failed[s] = True
-            why = ('status {}'.format(int(res[p, s, 3])) if res[p, s, 3] != 0 else
-                   '{} labels are not final yet, max_tail = {}'.format(length - old, mt))
-            failed = failed or StreamError('stream {}: the beam search gave up ({})'.format(s, why))
-            unwanted.update((q, s) for q in range(p, P))          # (the device wrote this final's record, and its later ones', all the same)
-            break
-          head = self._hyp[s][:old]
-          self._hyp[s] = head + tail[p, s, :length - old].tolist()
-          self._stable[s], self._logp[s] = stable, res[p, s, 2:3].view(np.float32)[0]
-          if limit >= 0:                                          # a final: the whole-utterance search on its rows alone
-            closed[at].ids, closed[at].logp = self._hyp[s], float(self._logp[s])
-            if used is not None:
-              listed.append((s, (p, s), head, closed[at]))
-            at += 1
-            self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
-        if fin[k] and last_kind == 3:                             # what was open at the end held no speech: dropped like any discard
-          self._hyp[s], self._stable[s], self._logp[s] = [], 0, 0.0
-        result.hyp[s], result.stable[s], result.logp[s] = list(self._hyp[s]), int(self._stable[s]), float(self._logp[s])
-      result.finals[s] += closed
-      new_finals += [(s, u) for u in closed]
-    if listed:                                                    # lists, then rescoring, then the words of the ids that are reported
-      self._final_lists(arena, used, listed, result, unwanted)
-    if self.words is not None:
-      self._final_words(new_finals)
+    if self._endpoint is not None:
+      closed, dropped, pieces = self._endpoint.read(words, slots, result)
+      if self._beam is not None:
+        failed = self._beam.read(words, slots, fin, result, closed=closed, dropped=dropped, pieces=pieces)
+      if self._words is not None:
+        self.launches += self._words.read([(s, u) for s in slots for u in closed[s]])
+    elif self._beam is not None:
+      failed = self._beam.read(words, slots, fin, result, read=read)
     if failed is not None:
-      failed.result = result
+      failed.result = result                                      # the other streams' results of this step
       raise failed
-
-  def _fetch_arena(self, used):
-    """The words a pass's lists wrote -- ``arena[:min(used, capacity)]``, the one additional copy (and wait) of a pass with finals -- and
-    the fill value back in their place, enqueued behind the copy."""
-    n = min(max(used, 0), self.nbest_words)
-    with torch.cuda.stream(self.engine.stream):
-      written = self.nbest_arena[:n]
-      host = written.cpu().numpy()
-      written.fill_(-1)
-    return host
-
-  def _final_lists(self, arena, used, listed, result, unwanted=()):
-    """The N-best lists of the finals a pass closed.  ``listed``: [(slot, (piece, slot), the ids the host holds below the record's stable
-    length, the `Utterance` or -- `finish` without endpointing -- None)].  The records of the arena become lists (`nbest.read_arena`), all
-    of them get their parts in one go (`nbest.components`: the first pass's model and weights, the slot's own hotword set), and with
-    ``rescore`` all are re-ranked together (`nbest.rescored`), the reported ids and log-probability becoming the first hypothesis's.  A
-    final whose record did not fit the arena keeps ``nbest = None`` and is counted in ``result.nbest_lost``.  ``unwanted``: the keys of
-    finishing read-outs the host gave up on (their streams have failed): their records are stepped over, so that one stream's failure
-    never costs the others their lists -- the pass still ends in that stream's `StreamError`, the others' results attached."""
-    from . import nbest as nb
-    bm = self.beam
-    found, _ = nb.read_arena(arena if arena is not None else np.zeros(0, np.int32), used if arena is not None else 0,
-                             {key: head for _, key, head, _ in listed}, skip=unwanted)
-    have = [f for f in listed if f[1] in found]
-    for slot, key, _, _ in listed:
-      if key not in found:
-        result.nbest_lost[slot] += 1
-    if not have:
-      return
-    hot = None
-    if bm.hotwords is not None:                                   # set 0 is the empty set: no bias
-      hot = [bm.hotwords.tables(int(self._set[slot])) if self._set[slot] else None for slot, _, _, _ in have]
-    lists = nb.components(self.engine, bm.lm, [found[key] for _, key, _, _ in have],
-                          (bm.lm_weight, bm.word_count_weight, bm.valid_word_count_weight), hotwords=hot)
-    if bm.rescore is not None:
-      r = bm.rescore
-      lists = nb.rescored(lists, self.engine, r['language_model'], r['lm_weight'], r['word_count_weight'], r['valid_word_count_weight'])
-    for (slot, _, _, utt), hyps in zip(have, lists):
-      if utt is not None:
-        utt.nbest = hyps
-        if bm.rescore is not None:
-          utt.ids, utt.logp = list(hyps[0]['ids']), float(hyps[0]['log_prob'])
-      else:
-        result.nbest[slot] = hyps
-        if bm.rescore is not None:
-          self._hyp[slot], self._logp[slot] = list(hyps[0]['ids']), hyps[0]['log_prob']
-          self._stable[slot] = len(self._hyp[slot])
-          result.hyp[slot], result.stable[slot], result.logp[slot] = list(self._hyp[slot]), int(self._stable[slot]), float(hyps[0]['log_prob'])
-
-  def _final_words(self, finals):
-    """The word times and confidences of the finals a pass closed, ``[(slot, Utterance)]``: one table (`final_jobs`), one upload, the
-    ring alignment and / or the ring confidences for all of them together, one copy back -- the pass's second wait.  Runs inside the
-    pass: the next pass's keep overwrites the ring."""
-    from . import alignment
-    from .engine_decode import MAX_ALIGN_LABELS
-    want = self.words
-    for _, u in finals:
-      if len(u.ids) == 0:
-        u.words = []
-        if want.timestamps:
-          u.spans = np.zeros((0, 2), dtype=np.int32)
-    space = self.ep_frames[3] if want.confidence else None
-    tab = final_jobs([(s, u.start_frame, u.end_frame, u.ids) for s, u in finals], space, MAX_ALIGN_LABELS)
-    J = len(tab['index'])
-    if not J:
-      return
-    lib = _lib.load()
-    eng, S, C = self.engine, self.max_streams, self.num_classes
-    N, W, T, max_len = int(tab['offsets'][-1]), len(tab['word_spans']), tab['max_rows'], tab['max_len']
-    parts = [tab['jobs'].reshape(-1), tab['ids'], tab['offsets'], tab['word_spans'].reshape(-1), np.zeros(1, np.int32)]
-    offs = np.cumsum([0] + [p.size for p in parts])
-    table = self._upload(np.concatenate(parts), torch.int32)
-    tptr = lambda i: ctypes.c_void_p(table.data_ptr() + 4 * int(offs[i]))
-    ptr, sp = eng._ptr, eng.stream_ptr
-    with torch.cuda.stream(eng.stream):
-      # the outputs in one buffer, one copy back: log_conf [W] | log_prob [J] (doubles) | spans [N][2] | score [J] | status [J] | status [J]
-      out = torch.zeros(2 * (W + J) + 2 * N + 3 * J, dtype=torch.int32, device=self.device)
-      at = lambda first: ctypes.c_void_p(out.data_ptr() + 4 * first)
-      o_spans = 2 * (W + J)
-      o_score, o_st_align, o_st_conf = o_spans + 2 * N, o_spans + 2 * N + J, o_spans + 2 * N + 2 * J
-      if want.timestamps:
-        need = int(lib.st_ctc_align_ws(J, T, max_len))
-        ws = torch.empty(need // 4 + 16, dtype=torch.int32, device=self.device)
-        call('st_ctc_align_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, at(o_spans), None,
-             at(o_score), at(o_st_align), ptr(ws), ws.numel() * 4, sp)
-        self.launches += 3
-      if want.confidence:
-        need = int(lib.st_ctc_word_conf_ws(J, T, max_len, J + W))
-        ws2 = torch.empty(need // 4 + 16, dtype=torch.int32, device=self.device)
-        call('st_ctc_word_conf_ring_f32', ptr(self.ring), S, self.ring_cap, C, tptr(0), J, T, tptr(1), tptr(2), max_len, space, tptr(3), W,
-             at(2 * W), at(0), at(o_st_conf), ptr(ws2), ws2.numel() * 4, sp)
-        self.launches += 3
-      host = out.cpu().numpy()                                     # the second wait of a pass that closed something
-    log_conf, log_prob = host[:2 * W].view(np.float64), host[2 * W:o_spans].view(np.float64)
-    spans, score = host[o_spans:o_score].reshape(N, 2), host[o_score:o_st_align].view(np.float32)
-    first_word = np.concatenate([[0], np.cumsum(tab['words'])]).astype(np.int64)
-    per_second = 100.0 if self.frame_rate is None else self.frame_rate
-    rate = 2.0 * alignment.HOP_LENGTH * per_second / self.total_stride   # frames_to_seconds(f, rate) = f * total_stride / per_second
-    for j, i in enumerate(tab['index']):
-      u = finals[i][1]
-      if host[o_st_align + j] != 0 or host[o_st_conf + j] != 0:     # the ids do not fit the rows: nothing, as offline
-        continue
-      probs = None
-      if want.timestamps:
-        u.spans = spans[tab['offsets'][j]:tab['offsets'][j + 1]].copy()
-        u.align_score = float(score[j])
-      if want.confidence:
-        probs = np.exp(log_conf[first_word[j]:first_word[j + 1]]).tolist()
-        u.confidence = dict(log_prob=float(log_prob[j]), words=probs)
-      if want.timestamps:
-        u.words = alignment.timed_words(u.ids, u.spans + u.start_frame, rate, confidence=probs)
-      else:
-        u.words = alignment.confident_words(u.ids, probs)
-
-  def _upload(self, array, dtype):
-    """Host array -> device as a stream operation (pinned staging from torch's caching host allocator: no wait for the stream's
-    earlier kernels, and the block is not reused before the copy has run)."""
-    host = torch.from_numpy(array).pin_memory()
-    with torch.cuda.stream(self.engine.stream):
-      return host.to(self.device, non_blocking=True)
 
 
 # ---- resampling live streams (csrc/resample_stream.hip) -------------------------------------------------------------------------

@@ -447,7 +447,7 @@ def test_without_endpointing_the_launches_are_the_old_ones(dev, tiny):
   x = EC.recognizer_features('b')[:200]
   for which, decoders in (('greedy', []), ('lm', ['ctc_beam_stream_lm<', 'ctc_beam_stream_read<'])):
     rec = StreamingRecognizer(tiny, 1, max_chunk_frames=64, beam=_beam(which, 10.0))
-    assert rec.endpoint is None and not hasattr(rec, 'ep_state') and rec.n_pieces == 1
+    assert rec.endpoint is None and not hasattr(rec, 'ep_state') and rec._endpoint is None and rec.n_pieces == 1
     slot = rec.open()
     rec.step({slot: x[:150]})
     with launch_trace() as tr:

@@ -233,7 +233,39 @@ def test_recogniser_however_the_audio_is_cut_and_beside_the_other_options(dev, s
   # the decoders, the endpointer and the spotter report what they report without a follower; its launches come on top: the
   # softmax, the tiles and the read-out (the last pass of these cuts has rows)
   assert rest_a == rest_plain and rec_a.launches - rec_plain.launches in (2, 3)
-  assert not hasattr(rec_plain, 'follow_state')
+  assert not hasattr(rec_plain, 'follow_state') and rec_plain._follow is None
+
+
+def _all_options_passes(eng):
+  """One stream with every option on, two steps of 64 frames and `finish` -> per pass (the kernels launched, ``launches``)."""
+  from speecht_amd._lib import launch_trace
+  from speecht_amd.streaming import Endpointing, FinalWords, StreamBeam, StreamingRecognizer, StreamSpotter
+  x = WL.synthetic_features(151, 151, 16).astype(np.float32)
+  rec = StreamingRecognizer(eng, 1, max_chunk_frames=64, beam=StreamBeam(beam_width=16, nbest=2),
+                            endpoint=Endpointing(silence=0.06, lead=0.2, max_utterance=0.6), words=FinalWords(),
+                            spot=StreamSpotter(['a', 'th'], threshold=-np.inf, hold=0.1, max_events=512), follow=_follower())
+  slot = rec.open(script=TEXT)
+  passes = []
+  for run in (lambda: rec.step({slot: x[:64]}), lambda: rec.step({slot: x[64:128]}), lambda: rec.finish(slot)):
+    with launch_trace() as tr:
+      run()
+    passes.append(([l.split(' ')[0] for l in tr.lines], rec.launches))
+  return passes
+
+
+# (22 pieces per pass; the first pass has rows in seven layers and none for the decoders; `finish` closes an utterance with words)
+_DECODERS = (['ctc_greedy_endpoint_stream'] + ['ctc_beam_stream<wave>', 'ctc_beam_stream_read_nbest<wave>'] * 22
+             + ['ctc_spot_stream<1>', 'ctc_follow_stream'])
+_PRODUCTS = ['stream_conv<32>'] * 8 + ['stream_conv<64>'] * 2 + ['stream_conv<32>', 'stream_keep']
+ALL_OPTIONS_PASSES = [(['stream_conv<32>'] * 7 + _DECODERS, 66), (_PRODUCTS + _DECODERS, 77),
+                      (_PRODUCTS + _DECODERS + ['ctc_align_ring<1>'], 79)]
+
+
+def test_all_options_launch_what_they_launched(dev, small):
+  """The kernels of each pass, in order, and ``launches``: recorded by running `_all_options_passes` on the commit before the options
+  owned their parts of a pass, on this file's tiny engine.  (The trace does not name the feed and the advance: of those only
+  ``launches`` tells.)"""
+  assert _all_options_passes(small) == ALL_OPTIONS_PASSES
 
 
 def test_follow_none_takes_the_old_path(dev, small):

@@ -257,7 +257,7 @@ def test_whole_path_two_chunkings_equal_the_host_form(dev, small, which):
   assert set(a) == want and count == len(a) and any(kind == 1 for _, _, _, kind, _ in a)
   # the decoders report what they report without a spotter; two launches come on top (the memset of the counts, the lattices)
   assert rest_a == rest_plain and rec_a.launches == rec_plain.launches + 2
-  assert not hasattr(rec_plain, 'spot_state')
+  assert not hasattr(rec_plain, 'spot_state') and rec_plain._spot is None
 
 
 def test_streams_side_by_side_lost_hits_and_reopened_slots(dev, small):

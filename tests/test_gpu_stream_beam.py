@@ -331,7 +331,7 @@ def test_whole_path_two_chunkings(dev, small, which):
   assert a[-1][3] == np.float32(ref_lp[0, 0]).tobytes()
   # beam=None: today's results and launches; with a beam the greedy ids stay, three launches come on top
   assert ids_plain == ids_a == ids_b and plain == []
-  assert not hasattr(rec_plain, 'beam_state') and rec_a.launches == rec_plain.launches + 3
+  assert not hasattr(rec_plain, 'beam_state') and rec_plain._beam is None and rec_a.launches == rec_plain.launches + 3
 
 
 def test_a_reopened_slot_starts_a_new_search(small):
@@ -373,7 +373,7 @@ def test_the_host_refuses_a_step_past_the_pool(small):
   assert rec.max_frames == 16
   a, b = rec.open(), rec.open()
   first = rec.step({a: x[:130], b: y[:60]})                       # a: (130 - 99) // 2 + 1 = 16 frames: the pool is full
-  assert rec._frames[a] == 16
+  assert rec._beam.frames[a] == 16
   launches = rec.launches
   from speecht_amd._lib import launch_trace
   with launch_trace() as tr:

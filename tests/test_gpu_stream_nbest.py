@@ -367,7 +367,7 @@ def test_lists_at_finish_and_nbest_none_is_untouched(dev, tiny):
 
   plain, r0, seen0, logits, counts0, lines0 = run(StreamBeam(beam_width=16, max_seconds=8.0))
   assert not any('nbest' in l for l in lines0) and sum(l.startswith('ctc_beam_stream_read<') for l in lines0) == len(counts0)
-  assert not hasattr(plain, 'nbest_arena') and r0.nbest == {} and r0.nbest_lost == {}
+  assert not hasattr(plain, 'nbest_arena') and not hasattr(plain._beam, 'arena') and r0.nbest == {} and r0.nbest_lost == {}
   greedy = StreamingRecognizer(tiny, 2, max_chunk_frames=64)
   g = greedy.open()
   for at in range(0, 200, 50):
@@ -514,6 +514,6 @@ def test_a_failed_stream_does_not_cost_the_others_their_lists(dev, tiny):
   with pytest.raises(StreamError, match='stream {}: the beam search gave up'.format(a)) as failure:
     rec.finish_many([a, b])
   r = failure.value.result
-  assert rec._failed[a] and not rec._failed[b], (rec._failed, r.hyp, r.nbest_lost)
+  assert rec._beam.failed[a] and not rec._beam.failed[b], (rec._beam.failed, r.hyp, r.nbest_lost)
   assert r.nbest[a] is None and r.nbest_lost[b] == 0 and r.nbest[b] is not None, (r.nbest, r.nbest_lost)
   assert _list_key(r.nbest[b]) == _list_key(whole.nbest[b]) and r.hyp[b] == whole.hyp[b] and 1 <= len(r.nbest[b]) <= 3

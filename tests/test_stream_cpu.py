@@ -1,6 +1,6 @@
 """Streaming recognition without a GPU: the float64 statement of the feature (tests/stream_oracle.py) against the oracle's
 whole-utterance forward pass and greedy decoder, and the index arithmetic of speecht_amd/streaming.py against a brute-force
-enumeration of receptive fields."""
+enumeration of receptive fields; the layout of a step's result buffer for every set of options, and the beam search's read-out."""
 import numpy as np
 import pytest
 
@@ -247,3 +247,74 @@ def test_plan_many_equals_plan():
       assert n_i == n_after[i].tolist() and e_i == (first[i] + count[i]).tolist()
     n, e = n_after, first + count
     done |= fin
+
+
+def test_step_layout_orders_the_result_buffer_for_every_set_of_options():
+  """All 32 sets of {endpoint, beam, spot, follow with trace, lists}; lists need a beam, one piece without endpointing."""
+  import itertools
+  from speecht_amd.streaming import StepLayout
+  S, NEW, TAIL, SPOT, FOLLOW, ROWS = 3, 5, 7, 3, 2, 15
+  order = ['ids', 'counts', 'scores', 'events', 'pieces', 'result', 'tail', 'spot_counts', 'spot_events', 'follow_records',
+           'follow_events', 'follow_trace', 'used']
+  assert StepLayout(S, NEW).size == 21
+  parities, seen = set(), 0
+  for ep, beam, spot, follow, lists in itertools.product([False, True], repeat=5):
+    if lists and not beam:
+      continue
+    seen += 1
+    P = 2 if ep else 1
+    lay = StepLayout(S, NEW, n_pieces=P if ep else None, max_tail=TAIL if beam else None, spot_events=SPOT if spot else None,
+                     follow_events=FOLLOW if follow else None, trace_rows=ROWS if follow else None, lists=lists)
+    names = list(lay.segments)
+    assert names == [n for n in order if n in names]
+    assert set(names) == ({'ids', 'counts', 'scores'} | ({'events', 'pieces'} if ep else set()) | ({'result', 'tail'} if beam else set())
+                          | ({'spot_counts', 'spot_events'} if spot else set()) | ({'used'} if lists else set())
+                          | ({'follow_records', 'follow_events', 'follow_trace'} if follow else set()))
+    end = 0
+    for name in names:                                            # contiguous and disjoint, but for the follower's even start
+      first, length, shape = lay.segments[name]
+      assert length == int(np.prod(shape)) > 0
+      if name == 'follow_records':
+        parities.add(end & 1)
+        assert first == end + (end & 1) and first % 2 == 0
+      else:
+        assert first == end, name
+      end = first + length
+    assert end == lay.size
+    if lists:
+      assert lay.segments['used'] == (lay.size - 1, 1, (1,))
+    total = S * NEW + S + S                                        # the sizes, written out again
+    total += S * P * 8 + P * S * 4 if ep else 0
+    total += P * S * 4 + P * S * TAIL if beam else 0
+    total += S + S * SPOT * 8 if spot else 0
+    total += total % 2 + S * 16 + S * FOLLOW * 2 + ROWS if follow else 0
+    total += 1 if lists else 0
+    assert lay.size == total, (ep, beam, spot, follow, lists)
+    words = np.arange(lay.size, dtype=np.int32)                    # a view is its segment of the words, in its shape
+    for name in names:
+      first, length, shape = lay.segments[name]
+      view, = lay.views(name)(words)
+      assert view.shape == shape and view.reshape(-1).tolist() == list(range(first, first + length))
+  assert seen == 24 and parities == {0, 1}
+  assert not StepLayout(S, NEW, follow_events=FOLLOW).segments.keys() & {'follow_trace'}
+  max_new = 11
+  assert StepLayout(1, max_new, max_tail=256).size == max_new + 2 + 4 + 256
+
+
+def test_read_beam_on_hand_written_rows():
+  from speecht_amd.streaming import read_beam
+  logp = np.float32(-3.25)
+  row = lambda length, stable, status=0: np.asarray([length, stable, int(logp.view(np.int32)), status], dtype=np.int32)
+  tail = np.asarray([7, 8, 9, 0, 0], dtype=np.int32)
+  hyp = [1, 2, 3, 4]
+  # two ids are final; the device reports five in all, three of them final now: the tail goes above the two
+  got = read_beam(hyp, 2, row(5, 3), tail, 5, False)
+  assert got[0] == [1, 2, 7, 8, 9] and got[1] == 3 and got[3] == [1, 2] and hyp == [1, 2, 3, 4]
+  assert isinstance(got[2], np.float32) and got[2].tobytes() == logp.tobytes()
+  assert read_beam(hyp, 2, row(5, 3), tail, 5, True)[:2] == ([1, 2, 7, 8, 9], 5)       # a final is final as a whole
+  assert read_beam(hyp, 2, row(2, 2), tail, 5, False)[:2] == ([1, 2], 2)               # nothing above the stable ids
+  assert read_beam([], 0, row(0, 0), tail, 5, True)[:2] == ([], 0)
+  assert read_beam(hyp, 2, row(5, 3, status=6), tail, 5, False) == 'status 6'
+  assert read_beam(hyp, 2, row(8, 3), tail, 5, False) == '6 labels are not final yet, max_tail = 5'
+  assert isinstance(read_beam(hyp, 2, row(7, 3), np.arange(5, dtype=np.int32), 5, False), tuple)    # exactly max_tail labels fit
+  assert isinstance(read_beam(hyp, 3, row(2, 2), tail, 5, False), str)                 # shorter than what is final already

@@ -271,11 +271,11 @@ def test_a_failed_finals_record_beside_a_good_one_costs_nothing():
     with pytest.raises(nbest.ArenaError):
       nbest.read_arena(twice, len(twice), {(0, 0): [7, 8]}, skip={(0, 1)})
     # the recogniser's own step from arena to results, on a recogniser that owns no device: the good final gets its list
-    rec = object.__new__(streaming.StreamingRecognizer)
-    rec.beam, rec.engine, rec._set = streaming.StreamBeam(beam_width=4, nbest=3), None, np.zeros(2, np.int64)
+    rec = object.__new__(streaming._BeamPart)
+    rec.beam, rec.engine, rec.slot_set = streaming.StreamBeam(beam_width=4, nbest=3), None, np.zeros(2, np.int64)
     result = streaming.StepResult()
     result.nbest, result.nbest_lost = {0: None, 1: None}, {0: 0, 1: 0}
-    rec._hyp, rec._logp, rec._stable = [[], []], np.zeros(2, np.float32), np.zeros(2, np.int64)
-    rec._final_lists(arena[:len(words)], len(words), [(0, (0, 0), [7, 8], None)], result, {(0, 1)})
+    rec.hyp, rec.logp, rec.stable = [[], []], np.zeros(2, np.float32), np.zeros(2, np.int64)
+    rec.final_lists(arena[:len(words)], len(words), [(0, (0, 0), [7, 8], None)], result, {(0, 1)})
     assert [h['ids'] for h in result.nbest[0]] == [list(i) for i, _ in RECORDS[(0, 0)][1]] and result.nbest[1] is None
     assert result.nbest_lost == {0: 0, 1: 0} and all(h['acoustic'] == h['log_prob'] for h in result.nbest[0])
