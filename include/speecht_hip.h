@@ -329,6 +329,21 @@ int st_ctc_loss_grad_hilo_f32(const st_tensor3* logits, const int32_t* label_ids
                               const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len,
                               float grad_scale, float* loss, float* loss_lo, const st_tensor3* grad, int32_t* status,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The same for partial transcripts: label ids may hold the wildcard, id num_classes (the slot after the blank, as in
+ * st_ctc_align_wild_f32), so num_classes <= 31 here.  The wildcard is a label state of the 2L+1 lattice like any other (blanks
+ * around it, at least one frame, the same skip rules, never two in a row; it counts as a label towards "not enough frames")
+ * whose emission is  w_t = e^wildcard_bias * sum_{c < blank} y_t(c),  wildcard_bias <= 0 in nats per frame: the frame reads
+ * some label, at a price (the star of Star Temporal Classification, Pratap et al. 2022, without its minus-next-token term).
+ * loss = -ln sum_paths prod emissions; grad[b,t,k] = grad_scale * (y_t(k) - occ_t(k) - [k < blank] occ_t(wild) y_t(k) / S_t),
+ * S_t = sum_{c < blank} y_t(c); the wildcard is no logit, columns num_classes .. 31 stay zero.  An utterance without a wildcard
+ * gets the bits of st_ctc_loss_grad_hilo_f32 (loss, loss_lo, status, gradient), whatever else the batch holds.  The gradient's
+ * wildcard term recovers log2 S_t from the fp32 value log2 S_t + wildcard_bias * log2 e that the workspace rows hold: its relative
+ * error grows with |wildcard_bias| (about 1e-7 per nat; negligible at a price of a few nats per frame, 1e-5 at hundreds).  Workspace:
+ * st_ctc_ws.  (tests/wild_ctc_oracle.py is the specification.) */
+int st_ctc_loss_grad_wild_f32(const st_tensor3* logits, const int32_t* label_ids,
+                              const int32_t* label_offsets, const int32_t* seq_lens, int max_label_len,
+                              float grad_scale, double wildcard_bias, float* loss, float* loss_lo, const st_tensor3* grad,
+                              int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K14: tf.nn.ctc_greedy_decoder(merge_repeated) (speech_model.py:113-115) ------------
  * ids [B][max_out] int32 (max_out >= frames), out_lens [B], neg_sum_logits [B].  Row b of ids is written in its first

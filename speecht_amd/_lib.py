@@ -112,6 +112,9 @@ _SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     'st_ctc_loss_grad_hilo_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, _T3P,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    # labels may hold the wildcard (id num_classes): the hilo arguments plus `double wildcard_bias` behind grad_scale
+    'st_ctc_loss_grad_wild_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_float, c_double, c_void_p, c_void_p, _T3P,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
     'st_ctc_greedy_decode': (c_int, [_T3P, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'st_ctc_align_ws': (c_size_t, [c_int, c_int, c_int]),
     'st_ctc_align_f32': (c_int, [_T3P, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -17,6 +17,8 @@
 //     rule, the chunk stage and the DPP move are ctc_lattice.h's, shared with ctc_align.hip.
 //  3. ctc_grad: fully parallel over (b, t): occupancy per class from alpha+beta with a fixed
 //     summation order (per-class position lists), so results are run-to-run deterministic.
+// st_ctc_loss_grad_wild_f32 (partial transcripts: labels may hold the wildcard, id C) runs WILD forms of stages 1 and 3 around the
+// same stage 2; the plain instantiations are untouched by it.
 #include <algorithm>
 
 #include "ctc_lattice.h"
@@ -65,9 +67,16 @@ constexpr float LN2 = 0.6931471805599453f;
 // frame's distribution is nearly the same (all logits ~0, log2 y ~ -4.86), so the float rounding of log2 y (2.4e-7) had the
 // same sign on all 501 frames and the loss came out 1e-4 low (measured round 4, scripts/diag_ctc_loss.py: -9.9e-5 on a loss
 // of 1 245; the recursion itself adds ~1e-6).  What remains is the float mantissa of the factor (3e-8 relative per frame).
+// WILD (st_ctc_loss_grad_wild_f32, C <= 31): lane C writes the wildcard label's emission into slot C of both rows,
+// log2 w_t = log2 S_t + wild_bias2, S_t = sum_{c < blank} y_t(c), wild_bias2 = bias * log2 e.  S_t is a butterfly sum of its own
+// over the label terms (1 - y(blank) would cancel on the blank-dominated frames, which are most of them), taken relative to the
+// LABEL classes' own maximum: relative to the frame's maximum the terms underflow once the blank leads by ~745 nats, where the
+// label classes themselves are still live under the 2^-30000 rule below.  The wildcard then is dead exactly when that rule says
+// so (no label class above -inf included).  Lanes below C compute what they always did.
+template <bool WILD>
 __global__ __launch_bounds__(256) void ctc_logsoftmax_kernel(const float* __restrict__ logits, RowMap map,
                                                              int B, int T, int C, float* __restrict__ logy,
-                                                             float* __restrict__ emis) {
+                                                             float* __restrict__ emis, double wild_bias2) {
   const int lane = threadIdx.x & 63, c = lane & 31;
   const int i = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
   const bool row_ok = i < B * T;
@@ -82,7 +91,16 @@ __global__ __launch_bounds__(256) void ctc_logsoftmax_kernel(const float* __rest
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   const double lz = (double)m + log(s);
-  const double l2 = c < C ? ((double)v - lz) * 1.4426950408889634074 : 0.0;
+  double l2 = c < C ? ((double)v - lz) * 1.4426950408889634074 : 0.0;
+  if constexpr (WILD) {
+    float mw = c < C - 1 ? v : NEG_INF;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) mw = fmaxf(mw, __shfl_xor(mw, o, 64));
+    double sw = c < C - 1 && mw > NEG_INF ? exp((double)v - (double)mw) : 0.0;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) sw += __shfl_xor(sw, o, 64);
+    if (c == C) l2 = ((double)mw + log(sw) - lz) * 1.4426950408889634074 + wild_bias2;      // (no label class: -inf, dead below)
+  }
   // a class 2^-30000 below the frame's best cannot be emitted (a logit of -inf, in practice): factor 0.  (The bound also
   // keeps every exponent sum of a 12 000-frame utterance inside int range.)
   const bool dead = !(l2 > -30000.0);
@@ -286,8 +304,16 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restr
 }
 
 // grad[b,t,c] = scale * (y_t(c) - sum_{u: l'_u = c} alpha_t(u) beta_t(u) / p)
+// WILD: labels may hold the wildcard (id C, emission w_t = e^bias S_t from slot C of the softmax rows).  Its states' occupancy
+// is no class's; it goes back to the label classes in proportion to what the frame already gives them:
+//   grad[b,t,k] -= scale * [k < blank] occ_t(wild) y_t(k) / S_t,     y_t(k) / S_t = 2^(logy[k] - (logy[C] - wild_bias2)),
+// (log2 S_t comes back out of the float that holds log2 S_t + wild_bias2 -- the price of keeping the wildcard in slot C of the
+// rows as they are: the exponent carries the fp32 rounding of numbers of the size of the bias, about 1e-7 |bias| nats: nothing
+// at the few nats a price per frame is, but at a bias of hundreds of nats the share's relative error reaches 1e-5),
+// occ_t(wild) summed over the wave under the frame's own normalisation like the blank's.  Exactly 0 where occ_t(wild) is
+// (S_t = 0 included: a dead wildcard holds no occupancy), so an utterance without a wildcard keeps the plain kernel's bits.
 constexpr int GF = 16;   // frames per block (4 waves x 4)
-template <int KPL>
+template <int KPL, bool WILD>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__ logy, const float* __restrict__ alpha,
                                                        const float* __restrict__ beta, int T, int C,
                                                        const int* __restrict__ label_ids,
@@ -295,7 +321,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
                                                        const int* __restrict__ seq_lens,
                                                        const int* __restrict__ status, float scale,
                                                        float* __restrict__ grad, RowMap gmap, int gcols,
-                                                       float* __restrict__ loss, float* __restrict__ loss_lo, int lmax) {
+                                                       float* __restrict__ loss, float* __restrict__ loss_lo, int lmax,
+                                                       float wild_bias2) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
   int* pos_off = smem;                 // [32]
   int* pos_list = smem + 32;           // [lmax]
@@ -319,7 +346,13 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
     int start = inc - cnt;
-    if (lane < 32) pos_off[lane] = lane < blank ? start : L;
+    if constexpr (WILD) {
+      // wildcards are in no class's list: the lists end at the count of the other labels, not at L
+      const int listed = __shfl(inc, 63, 64);
+      if (lane < 32) pos_off[lane] = lane < blank ? start : listed;
+    } else {
+      if (lane < 32) pos_off[lane] = lane < blank ? start : L;
+    }
     if (lane < blank) { int w = start; for (int i = 0; i < L; ++i) if (lab[i] == lane) pos_list[w++] = i; }
   }
   __syncthreads();
@@ -342,11 +375,22 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
     if (loss_lo) loss_lo[b] = (bad || !(hi < __builtin_inff())) ? 0.f : (float)(nll - (double)hi);
   }
 
+  // WILD: which of the lane's states are wildcard states (bit j: state lane*KPL + j)
+  unsigned wild_states = 0;
+  if constexpr (WILD) {
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      const int u = lane * KPL + j;
+      if ((u & 1) && u < U && lab[u >> 1] == C) wild_states |= 1u << j;
+    }
+  }
+
   float* wb = wbuf + wave * lmax;
   for (int k = 0; k < GF / 4; ++k) {
     const int t = blockIdx.x * GF + k * 4 + wave;
     const bool live = !bad && t < Tb && t < T;
     float blank_sum = 0.f, occ_scale = 1.f;
+    [[maybe_unused]] float wild_sum = 0.f;
     if (live) {
       const f32x2* al = reinterpret_cast<const f32x2*>(alpha) + ((long)b * T + t) * UP;
       const f32x2* be = reinterpret_cast<const f32x2*>(beta) + ((long)b * T + t) * UP;
@@ -363,6 +407,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
         float w = __builtin_ldexpf(av[j][0] * bv[j][0], ibits(av[j][1]) + ibits(bv[j][1]) - pe);
         w = u < U ? w : 0.f;                                       // (alpha's records beyond U hold numbers nobody may read)
         if (u & 1) { if (u < U) wb[u >> 1] = w; label_sum += w; } else blank_sum += w;
+        if constexpr (WILD) wild_sum += (wild_states >> j & 1) ? w : 0.f;
       }
       blank_sum = st::wave_sum(blank_sum);
       // sum_u alpha_t(u) beta_t(u) == p(l|x) for EVERY t: normalising by the frame's own total removes the rounding the two
@@ -370,6 +415,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
       const float total = blank_sum + st::wave_sum(label_sum);
       occ_scale = total > 0.f ? 1.f / total : 1.f;
       blank_sum *= occ_scale;
+      if constexpr (WILD) wild_sum = st::wave_sum(wild_sum) * occ_scale;
     }
     __syncthreads();
     if (t < T && lane < gcols) {
@@ -381,7 +427,13 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
           for (int i = pos_off[lane]; i < pos_off[lane + 1]; ++i) occ += wb[pos_list[i]];
           occ *= occ_scale;
         }
-        g = (ex2(logy[((long)b * T + t) * CP + lane]) - occ) * scale;
+        if constexpr (WILD) {
+          const float* ly = logy + ((long)b * T + t) * CP;
+          const float share = lane < blank && wild_sum > 0.f ? wild_sum * ex2(ly[lane] - (ly[C] - wild_bias2)) : 0.f;
+          g = ((ex2(ly[lane]) - occ) - share) * scale;
+        } else {
+          g = (ex2(logy[((long)b * T + t) * CP + lane]) - occ) * scale;
+        }
       }
       grad[gmap.off(b, t) + lane] = g;
     }
@@ -442,6 +494,49 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict
   if (tid == 0) neg_sum[b] = -fsum[0];
 }
 
+// the three launches of the loss: WILD = the wildcard forms of the softmax and the gradient kernel (the recursion is the same)
+template <bool WILD>
+int ctc_loss_grad(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets, const int32_t* seq_lens,
+                  int max_label_len, float grad_scale, double wildcard_bias, float* loss, float* loss_lo, const st_tensor3* grad,
+                  int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  ST_REQUIRE(logits && logits->base && grad && grad->base && label_ids && label_offsets && seq_lens && loss &&
+                 status && workspace, "ctc: null argument");
+  ST_REQUIRE(logits->channels >= 2 && logits->channels <= CP && logits->c_pitch >= CP && logits->c_pitch % 4 == 0,
+             "ctc: num_classes must be 2..32 with c_pitch >= 32");
+  if (WILD) {
+    ST_REQUIRE(logits->channels <= CP - 1, "ctc: the wildcard label needs num_classes <= 31, not %d", logits->channels);
+    ST_REQUIRE(wildcard_bias <= 0.0, "ctc: wildcard_bias must be <= 0");
+  }
+  ST_REQUIRE(grad->batch == logits->batch && grad->frames == logits->frames && grad->c_pitch >= logits->channels,
+             "ctc: grad tensor mismatch");
+  const int kpl = st::lattice_kpl(std::max(max_label_len, 0));   // (a negative max_label_len counts as 0, as in st_ctc_ws)
+  ST_REQUIRE(kpl > 0, "ctc: label length %d exceeds 511", max_label_len);
+  ST_REQUIRE(workspace_bytes >= st_ctc_ws(logits->batch, logits->frames, max_label_len), "ctc: workspace too small");
+  hipStream_t s = st::as_stream(stream);
+  const int B = logits->batch, T = logits->frames, C = logits->channels;
+  const size_t rows = (size_t)B * T;
+  const double bias2 = WILD ? wildcard_bias * 1.4426950408889634074 : 0.0;
+  float* logy = reinterpret_cast<float*>(workspace);
+  float* emis = logy + rows * CP;
+  float* alpha = emis + rows * CP * 2;             // (mantissa, exponent) records
+  float* beta = alpha + rows * kpl * 64 * 2;
+  hipLaunchKernelGGL(ctc_logsoftmax_kernel<WILD>, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
+                     st::row_map(*logits), B, T, C, logy, emis, bias2);
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL(ctc_alpha_beta_kernel<k()>, dim3(B, 2), dim3(64), 0, s, emis, T, C, label_ids, label_offsets, seq_lens,
+                       alpha, beta, status);
+  });
+  if (int e = st::check_launch("ctc_alpha_beta")) return e;
+  const int lmax = std::max(1, kpl * 32);
+  const size_t shm = (32 + (size_t)lmax * 5) * sizeof(int);
+  st::dispatch_kpl(kpl, [&](auto k) {
+    hipLaunchKernelGGL((ctc_grad_kernel<k(), WILD>), dim3(st::ceil_div(T, GF), B), dim3(256), shm, s, logy, alpha, beta, T, C,
+                       label_ids, label_offsets, seq_lens, status, grad_scale, grad->base, st::row_map(*grad),
+                       std::min(grad->c_pitch, CP), loss, loss_lo, lmax, (float)bias2);
+  });
+  return st::check_launch("ctc_grad");
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,37 +561,16 @@ int st_ctc_loss_grad_hilo_f32(const st_tensor3* logits, const int32_t* label_ids
                               const int32_t* seq_lens, int max_label_len, float grad_scale, float* loss, float* loss_lo,
                               const st_tensor3* grad, int32_t* status, void* workspace, size_t workspace_bytes,
                               void* stream) {
-  ST_REQUIRE(logits && logits->base && grad && grad->base && label_ids && label_offsets && seq_lens && loss &&
-                 status && workspace, "ctc: null argument");
-  ST_REQUIRE(logits->channels >= 2 && logits->channels <= CP && logits->c_pitch >= CP && logits->c_pitch % 4 == 0,
-             "ctc: num_classes must be 2..32 with c_pitch >= 32");
-  ST_REQUIRE(grad->batch == logits->batch && grad->frames == logits->frames && grad->c_pitch >= logits->channels,
-             "ctc: grad tensor mismatch");
-  const int kpl = st::lattice_kpl(std::max(max_label_len, 0));   // (a negative max_label_len counts as 0, as in st_ctc_ws)
-  ST_REQUIRE(kpl > 0, "ctc: label length %d exceeds 511", max_label_len);
-  ST_REQUIRE(workspace_bytes >= st_ctc_ws(logits->batch, logits->frames, max_label_len), "ctc: workspace too small");
-  hipStream_t s = st::as_stream(stream);
-  const int B = logits->batch, T = logits->frames, C = logits->channels;
-  const size_t rows = (size_t)B * T;
-  float* logy = reinterpret_cast<float*>(workspace);
-  float* emis = logy + rows * CP;
-  float* alpha = emis + rows * CP * 2;             // (mantissa, exponent) records
-  float* beta = alpha + rows * kpl * 64 * 2;
-  hipLaunchKernelGGL(ctc_logsoftmax_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, logits->base,
-                     st::row_map(*logits), B, T, C, logy, emis);
-  st::dispatch_kpl(kpl, [&](auto k) {
-    hipLaunchKernelGGL(ctc_alpha_beta_kernel<k()>, dim3(B, 2), dim3(64), 0, s, emis, T, C, label_ids, label_offsets, seq_lens,
-                       alpha, beta, status);
-  });
-  if (int e = st::check_launch("ctc_alpha_beta")) return e;
-  const int lmax = std::max(1, kpl * 32);
-  const size_t shm = (32 + (size_t)lmax * 5) * sizeof(int);
-  st::dispatch_kpl(kpl, [&](auto k) {
-    hipLaunchKernelGGL(ctc_grad_kernel<k()>, dim3(st::ceil_div(T, GF), B), dim3(256), shm, s, logy, alpha, beta, T, C, label_ids,
-                       label_offsets, seq_lens, status, grad_scale, grad->base, st::row_map(*grad), std::min(grad->c_pitch, CP),
-                       loss, loss_lo, lmax);
-  });
-  return st::check_launch("ctc_grad");
+  return ctc_loss_grad<false>(logits, label_ids, label_offsets, seq_lens, max_label_len, grad_scale, 0.0, loss, loss_lo, grad,
+                              status, workspace, workspace_bytes, stream);
+}
+
+int st_ctc_loss_grad_wild_f32(const st_tensor3* logits, const int32_t* label_ids, const int32_t* label_offsets,
+                              const int32_t* seq_lens, int max_label_len, float grad_scale, double wildcard_bias, float* loss,
+                              float* loss_lo, const st_tensor3* grad, int32_t* status, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return ctc_loss_grad<true>(logits, label_ids, label_offsets, seq_lens, max_label_len, grad_scale, wildcard_bias, loss, loss_lo,
+                             grad, status, workspace, workspace_bytes, stream);
 }
 
 int st_ctc_greedy_decode(const st_tensor3* logits, const int32_t* seq_lens, int merge_repeated, int32_t* ids,

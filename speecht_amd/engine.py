@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ._lib import Tensor3, call
 from .engine_buffers import DevTensor3, LayerSpec, ShapeState, _round_up, _StagedHostBatch, _Storage, channel_pitch, same_padding   # noqa: F401
+from . import engine_decode
 from .engine_decode import DecodeMixin, _PendingBeamDecode, _PendingDecode, beam_input_transform, merge_repeated_labels   # noqa: F401
 from .engine_streams import decoder_stream_pair, decoder_streams, role_stream   # noqa: F401
 from .modes import make_mode
@@ -104,6 +105,9 @@ class Wav2LetterEngine(DecodeMixin):
     self._h2d, self._pin_ring, self._pin_turn = None, [[None, None] for _ in range(8)], 0
     self._up_stream, self._uploads = None, []
     self.max_label_len, self._rejected_labels, self.defer_label_errors = 0, [], False
+    # partial transcripts: whether the labels of the current batch hold a wildcard (`set_labels(..., wildcard=True)`), and what a
+    # frame given to one costs in `ctc_loss_grad`, in nats (<= 0; the default is a guess, not tuned on data)
+    self._labels_wild, self.wildcard_bias = False, engine_decode.WILDCARD_BIAS
     self.augment_plan = None                       # int32 [B, 2 + 2 (mF + mT)] on the device: what the last augmented load_batch drew
     # the side streams of `_on_side_stream` and the event each one's last chain ended with; forward graphs by (shape, generation)
     self._side = self._side2 = self._side_done = self._side2_done = None
@@ -602,7 +606,35 @@ class Wav2LetterEngine(DecodeMixin):
     """[T', B, C] like tf.transpose(outputs, (1, 0, 2)) (speech_model.py:295)."""
     return self.shape.X[-1].interior().permute(1, 0, 2)
 
-  def set_labels(self, label_list):
+  def set_labels(self, label_list, wildcard=False):
+    """The labels of the current batch for `ctc_loss_grad`.  ``wildcard=True``: ids may hold ``engine_decode.WILDCARD``, audio
+    the transcript leaves out (never two in a row; num_classes <= 31); it is uploaded as the id num_classes, and a batch that
+    holds one is scored by st_ctc_loss_grad_wild_f32 at ``self.wildcard_bias``.  Every other id outside [0, num_classes - 1) is
+    the error it always was."""
+    self._labels_wild = False
+    if wildcard:
+      if self.num_classes > engine_decode.MAX_WILDCARD_CLASSES:
+        raise ValueError('set_labels: the wildcard needs num_classes <= {}, not {}'.format(engine_decode.MAX_WILDCARD_CLASSES,
+                                                                                          self.num_classes))
+      checked, bad = [], []
+      for b, l in enumerate(label_list):
+        try:
+          checked.append(engine_decode.wildcard_ids('set_labels', l, self.num_classes, True))
+        except ValueError:
+          bad.append(b)
+          checked.append(np.zeros(0, np.int32))            # (deferred mode: an empty label and status 2, as below)
+      if bad and not self.defer_label_errors:
+        raise ValueError('label ids must lie in [0, {}) (blank = {}) or be WILDCARD, never two of those in a row; offending '
+                         'utterances: {}'.format(self.num_classes - 1, self.num_classes - 1, bad))
+      lens = [len(l) for l in checked]
+      offs = np.zeros(len(checked) + 1, dtype=np.int32)
+      offs[1:] = np.cumsum(lens)
+      self.max_label_len = int(max(lens + [0]))
+      self._rejected_labels = bad
+      self._labels_wild = any(bool((l == self.num_classes).any()) for l in checked)
+      self.label_ids = self._upload_i32(np.concatenate(checked + [np.zeros(1, np.int32)]))
+      self.label_offs = self._upload_i32(offs)
+      return
     lens = [len(l) for l in label_list]
     offs = np.zeros(len(label_list) + 1, dtype=np.int32)
     offs[1:] = np.cumsum(lens)
@@ -680,9 +712,15 @@ class Wav2LetterEngine(DecodeMixin):
     # the CTC recursion runs (a latency chain of 500 dependent steps on 64 wavefronts: the rest of the chip is idle)
     self.mode.refresh_under_ctc()
     self._wait_uploads()
-    call('st_ctc_loss_grad_hilo_f32', logits.ref, self._ptr(self.label_ids), self._ptr(self.label_offs),
-         self._ptr(self.ctc_lens), self.max_label_len, float(grad_scale), self._ptr(sh.loss), self._ptr(sh.loss_lo), sh.dZ[-1].ref,
-         self._ptr(sh.ctc_status), self._ptr(self.ctc_ws), self.ctc_ws.numel() * 4, self.stream_ptr)
+    if self._labels_wild:                                  # only a batch that holds a wildcard: every other keeps the old call
+      bias = engine_decode._wildcard_bias('ctc_loss_grad', self.wildcard_bias)
+      call('st_ctc_loss_grad_wild_f32', logits.ref, self._ptr(self.label_ids), self._ptr(self.label_offs),
+           self._ptr(self.ctc_lens), self.max_label_len, float(grad_scale), bias, self._ptr(sh.loss), self._ptr(sh.loss_lo),
+           sh.dZ[-1].ref, self._ptr(sh.ctc_status), self._ptr(self.ctc_ws), self.ctc_ws.numel() * 4, self.stream_ptr)
+    else:
+      call('st_ctc_loss_grad_hilo_f32', logits.ref, self._ptr(self.label_ids), self._ptr(self.label_offs),
+           self._ptr(self.ctc_lens), self.max_label_len, float(grad_scale), self._ptr(sh.loss), self._ptr(sh.loss_lo), sh.dZ[-1].ref,
+           self._ptr(sh.ctc_status), self._ptr(self.ctc_ws), self.ctc_ws.numel() * 4, self.stream_ptr)
     if self._rejected_labels:                              # labels refused on the host (deferred mode): status 2
       with torch.cuda.stream(self.stream):
         sh.ctc_status.index_fill_(0, torch.as_tensor(self._rejected_labels, dtype=torch.int64).to(self.device, non_blocking=True), 2)

@@ -13,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from . import augmentation, vocabulary
+from . import augmentation, partial_labels, vocabulary
 from .speech_input import BaseInputLoader, SparseTensorValue, sparse_to_label_lists
 
 
@@ -266,6 +266,7 @@ class SpeechModel:
     self._rank = 0
     self._skips_seen = 0
     self.spec_augment = None
+    self.partial = None
 
   # ---- graph-building protocol ---------------------------------------------------------------
   def _convolution(self, value, filter_width, stride, input_channels, out_channels, apply_non_linearity=True):
@@ -279,11 +280,15 @@ class SpeechModel:
   def _create_network(self, num_classes):
     raise NotImplementedError()
 
-  def add_training_ops(self, learning_rate=1e-3, learning_rate_decay_factor=0, max_gradient_norm=5.0, momentum=0.9, spec_augment=None):
+  def add_training_ops(self, learning_rate=1e-3, learning_rate_decay_factor=0, max_gradient_norm=5.0, momentum=0.9, spec_augment=None,
+                       partial=None):
     """CTC loss -> mean -> clip_by_global_norm -> Adam(epsilon=1e-3) (speech_model.py:53-82).
     ``momentum`` is accepted and unused, exactly as in the reference.  ``spec_augment`` (extension): an
-    ``augmentation.SpecAugment`` (policy + seed) applied to the batches of updating steps, see ``step``."""
+    ``augmentation.SpecAugment`` (policy + seed) applied to the batches of updating steps, see ``step``.  ``partial``
+    (extension): a ``partial_labels.PartialTranscripts`` -- the labels of updating steps may leave audio out, marked with a
+    wildcard the CTC loss knows; evaluation and update=False steps keep the plain loss on the labels as they are."""
     self.spec_augment = spec_augment
+    self.partial = partial
     self.learning_rate = _Scalar(learning_rate, float)
     self.learning_rate_decay_op = self.learning_rate.assign(
         lambda: self.learning_rate.value * learning_rate_decay_factor)
@@ -412,7 +417,13 @@ class SpeechModel:
     out = []
     avg_loss = None
     if loss or update:
-      eng.set_labels(sparse_to_label_lists(labels))
+      if update and self.partial is not None:
+        # partial transcripts on updating steps only; the drop draws use SpecAugment's draw ids (step, row in the global batch)
+        eng.wildcard_bias = self.partial.bias
+        eng.set_labels(self.partial.apply(sparse_to_label_lists(labels), self.global_step.value, self._rank, self._world,
+                                          defer=eng.defer_label_errors), wildcard=True)
+      else:
+        eng.set_labels(sparse_to_label_lists(labels))
       # d(avg_loss)/d(loss_b) = 1 / global batch (speech_model.py:75)
       eng.ctc_loss_grad(1.0 / (len(seq_lens) * self._world))
       # single process: the loss read-back is enqueued right behind CTC and waited for after back-prop and the update have been
@@ -533,7 +544,7 @@ def create_default_model(flags, input_size: int, speech_input: BaseInputLoader) 
     model.add_training_ops(learning_rate=flags.learning_rate,
                            learning_rate_decay_factor=flags.learning_rate_decay_factor,
                            max_gradient_norm=flags.max_gradient_norm, momentum=flags.momentum,
-                           spec_augment=augmentation.from_flags(flags))
+                           spec_augment=augmentation.from_flags(flags), partial=partial_labels.from_flags(flags))
     model.add_decoding_ops()
   elif flags.command == 'export':
     model.add_training_ops()

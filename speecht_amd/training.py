@@ -81,6 +81,8 @@ class Training(execution.DatasetExecutor):
       print('Begin training')
       if getattr(model, 'spec_augment', None) is not None:
         print('SpecAugment: {}; seed {}'.format(model.spec_augment.policy.describe(), model.spec_augment.seed))
+      if getattr(model, 'partial', None) is not None:
+        print('Partial transcripts: {} (bias and drop are untuned guesses)'.format(model.partial))
       try:
         while not coordinator.should_stop():
           steps_done += 1
