@@ -1361,6 +1361,45 @@ int st_spec_augment_plan_host(const int32_t* host_seq_lens, const int64_t* host_
                               int time_warp, int freq_width, int freq_masks, int time_width, int time_masks, int time_ratio_q16,
                               int32_t* host_plan_out);
 
+/* ---- Waveform augmentation before the features (csrc/wave_augment.hip, csrc/wave_augment_core.h; no reference counterpart).  A
+ * batch of utterances stored one after the other (fp32; utterance u = in[in_offsets[u] .. in_offsets[u + 1])) is written to
+ * out[out_offsets[u] ..), each resampled by the speed its plan names and, when its plan says so, mixed with a clip of a noise bank at
+ * the planned signal-to-noise ratio.  The full definition (time map, tap order, the fixed order of the power sums, the draws) is at
+ * the top of csrc/wave_augment_core.h.
+ *   speeds    HOST int32 [n_speeds][2] = {num, den}: reduced fractions, terms 1 .. 32, 1/2 <= num/den <= 2; 1 .. 8 of them.  An
+ *             utterance of n samples at num/den becomes M = ceil(n den / num) samples; 1/1 is the copy, bit for bit.
+ *   tables    fp32, the speeds' phase tables one after the other, [den][2H] each with H = ceil(16 max(1, num/den)) (one of 1/1 is
+ *             present and never read).  The caller makes them (speecht_amd.augmentation.speed_table: resampy's kaiser_fast window,
+ *             rows normalised in float64): y[m] = sum_k fmaf(h[phi][k], x[i - H + 1 + k]) in float32, k ascending.
+ *   noise     fp32 clips one after the other, clip k = noise[clip_offsets[k] .. clip_offsets[k + 1]) (int64 [n_clips + 1], each clip
+ *             1 .. 2^31 - 1 samples), read circularly from the planned offset.  n_clips = 0: no bank, nothing is mixed.
+ *   plan      one 40-byte record per utterance, made by st_wave_augment_plan_host and uploaded by the caller:
+ *             {int64 M, int64 offset, double lin = 10^(snr/10), int32 speed index (-1: 1/1), int32 noisy, int32 clip, int32 snr in
+ *             hundredths of a dB}.  Gain a = sqrt(Ps / (Pn lin)) in double from the two mean powers over the M outputs (0 when
+ *             either is 0, and then nothing is mixed); out[m] = fmaf((float)a, noise sample, resampled sample).
+ * st_wave_augment_plan_host: the plans of n_utts utterances of `lengths` samples (0 .. 2^30 - 1), no GPU needed.  Draws are Philox4x32-10
+ *   with key = seed and counter = {draw id, block, 1} (SpecAugment's counter ends in 0: the two never share a stream), a function of
+ *   (seed, draw id) alone.  noise_prob_q16 in 0 .. 65536; the SNR is uniform over snr_lo_centi .. snr_hi_centi hundredths of a dB.  A
+ *   drawn speed that would leave M <= min_samples is replaced by 1/1 (speed index -1).
+ * st_wave_augment_f32: DEVICE pointers except `speeds`; two launches on `stream` (the second only with a bank).  in_total / out_total:
+ *   floats of `in` / `out`; max_out: the largest planned M (the caller knows every M from the plan).  The plan is device memory, so
+ *   the kernels clamp whatever it says to the offsets tables and the totals before they address anything.  Workspace (the tile
+ *   sums, needed with a bank): st_wave_augment_ws(n_utts, max_out) bytes, 8-byte aligned; any content.
+ * st_wave_augment_host: the same on HOST pointers, bit-identical to the kernels (the two share their arithmetic), every plan entry
+ *   checked.  sums_out: optional double [n_utts][2], the two sums of squares of each noisy utterance (0 otherwise).  No GPU needed. */
+int st_wave_augment_plan_host(const int64_t* host_lengths, const int64_t* host_draw_ids, int n_utts, uint64_t seed,
+                              const int32_t* host_speeds, int n_speeds, int noise_prob_q16, int snr_lo_centi, int snr_hi_centi,
+                              const int64_t* host_clip_lens, int n_clips, int64_t min_samples, void* host_plan_out);
+size_t st_wave_augment_ws(int n_utts, int64_t max_out);
+int st_wave_augment_f32(const float* in, const int64_t* in_offsets, int n_utts, int64_t in_total, const void* plan,
+                        const int32_t* host_speeds, int n_speeds, const float* tables, const float* noise, const int64_t* clip_offsets,
+                        int n_clips, float* out, const int64_t* out_offsets, int64_t out_total, int64_t max_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int st_wave_augment_host(const float* host_in, const int64_t* host_in_offsets, int n_utts, const void* host_plan,
+                         const int32_t* host_speeds, int n_speeds, const float* host_tables, const float* host_noise,
+                         const int64_t* host_clip_offsets, int n_clips, float* host_out, const int64_t* host_out_offsets,
+                         double* host_sums_out);
+
 /* ---- helpers -------------------------------------------------------------------------- */
 int st_fill_f32(float* dst, float value, size_t n, void* stream);
 /* zero the halo rows of a padded NWC tensor (needed when a buffer is re-described for a new shape) */

@@ -320,6 +320,13 @@ _SIGNATURES = {
                                      c_int, _T3P, c_void_p]),
     'st_spec_augment_plan_host': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_void_p]),
+    'st_wave_augment_plan_host': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                          c_int64, c_void_p]),
+    'st_wave_augment_ws': (c_size_t, [c_int, c_int64]),
+    'st_wave_augment_f32': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    'st_wave_augment_host': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_void_p]),
     'st_fill_f32': (c_int, [c_void_p, c_float, c_size_t, c_void_p]),
     'st_zero_halos_f32': (c_int, [_T3P, c_void_p]),
     'st_zero_regions': (c_int, [c_void_p, c_int, c_void_p]),

@@ -469,6 +469,57 @@ class Wav2LetterEngine(DecodeMixin):
     self.seq_lens_host = lens
     self.ctc_lens = table[ctc_at:]
 
+  def load_wave_batch(self, staged, lengths, global_lengths, feature_type, rate, wave=None, augment=None, rank=0, n_fft=512,
+                      hop_length=160):
+    """`load_batch` for a model fed WAVEFORMS: ``staged`` holds this rank's utterances one after the other (a float32 numpy
+    array or device tensor, or a ``speech_input.StagedBatch`` of one), ``lengths`` [B] their sample counts and
+    ``global_lengths`` [B * world] those of the whole global batch, of which this rank has rows [rank B, (rank + 1) B).
+    ``wave``: an ``augmentation.WaveAugment`` with one draw id per GLOBAL row -- every rank plans every row on the host, because
+    the padded length max_T is the global batch's; None leaves the waveforms as they are.  Then, on the engine's stream:
+    st_wave_augment_f32, the feature kernels of ``feature_type`` ('power' / 'mfcc') with their output staying in HBM, the padded
+    [B, max_T, C] batch, and `load_batch` with ``augment`` (SpecAugment) as for a feature batch.  ``self.wave_plan``: this rank's
+    plans (host), None without ``wave``; ``self.wave_frames``: the frame counts the batch was loaded with."""
+    from . import augmentation, preprocessing
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    glens = np.asarray(global_lengths, dtype=np.int64).reshape(-1)
+    B, lo = len(lens), int(rank) * len(lens)
+    if lo + B > len(glens) or not np.array_equal(glens[lo:lo + B], lens):
+      raise ValueError('load_wave_batch: rows {} .. {} of the global lengths are not this rank\'s lengths'.format(lo, lo + B))
+    if glens.min() <= n_fft // 2:
+      raise ValueError('load_wave_batch: utterances must be longer than n_fft/2 = {} samples'.format(n_fft // 2))
+    stream = self.stream
+    handle = staged if hasattr(staged, 'event') and hasattr(staged, 'tensor') else None
+    if handle is not None:
+      stream.wait_event(handle.event)
+      handle.tensor.record_stream(stream)
+      staged = handle.tensor
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    with torch.cuda.stream(stream):
+      audio = torch.as_tensor(staged).reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+      if audio.numel() != offsets[-1]:
+        raise ValueError('load_wave_batch: {} samples for lengths that sum to {}'.format(audio.numel(), offsets[-1]))
+      self.wave_plan = None
+      if wave is not None:
+        plan = augmentation.plan_wave_host(wave, glens, min_samples=n_fft // 2)
+        glens = np.asarray(plan['M'], dtype=np.int64)
+        self.wave_plan = plan[lo:lo + B].copy()
+        audio, offsets = augmentation.apply_wave_device(wave, audio, offsets, self.wave_plan, stream=stream, align=1)
+      max_T = int((1 + glens // hop_length).max())
+      feats, f_off = preprocessing.features_on_device(feature_type, audio, offsets, rate, n_fft, hop_length, n_mels=self.layers[0].cin,
+                                                      n_mfcc=self.layers[0].cin // 3)
+      frames = np.diff(f_off)
+      # row f of utterance u goes to row u max_T + (f - f_off[u]) of the padded batch; the rest stays zero
+      shift = torch.as_tensor(np.arange(B, dtype=np.int64) * max_T - f_off[:-1]).to(self.device)
+      index = torch.arange(int(f_off[-1]), device=self.device) + torch.repeat_interleave(shift, torch.as_tensor(frames).to(self.device),
+                                                                                         output_size=int(f_off[-1]))
+      padded = torch.zeros((B * max_T, feats.shape[1]), dtype=torch.float32, device=self.device)
+      padded.index_copy_(0, index, feats)
+      self.wave_frames = frames
+      self.load_batch(padded.view(B, max_T, -1), frames, augment=augment)
+    if handle is not None and hasattr(handle, 'consumed'):
+      handle.taken = True
+      handle.consumed.record(stream)
+
   def stage_host_batch(self, x_host):
     """Asynchronous H2D copy of a padded feature batch [B, T, C] (float32; a pinned torch tensor copies without
     an intermediate host copy) on the engine's copy stream into one of two staging buffers in HBM.  Returns a

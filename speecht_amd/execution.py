@@ -39,12 +39,25 @@ class DatasetExecutor(abc.ABC):
     if self.shuffle_seed is None and self.world > 1:
       self.shuffle_seed = data_parallel.broadcast_seed()
     self.reader = preprocessing.SpeechCorpusReader(flags.data_dir)
-    self.say('Determine input size from first sample')
-    self.input_size = self.determine_input_size()
+    # `train --waveforms` (extension): samples are waveforms, the step computes the features (128 mel channels or 39 MFCC values,
+    # what `preprocess` caches); an augmentation flag without it is refused here, before anything is read
+    from . import augmentation
+    training = getattr(flags, 'command', None) == 'train'
+    self.waveforms = bool(getattr(flags, 'waveforms', False)) and training
+    wave = None
+    if training:
+      augmentation.check_wave_flags(flags)
+    if self.waveforms:
+      flags.wave_rate = self.reader.wave_rate('train')
+      wave = dict(feature_type=flags.feature_type, rate=flags.wave_rate)
+      self.input_size = 128 if flags.feature_type == 'power' else 39
+    else:
+      self.say('Determine input size from first sample')
+      self.input_size = self.determine_input_size()
     self.say('Initialize InputBatchLoader')
     generator_factory = functools.partial(self.create_sample_generator, self.get_loader_limit_count())
     self.speech_input = speech_input.InputBatchLoader(self.input_size, flags.batch_size, generator_factory,
-                                                      self.get_max_steps(), shard=(self.rank, self.world))
+                                                      self.get_max_steps(), shard=(self.rank, self.world), wave=wave)
 
   def say(self, *args):
     if self.rank == 0:

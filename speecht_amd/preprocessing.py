@@ -85,6 +85,44 @@ def power_spectrogram_device(audio, sample_offsets, samplerate, n_mels=128, n_ff
   return [host[f_off[i]:f_off[i + 1]] for i in range(len(lens))]
 
 
+def features_on_device(feature_type, audio, sample_offsets, samplerate, n_fft=512, hop_length=160, n_mels=128, n_mfcc=13):
+  """power_spectrogram_device ('power') / mfccs_device ('mfcc') with the features STAYING in HBM, for the training step that is
+  fed waveforms (engine.load_wave_batch): the same launches on the current stream, returning (float32 device tensor
+  [total frames, channels], host int64 frame offsets [n + 1])."""
+  import torch
+  from . import _lib
+  if feature_type not in ('power', 'mfcc'):
+    raise ValueError('features_on_device: feature type {!r} (power or mfcc)'.format(feature_type))
+  dev = audio.device
+  lens, f_off = _frame_plan(sample_offsets, n_fft, hop_length)
+  s_off = np.asarray(sample_offsets, dtype=np.int64)
+  total = int(f_off[-1])
+  mels = n_mels if feature_type == 'power' else 128          # (mfccs_device: librosa.feature.mfcc's melspectrogram default)
+  channels = n_mels if feature_type == 'power' else 3 * n_mfcc
+  key = (str(dev), float(samplerate), n_fft, mels)
+  if key not in _BASIS:
+    _BASIS[key] = torch.as_tensor(mel_filterbank(float(samplerate), n_fft, mels).astype(np.float32)).contiguous().to(dev)
+  basis = _BASIS[key]
+  offsets = torch.as_tensor(np.concatenate([s_off, f_off])).to(dev)
+  d_soff, d_foff = offsets[:len(s_off)], offsets[len(s_off):]
+  out = torch.empty(total * channels, dtype=torch.float32, device=dev)
+  lib = _lib.load()
+  ws_bytes = lib.st_melspec_ws(len(lens), total, mels) if feature_type == 'power' else lib.st_mfcc_ws(len(lens), total, mels, n_mfcc)
+  ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
+  P = lambda t: ctypes.c_void_p(t.data_ptr())
+  stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+  if feature_type == 'power':
+    _lib.call('st_melspec_f32', P(audio), P(d_soff), len(lens), int(lens.max()), P(basis), mels, n_fft, hop_length, P(d_foff), total,
+              P(out), P(ws), ws.numel() * 4, stream)
+  else:
+    _lib.call('st_mfcc_f32', P(audio), P(d_soff), len(lens), int(lens.max()), P(basis), mels, n_mfcc, n_fft, hop_length, P(d_foff), total,
+              P(out), P(ws), ws.numel() * 4, stream)
+  return out.view(total, channels), f_off
+
+
+_BASIS = {}            # mel filter banks already in HBM, by (device, rate, n_fft, n_mels)
+
+
 def normalize(values):
   """(values - mean) / std over all elements (preprocessing.py:29-33); host helper kept for the
   API -- the device chain fuses this step."""
@@ -173,6 +211,8 @@ class SpeechCorpusReader:
     name = 'preprocessed'
     if feature_type == calc_power_spectrogram or feature_type == 'power':
       name += '-power'
+    elif feature_type == 'wave':
+      name += '-wave'
     return self._data_directory + '/' + name + '/' + sub_directory
 
   def generate_samples(self, directory, preprocess_fnc, audio_loader=None, pattern='*.flac'):
@@ -224,10 +264,80 @@ class SpeechCorpusReader:
       audio_id = self._extract_audio_id(f)
       np.savez(out_directory + '/' + audio_id, audio_fragments=feat, transcript=self._transcript_dict[audio_id])
 
-  def load_samples(self, directory, max_size=False, loop_infinitely=False, limit_count=0, feature_type='mfcc', shuffle_seed=None):
+  def store_waveforms(self, directory, audio_loader=None, patterns=('*.flac', '*.wav', '*.npy')):
+    """The waveform cache of `speecht-cli preprocess --waveforms`: ``<data>/preprocessed-wave/<directory>/<id>.npz`` with ``audio``
+    (float32, exactly what ``audio_loader`` -- default ``load_audio`` -- returns and the feature extractors would have been
+    given), ``rate`` and ``transcript``.  Training reads it with ``load_samples(..., feature_type='wave')`` and computes the
+    features inside the step, after the waveform augmentations.  Needs no GPU.  Returns the number of files written."""
+    loader = audio_loader or load_audio
+    out_directory = self._get_directory('wave', directory)
+    os.makedirs(out_directory, exist_ok=True)
+    count, cache_rate = 0, None
+    for pattern in patterns:
+      for path in iglob_recursive(self._data_directory + '/' + directory, pattern):
+        samples, rate = loader(path)
+        if cache_rate is None:
+          cache_rate = int(rate)
+        elif int(rate) != cache_rate:
+          # one cache, one rate: the step builds ONE mel basis for it (resample the corpus first, e.g. `--device-resample` features)
+          raise ValueError('{} is at {} Hz, the waveforms cached before it at {} Hz: a waveform cache holds one rate'.format(
+              path, rate, cache_rate))
+        audio_id = self._extract_audio_id(path)
+        np.savez(out_directory + '/' + audio_id, audio=np.asarray(samples, dtype=np.float32), rate=np.int64(rate),
+                 transcript=self._transcript_dict[audio_id])
+        count += 1
+    return count
+
+  def load_samples(self, directory, max_size=False, loop_infinitely=False, limit_count=0, feature_type='mfcc', shuffle_seed=None,
+                   hop_length=160):
     """Iterator over (audio_fragments, transcript), same semantics as preprocessing.py:243-279.
     ``shuffle_seed`` (not a reference argument): shuffle with a generator of its own seeded with it, over the SORTED file list,
-    instead of the process-wide ``random`` state -- every rank of a data-parallel job must walk the samples in the same order."""
+    instead of the process-wide ``random`` state -- every rank of a data-parallel job must walk the samples in the same order.
+    ``feature_type='wave'`` (extension): (audio, transcript) from the waveform cache; ``max_size`` then applies to the
+    unperturbed frame count 1 + len(audio) // hop_length."""
+    if feature_type == 'wave':
+      return self._load_waveforms(directory, max_size, loop_infinitely, limit_count, shuffle_seed, hop_length)
+    return self._load_features(directory, max_size, loop_infinitely, limit_count, feature_type, shuffle_seed)
+
+  def wave_rate(self, directory):
+    """The sample rate of the waveform cache (of its first file; a cache holds one rate)."""
+    files = sorted(iglob_recursive(self._get_directory('wave', directory), '*.npz'))
+    if not files:
+      raise ValueError('No waveform cache under {}: run `speecht-cli preprocess --waveforms`'.format(self._get_directory('wave', directory)))
+    with np.load(files[0]) as data:
+      return int(data['rate'])
+
+  def _load_waveforms(self, directory, max_size, loop_infinitely, limit_count, shuffle_seed, hop_length):
+    load_directory = self._get_directory('wave', directory)
+    if not os.path.exists(load_directory):
+      raise ValueError('Directory {} does not exist'.format(load_directory))
+    files = list(iglob_recursive(load_directory, '*.npz'))
+    shuffle = random.shuffle
+    if shuffle_seed is not None:
+      files.sort()
+      shuffle = random.Random(shuffle_seed).shuffle
+    shuffle(files)
+    if limit_count:
+      files = files[:limit_count]
+    cache_rate = None
+    while True:
+      for path in files:
+        with np.load(path) as data:
+          audio, rate = data['audio'], int(data['rate'])
+          if cache_rate is None:
+            cache_rate = rate
+          elif rate != cache_rate:
+            raise ValueError('{} is at {} Hz, the files read before it at {} Hz: a waveform cache holds one rate'.format(path, rate, cache_rate))
+          frames = 1 + audio.shape[0] // hop_length
+          if not max_size or frames <= max_size:
+            yield audio, data['transcript']
+          else:
+            logging.warning('Audio snippet too long: {}'.format(frames))
+      if not loop_infinitely:
+        break
+      shuffle(files)
+
+  def _load_features(self, directory, max_size, loop_infinitely, limit_count, feature_type, shuffle_seed):
     load_directory = self._get_directory(feature_type, directory)
     if not os.path.exists(load_directory):
       raise ValueError('Directory {} does not exist'.format(load_directory))
@@ -306,6 +416,9 @@ class Preprocessing:
           print('Skipping {} data: {}/{} does not exist'.format(title, self.flags.data_dir, split))
           continue
         print('Preprocessing {} data'.format(title))
+        if getattr(self.flags, 'waveforms', False):
+          print('  {} waveforms cached'.format(corpus_reader.store_waveforms(split, audio_loader=load_audio, patterns=self.AUDIO_PATTERNS)))
+          continue
         for pattern in self.AUDIO_PATTERNS:
           corpus_reader.store_samples(split, preprocess_fnc, audio_loader=load_audio, pattern=pattern,
                                       device_resample=getattr(self.flags, 'device_resample', False),

@@ -24,6 +24,20 @@ class StagedBatch:
     self.shape = tuple(tensor.shape)
 
 
+class WaveBatch:
+  """The queue item of a loader that feeds WAVEFORMS (``InputBatchLoader(..., wave=...)``): ``audio`` this rank's utterances one
+  after the other (float32; a host array, or after staging a StagedBatch of the device copy), ``lengths`` their sample counts,
+  ``global_lengths`` those of the WHOLE global batch (the step plans the augmentation of every global row: data parallelism pads a
+  shard to the global batch's longest member), ``rank`` this shard's place in it, and the features the step is to compute."""
+
+  def __init__(self, audio, lengths, global_lengths, rank, feature_type, rate, hop_length=160):
+    self.audio, self.lengths, self.global_lengths, self.rank = audio, lengths, global_lengths, rank
+    self.feature_type, self.rate, self.hop_length = feature_type, rate, hop_length
+
+  def staged(self, handle):
+    return WaveBatch(handle, self.lengths, self.global_lengths, self.rank, self.feature_type, self.rate, self.hop_length)
+
+
 class OutOfRangeError(Exception):
   """End-of-data signal, the role tf.errors.OutOfRangeError plays in training.py:92 / evaluation.py:109."""
 
@@ -178,8 +192,11 @@ class InputBatchLoader(BaseInputLoader):
   CAPACITY = 100
   DEVICE_PREFETCH = 3          # batches staged in HBM ahead of the consumer (copy stream, own thread)
 
-  def __init__(self, input_size, batch_size, data_generator_creator, max_steps=None, shard=None):
-    """``shard = (rank, world)`` (not a reference argument; data-parallel training): the loader forms the GLOBAL
+  def __init__(self, input_size, batch_size, data_generator_creator, max_steps=None, shard=None, wave=None):
+    """``wave = dict(feature_type=..., rate=...[, hop_length=...])`` (extension): the generator yields (waveform, labels) and a queue
+    item is (WaveBatch, sample counts of this rank's rows, labels) -- the features are computed inside the step, after the waveform
+    augmentation, which cannot run here: the feeder threads run ahead of the step counter the draws depend on.
+    ``shard = (rank, world)`` (not a reference argument; data-parallel training): the loader forms the GLOBAL
     batches of ``batch_size * world`` consecutive samples -- the batches one process with that batch size would see, every rank
     from an identically ordered generator -- pads each to the global batch's longest member (padding is never masked, SURVEY F7:
     an utterance's logits depend on the padded length, so the shard must be padded like the whole batch) and keeps rows
@@ -188,6 +205,7 @@ class InputBatchLoader(BaseInputLoader):
     self.batch_size = batch_size
     self.shard = tuple(shard) if shard is not None and int(shard[1]) > 1 else None
     self.data_generator_creator = data_generator_creator
+    self.wave = dict(wave) if wave else None
     self.steps_left = max_steps
     self.inputs = Placeholder('inputs')
     self.sequence_lengths = Placeholder('sequence_lengths')
@@ -207,6 +225,8 @@ class InputBatchLoader(BaseInputLoader):
   def _feed_item(self, sample_batch):
     """One (inputs, sequence_lengths, labels) queue item from a tuple of samples; with ``shard`` this rank's rows of it."""
     input_list, label_list = zip(*sample_batch)
+    if self.wave is not None:
+      return self._wave_item(input_list, label_list)
     if self.shard is None:
       input_tensor, sequence_lengths, max_time = self._get_inputs_feed_item(input_list)
       return input_tensor, sequence_lengths, self._get_labels_feed_item(label_list, max_time)
@@ -219,6 +239,17 @@ class InputBatchLoader(BaseInputLoader):
     for row, item in zip(input_tensor, mine):
       row[:item.shape[0]] = item
     return input_tensor, sequence_lengths, self._get_labels_feed_item(label_list[lo:hi], max_time)
+
+  def _wave_item(self, wave_list, label_list):
+    """The waveform form of a queue item: this rank's waveforms one after the other and the lengths of the whole global batch."""
+    rank = int(self.shard[0]) if self.shard else 0
+    lo, hi = rank * self.batch_size, (rank + 1) * self.batch_size
+    global_lengths = np.fromiter((len(w) for w in wave_list), dtype=np.int64, count=len(wave_list))
+    audio = np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in wave_list[lo:hi]])
+    hop = int(self.wave.get('hop_length', 160))
+    batch = WaveBatch(audio, global_lengths[lo:hi].copy(), global_lengths, rank, self.wave['feature_type'], self.wave['rate'], hop)
+    max_time = int(1 + global_lengths.max() // hop)                     # of the unperturbed global batch
+    return batch, batch.lengths, self._get_labels_feed_item(label_list[lo:hi], max_time)
 
   def _enqueue(self, sess, coord):
     try:
@@ -277,11 +308,13 @@ class InputBatchLoader(BaseInputLoader):
           inputs, seq_lens, labels = self._dequeue_host()
         except OutOfRangeError:
           break
+        wave = inputs if isinstance(inputs, WaveBatch) else None
         with torch.cuda.stream(stream):
-          tensor = torch.as_tensor(inputs).to(device)          # staged copy; the GIL is released meanwhile
+          tensor = torch.as_tensor(wave.audio if wave else inputs).to(device)          # staged copy; the GIL is released meanwhile
           event = torch.cuda.Event()
           event.record(stream)
-        item = (StagedBatch(tensor, event), seq_lens, labels)
+        handle = StagedBatch(tensor, event)
+        item = (wave.staged(handle) if wave else handle, seq_lens, labels)
         while not coord.should_stop():
           try:
             self._staged.put(item, timeout=0.1)

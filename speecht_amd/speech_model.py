@@ -266,6 +266,7 @@ class SpeechModel:
     self._rank = 0
     self._skips_seen = 0
     self.spec_augment = None
+    self.wave_augment = None
     self.partial = None
 
   # ---- graph-building protocol ---------------------------------------------------------------
@@ -281,7 +282,7 @@ class SpeechModel:
     raise NotImplementedError()
 
   def add_training_ops(self, learning_rate=1e-3, learning_rate_decay_factor=0, max_gradient_norm=5.0, momentum=0.9, spec_augment=None,
-                       partial=None):
+                       partial=None, wave_augment=None):
     """CTC loss -> mean -> clip_by_global_norm -> Adam(epsilon=1e-3) (speech_model.py:53-82).
     ``momentum`` is accepted and unused, exactly as in the reference.  ``spec_augment`` (extension): an
     ``augmentation.SpecAugment`` (policy + seed) applied to the batches of updating steps, see ``step``.  ``partial``
@@ -289,6 +290,9 @@ class SpeechModel:
     wildcard the CTC loss knows; evaluation and update=False steps keep the plain loss on the labels as they are."""
     self.spec_augment = spec_augment
     self.partial = partial
+    # (extension) an ``augmentation.WaveAugment``: speed perturbation and noise mixing on the waveforms of updating steps; needs a
+    # loader in its waveform form (``InputBatchLoader(..., wave=...)``)
+    self.wave_augment = wave_augment
     self.learning_rate = _Scalar(learning_rate, float)
     self.learning_rate_decay_op = self.learning_rate.assign(
         lambda: self.learning_rate.value * learning_rate_decay_factor)
@@ -406,7 +410,17 @@ class SpeechModel:
       labels = feed_dict.get(self.labels, labels) if self.labels is not None else labels
     if (loss or update) and labels is None:
       raise ValueError('loss/update requested but the input loader provides no labels')
-    if update and self.spec_augment is not None:
+    if hasattr(inputs, 'global_lengths'):
+      # a waveform-fed model (speech_input.WaveBatch): the features are computed inside the step.  Both augmentations on updating
+      # steps only; the waveform plan covers the whole global batch (its longest member after the speed change pads every rank)
+      B = len(seq_lens)
+      eng.load_wave_batch(inputs.audio, inputs.lengths, inputs.global_lengths, inputs.feature_type, inputs.rate, rank=inputs.rank,
+                          hop_length=inputs.hop_length,
+                          wave=self.wave_augment.for_step(self.global_step.value, B, self._world, self._rank)
+                          if update and self.wave_augment is not None else None,
+                          augment=self.spec_augment.for_step(self.global_step.value, B, self._world, self._rank)
+                          if update and self.spec_augment is not None else None)
+    elif update and self.spec_augment is not None:
       # SpecAugment on updating steps only (evaluation, decoding and update=False steps see the features as they are).  Draw ids:
       # global_step * global batch + the row in the global batch -- what one process that sees the whole global batch would give
       # the utterance; global_step is check-pointed, so a resumed run continues the same sequence of draws
@@ -544,7 +558,9 @@ def create_default_model(flags, input_size: int, speech_input: BaseInputLoader) 
     model.add_training_ops(learning_rate=flags.learning_rate,
                            learning_rate_decay_factor=flags.learning_rate_decay_factor,
                            max_gradient_norm=flags.max_gradient_norm, momentum=flags.momentum,
-                           spec_augment=augmentation.from_flags(flags), partial=partial_labels.from_flags(flags))
+                           spec_augment=augmentation.from_flags(flags), partial=partial_labels.from_flags(flags),
+                           wave_augment=augmentation.wave_from_flags(flags, getattr(flags, 'wave_rate', None),
+                                                                     getattr(flags, 'device', 'cuda:0')))
     model.add_decoding_ops()
   elif flags.command == 'export':
     model.add_training_ops()

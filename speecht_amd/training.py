@@ -34,7 +34,8 @@ class Training(execution.DatasetExecutor):
 
   def create_sample_generator(self, limit_count: int):
     samples = self.reader.load_samples('train', loop_infinitely=True, limit_count=limit_count,
-                                       feature_type=self.flags.feature_type, shuffle_seed=self.shuffle_seed)
+                                       feature_type='wave' if getattr(self, 'waveforms', False) else self.flags.feature_type,
+                                       shuffle_seed=self.shuffle_seed)
     window = getattr(self.flags, 'bucket_window', 0)
     if window and not getattr(self, 'peeking', False):
       # opt-in: batches of neighbouring lengths (4 % padding instead of ~40 % on 2-15 s speech, scripts/bench_varlen_train.py);
@@ -81,6 +82,11 @@ class Training(execution.DatasetExecutor):
       print('Begin training')
       if getattr(model, 'spec_augment', None) is not None:
         print('SpecAugment: {}; seed {}'.format(model.spec_augment.policy.describe(), model.spec_augment.seed))
+      if getattr(self, 'waveforms', False):
+        print('Training from waveforms at {} Hz: {} features computed in the step'.format(self.flags.wave_rate, self.flags.feature_type))
+      if getattr(model, 'wave_augment', None) is not None:
+        print('Waveform augmentation: {}; seed {} (the default SNR range 10 .. 30 dB is a guess, not tuned on data)'.format(
+            model.wave_augment.policy.describe(), model.wave_augment.seed))
       if getattr(model, 'partial', None) is not None:
         print('Partial transcripts: {} (bias and drop are untuned guesses)'.format(model.partial))
       try:
