@@ -15,7 +15,7 @@
 extern "C" {
 #endif
 
-/* fp32 [n] -> planes 3 x [n] (n % 4 == 0) */
+/* fp32 [n] -> planes 3 x [n] (n % 4 == 0; n == 0 succeeds and launches nothing) */
 int st_exp_split3_bf16(const float* src, size_t n, void* planes, void* stream);
 /* packed filters [k_pad][n_pad] fp32 -> planes 3 x [n_pad][k_pad] (transposed: reduction-contiguous) */
 int st_exp_split3_transpose_bf16(const float* packed, int k_pad, int n_pad, void* planes, void* stream);

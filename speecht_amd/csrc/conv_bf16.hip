@@ -47,6 +47,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BKB = 32;           // bf16 elements of reduction per LDS stage (2 MFMA k-steps)
 constexpr int NT_ = 256;
 
+// Domain: exact (h + m + l == x) for normal x whose last significand bit, 2^(e - 23), is still a bf16 value (e >= -110; the tests
+// use 2^-100 <= |x| <= 2^100, fp32 denormals are out of scope) and |x| below the bit pattern 0x7F7F8000: from there on
+// bf16(x) rounds to infinity and the planes are h = +-inf, m = -+inf, l = NaN.  x = +-inf gives (+-inf, NaN, NaN), NaN three NaNs.
 __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
   h = (__bf16)x;
   const float r1 = x - (float)h;          // exact
@@ -1019,6 +1022,7 @@ extern "C" {
 // planes: 3 * n bf16 elements (h | m | l)
 int st_exp_split3_bf16(const float* src, size_t n, void* planes, void* stream) {
   ST_REQUIRE(src && planes && n % 4 == 0, "split3: bad args");
+  if (n == 0) return ST_OK;
   const int blocks = (int)std::min<size_t>((n / 4 + 255) / 256, 4096);
   hipLaunchKernelGGL(split_kernel<3>, dim3(blocks), dim3(256), 0, st::as_stream(stream), src, n / 4,
                      reinterpret_cast<__bf16*>(planes));

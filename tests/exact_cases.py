@@ -6,7 +6,11 @@ reference bit for bit, stored bf16 results its round-to-nearest-even.  This modu
 the padded NWC tensors the tests build themselves, the references, the layout formulas of include/speecht_hip.h, the guard
 patterns and the comparison.  tests/test_exact_cases_cpu.py checks it without a GPU, tests/test_gpu_matrix_exact.py runs it.
 
-Data: x and dz from {+-1, +-2, +-3}, filters from {+-1, +-2}, bias from -4..4, the ReLU-mask source from -2..2."""
+Data: x and dz from {+-1, +-2, +-3}, filters from {+-1, +-2}, bias from -4..4, the ReLU-mask source from -2..2.
+
+The three-plane (bf16x6, NP = 3) kernels take their h | m | l planes from the caller, so the cases of the last section fill the three
+planes of every operand with INDEPENDENT small integers (no valid split of anything): the kernel must return the six kept plane
+products and nothing of the three dropped ones, bit for bit, and the three planes of its output must be split3 of that integer."""
 import collections
 import functools
 
@@ -547,3 +551,253 @@ def case_data(L):
   for a in d.values():
     a.setflags(write=False)
   return d
+
+
+# ---- three planes per operand (bf16x6: conv_bf16.hip, NP = 3) --------------------------------------------------------------------
+# The kernels multiply plane pairs, not numbers: with INDEPENDENT integer planes a_h, a_m, a_l and b_h, b_m, b_l they must return
+#   sum_k (a_h b_h + a_h b_m + a_m b_h + a_h b_l + a_l b_h + a_m b_m)
+# and nothing of a_m b_l, a_l b_m, a_l b_l.  (On a real split of small integers m = l = 0 and five of the six terms vanish.)
+PAIRS6 = ((0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1))      # (plane of the first operand, plane of the second), 0 1 2 = h m l
+BIAS6_MIN, BIAS6_MAX = 1 << 20, (1 << 23) - 1                   # |bias| of the forward cases: wide enough for a nonzero l plane
+
+
+def split3(x):
+  """numpy model of split3 in conv_bf16.hip: h = bf16(x), m = bf16(x - h), l = (x - h) - m, all in fp32 -> three float32 arrays.
+  h + m + l == x exactly for 2^-110 <= |x| < bit pattern 0x7F7F8000 (there bf16(x) overflows: h = +-inf, m = -+inf, l = NaN)."""
+  x = np.ascontiguousarray(x, dtype=np.float32)
+  with np.errstate(invalid='ignore', over='ignore'):
+    h = O.bf16_round(x).astype(np.float32)
+    r1 = x - h
+    m = O.bf16_round(r1).astype(np.float32)
+    l = r1 - m
+  return h, m, l
+
+
+def random_f32(rng, n, lo=-100, hi=100):
+  """n floats with full 23-bit mantissas, exponents lo..hi and both signs: all three planes of their split are nonzero"""
+  bits = (rng.integers(0, 2, n).astype(np.uint32) << 31) | ((rng.integers(lo, hi + 1, n) + 127).astype(np.uint32) << 23) | \
+      rng.integers(0, 1 << 23, n).astype(np.uint32)
+  return bits.view(np.float32)
+
+
+def make_planes(L, scale=1, positive_h=False):
+  """Three independent integer planes per operand, seeded from L.seed: x [3,B,T,cin] and dz [3,B,t_out,cout] from X_VALUES (int8),
+  F [3,W,cin,cout] from F_VALUES (int32), bias [cout] with |bias| in [2^20, 2^23) and random sign, act as make_data.  `scale` (a power
+  of two) multiplies the filters' h plane only, positive_h takes |.| of the h planes of x, dz and F: together they make back-prop's
+  sums wide enough to need all three output planes (the forward cases get there with the bias)."""
+  assert scale >= 1 and scale & (scale - 1) == 0 and scale * F_MAX <= 1 << 15
+  rng = np.random.default_rng([L.seed, 3])
+  x = X_VALUES[rng.integers(0, 6, (3, L.B, L.T, L.cin), dtype=np.uint8)]
+  F = F_VALUES[rng.integers(0, 4, (3, L.W, L.cin, L.cout), dtype=np.uint8)].astype(np.int32)
+  dz = X_VALUES[rng.integers(0, 6, (3, L.B, L.t_out, L.cout), dtype=np.uint8)]
+  bias = rng.integers(BIAS6_MIN, BIAS6_MAX + 1, L.cout) * rng.choice([-1, 1], L.cout)
+  act = rng.integers(-2, 3, (L.B, L.T, L.cin)).astype(np.int8)
+  if positive_h:
+    x[0], F[0], dz[0] = np.abs(x[0]), np.abs(F[0]), np.abs(dz[0])
+  F[0] *= scale
+  return dict(x=x, F=F, bias=bias.astype(np.int64), act=act, dz=dz)
+
+
+def ref_fwd6(xp, Fp, bias, pad_left, stride=1, relu=False):
+  """the six kept plane products of the forward pass (int64), bias and ReLU applied once"""
+  y = sum(ref_fwd(xp[a], Fp[b], 0, pad_left, stride) for a, b in PAIRS6) + np.asarray(bias, dtype=np.int64)
+  return np.maximum(y, 0) if relu else y
+
+
+def ref_bwd_data6(dzp, Fp, pad_left, T, stride=1, act=None):
+  """back-prop to the input: first operand dz, second the filters; the mask applied once"""
+  dx = sum(ref_bwd_data(dzp[a], Fp[b], pad_left, T, stride) for a, b in PAIRS6)
+  return dx * (act > 0) if act is not None else dx
+
+
+def ref_bwd_filter6(xp, dzp, W, pad_left, stride=1):
+  """filter gradient: first operand x (the rows of the product), second dz"""
+  return sum(ref_bwd_filter(xp[a], dzp[b], W, pad_left, stride)[0] for a, b in PAIRS6)
+
+
+def reductions6(L, what, scale=1):
+  """(terms, bound of the six plane products of one term, largest |addend outside the product|).  Forward and back-prop to the input:
+  the second operand is the filter, |b_h| <= scale * F_MAX, every other plane value is at most X_MAX or F_MAX -- three products with
+  b_h (a_h b_h, a_m b_h, a_l b_h) and three without (a_h b_m, a_h b_l, a_m b_m): 3 X_MAX F_MAX (scale + 1) = 18 (scale + 1).
+  Filter gradient: both operands from X_VALUES, 6 X_MAX^2 = 54."""
+  n = reductions(L, what)[0]
+  if what == 'bwd_filter':
+    assert scale == 1
+    return n, 6 * X_MAX * X_MAX, 0
+  return n, 3 * X_MAX * F_MAX * scale + 3 * X_MAX * F_MAX, BIAS6_MAX if what == 'fwd' else 0
+
+
+def assert_exact_range6(L, what, scale=1):
+  """n * 18 * (scale + 1) (filter gradient: n * 54), plus the forward bias below 2^23, stays below 2^24: every partial sum of every
+  subset of the plane products, in any order and under any split, is an integer below 2^24 and fp32 accumulation is exact -- and so is
+  the result with its bias, whose split3 planes then add up to it.  A bound on absolute values: it holds with positive_h too."""
+  n, term, extra = reductions6(L, what, scale)
+  assert term * n + extra < LIMIT, (L.name, what, n, scale)
+
+
+def plane_bits(planes):
+  """three float planes (bf16-representable values, as split3 returns them inside its domain) -> uint16 bit patterns [3, ...]"""
+  return np.stack([bf16_bits(p) for p in planes])
+
+
+def canonical16(bits):
+  """bf16 bit patterns with every NaN replaced by one pattern: non-finite planes compare by class (and infinities by sign)"""
+  bits = np.array(bits, dtype=np.uint16)
+  bits[(bits & np.uint16(0x7FFF)) > np.uint16(0x7F80)] = 0x7FC0
+  return bits
+
+
+def filter_planes_fwd(Fp, cin_pitch):
+  """the forward filter operand: 3 x [n_pad][k_pad] uint16, plane stride n_pad * k_pad"""
+  return np.stack([filters_bf16_ref(pack_ref(F.astype(np.float32), cin_pitch)) for F in Fp])
+
+
+def filter_planes_bwd(Fp, cin_pitch, cout_pitch):
+  """back-prop's filter operand (st_exp_split3_transpose_bf16 of the flipped, transposed filters): 3 x [n_pad(cin)][k_pad(W * cout_pitch)]"""
+  W, cin, cout = Fp[0].shape
+  return np.stack([filters_bwd_bf16_ref(pack_ref(F.astype(np.float32), cin_pitch), W, cin, cout, cin_pitch, cout_pitch) for F in Fp])
+
+
+def transposed_ref(image, row0, rows, tq, c_rows, slack=0, fill=0):
+  """transpose_split_kernel on one plane: out[c][b * tq + j] = image[b][row0 + j][c] for j < rows, c < c_pitch, flat with `slack`
+  elements behind; every other element is `fill` (the kernel leaves it alone)"""
+  B, _, cp = image.shape
+  body = np.full((c_rows, B, tq), fill, dtype=image.dtype)
+  body[:cp, :, :rows] = image[:, row0:row0 + rows].transpose(2, 0, 1)
+  return np.concatenate([body.reshape(-1), np.full(slack, fill, dtype=image.dtype)])
+
+
+XT_SLACK = 4096               # elements behind every transposed x plane (st_exp_conv1d_bwd_filter_bf16x6: shifted taps read into them)
+
+
+def wgrad6_tq(L):
+  """speecht_amd/modes/bf16x6.py: the transposed planes hold whole frame pitches of x, rounded up to 32"""
+  return round_up(max(L.x_geo.t_pitch, L.y_geo.frames), 32)
+
+
+def wgrad6_operands(L, xp, dzp):
+  """the operands of st_exp_conv1d_bwd_filter_bf16x6 as bf16 bit patterns, laid out as modes/bf16x6.py produces them: x planes
+  [3][cin_pitch * batch * tq + 4096] from row 0 of the padded tensor, dz planes [3][n_pad * batch * tq] from its first frame"""
+  xg, yg, tq = L.x_geo, L.y_geo, wgrad6_tq(L)
+  xt = np.stack([transposed_ref(bf16_bits(embed(xg, p)), 0, xg.t_pitch, tq, xg.c_pitch, XT_SLACK) for p in xp])
+  zt = np.stack([transposed_ref(bf16_bits(embed(yg, p)), yg.halo, yg.frames, tq, npad_of(L.cout)) for p in dzp])
+  return xt, zt
+
+
+def guarded_planes_image(g):
+  """[guard | h | m | l | guard], every plane a tensor image as in guarded_tensor_image, plane stride batch * t_pitch * c_pitch"""
+  one = guarded_tensor_image(g, True)
+  return np.concatenate([one[:GUARD_WORDS]] + [one[GUARD_WORDS:-GUARD_WORDS]] * 3 + [one[-GUARD_WORDS:]])
+
+
+def check_guarded_planes(after, g, ref, n_pad, what=''):
+  """the buffer of guarded_planes_image after the call: plane by plane the bit patterns of split3(ref), each held to everything
+  check_guarded_tensor asks of a 16-bit tensor (pad channels, fill, halo rows)"""
+  after = np.asarray(after).view(np.uint16)
+  n = g.batch * g.t_pitch * g.c_pitch
+  assert after.size == 3 * n + 2 * GUARD_WORDS
+  guard = np.full(GUARD_WORDS, GUARD16, np.uint16)
+  if not (np.all(after[:GUARD_WORDS] == GUARD16) and np.all(after[-GUARD_WORDS:] == GUARD16)):
+    return '{}: a guard region of the planes was written'.format(what)
+  for i, p in enumerate(split3(ref)):
+    one = np.concatenate([guard, after[GUARD_WORDS + i * n:GUARD_WORDS + (i + 1) * n], guard])
+    err = check_guarded_tensor(one, g, p, n_pad, bits16=True, what='{} plane {}'.format(what, 'hml'[i]))
+    if err:
+      return err
+  return None
+
+
+# host mirrors of the NP = 3 dispatch (bwd_data_splits is shared with NP = 1: bf16_bwd_data_splits; the forward entry point never splits)
+def x6_tile(M, n_pad, splits):
+  """conv_bf16.hip launch_gemm<3>: the 256 tile only when n_pad is a multiple of 256 (fits256) and the grid is wide"""
+  return 256 if n_pad % 256 == 0 and ceil_div(M, 256) * ceil_div(n_pad, 256) * max(1, splits) >= 192 else 128
+
+
+def x6_whole_stages(tile, taps, c_pitch, k_valid):
+  """conv_bf16.hip launch_gemm: FAST (whole stages: 32 deep for the 128 tile, 16 deep for the 256 tile) or clamped.
+  Every channel pitch is a multiple of 16 (st::tensor_ok; the filter gradient's reduction is batch * tq with tq % 32 == 0), so the
+  256 tile always has whole stages: gemm_nn_bf16_kernel<256, ..., NP = 3, FAST = false> cannot be reached through these entry
+  points.  (It stays instantiated: launch_gemm picks FAST at run time.)"""
+  bk = 32 if tile == 128 else 16
+  return (c_pitch if taps > 1 else k_valid) % bk == 0
+
+
+def x6_preconditions(L, what):
+  """the ST_REQUIRE lines of the st_exp_ entry points in conv_bf16.hip"""
+  x, y, pl = L.x_geo, L.y_geo, L.pad_left
+  if what == 'fwd':
+    return x.halo >= pl and y.frames == ceil_div(x.frames, L.stride) and x.c_pitch % 16 == 0 and npad_of(L.cout) % 128 == 0
+  if what == 'bwd_data':
+    lead = L.W - 1 - pl
+    return lead >= 0 and y.halo >= lead and y.frames == x.frames and y.batch == x.batch and npad_of(L.cin) % 128 == 0
+  if what == 'bwd_filter':
+    return wgrad6_tq(L) % 32 == 0 and x.c_pitch % 16 == 0 and npad_of(L.cout) % 128 == 0 and x.batch * wgrad6_tq(L) < 1 << 31
+  raise ValueError(what)
+
+
+X6_FWD = [
+    layer('x6-one-tile', 1, 100, 64, 128, 1),                                 # K = 64: two stages of the two-slot pipeline
+    layer('x6-k32', 1, 100, 32, 128, 1),                                      # one stage
+    layer('x6-k96', 1, 100, 96, 128, 1),                                      # three
+    layer('x6-clamped-taps', 2, 70, 40, 100, 7, xcp=48),
+    layer('x6-clamped-1tap', 2, 70, 40, 100, 1, xcp=48),
+    layer('x6-pad-left-0', 2, 70, 40, 100, 7, pad='l', xcp=48),
+    layer('x6-pad-left-w-1', 2, 70, 40, 100, 7, pad='r', xcp=48),
+    layer('x6-frames-below-taps', 3, 3, 40, 100, 7, xcp=48),
+    layer('x6-one-frame', 1, 1, 40, 100, 7, xcp=48),
+    layer('x6-stride2-clamped', 2, 75, 40, 100, 48, stride=2),
+    layer('x6-stride2-whole', 2, 75, 64, 100, 6, stride=2),
+    layer('x6-t256-k16', 3, 2007, 16, 2000, 1),                               # M = 6021, n_pad = 2048: 24 x 8 = 192 tiles of 256 x 256,
+    layer('x6-t256-k32', 3, 2007, 32, 2000, 1),                               # the threshold; one to four 16-deep stages of the ring of 3
+    layer('x6-t256-k48-taps', 3, 2007, 16, 2000, 3),
+    layer('x6-t256-k64', 3, 2007, 60, 2000, 1, xcp=64),
+]
+X6_BWD_DATA = [
+    layer('x6-bwd-clamped', 2, 70, 100, 100, 7),                              # dz pitch 112
+    layer('x6-bwd-whole', 2, 70, 100, 128, 7),
+    layer('x6-bwd-pad-left-0', 2, 70, 100, 100, 7, pad='l'),
+    layer('x6-bwd-pad-left-w-1', 2, 70, 100, 128, 7, pad='r'),
+    layer('x6-bwd-split', 2, 50, 100, 512, 16),                               # chunks * W = 128: two splits, slab_epilogue_kernel<3>
+    layer('x6-bwd-t256', 3, 2007, 2000, 60, 1, ycp=64),
+]
+X6_BWD_FILTER = [
+    layer('x6-wgrad-m-tail', 2, 100, 40, 100, 3, xcp=48),                     # M = 144: a row-tile tail
+    layer('x6-wgrad-long', 2, 300, 250, 100, 3),
+    layer('x6-wgrad-1tap', 3, 50, 128, 130, 1),
+    layer('x6-wgrad-x-first-row', 2, 100, 40, 100, 3, xcp=48, xe=(5, 0)),
+    layer('x6-wgrad-t256', 1, 40, 500, 1500, 16),                             # M = 8192, n_pad = 1536: 32 x 6 = 192 tiles
+]
+# the power of two on the filters' h plane in back-prop to the input (h planes positive): chosen on the CPU for the share of nonzero
+# elements in the reference's l plane, see test_exact_cases_cpu.py; the forward cases and the filter gradient use 1.  The largest
+# power of two that assert_exact_range6 admits at K = 700 .. 896 and at K = 8192 gives about 80 % nonzero l; at K = 60 no scale gives
+# any (the h plane holds the whole scaled part, the m plane the rest): that case checks that the l plane is written as zeros.
+X6_SCALE = {'x6-bwd-clamped': 1024, 'x6-bwd-whole': 1024, 'x6-bwd-pad-left-0': 1024, 'x6-bwd-pad-left-w-1': 1024, 'x6-bwd-split': 64,
+            'x6-bwd-t256': 128}
+X6_CALLS = [(X6_FWD, 'fwd'), (X6_BWD_DATA, 'bwd_data'), (X6_BWD_FILTER, 'bwd_filter')]
+
+
+def x6_params(L, what):
+  """(scale, positive_h) of a case"""
+  return (X6_SCALE[L.name], True) if what == 'bwd_data' else (1, False)
+
+
+@functools.lru_cache(maxsize=2)
+def case_planes(L, what):
+  d = make_planes(L, *x6_params(L, what))
+  for a in d.values():
+    a.setflags(write=False)
+  return d
+
+
+@functools.lru_cache(maxsize=2)
+def case_ref6(L, what):
+  """the reference of a case without ReLU and mask (either is one np.maximum / one product on top), made once"""
+  d = case_planes(L, what)
+  if what == 'fwd':
+    r = ref_fwd6(d['x'], d['F'], d['bias'], L.pad_left, L.stride)
+  elif what == 'bwd_data':
+    r = ref_bwd_data6(d['dz'], d['F'], L.pad_left, L.T)
+  else:
+    r = ref_bwd_filter6(d['x'], d['dz'], L.W, L.pad_left, L.stride)
+  r.setflags(write=False)
+  return r

@@ -4,6 +4,8 @@ The tests build the st_tensor3 descriptors themselves (halo, frame pitch, channe
 the engine's), put every written buffer between guard regions, keep the guard pattern in the halo rows of the output tensors and
 assert the launch-trace line that proves which kernel form ran; where the trace does not name the form (whole-stage or clamped
 bf16 kernel, ring depth and workgroup map of the transposing filter gradient) the host expression of the .hip file gives it.
+The three-plane (bf16x6) kernels run on planes of independent integers: six kept plane products, output planes equal to split3 of the
+result; their layout kernels are compared with the numpy model of split3 on real floats.
 The last test asserts that the union of the forms seen is the required list."""
 import ctypes
 import os
@@ -23,6 +25,7 @@ REQUIRED = {
     'gemm_nn<128,32,4,1,clamped>', 'gemm_nn<64,128,2,2,fast-bt>', 'gemm_nn<128,128,2,2,fast-bt>',
     'gemm_tn<128>', 'gemm_tn<64>', 'gemm_tn<32>',
     'gemm_nn_bf16<128,NP=1>', 'gemm_nn_bf16<256,NP=1>', 'conv_taps_bf16<128,128,64,panel>', 'wgrad_tr_bf16<128,128,32>',
+    'gemm_nn_bf16<128,NP=3>', 'gemm_nn_bf16<256,NP=3>',
 }
 BF16_FORMS = set()    # (tile, whole stages) of the bf16 general kernel, from the host expressions
 TR_FORMS = set()      # (ring, map, bias in tile) of the transposing filter gradient
@@ -540,12 +543,311 @@ def test_f32_filter_gradient(dev, L):
     assert L.T % 32 and L.T > 32 and M % 32                     # a 32-row step straddles an utterance end; M no multiple of 32
 
 
+# ---- three planes per operand (bf16x6): gemm_nn_bf16_kernel<..., NP = 3>, its epilogues, slab_epilogue_kernel<3>, the layout kernels ----
+# Planes of independent integers (E.make_planes): the result is the six kept plane products, bit for bit, and the output planes are
+# split3 of it.  Input planes lie at exactly the plane stride the entry point derives, slack only behind the last one.
+X6_FORMS = set()      # (tile, whole stages) of the NP = 3 kernel, from the host expressions
+
+
+def planes_in(dev, g, planes):
+  """three bf16 planes of a tensor, batch * t_pitch * c_pitch apart, SLACK_ROWS zero rows behind the last"""
+  img = np.concatenate([E.embed(g, p).reshape(-1) for p in planes] + [np.zeros(E.SLACK_ROWS * g.c_pitch, np.float32)])
+  return torch.from_numpy(img).to(dev).to(torch.bfloat16)
+
+
+def assert_x6(L, lines, M, n_pad, k_valid, taps, c_pitch, splits):
+  """the trace line of the NP = 3 kernel: tile and splits as the host mirrors give them; records (tile, whole stages)"""
+  tile = E.x6_tile(M, n_pad, splits)
+  line = only(lines, 'gemm_nn_bf16<')
+  assert line.startswith('gemm_nn_bf16<{},NP=3> splits={} M={} Np={} '.format(tile, splits, M, n_pad)), (L.name, line)
+  assert field(line, 'splits') == splits and field(line, 'taps') == taps, line
+  X6_FORMS.add((tile, E.x6_whole_stages(tile, taps, c_pitch, k_valid)))
+  return tile
+
+
+def run_fwd_x6(dev, L, relu, planes):
+  """st_exp_conv1d_fwd_bf16x6 into y (fp32) and, with `planes`, into the three planes of y"""
+  from speecht_amd import _lib
+  d = E.case_planes(L, 'fwd')
+  E.assert_exact_range6(L, 'fwd')
+  E.check_geometry(L, 'fwd')
+  assert E.x6_preconditions(L, 'fwd')
+  xg, yg = L.x_geo, L.y_geo
+  _, kp, n_pad = E.packed_dims(L.W, xg.c_pitch, L.cout)
+  xp = planes_in(dev, xg, d['x'])
+  wp = dev_bits16(dev, E.filter_planes_fwd(d['F'], xg.c_pitch))
+  bias = dev_f32(dev, bias_vector(L, d, n_pad))
+  y = Guarded(dev, E.guarded_tensor_image(yg))
+  yp = Guarded(dev, E.guarded_planes_image(yg)) if planes else None
+  X, Y = t3(xg, P(xp)), t3(yg, y.ptr)
+  lines = traced(lambda: _lib.call('st_exp_conv1d_fwd_bf16x6', ctypes.byref(X), P(xp), P(wp), P(bias), L.W, L.stride, L.pad_left, int(relu),
+                                   ctypes.byref(Y), yp.ptr if planes else None, None))
+  ref = E.case_ref6(L, 'fwd')
+  ref = np.maximum(ref, 0) if relu else ref
+  what = '{} fwd x6 relu={} planes={}'.format(L.name, relu, planes)
+  ok(E.check_guarded_tensor(y.read(), yg, ref, n_pad, what=what))
+  if planes:
+    ok(E.check_guarded_planes(yp.read(), yg, ref, n_pad, what=what))
+  return lines
+
+
+def run_bwd_data_x6(dev, L, mask, planes, use_ws=True):
+  """st_exp_conv1d_bwd_data_bf16x6 with the fp32 mask tensor or without, into dx and, with `planes`, into its three planes"""
+  from speecht_amd import _lib
+  lib = _lib.load()
+  d = E.case_planes(L, 'bwd_data')
+  E.assert_exact_range6(L, 'bwd_data', E.X6_SCALE[L.name])
+  E.check_geometry(L, 'bwd_data')
+  assert E.x6_preconditions(L, 'bwd_data')
+  xg, yg, ag = L.x_geo, L.y_geo, act_geo(L)
+  n_pad = E.npad_of(L.cin)
+  zp = planes_in(dev, yg, d['dz'])
+  a = in_f32(dev, ag, d['act'])
+  wp = dev_bits16(dev, E.filter_planes_bwd(d['F'], xg.c_pitch, yg.c_pitch))
+  dx = Guarded(dev, E.guarded_tensor_image(xg))
+  dxp = Guarded(dev, E.guarded_planes_image(xg)) if planes else None
+  Z, A, X = t3(yg, P(zp)), t3(ag, P(a)), t3(xg, dx.ptr)
+  need = lib.st_exp_conv1d_bwd_data_bf16x6_ws(ctypes.byref(Z), ctypes.byref(X), L.W)
+  assert (need > 0) == (E.bf16_bwd_data_splits(L) > 1)
+  ws = scratch(dev, need) if use_ws and need else None
+  lines = traced(lambda: _lib.call('st_exp_conv1d_bwd_data_bf16x6', ctypes.byref(Z), P(zp), P(wp), L.W, L.pad_left,
+                                   ctypes.byref(A) if mask else None, ctypes.byref(X), dxp.ptr if planes else None,
+                                   P(ws) if ws is not None else None, need if ws is not None else 0, None))
+  ref = E.case_ref6(L, 'bwd_data')
+  ref = ref * (d['act'] > 0) if mask else ref
+  what = '{} bwd_data x6 mask={} planes={} ws={}'.format(L.name, mask, planes, use_ws)
+  ok(E.check_guarded_tensor(dx.read(), xg, ref, n_pad, what=what))
+  if planes:
+    ok(E.check_guarded_planes(dxp.read(), xg, ref, n_pad, what=what))
+  return lines
+
+
+def run_wgrad_x6(dev, L):
+  """st_exp_conv1d_bwd_filter_bf16x6 on transposed planes laid out as modes/bf16x6.py produces them"""
+  from speecht_amd import _lib
+  d = E.case_planes(L, 'bwd_filter')
+  E.assert_exact_range6(L, 'bwd_filter')
+  E.check_geometry(L, 'bwd_filter')
+  assert E.x6_preconditions(L, 'bwd_filter')
+  xg, tq = L.x_geo, E.wgrad6_tq(L)
+  _, kp, n_pad = E.packed_dims(L.W, xg.c_pitch, L.cout)
+  xt, zt = E.wgrad6_operands(L, d['x'], d['dz'])
+  xtd, ztd = dev_bits16(dev, xt), dev_bits16(dev, zt)
+  dpacked = Guarded(dev, E.guarded_flat_image(kp * n_pad))
+  lines = traced(lambda: _lib.call('st_exp_conv1d_bwd_filter_bf16x6', P(xtd), P(ztd), L.B, tq, L.W, xg.c_pitch, xg.halo - L.pad_left, L.cout,
+                                   dpacked.ptr, None))
+  ok(E.check_guarded_flat(dpacked.read(), E.dpacked_ref(E.case_ref6(L, 'bwd_filter'), xg.c_pitch), what=L.name + ' x6 dpacked', shape=(kp, n_pad),
+                          kept_from=L.W * xg.c_pitch * n_pad, row_pitch=xg.c_pitch))
+  return lines
+
+
+X6_FWD_RUNS = [(L, relu, planes) for L in E.X6_FWD for relu in (False, True) for planes in (False, True)]      # case-major: one reference each
+X6_BWD_RUNS = [(L, mask, planes) for L in E.X6_BWD_DATA for mask in (False, True) for planes in (False, True)]
+run_id = lambda names: lambda r: '{}-{}{}-{}{}'.format(r[0].name, names[0], int(r[1]), names[1], int(r[2]))
+
+
+@pytest.mark.parametrize('L,relu,planes', X6_FWD_RUNS, ids=list(map(run_id(('relu', 'planes')), X6_FWD_RUNS)))
+def test_x6_forward(dev, L, relu, planes):
+  """the 128 tile with one, two and three 32-deep stages, clamped stages, both padding extremes, fewer frames than taps, stride 2; the
+  256 tile (ring of three, ping-pong) with one to four 16-deep stages at the threshold of 192 tiles"""
+  lines = run_fwd_x6(dev, L, relu, planes)
+  xg = L.x_geo
+  tile = assert_x6(L, lines, L.B * L.t_out, E.npad_of(L.cout), L.W * xg.c_pitch, L.W, xg.c_pitch, 1)
+  assert tile == (256 if L.name.startswith('x6-t256') else 128)
+
+
+@pytest.mark.parametrize('L,mask,planes', X6_BWD_RUNS, ids=list(map(run_id(('mask', 'planes')), X6_BWD_RUNS)))
+def test_x6_backprop(dev, L, mask, planes):
+  """in-kernel epilogue of both tiles and, in the split case, slab_epilogue_kernel<3>; without a workspace the split case falls back
+  to one launch and gives the same bits"""
+  splits = E.bf16_bwd_data_splits(L)
+  assert splits == (2 if L.name == 'x6-bwd-split' else 1)
+  lines = run_bwd_data_x6(dev, L, mask, planes)
+  yg = L.y_geo
+  tile = assert_x6(L, lines, L.B * L.T, E.npad_of(L.cin), L.W * yg.c_pitch, L.W, yg.c_pitch, splits)
+  assert tile == (256 if L.name == 'x6-bwd-t256' else 128)
+  if splits > 1:
+    lines = run_bwd_data_x6(dev, L, mask, planes, use_ws=False)
+    assert_x6(L, lines, L.B * L.T, E.npad_of(L.cin), L.W * yg.c_pitch, L.W, yg.c_pitch, 1)
+
+
+@pytest.mark.parametrize('L', E.X6_BWD_FILTER, ids=lambda L: L.name)
+def test_x6_filter_gradient(dev, L):
+  lines = run_wgrad_x6(dev, L)
+  xg = L.x_geo
+  tile = assert_x6(L, lines, L.W * xg.c_pitch, E.npad_of(L.cout), L.B * E.wgrad6_tq(L), 1, xg.c_pitch, 1)
+  assert tile == (256 if L.name == 'x6-wgrad-t256' else 128)
+
+
+def check_planes_flat(after, want, what, shape):
+  """check_guarded_flat for planes that may be non-finite: where the model gives a NaN the kernel must have written one (any NaN but
+  the fill pattern); finite values, zeros and infinities compare by bits, so infinities by sign"""
+  after = np.array(after, dtype=np.uint16)
+  body = after[E.GUARD_WORDS:-E.GUARD_WORDS]
+  want = np.asarray(want, dtype=np.uint16).reshape(-1)
+  is_nan = lambda b: (b & np.uint16(0x7FFF)) > np.uint16(0x7F80)
+  agree = is_nan(want) & is_nan(body) & (body != E.FILL16)
+  body[agree] = want[agree]
+  return E.check_guarded_flat(after, want, bits16=True, what=what, shape=shape)
+
+
+SPECIAL_F32 = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7F8001, 0xFF7F7FFF,
+                        0xFF7F8000, 0xFF7F8001, 0x7F7FFFFF, 0xFF7FFFFF], dtype=np.uint32).view(np.float32)
+
+
+@pytest.mark.parametrize('n', [4, 1020, 4 * (4096 * 256) + 4])
+def test_split3_planes(dev, n):
+  """st_exp_split3_bf16 against E.split3 on floats with full mantissas (exponents -100..100), +-0, +-inf, NaN and both sides of the bit
+  pattern 0x7F7F8000 where bf16(x) overflows; the largest n enters the grid-stride loop (4096 blocks of 256 lanes of 4 elements)"""
+  from speecht_amd._lib import call
+  src = E.random_f32(np.random.default_rng(n), n)
+  k = min(SPECIAL_F32.size, n - 2)
+  src[1:1 + k] = SPECIAL_F32[:k]
+  src[n - 1 - k:n - 1] = SPECIAL_F32[:k]
+  want = E.plane_bits(E.split3(src))
+  assert np.count_nonzero(want[2] & 0x7FFF) > 0.4 * n
+  out = Guarded(dev, E.guarded_flat_image(3 * n, bits16=True))
+  sd = dev_f32(dev, src)
+  call('st_exp_split3_bf16', P(sd), n, out.ptr, None)
+  torch.cuda.synchronize()
+  ok(check_planes_flat(out.read(), want, 'split3 n={}'.format(n), (3, n)))
+
+
+def test_split3_of_nothing_succeeds_and_writes_nothing(dev):
+  from speecht_amd import _lib
+  lib = _lib.load()
+  image = E.guarded_flat_image(48, bits16=True)
+  out = Guarded(dev, image)
+  sd = dev_f32(dev, np.ones(16, np.float32))
+  assert lib.st_exp_split3_bf16(P(sd), 0, out.ptr, None) == 0
+  torch.cuda.synchronize()
+  assert np.array_equal(out.read(), image)
+
+
+@pytest.mark.parametrize('k_pad,n_pad', [(32, 32), (96, 128), (2080, 160)])
+def test_split3_transpose_planes(dev, k_pad, n_pad):
+  """st_exp_split3_transpose_bf16: planes 3 x [n_pad][k_pad] of packed [k_pad][n_pad]"""
+  from speecht_amd._lib import call
+  packed = E.random_f32(np.random.default_rng(k_pad + n_pad), k_pad * n_pad).reshape(k_pad, n_pad)
+  want = E.plane_bits(E.split3(packed.T))
+  out = Guarded(dev, E.guarded_flat_image(3 * n_pad * k_pad, bits16=True))
+  pd = dev_f32(dev, packed)
+  call('st_exp_split3_transpose_bf16', P(pd), k_pad, n_pad, out.ptr, None)
+  torch.cuda.synchronize()
+  ok(E.check_guarded_flat(out.read(), want, bits16=True, what='split3_transpose', shape=(3, n_pad, k_pad)))
+
+
+@pytest.mark.parametrize('c_pitch,rows,row0,t_pitch', [(48, 45, 2, 50), (256, 64, 1, 66)])
+def test_transpose_split3_planes(dev, c_pitch, rows, row0, t_pitch):
+  """st_exp_transpose_split3_bf16: plane[c][b * tq + j] = split3(t[b][row0 + j][c]) for j < rows; the frames from `rows` to tq and the
+  slack behind every plane keep the fill pattern"""
+  from speecht_amd._lib import call
+  batch, tq = 3, 64
+  plane_elems = c_pitch * batch * tq + E.XT_SLACK
+  g = E.Geo(batch, rows, c_pitch, row0, t_pitch, c_pitch)
+  src = E.random_f32(np.random.default_rng(c_pitch), batch * t_pitch * c_pitch).reshape(batch, t_pitch, c_pitch)
+  bits = E.plane_bits(E.split3(src))
+  want = np.stack([E.transposed_ref(b, row0, rows, tq, c_pitch, E.XT_SLACK, fill=E.FILL16) for b in bits])
+  assert want.shape == (3, plane_elems) and (rows == tq or np.count_nonzero(want == E.FILL16) > 3 * E.XT_SLACK)
+  out = Guarded(dev, E.guarded_flat_image(3 * plane_elems, bits16=True))
+  sd = dev_f32(dev, src)
+  T = t3(g, P(sd))
+  call('st_exp_transpose_split3_bf16', ctypes.byref(T), row0, rows, tq, plane_elems, out.ptr, None)
+  torch.cuda.synchronize()
+  ok(E.check_guarded_flat(out.read(), want, bits16=True, what='transpose_split3', shape=(3, plane_elems)))
+
+
+def test_x6_filter_gradient_chain_as_the_mode_calls_it(dev):
+  """st_exp_transpose_split3_bf16 of integer tensors (m = l = 0), then st_exp_conv1d_bwd_filter_bf16x6 on its planes, with the arguments
+  of modes/bf16x6.py: the two agree on tq, x_first_row and the slack, and the product is E.ref_bwd_filter"""
+  from speecht_amd import _lib
+  L = E.X6_BWD_FILTER[3]
+  d = E.case_data(L)
+  E.assert_exact_range(L, 'bwd_filter')
+  xg, yg, tq = L.x_geo, L.y_geo, E.wgrad6_tq(L)
+  _, kp, n_pad = E.packed_dims(L.W, xg.c_pitch, L.cout)
+  red = L.B * tq
+  x, z = in_f32(dev, xg, d['x']), in_f32(dev, yg, d['dz'])
+  xt = torch.zeros(3 * (xg.c_pitch * red + E.XT_SLACK) + OPERAND_SLACK, dtype=torch.bfloat16, device=dev)       # zero planes, as the engine's
+  zt = torch.zeros(3 * n_pad * red + OPERAND_SLACK, dtype=torch.bfloat16, device=dev)
+  dpacked = Guarded(dev, E.guarded_flat_image(kp * n_pad))
+  X, Z = t3(xg, P(x)), t3(yg, P(z))
+
+  def fn():
+    _lib.call('st_exp_transpose_split3_bf16', ctypes.byref(X), 0, xg.t_pitch, tq, xg.c_pitch * red + E.XT_SLACK, P(xt), None)
+    _lib.call('st_exp_transpose_split3_bf16', ctypes.byref(Z), yg.halo, yg.frames, tq, n_pad * red, P(zt), None)
+    _lib.call('st_exp_conv1d_bwd_filter_bf16x6', P(xt), P(zt), L.B, tq, L.W, xg.c_pitch, xg.halo - L.pad_left, L.cout, dpacked.ptr, None)
+  lines = traced(fn)
+  only(lines, 'gemm_nn_bf16<128,NP=3>')
+  dF, _ = E.ref_bwd_filter(d['x'], d['dz'], L.W, L.pad_left)
+  ok(E.check_guarded_flat(dpacked.read(), E.dpacked_ref(dF, xg.c_pitch), what='x6 filter gradient chain', shape=(kp, n_pad),
+                          kept_from=L.W * xg.c_pitch * n_pad, row_pitch=xg.c_pitch))
+  planes = xt.cpu().view(torch.int16).numpy().view(np.uint16)[:3 * (xg.c_pitch * red + E.XT_SLACK)].reshape(3, -1)
+  assert np.array_equal(planes[0], E.transposed_ref(E.bf16_bits(E.embed(xg, d['x'])), 0, xg.t_pitch, tq, xg.c_pitch, E.XT_SLACK))
+  assert not (planes[1:] & 0x7FFF).any()
+
+
+def test_x6_entry_points_refuse_what_they_cannot_run(dev):
+  """n_pad 32 forward, n_pad 64 in back-prop to the input, tq = 48 in the filter gradient, n = 6 in split3: an error status, no launch,
+  and every output buffer as it was"""
+  from speecht_amd import _lib
+  lib = _lib.load()
+
+  def refused(fn, *outs):
+    before = [o.read() for o in outs]
+    with _lib.launch_trace() as tr:
+      rc = fn()
+    torch.cuda.synchronize()
+    assert rc != 0 and tr.lines == [] and lib.st_last_error()
+    for o, b in zip(outs, before):
+      assert np.array_equal(o.read(), b)
+
+  L = E.layer('x6-refused-fwd', 2, 50, 40, 29, 7, xcp=48)
+  assert E.npad_of(L.cout) == 32 and not E.x6_preconditions(L, 'fwd')
+  d = E.make_planes(L)
+  xg, yg = L.x_geo, L.y_geo
+  xp = planes_in(dev, xg, d['x'])
+  wp = dev_bits16(dev, E.filter_planes_fwd(d['F'], xg.c_pitch))
+  bias = dev_f32(dev, bias_vector(L, d, 32))
+  y, yp = Guarded(dev, E.guarded_tensor_image(yg)), Guarded(dev, E.guarded_planes_image(yg))
+  X, Y = t3(xg, P(xp)), t3(yg, y.ptr)
+  refused(lambda: lib.st_exp_conv1d_fwd_bf16x6(ctypes.byref(X), P(xp), P(wp), P(bias), L.W, 1, L.pad_left, 1, ctypes.byref(Y), yp.ptr, None), y, yp)
+
+  L = E.layer('x6-refused-bwd', 2, 50, 40, 100, 7, xcp=48)
+  assert E.npad_of(L.cin) == 64 and not E.x6_preconditions(L, 'bwd_data')
+  d = E.make_planes(L)
+  xg, yg = L.x_geo, L.y_geo
+  zp = planes_in(dev, yg, d['dz'])
+  wp = dev_bits16(dev, E.filter_planes_bwd(d['F'], xg.c_pitch, yg.c_pitch))
+  dx, dxp = Guarded(dev, E.guarded_tensor_image(xg)), Guarded(dev, E.guarded_planes_image(xg))
+  Z, X = t3(yg, P(zp)), t3(xg, dx.ptr)
+  refused(lambda: lib.st_exp_conv1d_bwd_data_bf16x6(ctypes.byref(Z), P(zp), P(wp), L.W, L.pad_left, None, ctypes.byref(X), dxp.ptr, None, 0, None),
+          dx, dxp)
+
+  L = E.X6_BWD_FILTER[0]
+  d = E.case_planes(L, 'bwd_filter')
+  xg = L.x_geo
+  _, kp, n_pad = E.packed_dims(L.W, xg.c_pitch, L.cout)
+  xt, zt = E.wgrad6_operands(L, d['x'], d['dz'])
+  xtd, ztd = dev_bits16(dev, xt), dev_bits16(dev, zt)
+  dpacked = Guarded(dev, E.guarded_flat_image(kp * n_pad))
+  assert E.wgrad6_tq(L) > 48
+  refused(lambda: lib.st_exp_conv1d_bwd_filter_bf16x6(P(xtd), P(ztd), L.B, 48, L.W, xg.c_pitch, xg.halo - L.pad_left, L.cout, dpacked.ptr, None), dpacked)
+
+  out = Guarded(dev, E.guarded_flat_image(24, bits16=True))
+  sd = dev_f32(dev, np.ones(8, np.float32))
+  refused(lambda: lib.st_exp_split3_bf16(P(sd), 6, out.ptr, None), out)
+
+
 def test_every_required_form_ran():
   """Runs last: the union of the trace forms of this module's cases is the required list, the bf16 general kernel ran in both tiles
-  with whole and with clamped stages, the transposing filter gradient in both ring depths, both maps and both bias paths."""
+  with whole and with clamped stages, the transposing filter gradient in both ring depths, both maps and both bias paths, the
+  three-plane kernel in both tiles with whole stages and in the 128 tile with clamped ones (its 256 tile has no clamped form to reach:
+  E.x6_whole_stages)."""
   for case, line in COVERAGE:
     print('{:<75} {}'.format(case, line))
   assert SEEN == REQUIRED, (sorted(SEEN - REQUIRED), sorted(REQUIRED - SEEN))
   assert BF16_FORMS == {(128, True), (128, False), (256, True), (256, False)}, BF16_FORMS
   assert {f[0] for f in TR_FORMS} == {4, 8} and {f[1] for f in TR_FORMS} == {1, 2} and {f[2] for f in TR_FORMS} == {True, False}
   assert {f[3] for f in TR_FORMS} == {True, False}
+  assert X6_FORMS == {(128, True), (128, False), (256, True)}, X6_FORMS
